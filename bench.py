@@ -30,6 +30,13 @@ planned on the estimates - what a real checkpoint's end-of-sequence does to a pl
 
 `value` counts DELIVERED audio: the samples of the post-processed waveforms the caller receives
 (after silence trim), not the vocoder's raw output.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line (`ms_per_step` = wall ms of
+one timed step).  `--full` adds what takes runs of its own: the instrumented roofline step and the
+decode-frame timing, time to first audio, and the CPU baseline (`--no-roofline` / `--no-cpu-baseline`
+drop parts of it).  `--dump-outputs DIR` writes the post-processed waveforms of the last timed step
+as DIR/waveform_<item>.npy (float32, item order = corpus order or rank-major; at most 64 MB - a
+seeded sample of the items beyond that), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -104,6 +111,34 @@ def launch_plan(gpus: int, env, n_devices: int, backend: str = "nccl"):
     return "spawn", gpus
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(waves, out_dir: str, limit: int = DUMP_LIMIT_BYTES, seed: int = 0):
+    """Write the waveforms a caller of the timed path receives as out_dir/waveform_<index>.npy (float32).  When they hold more
+    than `limit` bytes, a fixed seeded sample of the items is written instead (items in a seeded order while they fit).
+    Earlier waveform_*.npy files in out_dir are removed first.  Returns the indices written."""
+    os.makedirs(out_dir, exist_ok=True)
+    for f in os.listdir(out_dir):
+        if f.startswith("waveform_") and f.endswith(".npy"):
+            os.remove(os.path.join(out_dir, f))
+    arrays = [None if w is None else np.ascontiguousarray(np.asarray(w, dtype=np.float32).reshape(-1)) for w in waves]
+    sizes = [0 if a is None else a.nbytes + 128 for a in arrays]          # (+ the .npy header of a 1-D float32 array)
+    if sum(sizes) <= limit:
+        keep = [i for i, a in enumerate(arrays) if a is not None]
+    else:
+        keep, used = [], 0
+        for i in np.random.default_rng(seed).permutation(len(arrays)):
+            if arrays[i] is not None and used + sizes[i] <= limit:
+                keep.append(int(i))
+                used += sizes[i]
+        keep.sort()
+    width = max(4, len(str(max(0, len(arrays) - 1))))
+    for i in keep:
+        np.save(os.path.join(out_dir, f"waveform_{i:0{width}d}.npy"), arrays[i])
+    return keep
+
+
 def spawn_ranks(gpus: int, argv) -> int:
     """Start the N ranks as a child `torch.distributed.run` (never os.exec*: this process may already hold a HIP runtime) on
     127.0.0.1 and a free port; rank 0's JSON line goes to our stdout unchanged.  Returns the child's exit code."""
@@ -143,7 +178,14 @@ def main():
     ap.add_argument("--static-batches", action="store_true", help="corpus mode: length-bucketed static batches instead of continuous batching")
     ap.add_argument("--eos-live", action="store_true", help="decode with end-of-sequence live (as a real checkpoint does) instead of fixed lengths")
     ap.add_argument("--tune", default="", help="comma-separated rt_debug_tune codes (100/101 legacy/column decode, 200/201 eager/graph)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline and decode-frame "
+                    "timing, time to first audio, CPU baseline (each still switched off by --no-roofline / --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the waveforms of the last timed step as DIR/waveform_<item>.npy "
+                    "(float32, at most 64 MB: a seeded sample of the items beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    roofline_on = args.full and not args.no_roofline
 
     # ---- how many ranks?  decided before anything touches the GPU (torch.cuda.device_count() does not initialise it here)
     what, detail = launch_plan(args.gpus, os.environ, torch.cuda.device_count(), args.backend)
@@ -289,6 +331,11 @@ def main():
         assert len(_host) == len(corpus) and all(w is not None and w.numel() > 0 for w in _host), "corpus: a waveform is missing"
     dt = time.perf_counter() - t0
     log(f"timed region: {args.steps} steps in {dt:.3f} s")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed to the caller: rank 0's waveforms (corpus order, or every rank's batch in rank order)
+        waves = _host if (dist is None or corpus is not None) else [w for part in _host for w in part]
+        kept = dump_outputs(waves, args.dump_outputs)
+        log(f"outputs: {len(kept)} of {len(waves)} waveforms written to {args.dump_outputs}")
     phase_ms = {k: round(v / max(1, args.steps), 3) for k, v in phases.items()} if args.phase_times else None
     t = torch.tensor([dt, audio_local], dtype=torch.float64, device=comm_dev)
     if dist is not None:
@@ -304,7 +351,7 @@ def main():
     roof = None
     extra = {}
     extra_families = None
-    if not args.no_roofline:
+    if roofline_on:
         eng.model.profile(True)
         step()
         n_l, ms, by = eng.model.profile_read()
@@ -407,7 +454,7 @@ def main():
 
     # time to first audio of the streaming entry (BaseTTS.stream yields per segment, base_tts.py:1132-1190): one text alone,
     # call -> decoded, vocoded, post-processed, 16-bit PCM of the first segment on the host
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline_on:
         one = sentences(1, args.words, seed=4242)
         tt = []
         for _ in range(3):
@@ -437,7 +484,7 @@ def main():
         extra["ttfa_first_chunk_audio_s"] = round(first_s, 2)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, args, eng)
 
     if rank == 0:

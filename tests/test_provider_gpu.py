@@ -350,6 +350,24 @@ def test_bench_one_gpu_direct_and_under_the_launcher_agree():
     assert abs(direct["value"] - ranked["value"]) <= 0.03 * direct["value"], (direct["value"], ranked["value"])
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps, reports ms_per_step, measures nothing beyond the headline (no roofline,
+    no CPU baseline: those are --full), and --dump-outputs writes the waveforms of its last step - the same ones, bit for bit, in
+    a second run with the same flags."""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "tiny", "--batch", "4", "--ref-seconds", "1"]
+    got = []
+    for name in ("a", "b"):
+        r, line = _bench(common + ["--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, r.stdout[-1500:] + "\n" + r.stderr[-3000:]
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["roofline"] is None and line["cpu_baseline"] is None and "ttfa_ms_one_text" not in line["extra"]
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == [f"waveform_{i:04d}.npy" for i in range(4)], files
+        got.append([np.load(tmp_path / name / f) for f in files])
+    for x, y in zip(*got):
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+
+
 def test_pinned_ring_views_live_until_the_call_after_next():
     """dist.waveforms_to_host(copy=False) hands out views of a two-buffer pinned ring (bench.py reads a step's waveforms before the
     step after next): the views of one call survive the next call and equal the copying form's result."""

@@ -14,7 +14,7 @@ P=/tmp/prof_$TAG
 rm -rf "$P"
 
 echo "[1] kernel trace + stats of the default bench run"
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/a -- python3 $ROOT/bench.py --no-cpu-baseline > $OUT/a_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/a -- python3 $ROOT/bench.py --full --no-cpu-baseline > $OUT/a_bench.log 2>&1
 python3 $ROOT/tools/summarize_trace.py $P/a $OUT/a_by_grid.csv > /dev/null
 find $P/a -name "*kernel_stats.csv" -exec cp {} $OUT/a_kernel_stats_raw.csv \;
 grep -v "at::native\|rocclr\|Cijk_\|elementwise\|vectorized" $OUT/a_kernel_stats_raw.csv > $OUT/a_kernel_stats.csv
