@@ -81,6 +81,7 @@ def declare(lib: C.CDLL) -> None:
     lib.rt_profile_read_class.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.rt_debug_gemm.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, i32, i32]
     lib.rt_debug_attention.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp]
+    lib.rt_debug_attention_planes.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp]
     f32 = C.c_float
     lib.rt_debug_gemm_col.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.rt_debug_attention_fused.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]

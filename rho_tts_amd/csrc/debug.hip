@@ -141,6 +141,21 @@ int rt_debug_attention(rt_ctx* ctx, const float* d_q, int32_t M, int32_t heads, 
     return rc;
 }
 
+// hi + lo plane caches with a float32 output, launched as stack_forward launches the codec / encoder stacks' attention
+int rt_debug_attention_planes(rt_ctx* ctx, const float* d_q, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim, const int32_t* d_row_slot,
+                              const int32_t* d_row_pos, int32_t window, const void* d_k_hi, const void* d_k_lo, const void* d_v_hi, const void* d_v_lo,
+                              int32_t slots, int32_t max_pos, float* d_out_f32) {
+    if (!ctx || !d_q || !d_k_hi || !d_k_lo || !d_v_hi || !d_v_lo || !d_out_f32) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_attention_planes: null argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    KvCache kv;
+    kv.k = (bf16_t*)d_k_hi; kv.v = (bf16_t*)d_v_hi; kv.k_lo = (bf16_t*)d_k_lo; kv.v_lo = (bf16_t*)d_v_lo;
+    kv.layers = 1; kv.slots = slots; kv.kv_heads = kv_heads; kv.max_pos = max_pos; kv.head_dim = head_dim;
+    int rc = launch_attention(ctx, d_q, M, heads, kv_heads, head_dim, d_row_slot, d_row_pos, 0, window, kv, 0, nullptr, nullptr, 0, d_out_f32);
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return rc;
+}
+
 // The column-owner decode GEMM (k_gemm_col) on its own, launched exactly as model_stack.hip's col_gemm launches it (row blocks of
 // 64 / 32, the production sub-tile split unless one is forced).  Row-major operands at the ABI; the hook tiles / un-tiles.
 int rt_debug_gemm_col(rt_ctx* ctx, const void* d_a_bf16, int32_t M, int32_t K, const void* d_w_bf16, int32_t N, int32_t epi, int32_t split,
