@@ -105,7 +105,9 @@ RT_API int rt_debug_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_
  *   2400/2401 gate/up decode GEMM whose tile pairs are 1.5x the CUs: one pair per workgroup (1.5 rounds) / 1.5 pairs per workgroup (one round) |
  *   2600/2601 the codec decoder's k = 7 convs on the generic / the tap-unrolled instantiation of k_conv_win |
  *   2700/2701 the decode frame counter advanced by a launch of its own / by the last workgroup of the frame's talker-input launch |
- *   2800/2801 the predictor's two-position first pass: q/k norm + RoPE + append as a launch of its own in front of the attention / inside the fused attention
+ *   2800/2801 the predictor's two-position first pass: q/k norm + RoPE + append as a launch of its own in front of the attention / inside the fused attention |
+ *   2900/2901 rt_code2wav with / without the residual-stream store of every stage's third unit (no reader) and the waveform copy behind the last conv |
+ *   3000/3001 the codec decoder's 192-channel residual units as two launches / one fused launch (k = 7 with tap unrolling; 2100 switches both widths off)
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
 RT_API int rt_debug_tune(int32_t skinny_variant, int32_t skinny_waves_per_cu);

@@ -133,6 +133,8 @@ int rt_code2wav(rt_model* m, int32_t n_items, int32_t t_max, const int32_t* h_co
             if (j < 2) { e2.snake2_a = VEC(m, bn + ".u" + std::to_string(j + 1) + ".a1"); e2.snake2_ib = VEC(m, bn + ".u" + std::to_string(j + 1) + ".ib1"); }
             else if (i + 1 < c.n_upsample_rates) { e2.snake2_a = VEC(m, "codec.b" + std::to_string(i + 1) + ".sa"); e2.snake2_ib = VEC(m, "codec.b" + std::to_string(i + 1) + ".sib"); }
             else { e2.snake2_a = VEC(m, "codec.fin_a"); e2.snake2_ib = VEC(m, "codec.fin_ib"); }
+            // the last unit's residual stream has no reader: the next transposed conv / the last conv take the SnakeBeta planes only
+            if (j == 2 && g_c2w_lean) e2.out_f32 = nullptr;
             // NOTE: the fused form writes s1 (the NEXT unit's operand planes) while other workgroups still read s1 as THIS unit's
             // input window, so it needs a second pair of planes to write to: s1 and s2 swap roles from unit to unit
             if (conv_pair_fusable(a, PW(m, u + ".c1"), e, PW(m, u + ".c2"))) {
@@ -147,22 +149,28 @@ int rt_code2wav(rt_model* m, int32_t n_items, int32_t t_max, const int32_t* h_co
         s_in = s1;
         Tc = To;
     }
-    float* wav_tmp = nullptr;
-    RT_TRY(pool_arr(m, (size_t)B * Tc, &wav_tmp));
     {
         // last conv: channels -> 1, k = 7, causal, then clamp(-1, 1): the 7 x C taps of one output sample are contiguous
         // in the channels-last buffer, so it is the same implicit GEMM with a single output column
         const int cl = m->dec_ch.back();
-        GemmA a; a.ptr = s_in.hi; a.ptr_lo = s_in.lo; a.split = 1; a.M = (int64_t)B * Tc; a.Cin = cl; a.taps = 7; a.tap_stride = 1; a.tap_offset = -6;
-        a.rows_out = (int)Tc; a.rows_in = (int)Tc;
-        if (launch_final_conv_ok(cl) && g_final_conv) {
-            RT_TRY(launch_final_conv(ctx, s_in.hi, s_in.lo, B, (int)Tc, cl, VEC(m, "codec.fin_wv"), VEC(m, "codec.fin_b"), wav_tmp));
+        const bool own = launch_final_conv_ok(cl) && g_final_conv;
+        if (own && g_c2w_lean) {
+            // straight into the caller's rows
+            RT_TRY(launch_final_conv(ctx, s_in.hi, s_in.lo, B, (int)Tc, cl, VEC(m, "codec.fin_wv"), VEC(m, "codec.fin_b"), d_wav, wav_stride));
         } else {
-            GemmEpi e; e.bias = VEC(m, "codec.fin_b"); e.act = ACT_CLAMP1; e.out_f32 = wav_tmp; e.ldc = 1;
-            RT_TRY(launch_gemm(ctx, a, PW(m, "codec.fin_w"), e));
+            float* wav_tmp = nullptr;
+            RT_TRY(pool_arr(m, (size_t)B * Tc, &wav_tmp));
+            if (own) {
+                RT_TRY(launch_final_conv(ctx, s_in.hi, s_in.lo, B, (int)Tc, cl, VEC(m, "codec.fin_wv"), VEC(m, "codec.fin_b"), wav_tmp, Tc));
+            } else {
+                GemmA a; a.ptr = s_in.hi; a.ptr_lo = s_in.lo; a.split = 1; a.M = (int64_t)B * Tc; a.Cin = cl; a.taps = 7; a.tap_stride = 1; a.tap_offset = -6;
+                a.rows_out = (int)Tc; a.rows_in = (int)Tc;
+                GemmEpi e; e.bias = VEC(m, "codec.fin_b"); e.act = ACT_CLAMP1; e.out_f32 = wav_tmp; e.ldc = 1;
+                RT_TRY(launch_gemm(ctx, a, PW(m, "codec.fin_w"), e));
+            }
+            RT_HIP(ctx, hipMemcpy2DAsync(d_wav, (size_t)wav_stride * 4, wav_tmp, (size_t)Tc * 4, (size_t)Tc * 4, B, hipMemcpyDeviceToDevice, ctx->stream));
         }
     }
-    RT_HIP(ctx, hipMemcpy2DAsync(d_wav, (size_t)wav_stride * 4, wav_tmp, (size_t)Tc * 4, (size_t)Tc * 4, B, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < B; ++b) h_wav_len[b] = rt_wav_length(m, h_n_frames[b]);
     pool_release_all(m);

@@ -765,18 +765,30 @@ __global__ __launch_bounds__(256, 2) void k_gemm_mid(MidArgs g) {
 // (SQ_INSTS_VALU against SQ_INSTS_MFMA, profiles/r04_pmc_vocoder_sq.txt) showed 4.5-6 vector instructions per MFMA in these
 // kernels - copies, the zero select of the causal padding, LDS addressing - competing with the MFMAs for the SIMD's issue slots:
 // the matrix pipe sat at 0.3-0.5 while the waves waited to ISSUE (SQ_WAIT_INST_ANY 0.4-0.47 of their cycles), not for memory.
+//
+// FUSE with NTT = 6 (the 192-channel residual units): a wave again holds every output channel of its rows - 6 column tiles of one
+// 32-row tile, 128 rows per workgroup - so its four waves need the SAME 12 KiB of weight fragments per (tap, chunk).  Four waves
+// each fetching them would ask the CU's vector L1 for 48 KiB per 24 MFMAs a wave (64 B/clk: all the L1 has); here the workgroup
+// requests them once, 3 pieces a thread, a tap ahead, and the waves read them from a double-buffered LDS region (one barrier per
+// tap).  The intermediate planes are staged for the 1x1 conv in two 96-channel halves (its K = 192 in two runs of 6 k-tiles,
+// ascending), which keeps LDS at 72 KiB: two workgroups per CU.
 template <int WGM, int WGN, int MT, int NTT, bool FUSE = false, int TAPS = 0>
-__global__ __launch_bounds__(256, (WGM * MT * 32 > 128) ? 2 : 3) void k_conv_win(TiledArgs g) {
+__global__ __launch_bounds__(256, (WGM * MT * 32 > 128 || NTT > 3) ? 2 : 3) void k_conv_win(TiledArgs g) {
     static_assert(WGM * WGN == 4, "4 waves");
-    static_assert(!FUSE || (WGN == 1 && NTT == 3), "the fused 1x1 conv needs every output channel of a row in one wave");
+    static_assert(!FUSE || (WGN == 1 && (NTT == 3 || (NTT == 6 && MT == 1))), "the fused 1x1 conv needs every output channel of a row in one wave");
+    constexpr bool WLDS = FUSE && NTT == 6;               // weight fragments through LDS, once per workgroup
     constexpr int BMT = WGM * MT * 32;
     constexpr int WIN_ROWS = BMT + 64;
     constexpr int NP = (WIN_ROWS * 4 + 255) / 256;        // 16-B window pieces per thread and plane
     constexpr int BNT = WGN * NTT * 32;
     constexpr int PLANE = WIN_ROWS * 64;                  // bytes per plane and stage
-    constexpr int F_ROWB = NTT * 32 * 2 + 16;             // fused form: bytes per row of a wave's staged tile (96 bf16 + padding)
+    constexpr int F_ROWB = 96 * 2 + 16;                   // fused form: bytes per row of a wave's staged tile (96 bf16 + padding)
     constexpr int F_WAVE = 2 * 32 * F_ROWB;               // ... hi and lo planes of 32 rows
-    constexpr int LDS_BYTES = (FUSE && 4 * F_WAVE > 2 * 2 * PLANE) ? 4 * F_WAVE : 2 * 2 * PLANE;
+    constexpr int W_BUF = NTT * 2 * 1024;                 // WLDS: the fragments of one (tap, chunk), verbatim
+    constexpr int W_OFF = 2 * 2 * PLANE;                  // ... two such buffers behind the window stages
+    constexpr int NWP = NTT * 2 * 64 / 256;               // ... 16-B pieces per thread and buffer
+    constexpr int K_BYTES = 2 * 2 * PLANE + (WLDS ? 2 * W_BUF : 0);
+    constexpr int LDS_BYTES = (FUSE && 4 * F_WAVE > K_BYTES) ? 4 * F_WAVE : K_BYTES;
     __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WGN, wn = w % WGN;
@@ -866,6 +878,71 @@ __global__ __launch_bounds__(256, (WGM * MT * 32 > 128) ? 2 : 3) void k_conv_win
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
 
+    if constexpr (WLDS) {
+        // fragment f = 2 nt + kk of a (tap, chunk): wave w requests f = w, w + 4, w + 8 and every wave reads all twelve
+        unsigned w_off[NWP];
+#pragma unroll
+        for (int i = 0; i < NWP; ++i) {
+            const int f = w + 4 * i;
+            w_off[i] = (unsigned)((((f >> 1) * g.KT + (f & 1)) * 64 + lane) * 16);
+        }
+        auto load_w = [&](int tap, int cc, s8_t (&q)[NWP]) {
+            const int t_k0 = (tap * Cin + cc * 32) >> 4;
+#pragma unroll
+            for (int i = 0; i < NWP; ++i) q[i] = __builtin_bit_cast(s8_t, __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_off[i], t_k0 * 1024, 0));
+        };
+        auto store_w = [&](int wb, const s8_t (&q)[NWP]) {
+#pragma unroll
+            for (int i = 0; i < NWP; ++i) *reinterpret_cast<s8_t*>(lds + W_OFF + wb * W_BUF + (w + 4 * i) * 1024 + lane * 16) = q[i];
+        };
+        s8_t ra[NP], rl[NP], rw[NWP];
+        load_win(0, ra, rl);
+        load_w(0, 0, rw);
+        store_win(0, ra, rl);
+        store_w(0, rw);
+        __syncthreads();
+        int wb = 0;
+        for (int cc = 0; cc < n_cc; ++cc) {
+            const int buf = cc & 1;
+            const bool more = cc + 1 < n_cc;
+            if (more) load_win(cc + 1, ra, rl);
+#pragma unroll
+            for (int tap = 0; tap < (TAPS > 0 ? TAPS : taps); ++tap) {
+                const bool last = tap + 1 == taps;
+                // the next (tap, chunk)'s fragments, requested with no branch around them - behind the last tap of the last chunk that is
+                // k-tile Cin / 16, a valid one, staged and never read - so that every wait below is a counted one
+                load_w(last ? 0 : tap + 1, last ? cc + 1 : cc, rw);
+                __builtin_amdgcn_sched_barrier(0);       // (the scheduler sinks the three requests to the LDS stores at the tap's end: a round trip per tap in the open)
+                const int reach = (taps - 1 - tap) * stride;
+                s8_t fa[MT][2], fl[MT][2];
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    const int wrow = t_row[mt] >= reach ? (wm * MT + mt) * 32 + r + tap * stride : WIN_ROWS - 1;      // (the ZERO ROW, as below)
+#pragma unroll
+                    for (int kk = 0; kk < 2; ++kk) {
+                        fa[mt][kk] = *reinterpret_cast<const s8_t*>(lds + buf * 2 * PLANE + lds_a_off(wrow, kk * 2 + h));
+                        fl[mt][kk] = *reinterpret_cast<const s8_t*>(lds + buf * 2 * PLANE + PLANE + lds_a_off(wrow, kk * 2 + h));
+                    }
+                }
+                const unsigned char* wl = lds + W_OFF + wb * W_BUF + lane * 16;
+#pragma unroll
+                for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+                    for (int nt = 0; nt < NTT; ++nt) {
+                        const s8_t fb = *reinterpret_cast<const s8_t*>(wl + (nt * 2 + kk) * 1024);
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) {
+                            acc[mt][nt] = mfma32(fa[mt][kk], fb, acc[mt][nt]);
+                            acc[mt][nt] = mfma32(fl[mt][kk], fb, acc[mt][nt]);
+                        }
+                    }
+                store_w(wb ^ 1, rw);
+                if (last && more) store_win(buf ^ 1, ra, rl);
+                __syncthreads();
+                wb ^= 1;
+            }
+        }
+    } else {
     s8_t ra[NP], rl[NP], rb[NTT][2], rb_next[NTT][2];
     load_win(0, ra, rl);
     load_b(0, 0, rb);
@@ -913,6 +990,7 @@ __global__ __launch_bounds__(256, (WGM * MT * 32 > 128) ? 2 : 3) void k_conv_win
         if (more) store_win(buf ^ 1, ra, rl);
         __syncthreads();
     }
+    }
     if constexpr (!FUSE) {
         tile_epilogue<MT, NTT>(g, acc, m0, n0, wm, wn, r, h);
     } else {
@@ -946,39 +1024,44 @@ __global__ __launch_bounds__(256, (WGM * MT * 32 > 128) ? 2 : 3) void k_conv_win
         for (int mt = 0; mt < MT; ++mt) {
             s8_t b2[2][NTT];
             load_b2(0, b2[0]);
-            // 1. this conv's epilogue (bias, SnakeBeta) into LDS as hi / lo planes, [row][channel]
-#pragma unroll
-            for (int nt = 0; nt < NTT; ++nt) {
-                const int n = nt * 32 + r;
-                const float bias = f_bias[nt], sa = f_sa[nt], sib = f_sib[nt];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    float v = acc[mt][nt][i] + bias;
-                    const float sn = __sinf(v * sa);
-                    v = v + sib * sn * sn;
-                    const bf16_t hi = f32_to_bf16(v);
-                    const bf16_t lo = f32_to_bf16(v - bf16_to_f32(hi));
-                    const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-                    *reinterpret_cast<bf16_t*>(my + row * F_ROWB + n * 2) = hi;
-                    *reinterpret_cast<bf16_t*>(my + 32 * F_ROWB + row * F_ROWB + n * 2) = lo;
-                }
-            }
-            // (the same wave reads what it wrote: a wave's LDS operations complete in order)
-            // 2. the 1x1 conv: [32 rows][96] x W2^T, hi + lo planes against each weight fragment
             f16_t acc2[1][NTT];
 #pragma unroll
             for (int nt = 0; nt < NTT; ++nt)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc2[0][nt][i] = 0.f;
+            // (NTT = 6: 96 channels of the intermediate at a time; the 1x1 conv's K sum runs through both halves in ascending order)
 #pragma unroll
-            for (int k2 = 0; k2 < NTT * 2; ++k2) {
-                if (k2 + 1 < NTT * 2) load_b2(k2 + 1, b2[(k2 + 1) & 1]);          // the next k-step's fragments fly during this step's MFMAs
-                const s8_t a_hi = *reinterpret_cast<const s8_t*>(my + r * F_ROWB + (k2 * 16 + h * 8) * 2);
-                const s8_t a_lo = *reinterpret_cast<const s8_t*>(my + 32 * F_ROWB + r * F_ROWB + (k2 * 16 + h * 8) * 2);
+            for (int hf = 0; hf < NTT / 3; ++hf) {
+                // 1. this conv's epilogue (bias, SnakeBeta) into LDS as hi / lo planes, [row][channel]
 #pragma unroll
-                for (int nt = 0; nt < NTT; ++nt) {
-                    acc2[0][nt] = mfma32(a_hi, b2[k2 & 1][nt], acc2[0][nt]);
-                    acc2[0][nt] = mfma32(a_lo, b2[k2 & 1][nt], acc2[0][nt]);
+                for (int j = 0; j < 3; ++j) {
+                    const int nt = hf * 3 + j, n = j * 32 + r;
+                    const float bias = f_bias[nt], sa = f_sa[nt], sib = f_sib[nt];
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        float v = acc[mt][nt][i] + bias;
+                        const float sn = __sinf(v * sa);
+                        v = v + sib * sn * sn;
+                        const bf16_t hi = f32_to_bf16(v);
+                        const bf16_t lo = f32_to_bf16(v - bf16_to_f32(hi));
+                        const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+                        *reinterpret_cast<bf16_t*>(my + row * F_ROWB + n * 2) = hi;
+                        *reinterpret_cast<bf16_t*>(my + 32 * F_ROWB + row * F_ROWB + n * 2) = lo;
+                    }
+                }
+                // (the same wave reads what it wrote: a wave's LDS operations complete in order)
+                // 2. the 1x1 conv: [32 rows][96] x W2^T, hi + lo planes against each weight fragment
+#pragma unroll
+                for (int kl = 0; kl < 6; ++kl) {
+                    const int k2 = hf * 6 + kl;
+                    if (k2 + 1 < NTT * 2) load_b2(k2 + 1, b2[(k2 + 1) & 1]);          // the next k-step's fragments fly during this step's MFMAs
+                    const s8_t a_hi = *reinterpret_cast<const s8_t*>(my + r * F_ROWB + (kl * 16 + h * 8) * 2);
+                    const s8_t a_lo = *reinterpret_cast<const s8_t*>(my + 32 * F_ROWB + r * F_ROWB + (kl * 16 + h * 8) * 2);
+#pragma unroll
+                    for (int nt = 0; nt < NTT; ++nt) {
+                        acc2[0][nt] = mfma32(a_hi, b2[k2 & 1][nt], acc2[0][nt]);
+                        acc2[0][nt] = mfma32(a_lo, b2[k2 & 1][nt], acc2[0][nt]);
+                    }
                 }
             }
             // 3. the 1x1 conv's epilogue on this wave's 32 rows
@@ -1126,11 +1209,14 @@ int launch_gemm_mid(rt_ctx* ctx, const bf16_t* A, int M, const PackedW& w, float
 }
 
 rt_knob g_fuse_conv{1};            // 1: a 96-channel k>1 conv and the 1x1 conv behind its activation run as one launch (launch_conv_pair)
+rt_knob g_fuse_conv192{1};         // 1: so do the 192-channel pairs, weight fragments staged through LDS (rt_debug_tune 3000 / 3001)
+rt_knob g_c2w_lean{1};             // 1: rt_code2wav drops the third unit's unread residual-stream store and the waveform copy (rt_debug_tune 2900 / 2901)
 
 // a k > 1 conv with SnakeBeta whose hi / lo output planes feed only the 1x1 conv (w2, e2): both in one launch when the first
-// conv's workgroup tile holds every output channel (96 channels, the LDS-window kernel) - else two launches through the planes
+// conv's workgroup tile holds every output channel (96 or 192 channels, the LDS-window kernel) - else two launches through the planes
 bool conv_pair_fusable(const GemmA& a, const PackedW& w, const GemmEpi& e, const PackedW& w2) {
-    return g_fuse_conv && g_conv_win && g_tile96 && w.N == 96 && w2.N == 96 && w2.K == 96 && w2.Kp == 96 && e.act == ACT_SNAKE && a.split && !a.is_f32 && a.ptr_lo && a.taps >= 2 &&
+    const bool c96 = w.N == 96, c192 = w.N == 192 && g_fuse_conv192 && w.Np == 192 && a.taps == 7 && g_conv_unroll;   // (192: the tap-unrolled kernel only - the generic tap loop spills there)
+    return g_fuse_conv && g_conv_win && g_tile96 && (c96 || c192) && w2.N == w.N && w2.K == w.N && w2.Kp == w.N && w2.Np == w.N && e.act == ACT_SNAKE && a.split && !a.is_f32 && a.ptr_lo && a.taps >= 2 &&
            a.Cin % 32 == 0 && a.rows_out > 0 && a.rows_in == a.rows_out && a.tap_offset == -(a.taps - 1) * a.tap_stride && (a.taps - 1) * a.tap_stride <= 63 &&
            a.M % a.rows_out == 0;
 }
@@ -1166,11 +1252,20 @@ int launch_gemm(rt_ctx* ctx, const GemmA& a, const PackedW& w, const GemmEpi& e,
         ((e.out_hi || e.out2_hi) && e.split_k > 1))
         return rt_fail(ctx, RT_ERR_INVALID, "gemm: incomplete hi/lo plane output");
     if (w2) {           // fused conv pair: only the form conv_pair_fusable() describes
-        if (!e2 || !conv_win || !narrow || ny != 1 || w.N != 96 || w2->N != 96 || w2->K != 96 || e.act != ACT_SNAKE || !e.snake_a || !e.snake_ib ||
-            e2->split_k != 1 || e2->ldc < 96)
-            return rt_fail(ctx, RT_ERR_INVALID, "gemm: this conv pair cannot be fused (96 channels, k > 1 conv with SnakeBeta, then a 96 x 96 1x1 conv)");
+        const bool wide = w.N == 192;
+        if (!e2 || !conv_win || !narrow || (!wide && ny != 1) || (w.N != 96 && !wide) || w.Np != w.N || w2->N != w.N || w2->K != w.N || w2->Np != w.N || w2->Kp != w.N ||
+            e.act != ACT_SNAKE || !e.snake_a || !e.snake_ib || e2->split_k != 1 || e2->ldc < w.N)
+            return rt_fail(ctx, RT_ERR_INVALID, "gemm: this conv pair cannot be fused (96 or 192 channels, k > 1 conv with SnakeBeta, then a 1x1 conv of the same width)");
         g.Wp2 = w2->data; g.NT2 = w2->Np / 32; g.KT2 = w2->Kp / 16; g.N2 = w2->N; g.e2 = *e2;
         const bool t7f = a.taps == 7 && g_conv_unroll;
+        if (wide) {         // one 128-row workgroup tile holds all 192 channels
+            g.xcd_order = 0;
+            const dim3 grid_w((unsigned)((a.M + 127) / 128), 1, 1);
+            if (!t7f) return rt_fail(ctx, RT_ERR_INVALID, "gemm: the fused 192-channel conv pair exists for k = 7 with tap unrolling only");
+            hipLaunchKernelGGL((k_conv_win<4, 1, 1, 6, true, 7>), grid_w, dim3(256), 0, ctx->stream, g);
+            RT_HIP(ctx, hipGetLastError());
+            return RT_OK;
+        }
         if (tall && t7f) hipLaunchKernelGGL((k_conv_win<4, 1, 2, 3, true, 7>), grid, dim3(256), 0, ctx->stream, g);
         else if (tall) hipLaunchKernelGGL((k_conv_win<4, 1, 2, 3, true>), grid, dim3(256), 0, ctx->stream, g);
         else hipLaunchKernelGGL((k_conv_win<4, 1, 1, 3, true>), grid, dim3(256), 0, ctx->stream, g);

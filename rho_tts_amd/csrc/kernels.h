@@ -73,6 +73,8 @@ int launch_pack_weight16(rt_ctx* ctx, const bf16_t* d_src, int N, int K, bf16_t*
 int launch_gemm(rt_ctx* ctx, const GemmA& a, const PackedW& w, const GemmEpi& e, const PackedW* w2 = nullptr, const GemmEpi* e2 = nullptr);
 bool conv_pair_fusable(const GemmA& a, const PackedW& w, const GemmEpi& e, const PackedW& w2);
 extern rt_knob g_fuse_conv;
+extern rt_knob g_fuse_conv192;         // 1: the 192-channel conv pairs fuse as well (weights staged through LDS)
+extern rt_knob g_c2w_lean;             // 1: rt_code2wav skips the residual-stream store nobody reads and the last conv writes the caller's buffer
 // prompt-prefill GEMM (65..1024 rows): out[M][N] f32 = A[M][K] bf16 . W^T, whole K per 64 x 64 tile, final sums (no slabs)
 extern rt_knob g_prefill_mid;
 bool gemm_mid_ok(int M, const PackedW& w);
@@ -302,7 +304,8 @@ int launch_code_embed_mean(rt_ctx* ctx, const bf16_t* table, int codebook, int Q
 
 // last conv of the codec decoder (C -> 1, k = 7, causal) + clamp on hi / lo operand planes [B][T][C]; w = [7][C] f32
 bool launch_final_conv_ok(int C);
-int launch_final_conv(rt_ctx* ctx, const bf16_t* hi, const bf16_t* lo, int B, int T, int C, const float* w, const float* bias, float* wav);
+int launch_final_conv(rt_ctx* ctx, const bf16_t* hi, const bf16_t* lo, int B, int T, int C, const float* w, const float* bias, float* wav,
+                      int64_t wav_stride);   // item b's samples at wav + b * wav_stride
 int launch_f32_to_bf16(rt_ctx* ctx, const float* x, int64_t n, bf16_t* out);
 
 // ------------------------------------------------------------------------------ conditioning front-end (encoder.hip)

@@ -453,7 +453,8 @@ __global__ __launch_bounds__(256) void k_code_embed_mean(const bf16_t* __restric
 // consecutive samples of one item: the (128 + 6) x C input window is summed (hi + lo, exact in f32) into LDS once with
 // coalesced 16-B loads, then every thread does half a sample's 7 x C dot product out of LDS (row stride C + 1).
 __global__ __launch_bounds__(256) void k_final_conv(const bf16_t* __restrict__ hi, const bf16_t* __restrict__ lo, int T, int C,
-                                                    const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ wav) {
+                                                    const float* __restrict__ w, const float* __restrict__ bias, float* __restrict__ wav,
+                                                    int64_t wav_stride) {
     extern __shared__ float sm[];
     const int stride = C + 1;
     float* tile = sm;
@@ -505,7 +506,7 @@ __global__ __launch_bounds__(256) void k_final_conv(const bf16_t* __restrict__ h
     }
     acc += __shfl_xor(acc, 1, 64);
     const int t = t0 + s;
-    if (half == 0 && t < T) wav[(int64_t)b * T + t] = fminf(1.f, fmaxf(-1.f, acc + bias[0]));
+    if (half == 0 && t < T) wav[(int64_t)b * wav_stride + t] = fminf(1.f, fmaxf(-1.f, acc + bias[0]));
 }
 
 __global__ void k_f32_to_bf16(const float* __restrict__ x, int64_t n, bf16_t* __restrict__ out) {
@@ -640,11 +641,13 @@ int launch_code_embed_mean(rt_ctx* ctx, const bf16_t* table, int codebook, int Q
 
 bool launch_final_conv_ok(int C) { return C % 16 == 0 && (size_t)(134 * (C + 1) + 7 * C) * 4 <= 64 * 1024; }
 
-int launch_final_conv(rt_ctx* ctx, const bf16_t* hi, const bf16_t* lo, int B, int T, int C, const float* w, const float* bias, float* wav) {
+int launch_final_conv(rt_ctx* ctx, const bf16_t* hi, const bf16_t* lo, int B, int T, int C, const float* w, const float* bias, float* wav,
+                      int64_t wav_stride) {
     if (B <= 0 || T <= 0) return RT_OK;
+    if (wav_stride < T) return rt_fail(ctx, RT_ERR_INVALID, "final conv: wav_stride %lld < %d samples", (long long)wav_stride, T);
     if (!launch_final_conv_ok(C)) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "final conv: %d channels do not fit the LDS window", C);
     const size_t lds = (size_t)(134 * (C + 1) + 7 * C) * 4;
-    hipLaunchKernelGGL(k_final_conv, dim3((T + 127) / 128, B), dim3(256), lds, ctx->stream, hi, lo, T, C, w, bias, wav);
+    hipLaunchKernelGGL(k_final_conv, dim3((T + 127) / 128, B), dim3(256), lds, ctx->stream, hi, lo, T, C, w, bias, wav, wav_stride);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }

@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Codec decoder A/B on one box: wall time per call under each set of rt_debug_tune codes given as arguments (comma-separated sets),
 and whether every set produces bit-identical waveforms (the switches compared here only change WHEN operands are requested).
-usage: python tools/ab_vocoder.py 2600 2601 2602"""
+usage: python tools/ab_vocoder.py 2600 2601 2602
+Codes of the codec decoder: 600/601 128x96 tiles, 1000/1001 XCD tile order, 1100/1101 last conv as GEMM / own kernel, 1200/1201 LDS
+window, 1800/1801 256-row tiles, 2100/2101 conv pairs as two launches / fused (96 channels), 2600/2601 generic / tap-unrolled k = 7,
+2900/2901 with / without the third unit's unread residual-stream store and the waveform copy, 3000/3001 192-channel conv pairs as
+two launches / fused.  Round 5's A/B: python tools/ab_vocoder.py 2900,3000 2901,3000 2900,3001 2901,3001"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
