@@ -86,31 +86,42 @@ RT_API int rt_debug_attention_prefill(rt_ctx* ctx, const float* d_q, int32_t M, 
 RT_API int rt_debug_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_t V, const rt_sampling* sp, uint64_t seed,
                            int32_t frame, int32_t group, int32_t suppress_from, int32_t allow_token, uint8_t* d_seen, int32_t* d_out);
 
-/* A/B switches for measurements and tests (process-wide; the defaults are the fast path).  First argument:
- *   0..2 legacy skinny-GEMM variant (second argument: its waves per CU) | 100/101 legacy 9-launch / column-owner decode |
- *   200/201 eager / hipGraph frames | 300/301 predictor weights cacheable / non-temporal | 40n n decode lanes |
- *   500 automatic, 501/502/504 forced sub-tile split of narrow decode GEMMs | 600/601 128x96 codec tiles off/on |
- *   700/701 32-row / 64-row decode GEMM launches | 800/801 separate / fused sampler + next-input embedding |
- *   90n prefill split-K target of n workgroups per CU | 1000/1001 XCD-aware tile order of the tiled GEMM off/on |
- *   1300/1301 stream sync after every decode frame part off/on (bounds the dispatches in flight under rocprofv3 --pmc) |
- *   14nn end-of-sequence flags fetched every nn frames (default 8; 1401 = a copy + wait per frame) |
- *   1500/1501/1502 shared-prefix decode attention on the vector unit / on the matrix cores with four rows / one row per workgroup | 1600/1601 quarter-tile split off/on |
- *   17nn queued items (rt_generate with n_items > max_batch) take over finished rows every nn frames (default 4) |
- *   20nn batches of up to nn rows (default 64) decode on the column-owner path, larger ones on the legacy split-K path |
- *   1900/1901/1902/1903 prompt-prefill GEMMs on the split-K tiled kernel / on k_gemm_mid (automatic, 64 x 64, 128 x 128 tiles) |
- *   1800/1801/1802 narrow-channel (96 / 192) k>1 convs on 128-row tiles / 256-row tiles for long inputs / 256-row tiles always |
- *   2100/2101 the codec decoder's 96-channel residual units as two launches (k = 7 conv, 1x1 conv) / one fused launch |
- *   2200/2201 prompt-prefill attention behind a shared voice prefix on the vector unit / on the matrix cores |
- *   2300/2301 decode GEMMs of <= 16 rows on the 32-row / the two-workgroups-per-CU 16-row instantiation |
- *   2400/2401 gate/up decode GEMM whose tile pairs are 1.5x the CUs: one pair per workgroup (1.5 rounds) / 1.5 pairs per workgroup (one round) |
- *   2600/2601 the codec decoder's k = 7 convs on the generic / the tap-unrolled instantiation of k_conv_win |
- *   2700/2701 the decode frame counter advanced by a launch of its own / by the last workgroup of the frame's talker-input launch |
- *   2800/2801 the predictor's two-position first pass: q/k norm + RoPE + append as a launch of its own in front of the attention / inside the fused attention |
- *   2900/2901 rt_code2wav with / without the residual-stream store of every stage's third unit (no reader) and the waveform copy behind the last conv |
+/* A/B switches for measurements and tests (process-wide; the defaults are the fast path).  One row per switch, as in the table
+ * they are generated from (rho_tts_amd/csrc/knobs.h: defaults, accepted ranges, measurement notes).  A code that no row accepts is
+ * refused with RT_ERR_INVALID and changes nothing.  `code`:
+ *   0..2 legacy skinny-GEMM variant (`arg` > 0: its waves per CU; `arg` is ignored by every other code)
+ *   100/101 legacy 9-launch / column-owner decode
+ *   200/201 eager / hipGraph frames
+ *   300/301 predictor weights cacheable / non-temporal
+ *   400 + n: n decode lanes (n = 1..8)
+ *   500 automatic, 501/502/504 forced sub-tile split of narrow decode GEMMs
+ *   600/601 128x96 codec tiles off/on
+ *   700/701 32-row / 64-row decode GEMM launches
+ *   800/801 separate / fused sampler + next-input embedding
+ *   900 + n: prefill split-K target of n workgroups per CU (n = 0..99, default 3)
+ *   1000/1001 XCD-aware tile order of the tiled GEMM off/on
+ *   1100/1101 the codec decoder's last conv as a one-column GEMM / in its own kernel
+ *   1200/1201 k>1 convs on operand planes on the per-tap kernel / with their input window in LDS
+ *   1300/1301 stream sync after every decode frame part off/on (bounds the dispatches in flight under rocprofv3 --pmc)
+ *   1400 + n: end-of-sequence flags fetched every n frames (n = 1..99, default 8; 1401 = a copy + wait per frame)
+ *   1500/1501/1502 shared-prefix decode attention on the vector unit / on the matrix cores with four rows / one row per workgroup
+ *   1600/1601 quarter-tile split off/on
+ *   1700 + n: queued items (rt_generate with n_items > max_batch) take over finished rows every n frames (n = 1..99, default 4)
+ *   1800/1801/1802 narrow-channel (96 / 192) k>1 convs on 128-row tiles / 256-row tiles for long inputs / 256-row tiles always
+ *   1900/1901/1902/1903 prompt-prefill GEMMs on the split-K tiled kernel / on k_gemm_mid (automatic, 64 x 64, 128 x 128 tiles)
+ *   2000 + n: batches of up to n rows (n = 1..64, default 64) decode on the column-owner path, larger ones on the legacy split-K path
+ *   2100/2101 the codec decoder's 96-channel residual units as two launches (k = 7 conv, 1x1 conv) / one fused launch
+ *   2200/2201 prompt-prefill attention behind a shared voice prefix on the vector unit / on the matrix cores
+ *   2300/2301 decode GEMMs of <= 16 rows on the 32-row / the two-workgroups-per-CU 16-row instantiation
+ *   2400/2401 gate/up decode GEMM whose tile pairs are 1.5x the CUs: one pair per workgroup (1.5 rounds) / 1.5 pairs per workgroup (one round)
+ *   2600/2601 the codec decoder's k = 7 convs on the generic / the tap-unrolled instantiation of k_conv_win
+ *   2700/2701 the decode frame counter advanced by a launch of its own / by the last workgroup of the frame's talker-input launch
+ *   2800/2801 the predictor's two-position first pass: q/k norm + RoPE + append as a launch of its own in front of the attention / inside the fused attention
+ *   2900/2901 rt_code2wav with / without the residual-stream store of every stage's third unit (no reader) and the waveform copy behind the last conv
  *   3000/3001 the codec decoder's 192-channel residual units as two launches / one fused launch (k = 7 with tap unrolling; 2100 switches both widths off)
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
-RT_API int rt_debug_tune(int32_t skinny_variant, int32_t skinny_waves_per_cu);
+RT_API int rt_debug_tune(int32_t code, int32_t arg);
 RT_API int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_norm, int32_t epi, int32_t n_mats, int32_t iters,
                              double* avg_us, int64_t* stamps8);
 RT_API int rt_bench_launch(rt_ctx* ctx, int32_t grid_wgs, int32_t n, int32_t use_graph, int32_t reps, double* us_per_launch);

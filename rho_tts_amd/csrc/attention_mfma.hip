@@ -445,10 +445,12 @@ int launch_attention_prefix_mfma(rt_ctx* ctx, const float* qkv, int M, int heads
 }
 
 // prompt rows behind a shared prefix (see the kernel's header): the same preconditions as the decode form but q comes prepared
-rt_knob g_prefill_attn_mfma{1};
-bool attention_prefill_mfma_ok(int heads, int kv_heads, int head_dim, int window, const KvCache& kv) {
-    return g_prefill_attn_mfma && head_dim == D && kv.head_dim == D && heads == REP * kv_heads && window <= 0 && !kv.k_lo && kv.prefix_slot >= 0 &&
+bool attention_prefill_mfma_shape_ok(int heads, int kv_heads, int head_dim, int window, const KvCache& kv) {
+    return head_dim == D && kv.head_dim == D && heads == REP * kv_heads && window <= 0 && !kv.k_lo && kv.prefix_slot >= 0 &&
            kv.vt_prefix && kv.kt_prefix && kv.prefix_len >= 64 && kv.tiles_len == kv.prefix_len && (kv.prefix_len + 31) / 32 * 4096 <= kv.vt_stride;
+}
+bool attention_prefill_mfma_ok(int heads, int kv_heads, int head_dim, int window, const KvCache& kv) {
+    return g_prefill_attn_mfma && attention_prefill_mfma_shape_ok(heads, kv_heads, head_dim, window, kv);
 }
 int launch_attention_prefill_mfma(rt_ctx* ctx, const float* q, int M, int heads, int kv_heads, const int32_t* row_slot, const int32_t* row_pos, int pos_add,
                                   const KvCache& kv, int layer, bf16_t* out) {
@@ -467,9 +469,12 @@ int launch_attention_prefill_mfma(rt_ctx* ctx, const float* q, int M, int heads,
 // by layer, right after k_qkv_post has written the layer's K / V rows, their fragment-tiled copies are made - the copies every later
 // prompt prefill reads anyway - and the attention of the layer runs on them: for a workgroup's 8 rows the keys in front of its
 // first row go through the matrix cores, the <= 8 keys from there on through the vector part.
-bool attention_block_prefix_ok(int M, int heads, int kv_heads, int head_dim, int window, const KvCache& kv) {
-    return g_prefill_attn_mfma && head_dim == D && kv.head_dim == D && heads == REP * kv_heads && window <= 0 && !kv.k_lo && kv.vt_prefix && kv.kt_prefix &&
+bool attention_block_prefix_shape_ok(int M, int heads, int kv_heads, int head_dim, int window, const KvCache& kv) {
+    return head_dim == D && kv.head_dim == D && heads == REP * kv_heads && window <= 0 && !kv.k_lo && kv.vt_prefix && kv.kt_prefix &&
            kv.prefix_slot_alloc >= 0 && M >= 64 && (M + 31) / 32 * 4096 <= kv.vt_stride;
+}
+bool attention_block_prefix_ok(int M, int heads, int kv_heads, int head_dim, int window, const KvCache& kv) {
+    return g_prefill_attn_mfma && attention_block_prefix_shape_ok(M, heads, kv_heads, head_dim, window, kv);
 }
 int launch_attention_block_prefix(rt_ctx* ctx, const float* q, int M, int heads, int kv_heads, const int32_t* row_slot, const int32_t* row_pos,
                                   KvCache& kv, int layer, bf16_t* out) {

@@ -33,7 +33,7 @@ struct rt_ctx {
 // SHARED for its whole duration (CtxLock, together with its context's mutex); rt_debug_tune takes it EXCLUSIVELY - so it waits
 // until no call is executing on any context and no call can see a half-changed plan - and refuses while a resumable generation
 // (rt_generate_begin .. rt_generate_end) is in flight on any model (g_runs_in_flight).  The switches themselves are atomics
-// (kernels.h): read relaxed on the launch paths, written only under the exclusive lock.
+// (knobs.h, the one table of them): read on the launch paths, written by rt_debug_tune alone, under the exclusive lock.
 typedef std::atomic<int> rt_knob;
 extern std::shared_mutex g_tune_mu;
 extern std::atomic<int> g_runs_in_flight;

@@ -73,6 +73,20 @@ __global__ void k_untile_rows(const T* __restrict__ src, int M, int K, int row_o
 }
 }  // namespace
 
+// The launch-plan switches: defined here, from the table in knobs.h, next to the one function that writes them.
+#define RT_KNOB_DEFINE(base, name, def, lo, hi, doc) rt_knob name{def};
+RT_KNOBS(RT_KNOB_DEFINE)
+RT_KNOB_ARG(RT_KNOB_DEFINE)
+#undef RT_KNOB_DEFINE
+std::atomic<int> g_tune_epoch{0};
+namespace {
+struct KnobRow { int base, lo, hi; rt_knob* knob; };
+#define RT_KNOB_ROW(base, name, def, lo, hi, doc) {base, lo, hi, &name},
+const KnobRow kKnobs[] = {RT_KNOBS(RT_KNOB_ROW)};
+const KnobRow kKnobArg[] = {RT_KNOB_ARG(RT_KNOB_ROW)};       // set by the second argument of the codes of the row with its base
+#undef RT_KNOB_ROW
+}  // namespace
+
 extern "C" {
 
 int rt_debug_gemm(rt_ctx* ctx, const void* d_a, int32_t a_is_f32, int64_t M, int32_t cin, int32_t taps, int32_t tap_stride,
@@ -282,19 +296,17 @@ int rt_debug_attention_prefill(rt_ctx* ctx, const float* d_q, int32_t M, int32_t
     kv.k = (bf16_t*)d_k; kv.v = (bf16_t*)d_v; kv.layers = 1; kv.slots = slots; kv.kv_heads = kv_heads; kv.max_pos = max_pos; kv.head_dim = head_dim;
     kv.prefix_slot = prefix_slot; kv.prefix_len = prefix_len;
     bf16_t* vt = nullptr;
-    const int saved = g_prefill_attn_mfma;
-    g_prefill_attn_mfma = mode ? 1 : 0;
-    if (mode) {
-        if (head_dim != 128) { g_prefill_attn_mfma = saved; return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_debug_attention_prefill: the matrix-core form needs head_dim 128"); }
+    if (mode) {             // (mode 0 builds no tiles: launch_attention cannot take the matrix-core form, whatever g_prefill_attn_mfma says)
+        if (head_dim != 128) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_debug_attention_prefill: the matrix-core form needs head_dim 128");
         kv.vt_stride = (prefix_len + 31) / 32 * 4096;
         kv.prefix_slot_alloc = prefix_slot;
         RT_HIP(ctx, hipMalloc((void**)&vt, (size_t)2 * kv_heads * kv.vt_stride * 2));
         kv.kt_prefix = vt;
         kv.vt_prefix = vt + (size_t)kv_heads * kv.vt_stride;
         const int rt = launch_transpose_prefix_v(ctx, kv, prefix_len);
-        if (rt) { (void)hipFree(vt); g_prefill_attn_mfma = saved; return rt; }
-        if (!attention_prefill_mfma_ok(heads, kv_heads, head_dim, 0, kv)) {
-            (void)hipFree(vt); g_prefill_attn_mfma = saved;
+        if (rt) { (void)hipFree(vt); return rt; }
+        if (!attention_prefill_mfma_shape_ok(heads, kv_heads, head_dim, 0, kv)) {
+            (void)hipFree(vt);
             return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_debug_attention_prefill: shape not served by the matrix-core form");
         }
     }
@@ -304,17 +316,18 @@ int rt_debug_attention_prefill(rt_ctx* ctx, const float* d_q, int32_t M, int32_t
         kv.vt_stride = std::max(kv.vt_stride, (M + 31) / 32 * 4096);
         if (vt) { (void)hipFree(vt); vt = nullptr; }
         hipError_t me = hipMalloc((void**)&vt, (size_t)2 * kv_heads * kv.vt_stride * 2);
-        if (me != hipSuccess) { g_prefill_attn_mfma = saved; return rt_fail(ctx, rt_hip_status(me), "rt_debug_attention_prefill: out of memory"); }
+        if (me != hipSuccess) return rt_fail(ctx, rt_hip_status(me), "rt_debug_attention_prefill: out of memory");
         kv.kt_prefix = vt;
         kv.vt_prefix = vt + (size_t)kv_heads * kv.vt_stride;
-        rc = attention_block_prefix_ok(M, heads, kv_heads, head_dim, 0, kv)
+        rc = attention_block_prefix_shape_ok(M, heads, kv_heads, head_dim, 0, kv)
                  ? launch_attention_block_prefix(ctx, d_q, M, heads, kv_heads, d_row_slot, d_row_pos, kv, 0, (bf16_t*)d_out_bf16)
                  : rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_debug_attention_prefill: shape not served by the block-prefix form");
+    } else if (mode) {
+        rc = launch_attention_prefill_mfma(ctx, d_q, M, heads, kv_heads, d_row_slot, d_row_pos, 0, kv, 0, (bf16_t*)d_out_bf16);
     } else {
         rc = launch_attention(ctx, d_q, M, heads, kv_heads, head_dim, d_row_slot, d_row_pos, 0, 0, kv, 0, (bf16_t*)d_out_bf16);
     }
     const hipError_t se = hipStreamSynchronize(ctx->stream);
-    g_prefill_attn_mfma = saved;
     if (vt) (void)hipFree(vt);
     RT_HIP(ctx, se);
     return rc;
@@ -340,43 +353,19 @@ int rt_debug_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_t V, co
     return rc;
 }
 
-int rt_debug_tune(int32_t skinny_variant, int32_t skinny_waves_per_cu) {
+int rt_debug_tune(int32_t code, int32_t arg) {
     // exclusive: waits until no call is executing on any context (CtxLock holds this lock shared), and a resumable generation in
     // flight keeps the plan it began with - the switch is refused rather than applied under it
     std::unique_lock<std::shared_mutex> all(g_tune_mu);
     if (g_runs_in_flight.load() > 0) return RT_ERR_STATE;
-    if (skinny_variant >= 3000) { g_fuse_conv192 = skinny_variant - 3000; return RT_OK; }           // 3000/3001: the 192-channel conv pairs of the codec decoder as two launches / one
-    if (skinny_variant >= 2900) { g_c2w_lean = skinny_variant - 2900; return RT_OK; }               // 2900/2901: codec decoder with / without the unread residual-stream store and the waveform copy
-    if (skinny_variant >= 2800) { g_pair_attn = skinny_variant - 2800; return RT_OK; }              // 2800/2801: the predictor's two-position first pass with k_qkv_post + attention / on the fused attention
-    if (skinny_variant >= 2700) { g_frame_inc_fold = skinny_variant - 2700; return RT_OK; }         // 2700/2701: frame += 1 as a launch of its own / by the last workgroup of the talker-input launch
-    if (skinny_variant >= 2600) { g_conv_unroll = skinny_variant - 2600; return RT_OK; }            // 2600/2601: k = 7 convs on the generic / the tap-unrolled k_conv_win
-    if (skinny_variant >= 2400) { g_col_silu_x = skinny_variant - 2400; return RT_OK; }            // 2400/2401: gate/up decode GEMM as pairs in 1.5 rounds / as one round of 1.5-pair workgroups
-    if (skinny_variant >= 2300) { g_col_rows16 = skinny_variant - 2300; return RT_OK; }           // 2300/2301: <= 16-row decode GEMMs on the 32-row / the 2-workgroups-per-CU 16-row instantiation
-    if (skinny_variant >= 2200) { g_prefill_attn_mfma = skinny_variant - 2200; return RT_OK; }    // 2200/2201: prompt attention behind a shared prefix on the vector unit / matrix cores
-    if (skinny_variant >= 2100) { g_fuse_conv = skinny_variant - 2100; return RT_OK; }            // 2100/2101: the 96-channel conv pairs of the codec decoder as two launches / one
-    if (skinny_variant >= 2000) { g_col_max_rows = std::min(64, std::max(1, skinny_variant - 2000)); return RT_OK; }   // 20nn: batches up to nn rows take the column decode path
-    if (skinny_variant >= 1900) { g_prefill_mid = skinny_variant - 1900; return RT_OK; }         // 1900/1901: prompt-prefill GEMMs on the split-K tiled kernel / on k_gemm_mid
-    if (skinny_variant >= 1800) { g_conv_tall = skinny_variant - 1800; return RT_OK; }           // 1800/1801: 128- / 256-row tiles for the narrow-channel k>1 convs
-    if (skinny_variant >= 1700) { g_handover_every = std::max(1, skinny_variant - 1700); return RT_OK; }  // 17nn: queued items take over finished rows every nn frames
-    if (skinny_variant >= 1600) { g_col_split4 = skinny_variant - 1600; return RT_OK; }           // 1600/1601: quarter-tile split of N <= 1024 decode GEMMs off/on
-    if (skinny_variant >= 1500) { g_attn_mfma = skinny_variant - 1500; return RT_OK; }            // 1500/1501/1502: shared-prefix decode attention on the vector unit / matrix cores, 4 rows per workgroup / matrix cores, 1 row
-    if (skinny_variant >= 1400) { g_eos_check_every = std::max(1, skinny_variant - 1400); return RT_OK; }   // 14nn: look at the end-of-sequence flags every nn frames
-    if (skinny_variant >= 1300) { g_sync_parts = skinny_variant - 1300; return RT_OK; }             // 1300/1301: stream sync after every frame part off/on
-    if (skinny_variant >= 1200) { g_conv_win = skinny_variant - 1200; return RT_OK; }               // 1200/1201: conv input window in LDS off/on
-    if (skinny_variant >= 1100) { g_final_conv = skinny_variant - 1100; return RT_OK; }             // 1100/1101: last conv as GEMM / own kernel
-    if (skinny_variant >= 1000) { g_xcd_order = skinny_variant - 1000; return RT_OK; }              // 1000/1001: XCD-aware tile order off/on
-    if (skinny_variant >= 900) { g_prefill_fill = skinny_variant - 900; return RT_OK; }            // 90n: prefill split-K target, n workgroups per CU
-    if (skinny_variant >= 800) { g_fuse_sample_embed = skinny_variant - 800; return RT_OK; }      // 800/801: separate / fused sampler + embedding
-    if (skinny_variant >= 700) { g_col_rows64 = skinny_variant - 700; return RT_OK; }             // 700/701: 32-row / 64-row decode GEMM launches
-    if (skinny_variant >= 600) { g_tile96 = skinny_variant - 600; return RT_OK; }                 // 600/601: 128x96 tiles off/on
-    if (skinny_variant >= 500) { g_col_split = skinny_variant - 500; return RT_OK; }             // 500: automatic sub-tile split, 501/502/504: forced
-    if (skinny_variant >= 400) { g_decode_lanes = skinny_variant - 400; return RT_OK; }          // 40n: n decode lanes
-    if (skinny_variant >= 300) { g_pred_nt = skinny_variant - 300; return RT_OK; }               // 300: predictor weights cacheable, 301: nt
-    if (skinny_variant >= 200) { g_use_graph = skinny_variant - 200; return RT_OK; }            // 200: eager frames, 201: graph replay
-    if (skinny_variant >= 100) { g_decode_col = skinny_variant - 100; return RT_OK; }   // 100: legacy 9-launch decode, 101: column path
-    if (skinny_variant >= 0) g_skinny_variant = skinny_variant;
-    if (skinny_waves_per_cu > 0) g_skinny_waves_per_cu = skinny_waves_per_cu;
-    return RT_OK;
+    for (const KnobRow& r : kKnobs)
+        if (code >= r.base + r.lo && code <= r.base + r.hi) {
+            *r.knob = code - r.base;
+            if (r.base == kKnobArg[0].base && arg >= kKnobArg[0].lo && arg <= kKnobArg[0].hi) *kKnobArg[0].knob = arg;
+            ++g_tune_epoch;
+            return RT_OK;
+        }
+    return RT_ERR_INVALID;          // a code no row of knobs.h accepts: nothing changes
 }
 
 int rt_bench_gemm_skinny(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t split_k, int32_t n_mats, int32_t iters, double* avg_us,

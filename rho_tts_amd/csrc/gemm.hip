@@ -1104,35 +1104,6 @@ int launch_pack_weight(rt_ctx* ctx, const bf16_t* d_src, int N, int K, bf16_t* d
     return RT_OK;
 }
 
-rt_knob g_pred_nt{0};              // predictor weights: 0 = cacheable loads (Infinity-Cache resident across its 15 passes), 1 = non-temporal
-rt_knob g_use_graph{1};            // 1: the decode frame is replayed from captured hipGraphs
-rt_knob g_col_rows64{1};           // 1: one 64-row decode GEMM launch for the predictor's two-position pass, 0: two 32-row launches
-rt_knob g_pair_attn{1};            // 1: two-position decode passes append both positions inside the fused attention launch, 0: k_qkv_post + k_attention (rt_debug_tune 2800/2801)
-rt_knob g_frame_inc_fold{0};       // 1: frame += 1 by the last workgroup of the frame's talker-input launch, 0: k_frame_inc (rt_debug_tune 2700/2701; the fold measured 1-1.8 ms per step SLOWER)
-rt_knob g_fuse_sample_embed{1};    // 1: sampler + next-input embedding in one launch (predictor groups), 0: separate k_embed_rowsq
-rt_knob g_prefill_fill{3};          // workgroups per CU a prefill GEMM's split-K aims for
-rt_knob g_xcd_order{1};             // 1: tiled GEMMs run a row tile's column tiles back to back on one XCD
-rt_knob g_final_conv{1};           // 1: the codec decoder's last conv runs in its own LDS-window kernel
-rt_knob g_col_max_rows{64};         // batches up to this many rows decode on the column-owner path (tune 20nn).  Above 32 the talker's GEMMs take 64 rows per
-                                // launch and the predictor's two-position first pass runs as two 64-row launches: 715 audio-s/s at batch 64 against
-                                // 510 at batch 32 (1.7B, bench.py --batch 64) - every weight byte serves twice the rows for ~1.4x the launch time
-rt_knob g_conv_tall{1};            // 1: 256-row tiles for the k>1 convs of the 96- / 192-channel stages
-rt_knob g_conv_unroll{1};          // 1: k = 7 convs run the tap-unrolled instantiation of k_conv_win (rt_debug_tune 2600 / 2601)
-rt_knob g_conv_win{1};             // 1: k>1 convs on operand planes keep their input window in LDS (k_conv_win)
-rt_knob g_tile96{1};               // 1: 128x96 workgroup tiles for N = 96 / 192 (codec decoder), 0: always 128x128
-rt_knob g_col_split{0};            // 0: automatic (col_split_for), else forced 1 / 2 / 4
-rt_knob g_attn_mfma{0};             // 1: the talker's decode attention runs its shared-prefix part on the matrix cores (attention_mfma.hip);
-                                // measured 16.6 us per launch against 13.3 us for the vector-unit kernel at batch 32 / 460 prefix rows, so off
-rt_knob g_handover_every{4};       // queued items (n_items > rows): frames between two looks at the flags + row hand-overs.  Measured on the
-                                // 1.7B model, 512 / 64 ragged texts on 32 rows: 2 -> 487 / 445, 3 -> 489 / 445, 4 -> 491 / 447, 6 -> 485 / 445,
-                                // 8 -> 477 / 428, 12 -> 475 / 434 audio-s/s (a hand-over costs ~1.4 ms, a waiting row 0.13 ms per frame)
-rt_knob g_eos_check_every{8};      // frames between two host looks at the device-side end-of-sequence flags (1 = every frame)
-rt_knob g_sync_parts{0};           // 1: rt_generate waits for the stream after every frame part (bounds the dispatches in flight; profiling aid)
-rt_knob g_decode_lanes{1};         // decode lanes: groups of items decoding concurrently on their own streams (rt_generate)
-rt_knob g_decode_col{1};           // 1: decode stacks use the column-owner GEMM + fused attention (5 launches per layer)
-rt_knob g_skinny_variant{0};       // 0: k_gemm_skinny, 1: k_gemm_skinny2<.,4>, 2: k_gemm_skinny2<.,8>
-rt_knob g_skinny_waves_per_cu{4};  // split-K is chosen so that about this many waves per CU stream weights
-
 int skinny_pick_split(int M, int N, int K, int n_cu) {
     const int tiles = (N + 31) / 32, KT = (K + 15) / 16;
     const int target = n_cu * g_skinny_waves_per_cu;
@@ -1181,9 +1152,8 @@ int launch_gemm_skinny(rt_ctx* ctx, const bf16_t* d_a, int M, const PackedW& w, 
     return RT_OK;
 }
 
-rt_knob g_prefill_mid{1};           // 1: prompt prefills of 65..1024 rows run their GEMMs on k_gemm_mid (no split-K slabs); 2 / 3 force its 64 / 128 tiles
-bool gemm_mid_shape_ok(const PackedW& w) { return g_prefill_mid && w.K % MID_BK == 0 && w.K >= 128 && w.Kp == w.K; }
-bool gemm_mid_ok(int M, const PackedW& w) { return gemm_mid_shape_ok(w) && M > 64 && M <= 1024; }
+bool gemm_mid_shape_ok(int N, int K) { (void)N; return g_prefill_mid && K % MID_BK == 0 && K >= 128; }     // (K % 64 == 0: no K padding, Kp == K)
+bool gemm_mid_ok(int M, const PackedW& w) { return gemm_mid_shape_ok(w.N, w.K) && w.Kp == w.K && M > 64 && M <= 1024; }
 int launch_gemm_mid(rt_ctx* ctx, const bf16_t* A, int M, const PackedW& w, float* out, int64_t ldc) {
     if (!gemm_mid_ok(M, w)) return rt_fail(ctx, RT_ERR_INVALID, "gemm_mid: M=%d K=%d outside its range", M, w.K);
     MidArgs g{A, w.data, out, M, w.N, w.K, w.Np / 32, w.Kp / 16, ldc, 0};
@@ -1208,17 +1178,17 @@ int launch_gemm_mid(rt_ctx* ctx, const bf16_t* A, int M, const PackedW& w, float
     return RT_OK;
 }
 
-rt_knob g_fuse_conv{1};            // 1: a 96-channel k>1 conv and the 1x1 conv behind its activation run as one launch (launch_conv_pair)
-rt_knob g_fuse_conv192{1};         // 1: so do the 192-channel pairs, weight fragments staged through LDS (rt_debug_tune 3000 / 3001)
-rt_knob g_c2w_lean{1};             // 1: rt_code2wav drops the third unit's unread residual-stream store and the waveform copy (rt_debug_tune 2900 / 2901)
+// codec decoder k>1 convs on operand planes that can keep their input window in LDS (k_conv_win); the caller adds split_k == 1
+static bool conv_win_ok(const GemmA& a) {
+    return g_conv_win && a.split && !a.is_f32 && a.ptr_lo && a.taps >= 2 && a.Cin % 32 == 0 && a.rows_out > 0 && a.rows_in == a.rows_out &&
+           a.tap_offset == -(a.taps - 1) * a.tap_stride && (a.taps - 1) * a.tap_stride <= 63 && a.M % a.rows_out == 0;
+}
 
 // a k > 1 conv with SnakeBeta whose hi / lo output planes feed only the 1x1 conv (w2, e2): both in one launch when the first
 // conv's workgroup tile holds every output channel (96 or 192 channels, the LDS-window kernel) - else two launches through the planes
 bool conv_pair_fusable(const GemmA& a, const PackedW& w, const GemmEpi& e, const PackedW& w2) {
     const bool c96 = w.N == 96, c192 = w.N == 192 && g_fuse_conv192 && w.Np == 192 && a.taps == 7 && g_conv_unroll;   // (192: the tap-unrolled kernel only - the generic tap loop spills there)
-    return g_fuse_conv && g_conv_win && g_tile96 && (c96 || c192) && w2.N == w.N && w2.K == w.N && w2.Kp == w.N && w2.Np == w.N && e.act == ACT_SNAKE && a.split && !a.is_f32 && a.ptr_lo && a.taps >= 2 &&
-           a.Cin % 32 == 0 && a.rows_out > 0 && a.rows_in == a.rows_out && a.tap_offset == -(a.taps - 1) * a.tap_stride && (a.taps - 1) * a.tap_stride <= 63 &&
-           a.M % a.rows_out == 0;
+    return g_fuse_conv && g_tile96 && (c96 || c192) && w2.N == w.N && w2.K == w.N && w2.Kp == w.N && w2.Np == w.N && e.act == ACT_SNAKE && conv_win_ok(a);
 }
 
 int launch_gemm(rt_ctx* ctx, const GemmA& a, const PackedW& w, const GemmEpi& e, const PackedW* w2, const GemmEpi* e2) {
@@ -1236,9 +1206,7 @@ int launch_gemm(rt_ctx* ctx, const GemmA& a, const PackedW& w, const GemmEpi& e,
     g.kt_per_split = per;
     // 96-wide workgroup tiles when N is a multiple of 96 but not of 128 (the decoder's 96- and 192-channel stages)
     const bool narrow = g_tile96 && e.split_k == 1 && w.N % 96 == 0 && w.N % 128 != 0;
-    // codec decoder k>1 convs on operand planes: input window in LDS (k_conv_win)
-    const bool conv_win = g_conv_win && a.split && !a.is_f32 && a.ptr_lo && a.taps >= 2 && a.Cin % 32 == 0 && a.rows_out > 0 && a.rows_in == a.rows_out &&
-        a.tap_offset == -(a.taps - 1) * a.tap_stride && (a.taps - 1) * a.tap_stride <= 63 && e.split_k == 1 && a.M % a.rows_out == 0;
+    const bool conv_win = conv_win_ok(a) && e.split_k == 1;
     const bool tall = conv_win && narrow && (g_conv_tall == 2 || (g_conv_tall == 1 && a.M >= 256 * 1024));   // 256-row tiles (see k_conv_win; 2 = forced, tests)
     const int bm = tall ? 256 : BM;
     const int64_t my = (a.M + bm - 1) / bm;

@@ -33,7 +33,7 @@ int gemm_rows(rt_model* m, const bf16_t* A, int rows, const PackedW& W, float* s
         prof_events(m, (double)W.N * W.K * 2.0, &e0, &e1);
         RT_TRY(launch_gemm_skinny(m->ctx, A, rows, W, slabs, W.N, S, e0, e1));
         *n_slabs = S;
-    } else if (gemm_mid_shape_ok(W)) {
+    } else if (gemm_mid_shape_ok(W.N, W.K)) {
         // prompt prefill: final sums from 64 x 64 tiles over the whole K, K added in the skinny kernel's segments - a row gets the
         // same float32 sums among 13 rows (skinny) as among 416 or 3000: more than 1024 rows go down in equal chunks of <= 1024
         // (32 rows x > 30-token texts; the split-K tiled kernel's association would depend on the row count)
@@ -82,7 +82,7 @@ size_t slab_floats(const rt_stack_dims& d, int M, int n_cu) {
         const int q = d.heads * d.head_dim, qkv = (d.heads + 2 * d.kv_heads) * d.head_dim;
         const int shapes[4][2] = {{qkv, d.hidden}, {d.hidden, q}, {2 * d.inter, d.hidden}, {d.hidden, d.inter}};
         for (auto& s : shapes)
-            if (!(g_prefill_mid && s[1] % 64 == 0 && s[1] >= 128))
+            if (!gemm_mid_shape_ok(s[0], s[1]))
                 need = std::max<size_t>(need, (size_t)M * s[0] * skinny_pick_split(M, s[0], s[1], n_cu));
     }
     return need;
