@@ -119,6 +119,7 @@ RT_API int rt_debug_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_
  *   2800/2801 the predictor's two-position first pass: q/k norm + RoPE + append as a launch of its own in front of the attention / inside the fused attention
  *   2900/2901 rt_code2wav with / without the residual-stream store of every stage's third unit (no reader) and the waveform copy behind the last conv
  *   3000/3001 the codec decoder's 192-channel residual units as two launches / one fused launch (k = 7 with tap unrolling; 2100 switches both widths off)
+ *   3100/3101 predictor passes 2..G-1: layer 0's qkv GEMM launch / its q/k/v row copied from the per-code table built by rt_model_finalize
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
 RT_API int rt_debug_tune(int32_t code, int32_t arg);

@@ -457,24 +457,29 @@ int rt_gen_run::enqueue_a(Lane& ln) {
         sp.copy_fs = (int64_t)(G - 1) * B * Vp;
         sp.frame_ptr = ln.d_frame; sp.frame_off = ln.d_frame_off; sp.eos_live = 0; sp.min_frames = 0;
         const bool fuse_emb = col && m->has_mtp() && g_fuse_sample_embed && q < G - 2 && Vp <= 4096 && Hp % 8 == 0;
+        // the launch that embeds the drawn code also copies the next pass's layer-0 q/k/v row from the table of finalize
+        // (rt_model::pred_qkv0): that pass then starts at its attention - one dependent launch less
+        const float* qkv_tab = (col && g_pred_qkv_table && q < G - 2 && q < (int)m->pred_qkv0.size()) ? m->pred_qkv0[q] : nullptr;
+        const int qw_p = (c.predictor.heads + 2 * c.predictor.kv_heads) * c.predictor.head_dim;
         if (fuse_emb) {     // the sampler itself turns the drawn code into the next pass's input
             sp.emb_table = m->proj_emb[q]; sp.emb_H = Hp; sp.emb_norm_w = m->pred.L[0].ln1; sp.emb_rowsq = ln.rowsq_p; sp.emb_rowsq_n = NTp;
             sp.emb_x_tiled = ln.dwp.xT; sp.emb_a_tiled = ln.dwp.xa;
+            sp.emb_qkv_table = qkv_tab; sp.emb_qkv_out = ln.dwp.qkv; sp.emb_qkv_n = qw_p;
         }
         RT_TRY(launch_sample(ctx, sp));
         if (q < G - 2) {
             if (fuse_emb) {
             } else if (col && m->has_mtp()) {
                 RT_TRY(launch_embed_rowsq(ctx, nullptr, 0, m->proj_emb[q], codes + q + 1, G, ln.d_frame, codes_fs, n, Hp, nullptr, ln.rowsq_p,
-                                          NTp, ln.dwp.xT, ln.dwp.xa, m->pred.L[0].ln1));
+                                          NTp, ln.dwp.xT, ln.dwp.xa, m->pred.L[0].ln1, nullptr, nullptr, qkv_tab, ln.dwp.qkv, qw_p));
             } else if (col) {      // equal-width predictor: the group's own bf16 embedding table
                 RT_TRY(launch_embed_rowsq(ctx, m->d_frame_srcs + q + 1, 1, nullptr, codes + q + 1, G, ln.d_frame, codes_fs, n, Hp, nullptr,
-                                          ln.rowsq_p, NTp, ln.dwp.xT, ln.dwp.xa, m->pred.L[0].ln1));
+                                          ln.rowsq_p, NTp, ln.dwp.xT, ln.dwp.xa, m->pred.L[0].ln1, nullptr, nullptr, qkv_tab, ln.dwp.qkv, qw_p));
             } else if (m->has_mtp()) RT_TRY(launch_gather_f32(ctx, m->proj_emb[q], Hp, codes + q + 1, n, ln.xp, nullptr, G, ln.d_frame, codes_fs));
             else RT_TRY(launch_gather_sum(ctx, m->d_frame_srcs + q + 1, 1, codes + q + 1, n, H, nullptr, nullptr, nullptr, ln.xp, nullptr, G, ln.d_frame, codes_fs));
             m->prof_class = 2;
             if (col) {
-                RT_TRY(stack_decode(m, m->pred, ln.dwp, ln.dwp.xT, ln.rowsq_p, n, ln.d_slot_b, ln.d_zero_pos, q + 2, true, nullptr, ln.b0, true));
+                RT_TRY(stack_decode(m, m->pred, ln.dwp, ln.dwp.xT, ln.rowsq_p, n, ln.d_slot_b, ln.d_zero_pos, q + 2, true, nullptr, ln.b0, true, qkv_tab != nullptr));
             } else {
                 RT_TRY(stack_forward(m, m->pred, ln.wp, ln.xp, n, ln.d_slot_b, ln.d_zero_pos, q + 2, ln.hn_p, nullptr));
             }

@@ -136,8 +136,11 @@ int launch_rowsq(rt_ctx* ctx, const float* x, int M, int H, float* rowsq, int ro
 struct GatherSrc;
 int launch_embed_rowsq(rt_ctx* ctx, const GatherSrc* d_srcs, int n_src, const float* f32_table, const int32_t* d_idx, int idx_stride,
                        const int32_t* frame_ptr, int64_t idx_frame_stride, int M, int H, const float* add_vec, float* rowsq, int rowsq_n,
-                       float* x_tiled, bf16_t* a_tiled, const float* norm_w, int32_t* frame_inc = nullptr, unsigned* arrive = nullptr);
+                       float* x_tiled, bf16_t* a_tiled, const float* norm_w, int32_t* frame_inc = nullptr, unsigned* arrive = nullptr,
+                       const float* qkv_table = nullptr, float* qkv_out = nullptr, int qkv_n = 0);
 // (frame_inc == frame_ptr, arrive = a zeroed device counter: the last workgroup of the launch also advances the frame counter)
+// (qkv_table [V][qkv_n] f32, one index per row: row r of qkv_out [M][qkv_n] = qkv_table[idx[r * idx_stride]] - the next stack's
+//  layer-0 q/k/v row of that code, requested together with its embedding row; qkv_n % 4 == 0)
 
 // out[M][H] (row-major f32) = norm_w .* x * inv_rms(row) from the column path's tiled x and its rowsq partials
 int launch_norm_tiled_rows(rt_ctx* ctx, const float* x_tiled, const float* rowsq, int rowsq_n, const float* w, float eps, int M, int H,
@@ -264,6 +267,12 @@ struct SampleArgs {
     int emb_rowsq_n;
     float* emb_x_tiled;
     bf16_t* emb_a_tiled;
+    // optional, with emb_table: row `token` of emb_qkv_table [V][emb_qkv_n] f32 (the next pass's layer-0 q/k/v of that code) is copied
+    // to emb_qkv_out [M][emb_qkv_n].  Layer 0's qkv launch is then skipped, and with it the only reader of emb_a_tiled / emb_rowsq
+    // (the o-projection rewrites both): only the tiled x is stored in this mode
+    const float* emb_qkv_table;
+    float* emb_qkv_out;
+    int emb_qkv_n;
 };
 int launch_sample(rt_ctx* ctx, const SampleArgs& a);
 

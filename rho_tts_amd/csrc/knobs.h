@@ -44,7 +44,9 @@
     X(2700, g_frame_inc_fold, 0, 0, 1, "1: frame += 1 by the last workgroup of the frame's talker-input launch, 0: k_frame_inc (the fold measured 1-1.8 ms per step SLOWER)") \
     X(2800, g_pair_attn, 1, 0, 1, "1: two-position decode passes append both positions inside the fused attention launch, 0: k_qkv_post + k_attention") \
     X(2900, g_c2w_lean, 1, 0, 1, "1: rt_code2wav drops the third unit's unread residual-stream store and the waveform copy (the last conv writes the caller's buffer)") \
-    X(3000, g_fuse_conv192, 1, 0, 1, "1: the 192-channel conv pairs fuse as well, weight fragments staged through LDS")
+    X(3000, g_fuse_conv192, 1, 0, 1, "1: the 192-channel conv pairs fuse as well, weight fragments staged through LDS") \
+    X(3100, g_pred_qkv_table, 1, 0, 1, "predictor passes 2..G-1: 1 layer 0's q/k/v row of the drawn code is copied from the table rt_model_finalize builds (by the launch " \
+        "that embeds the code), 0 the layer-0 qkv GEMM launch runs (same bits either way)")
 
 // The one switch set by rt_debug_tune's SECOND argument: applied when the code is 0..2 and the argument lies in lo..hi.
 #define RT_KNOB_ARG(X) \

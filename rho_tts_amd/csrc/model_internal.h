@@ -65,6 +65,9 @@ struct rt_model {
     int pad_t_id = -1;
     float* proj_c0 = nullptr;              // [codec_vocab][Hp] f32 (mtp only)
     std::vector<float*> proj_emb;          // [G-1] x [Vp][Hp] f32 (mtp only)
+    // [G-2] x [Vp][qw] f32: layer 0's q/k/v row (before q/k norm and RoPE) of every code of groups 1..G-2 as the predictor's input -
+    // what the layer-0 qkv launch of passes 2..G-1 would compute (build_pred_qkv0, model_load.hip).  Empty: the table route is off.
+    std::vector<float*> pred_qkv0;
     GatherSrc* d_frame_srcs = nullptr;     // n_groups sources for frame embedding
     std::vector<float*> exp_vecs;          // expanded per-column vectors (owned)
     std::map<std::string, float*> xvec;    // name -> expanded vector (SnakeBeta parameters tiled over a transposed conv's r phases)
@@ -150,8 +153,12 @@ int stack_forward(rt_model* m, StackW& S, StackWs& w, float* x, int M, const int
                   bf16_t* out_bf16, float* out_f32, const int32_t* frame_ptr = nullptr, bool prefix_rows = false);
 int alloc_dec_ws(rt_model* m, const rt_stack_dims& d, int M, DecWs* w);
 int col_gemm(rt_model* m, const ColArgs& a0, const PackedW& W, bool is_predictor = false);
+// layer `layer`'s qkv launch of the decode stack: out [M][ldc = (heads + 2 kv) * d] = rmsnorm(x; ln1) Wqkv^T from the tiled operand xa and the rowsq partials
+int stack_qkv(rt_model* m, StackW& S, int layer, const bf16_t* xa, const float* rowsq, int M, float* out);
+// qkv0_ready: w.qkv already holds layer 0's q/k/v rows (the producer of x copied them from rt_model::pred_qkv0) - that launch is skipped
 int stack_decode(rt_model* m, StackW& S, DecWs& w, float* x, float* rowsq, int M, const int32_t* row_slot, const int32_t* row_pos,
-                 int pos_add, bool one_row_per_slot = true, const int32_t* frame_ptr = nullptr, int slot_base = -1, bool zero_pos = false);
+                 int pos_add, bool one_row_per_slot = true, const int32_t* frame_ptr = nullptr, int slot_base = -1, bool zero_pos = false,
+                 bool qkv0_ready = false);
 int col_head(rt_model* m, const bf16_t* xa, const float* rowsq, int rowsq_n, int row_off, int M, int K, float eps,
              const PackedW& W, const float* bias, float* out);
 int alloc_text_ws(rt_model* m, int n, TextWs* w);

@@ -215,6 +215,59 @@ int expand_vec(rt_model* m, const float* src, int n, int reps, float** out) {
     return RT_OK;
 }
 
+// rt_model::pred_qkv0: for every group q whose drawn code feeds another predictor pass (q = 0 .. G-3) and every code, what layer 0
+// does to that code's input row before q/k norm and RoPE - inv_rms(row) * (bf16(ln1 .* row) Wqkv^T).  It depends on (group, code) and
+// the weights alone, so passes 2 .. G-1 copy the row instead of launching the GEMM.  Filled by the decode path's OWN launches (the
+// embedding launch of the frame loop over identity code indices, then stack_qkv) in blocks of <= 32 codes: a row comes out of the
+// column GEMM with the same bits whatever rows share its launch, so table route and GEMM route give identical results.
+// Derived data like proj_emb (not part of weight_bytes).  If the memory is not there the model works without the table.
+int build_pred_qkv0(rt_model* m) {
+    rt_ctx* ctx = m->ctx;
+    const rt_model_config& c = m->cfg;
+    const rt_stack_dims& d = c.predictor;
+    const int G = c.n_groups, Hp = d.hidden, Vp = c.predictor_vocab, qw = (d.heads + 2 * d.kv_heads) * d.head_dim;
+    // (only models whose predictor can take the column path - generate.hip's `col` - and rows that 16-byte requests can copy)
+    if (G < 3 || Vp < 1 || Hp % 32 || d.inter % 32 || c.talker.hidden % 32 || c.talker.inter % 32 || qw % 4 || !m->pred.L[0].wqkv.data16) return RT_OK;
+    const int NTp = Hp / 16 * col_split_for(Hp, ctx->n_cu);
+    const size_t table_bytes = (size_t)Vp * qw * sizeof(float);
+    m->pred_qkv0.assign(G - 2, nullptr);
+    for (int q = 0; q < G - 2; ++q)
+        if (hipMalloc((void**)&m->pred_qkv0[q], table_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            for (auto p : m->pred_qkv0) if (p) (void)hipFree(p);
+            m->pred_qkv0.clear();
+            fprintf(stderr, "rho_tts_amd: no memory for the predictor's layer-0 q/k/v tables (%d x %.1f MB): their GEMM launches stay (same results)\n",
+                    G - 2, table_bytes / 1e6);
+            return RT_OK;
+        }
+    struct Tmp {       // the build's workspace: one 32-row block in the decode layouts
+        float *xT = nullptr, *rowsq = nullptr;
+        bf16_t* xa = nullptr;
+        int32_t* idx = nullptr;
+        ~Tmp() { (void)hipFree(xT); (void)hipFree(rowsq); (void)hipFree(xa); (void)hipFree(idx); }
+    } t;
+    RT_HIP(ctx, hipMalloc((void**)&t.xT, (size_t)32 * Hp * sizeof(float)));
+    RT_HIP(ctx, hipMalloc((void**)&t.xa, (size_t)32 * Hp * sizeof(bf16_t)));
+    RT_HIP(ctx, hipMalloc((void**)&t.rowsq, (size_t)32 * NTp * sizeof(float)));
+    RT_HIP(ctx, hipMalloc((void**)&t.idx, (size_t)Vp * sizeof(int32_t)));
+    RT_HIP(ctx, hipMemsetAsync(t.xT, 0, (size_t)32 * Hp * sizeof(float), ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(t.xa, 0, (size_t)32 * Hp * sizeof(bf16_t), ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(t.rowsq, 0, (size_t)32 * NTp * sizeof(float), ctx->stream));
+    int rc = launch_fill_i32(ctx, t.idx, Vp, 0, 1, 1);                  // idx[i] = i
+    for (int q = 0; q < G - 2 && !rc; ++q)
+        for (int c0 = 0; c0 < Vp && !rc; c0 += 32) {
+            const int nb = std::min(32, Vp - c0);
+            // the input rows of codes c0 .. c0 + nb - 1 exactly as the frame loop's producers leave them (generate.hip enqueue_a)
+            if (m->has_mtp()) rc = launch_embed_rowsq(ctx, nullptr, 0, m->proj_emb[q], t.idx + c0, 1, nullptr, 0, nb, Hp, nullptr, t.rowsq, NTp, t.xT, t.xa, m->pred.L[0].ln1);
+            else rc = launch_embed_rowsq(ctx, m->d_frame_srcs + q + 1, 1, nullptr, t.idx + c0, 1, nullptr, 0, nb, Hp, nullptr, t.rowsq, NTp, t.xT, t.xa, m->pred.L[0].ln1);
+            if (!rc) rc = stack_qkv(m, m->pred, 0, t.xa, t.rowsq, nb, m->pred_qkv0[q] + (size_t)c0 * qw);
+        }
+    const hipError_t se = hipStreamSynchronize(ctx->stream);            // (the workspace is freed on return)
+    if (rc) return rc;
+    RT_HIP(ctx, se);
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -274,6 +327,7 @@ int rt_model_destroy(rt_model* m) {
     for (auto& b : m->pool) (void)hipFree(b.p);
     for (auto p : m->exp_vecs) (void)hipFree(p);
     for (auto p : m->proj_emb) (void)hipFree(p);
+    for (auto p : m->pred_qkv0) (void)hipFree(p);
     if (m->proj_c0) (void)hipFree(m->proj_c0);
     if (m->pad_t) (void)hipFree(m->pad_t);
     if (m->d_frame_srcs) (void)hipFree(m->d_frame_srcs);
@@ -417,6 +471,7 @@ int rt_model_finalize(rt_model* m, const float* h_rope_cos[3], const float* h_ro
         m->proj_emb.resize(c.n_groups - 1, nullptr);
         for (int gq = 0; gq < c.n_groups - 1; ++gq) RT_TRY(project(TBL(m, "pred.emb" + std::to_string(gq)), c.predictor_vocab, &m->proj_emb[gq]));
     }
+    RT_TRY(build_pred_qkv0(m));
     // SnakeBeta parameters of each block's first residual unit, tiled over the r output phases of the transposed conv
     for (int i = 0; i < c.n_upsample_rates; ++i) {
         const std::string bn = "codec.b" + std::to_string(i);

@@ -188,21 +188,27 @@ int col_gemm(rt_model* m, const ColArgs& a0, const PackedW& W, bool is_predictor
     }
     return RT_OK;
 }
+// layer `layer`'s qkv launch (also what fills rt_model::pred_qkv0 at load time: the same arguments, so the same bits)
+int stack_qkv(rt_model* m, StackW& S, int layer, const bf16_t* xa, const float* rowsq, int M, float* out) {
+    const rt_stack_dims& d = S.d;
+    const int H = d.hidden, n_cu = m->ctx->n_cu, qw = (d.heads + 2 * d.kv_heads) * d.head_dim;
+    ColArgs a;      // qkv = rmsnorm(x; ln1) Wqkv^T : operand xa = bf16(ln1 .* x), row scale from rowsq
+    a.A = xa; a.post_scale = 1; a.rowsq = rowsq; a.rowsq_n = H / 16 * col_split_for(H, n_cu); a.eps = d.rms_eps; a.M = M; a.K = H;
+    a.epi = COL_STORE; a.out = out; a.ldc = qw; a.split = col_split_for(qw, n_cu);
+    return col_gemm(m, a, S.L[layer].wqkv, &S == &m->pred);
+}
 // one_row_per_slot = false (the predictor's 2-row first pass): a row must see the K/V another row of the same launch
 // appends, so q/k-norm + RoPE + append run as their own launch before the attention.
 int stack_decode(rt_model* m, StackW& S, DecWs& w, float* x, float* rowsq, int M, const int32_t* row_slot, const int32_t* row_pos,
-                 int pos_add, bool one_row_per_slot, const int32_t* frame_ptr, int slot_base, bool zero_pos) {
+                 int pos_add, bool one_row_per_slot, const int32_t* frame_ptr, int slot_base, bool zero_pos, bool qkv0_ready) {
     rt_ctx* ctx = m->ctx;
     const rt_stack_dims& d = S.d;
-    const int H = d.hidden, sp_h = col_split_for(H, ctx->n_cu), NTh = H / 16 * sp_h, qw = (d.heads + 2 * d.kv_heads) * d.head_dim;
+    const int H = d.hidden, sp_h = col_split_for(H, ctx->n_cu), NTh = H / 16 * sp_h;
     const bool isp = &S == &m->pred;
     for (int i = 0; i < d.layers; ++i) {
         LayerW& L = S.L[i];
         const float* next_w = (i + 1 < d.layers) ? S.L[i + 1].ln1 : S.norm;   // the norm that reads x after this layer
-        ColArgs a;      // qkv = rmsnorm(x; ln1) Wqkv^T : operand w.xa = bf16(ln1 .* x), row scale from rowsq
-        a.A = w.xa; a.post_scale = 1; a.rowsq = rowsq; a.rowsq_n = NTh; a.eps = d.rms_eps; a.M = M; a.K = H;
-        a.epi = COL_STORE; a.out = w.qkv; a.ldc = qw; a.split = col_split_for(qw, ctx->n_cu);
-        RT_TRY(col_gemm(m, a, L.wqkv, isp));
+        if (i > 0 || !qkv0_ready) RT_TRY(stack_qkv(m, S, i, w.xa, rowsq, M, w.qkv));
         if (one_row_per_slot) {
             // (slot_base >= 0: rows sit in consecutive slots; zero_pos: every row at pos_add - the attention then needs no slot /
             //  position arrays, i.e. no dependent scalar loads in front of its K / V requests)

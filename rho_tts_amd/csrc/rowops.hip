@@ -187,7 +187,8 @@ __global__ __launch_bounds__(256) void k_embed_rowsq(const GatherSrc* __restrict
                                                      const int32_t* __restrict__ frame_ptr, int64_t idx_frame_stride, int H,
                                                      const float* __restrict__ add_vec, float* __restrict__ rowsq, int rowsq_n,
                                                      float* __restrict__ x_tiled, bf16_t* __restrict__ a_tiled,
-                                                     const float* __restrict__ norm_w, int32_t* frame_inc, unsigned* arrive) {
+                                                     const float* __restrict__ norm_w, int32_t* frame_inc, unsigned* arrive,
+                                                     const float* __restrict__ qkv_table, float* __restrict__ qkv_out, int qkv_n) {
     constexpr int MAXS = 16;
     __shared__ const bf16_t* sh_tab[MAXS];
     __shared__ float sh[4];
@@ -204,6 +205,21 @@ __global__ __launch_bounds__(256) void k_embed_rowsq(const GatherSrc* __restrict
         sh_tab[tid] = p;
     }
     const int fid = f32_table ? idx[(int64_t)row * idx_stride] : -1;
+    // (optional) the next stack's layer-0 q/k/v row of the row's code, copied from a per-code table: requested here, ahead of the
+    // embedding rows and with clamped indices (no branch around a load), stored behind them - no round trip of its own
+    constexpr int QU = 4;
+    const int n4 = qkv_n >> 2;
+    f4_t qv[QU];
+    const f4_t* qsrc = nullptr;
+    if (qkv_table) {
+        const int qid = idx[(int64_t)row * idx_stride];
+        qsrc = reinterpret_cast<const f4_t*>(qkv_table + (int64_t)(qid < 0 ? 0 : qid) * qkv_n);
+#pragma unroll
+        for (int u = 0; u < QU; ++u) {
+            const int i = tid + u * 256;
+            qv[u] = qsrc[i < n4 ? i : n4 - 1];
+        }
+    }
     __syncthreads();
     // frame += 1 by the LAST workgroup to get here (instead of a launch of its own, k_frame_inc).  The only readers of the counter
     // in this launch are the lanes that filled sh_tab: their index loads - which needed the counter - had to return before the
@@ -253,6 +269,15 @@ __global__ __launch_bounds__(256) void k_embed_rowsq(const GatherSrc* __restrict
         pk.z = f32x2_to_bf16x2(w1[0] * v[4], w1[1] * v[5]);
         pk.w = f32x2_to_bf16x2(w1[2] * v[6], w1[3] * v[7]);
         *reinterpret_cast<uint4*>(a_tiled + o) = pk;
+    }
+    if (qkv_table) {
+        f4_t* qdst = reinterpret_cast<f4_t*>(qkv_out + (int64_t)row * qkv_n);
+#pragma unroll
+        for (int u = 0; u < QU; ++u) {
+            const int i = tid + u * 256;
+            if (i < n4) qdst[i] = qv[u];
+        }
+        for (int i = tid + QU * 256; i < n4; i += 256) qdst[i] = qsrc[i];
     }
     const float tot = block_sum_f32(ss, sh);
     for (int j = tid; j < rowsq_n; j += 256) rowsq[(int64_t)row * rowsq_n + j] = j == 0 ? tot : 0.f;
@@ -548,14 +573,17 @@ int launch_rowsq(rt_ctx* ctx, const float* x, int M, int H, float* rowsq, int ro
 
 int launch_embed_rowsq(rt_ctx* ctx, const GatherSrc* d_srcs, int n_src, const float* f32_table, const int32_t* d_idx, int idx_stride,
                        const int32_t* frame_ptr, int64_t idx_frame_stride, int M, int H, const float* add_vec, float* rowsq, int rowsq_n,
-                       float* x_tiled, bf16_t* a_tiled, const float* norm_w, int32_t* frame_inc, unsigned* arrive) {
+                       float* x_tiled, bf16_t* a_tiled, const float* norm_w, int32_t* frame_inc, unsigned* arrive, const float* qkv_table,
+                       float* qkv_out, int qkv_n) {
     if (M <= 0) return RT_OK;
     if (n_src > 16 || H % 8 || !x_tiled || !a_tiled || !norm_w || !rowsq || rowsq_n < 1 || (n_src > 0 && !d_srcs))
         return rt_fail(ctx, RT_ERR_INVALID, "embed_rowsq: n_src %d (<= 16), H %d (multiple of 8) or a missing buffer", n_src, H);
     if (frame_inc && (f32_table || !arrive || frame_inc != frame_ptr))
         return rt_fail(ctx, RT_ERR_INVALID, "embed_rowsq: the frame counter is advanced by launches over bf16 sources only, with an arrival counter");
+    if (qkv_table && (!qkv_out || qkv_n < 4 || qkv_n % 4 || frame_inc || (f32_table ? n_src != 0 : n_src != 1)))
+        return rt_fail(ctx, RT_ERR_INVALID, "embed_rowsq: the q/k/v table takes one code per row, an output and a row width that is a multiple of 4");
     hipLaunchKernelGGL(k_embed_rowsq, dim3(M), dim3(256), 0, ctx->stream, d_srcs, n_src, f32_table, d_idx, idx_stride, frame_ptr,
-                       idx_frame_stride, H, add_vec, rowsq, rowsq_n, x_tiled, a_tiled, norm_w, frame_inc, arrive);
+                       idx_frame_stride, H, add_vec, rowsq, rowsq_n, x_tiled, a_tiled, norm_w, frame_inc, arrive, qkv_table, qkv_out, qkv_n);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }

@@ -551,6 +551,43 @@ __global__ __launch_bounds__(NW * 64) void k_sample_w(SampleArgs A) {
         __syncthreads();    // 256 threads x 8 elements, wave sums, then waves 0..3 - threads beyond 256 only keep the barriers)
         const int tok = sh_i[0];
         const int H = A.emb_H;
+        if (A.emb_qkv_table) {
+            // table mode: the next pass's layer-0 q/k/v row of the code rides along with its embedding row.  Both rows are requested
+            // together - one dependent round trip behind the token, as without the table - with clamped indices instead of a per-lane
+            // `if` around the loads (see the logits loads above).  Only the tiled x is stored: bf16(norm_w .* x) and rowsq fed the
+            // skipped qkv launch alone (layer 0's o-projection rewrites both), so the sum of squares and its barriers go as well.
+            constexpr int QU = 2;
+            const int n4 = A.emb_qkv_n >> 2, H8 = H >> 3;
+            const f4s_t* __restrict__ qsrc = reinterpret_cast<const f4s_t*>(A.emb_qkv_table + (int64_t)tok * A.emb_qkv_n);
+            f4s_t* __restrict__ qdst = reinterpret_cast<f4s_t*>(A.emb_qkv_out + (int64_t)row * A.emb_qkv_n);
+            const float* __restrict__ esrc = A.emb_table + (int64_t)tok * H;
+            const int e0 = tid < H8 ? tid : H8 - 1;
+            const f4s_t ea = *reinterpret_cast<const f4s_t*>(esrc + e0 * 8), eb = *reinterpret_cast<const f4s_t*>(esrc + e0 * 8 + 4);
+            f4s_t qv[QU];
+#pragma unroll
+            for (int u = 0; u < QU; ++u) {
+                const int i = tid + u * NT;
+                qv[u] = qsrc[i < n4 ? i : n4 - 1];
+            }
+            if (tid < H8) {
+                const int64_t o = tile_off(row, tid * 8, H);
+                *reinterpret_cast<f4s_t*>(A.emb_x_tiled + o) = f4s_t{0.f + ea[0], 0.f + ea[1], 0.f + ea[2], 0.f + ea[3]};
+                *reinterpret_cast<f4s_t*>(A.emb_x_tiled + o + 4) = f4s_t{0.f + eb[0], 0.f + eb[1], 0.f + eb[2], 0.f + eb[3]};
+            }
+#pragma unroll
+            for (int u = 0; u < QU; ++u) {
+                const int i = tid + u * NT;
+                if (i < n4) qdst[i] = qv[u];
+            }
+            for (int e = tid + NT; e < H8; e += NT) {          // (rows wider than one round of the workgroup: not at the shipped shapes)
+                const f4s_t a = *reinterpret_cast<const f4s_t*>(esrc + e * 8), b = *reinterpret_cast<const f4s_t*>(esrc + e * 8 + 4);
+                const int64_t o = tile_off(row, e * 8, H);
+                *reinterpret_cast<f4s_t*>(A.emb_x_tiled + o) = f4s_t{0.f + a[0], 0.f + a[1], 0.f + a[2], 0.f + a[3]};
+                *reinterpret_cast<f4s_t*>(A.emb_x_tiled + o + 4) = f4s_t{0.f + b[0], 0.f + b[1], 0.f + b[2], 0.f + b[3]};
+            }
+            for (int i = tid + QU * NT; i < n4; i += NT) qdst[i] = qsrc[i];
+            return;
+        }
         float ss = 0.f;
         if (tid < 256) {
             for (int c = tid * 8; c < H; c += 2048) {
@@ -591,6 +628,8 @@ int launch_sample(rt_ctx* ctx, const SampleArgs& a) {
     if (a.V > 16384) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "vocabulary %d too large for the sampler", a.V);
     if (a.emb_table && (a.V > 4096 || a.emb_H % 8 || !a.emb_norm_w || !a.emb_rowsq || a.emb_rowsq_n < 1 || !a.emb_x_tiled || !a.emb_a_tiled))
         return rt_fail(ctx, RT_ERR_INVALID, "sample: fused embedding needs V <= 4096, H %% 8 == 0 and all its buffers");
+    if (a.emb_qkv_table && (!a.emb_table || !a.emb_qkv_out || a.emb_qkv_n < 4 || a.emb_qkv_n % 4))
+        return rt_fail(ctx, RT_ERR_INVALID, "sample: the q/k/v table needs the fused embedding, an output and a row width that is a multiple of 4");
     if (a.V <= 1024) hipLaunchKernelGGL((k_sample_w<4, 4>), dim3(a.M), dim3(256), 0, ctx->stream, a);
     else if (a.V <= 2048) hipLaunchKernelGGL((k_sample_w<4, 8>), dim3(a.M), dim3(512), 0, ctx->stream, a);
     else if (a.V <= 4096) hipLaunchKernelGGL((k_sample_w<4, 16>), dim3(a.M), dim3(1024), 0, ctx->stream, a);
