@@ -367,8 +367,9 @@ RT_API int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32
  *     zero-padded centre, periodic Hann, 128 slaney mel filters, power_to_db with top_db 80, orthonormal DCT-II).
  *   h_cmnd [n_frames][max_period - min_period + 1] float64 (optional, room for cmnd_cap_frames frames): the cumulative-mean-
  *     normalised difference function of probabilistic YIN per pitch frame (frame 2048, window 1024, hop 512, zero-padded
- *     centre) for the lags min_period .. max_period (rt_features_geometry); the trough statistics and the Viterbi pass that
- *     turn it into F0 are host arithmetic (rho_tts_amd/features.py).
+ *     centre) for the lags min_period .. max_period (rt_features_geometry).  rt_features_extract hands it to the caller; the
+ *     trough statistics and the Viterbi pass that turn it into F0 are defined by the host functions observation_log_probs and
+ *     viterbi_banded of rho_tts_amd/features.py, and run as HIP kernels with that definition in rt_features_extract_batch.
  *   h_lpc [lpc_order + 1] float64: Burg LPC of the pre-emphasised (0.97), symmetric-Hann-windowed 25-ms frame about the middle
  *     sample; the formants are the angles of its roots.
  * Frames: 1 + n16 / 512 for both (n16 = samples at 16 kHz).  Parity with librosa is UNPINNED (not installable offline). */
@@ -381,6 +382,28 @@ RT_API int rt_features_geometry(int32_t pitch_sr, double fmin, double fmax, int3
 RT_API int rt_features_extract(rt_features* f, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, int32_t min_period,
                                int32_t max_period, int32_t lpc_order, double* h_mfcc_stats26, int32_t* h_n_mfcc_frames, double* h_cmnd,
                                int32_t cmnd_cap_frames, int32_t* h_n_pitch_frames, double* h_lpc);
+
+/* The pitch model of probabilistic YIN's back half, uploaded once per rt_features (rho_tts_amd/features.py pitch_model builds it
+ * with the numpy expressions of the host definition, so the device compares and adds the host's own bits):
+ *   h_thresholds, h_beta [n_thresholds]: the ascending trough thresholds and the prior mass of each;
+ *   h_log_trans [2][2 half_width + 1][n_bins]: log(w_local[offset][to-bin] * p + tiny), p = stay (index 0) / switch (index 1)
+ *     probability of the voicing, offset = from-bin - to-bin + half_width; h_log_init [2 n_bins] = log(p_init + tiny);
+ *   log_tiny = log(tiny), the transition from every state outside the band;
+ *   pitch_sr, fmin, bins_per_semitone: bin of a period = round(12 bins_per_semitone log2(pitch_sr / period / fmin)), clipped to
+ *     0 .. n_bins; no_trough_prob: the mass the global minimum gets from the thresholds that are not above it.
+ * n_bins <= 2000, n_thresholds <= 1024. */
+RT_API int rt_features_set_pitch_model(rt_features* f, int32_t n_bins, int32_t half_width, int32_t n_thresholds, const double* h_thresholds,
+                                       const double* h_beta, const double* h_log_trans, const double* h_log_init, double log_tiny,
+                                       double pitch_sr, double fmin, int32_t bins_per_semitone, double no_trough_prob);
+/* The whole feature extraction of n_clips waveforms in HBM (d_pcm[c]: n_samples[c] floats at sample_rate_in) in one call, with one
+ * stream synchronisation and one set of device-to-host copies whatever n_clips is:
+ *   h_mfcc_stats26 [n_clips][26], h_lpc [n_clips][lpc_order + 1]: per clip the bits rt_features_extract gives for it alone;
+ *   h_states [n_clips][cap_frames] int32: the Viterbi state path of every clip (voiced pitch bin b = state b, unvoiced = n_bins + b;
+ *     -1 behind the clip's last frame); h_n_pitch_frames [n_clips] = 1 + n16 / 512.
+ * RT_ERR_INVALID: a clip below two samples, cap_frames below a clip's frame count, no pitch model set. */
+RT_API int rt_features_extract_batch(rt_features* f, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips,
+                                     int32_t sample_rate_in, int32_t min_period, int32_t max_period, int32_t lpc_order,
+                                     double* h_mfcc_stats26, double* h_lpc, int32_t* h_states, int32_t cap_frames, int32_t* h_n_pitch_frames);
 
 /* Measurement and test entry points (rt_profile_*, rt_debug_*, rt_bench_*) are declared in rho_tts_amd_debug.h: a host binding of
  * the generation path needs none of them. */

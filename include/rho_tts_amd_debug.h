@@ -85,6 +85,16 @@ RT_API int rt_debug_attention_prefill(rt_ctx* ctx, const float* d_q, int32_t M, 
 /* One draw per row: logits [M][V] f32 -> tokens [M].  item ids 0..M-1. */
 RT_API int rt_debug_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_t V, const rt_sampling* sp, uint64_t seed,
                            int32_t frame, int32_t group, int32_t suppress_from, int32_t allow_token, uint8_t* d_seen, int32_t* d_out);
+/* The two stages of probabilistic YIN's back half on their own (tests/test_features_batch_gpu.py); the pitch model must be set
+ * (rt_features_set_pitch_model).  HOST pointers on both sides; one stream synchronisation per call.
+ * rt_debug_features_observe: h_cmnd [n_frames][n_lags] float64 -> h_log_obs [n_frames][2 n_bins] (definition: observation_log_probs
+ *   of rho_tts_amd/features.py).
+ * rt_debug_features_viterbi: h_log_obs = the log-obs of n_clips clips back to back, clip c with h_n_frames[c] rows of 2 n_bins
+ *   -> h_states [n_clips][stride] int32, -1 behind a clip's last frame (definition: viterbi_banded; one workgroup per clip). */
+RT_API int rt_debug_features_observe(rt_features* f, const double* h_cmnd, int32_t n_frames, int32_t n_lags, int32_t min_period,
+                                     double* h_log_obs);
+RT_API int rt_debug_features_viterbi(rt_features* f, const double* h_log_obs, const int32_t* h_n_frames, int32_t n_clips, int32_t* h_states,
+                                     int32_t stride);
 
 /* A/B switches for measurements and tests (process-wide; the defaults are the fast path).  One row per switch, as in the table
  * they are generated from (rho_tts_amd/csrc/knobs.h: defaults, accepted ranges, measurement notes).  A code that no row accepts is

@@ -8,8 +8,11 @@
 //        128 slaney mel filters, 10 log10 (floor 1e-10), max - 80 dB floor, DCT-II (orthonormal) rows 0..12 -> mean and
 //        standard deviation of every coefficient over the frames (26 numbers)
 //     -> pYIN front half: per frame d(tau) = sum_{j=1..1024} (x[j] - x[j + tau])^2, cumulative-mean-normalised, for the lags
-//        min_period .. max_period ([frames][lags] float64; troughs, thresholds and the Viterbi pass over 1202 states are a
-//        few hundred kilobytes of host arithmetic: rho_tts_amd/features.py)
+//        min_period .. max_period ([frames][lags] float64)
+//     -> pYIN back half (rt_features_extract_batch only; the single-clip call hands the difference function to the host functions
+//        of rho_tts_amd/features.py, which are the reference definition of both kernels): trough statistics -> log observation
+//        probabilities [frames][2 n_bins] (k_feat_observe), Viterbi pass over the 2 n_bins states, one workgroup per clip
+//        (k_feat_viterbi) -> one state per pitch frame
 //     -> LPC: pre-emphasis 0.97 in float32, 400-sample symmetric-Hann frame about the middle sample, Burg's recursion in
 //        float64 -> order + 1 coefficients (their roots - an 18 x 18 eigenproblem - are taken on the host)
 //
@@ -17,7 +20,9 @@
 // the kernels are the simple forms: direct DFT and direct difference sums in float64, one workgroup per frame.
 // PARITY UNPINNED (librosa absent): the definitions are those of oracle/features.py, which restates librosa 0.10's defaults.
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <vector>
 
 #include "kernels.h"
 
@@ -38,6 +43,22 @@ struct rt_features {
     size_t frame_cap = 0;
     int* d_gmax = nullptr;
     double *d_stats = nullptr, *d_lpc = nullptr;   // [26], [order + 1]
+    // pYIN's back half (rt_features_set_pitch_model): every table comes from the host, so the device compares and adds the host's bits
+    bool pm_set = false;
+    int pm_bins = 0, pm_hw = 0, pm_thr = 0;
+    double *pm_d_thr = nullptr, *pm_d_beta = nullptr;          // [n_thresholds] each
+    double *pm_d_trans = nullptr, *pm_d_init = nullptr;        // [2][2 hw + 1][n_bins] (stay, switch), [2 n_bins]
+    double pm_log_tiny = 0.0, pm_sr = 0.0, pm_fmin = 0.0, pm_bins_per_octave = 0.0, pm_no_trough = 0.0;
+    // workspaces of the batched path (rt_features_extract_batch and the two stage hooks), sized by the batch, grown on demand
+    float* b_pcm = nullptr;                        // every clip at 16 kHz, back to back
+    float* b_logmel = nullptr;                     // [frames of the batch][128]
+    double *b_mfcc = nullptr, *b_cmnd = nullptr, *b_logobs = nullptr;    // [frames][13], [frames][lags], [frames][2 n_bins]
+    int *b_ptr = nullptr, *b_states = nullptr;     // Viterbi backpointers [frames][2 n_bins], state paths [clips][stride]
+    double *b_stats = nullptr, *b_lpc = nullptr;   // [clips][26], [clips][order + 1]
+    int *b_gmax = nullptr, *b_meta = nullptr;      // [clips], first frame | frame count per clip [2][clips]
+    size_t b_pcm_cap = 0, b_logmel_cap = 0, b_mfcc_cap = 0, b_cmnd_cap = 0, b_logobs_cap = 0, b_ptr_cap = 0, b_states_cap = 0, b_stats_cap = 0,
+           b_lpc_cap = 0, b_gmax_cap = 0, b_meta_cap = 0;
+    std::vector<int> h_meta;
 };
 
 namespace {
@@ -225,6 +246,229 @@ __global__ __launch_bounds__(64) void k_feat_lpc(const float* __restrict__ pcm, 
     for (int i = lane; i <= order; i += 64) a_out[i] = pa[i];
 }
 
+// ---- pYIN's back half.  The definitions are the host functions of rho_tts_amd/features.py, point by point: observation_log_probs
+// for k_feat_observe, viterbi_banded for k_feat_viterbi.
+constexpr double F_TINY = 2.2250738585072014e-308;
+
+// One pitch frame per workgroup: cmnd[f][0 .. n_lags) -> out[f][0 .. 2 n_bins) = log(observation + tiny).
+// Troughs are compacted in ascending lag by one wave (ballot).  The thresholds ascend, so "trough i is below threshold k" holds
+// exactly for k >= k0[i], the first threshold above its height (found with the host's own comparison h < thr[k] on the uploaded
+// thresholds): the count of troughs below threshold k is #{i : k0[i] <= k}, the rank of trough i among them #{i' < i : k0[i'] <= k}.
+// Dynamic LDS: c[n_lags] | obs[n_bins] | h[mcap] | pr[mcap] (doubles) | idx[mcap] | k0[mcap] | bin[mcap] | nk[n_thr] (ints),
+// mcap = (n_lags + 1) / 2 + 1 (two neighbouring lags cannot both be troughs).
+__global__ __launch_bounds__(256) void k_feat_observe(const double* __restrict__ cmnd, int n_lags, int min_p, int n_bins, int n_thr,
+                                                      const double* __restrict__ thr, const double* __restrict__ beta, double pitch_sr, double f_min,
+                                                      double bins_per_octave, double no_trough, double* __restrict__ out) {
+    extern __shared__ double osh[];
+    const int mcap = (n_lags + 1) / 2 + 1;
+    double* c = osh;
+    double* obs = c + n_lags;
+    double* h = obs + n_bins;
+    double* pr = h + mcap;
+    int* idx = (int*)(pr + mcap);
+    int* k0 = idx + mcap;
+    int* bin = k0 + mcap;
+    int* nk = bin + mcap;
+    __shared__ int s_m;
+    __shared__ double s_voiced;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const double* row = cmnd + (int64_t)f * n_lags;
+    for (int i = tid; i < n_lags; i += 256) c[i] = row[i];
+    for (int i = tid; i < n_bins; i += 256) obs[i] = 0.0;
+    __syncthreads();
+    if (tid < 64) {                                 // troughs in ascending lag: interior c[i] < c[i-1] && c[i] <= c[i+1], and the two edge rules
+        int m = 0;
+        for (int base = 0; base < n_lags; base += 64) {
+            const int i = base + tid;
+            bool tr = false;
+            if (i < n_lags) {
+                if (i == 0) tr = c[0] < c[1];
+                else if (i == n_lags - 1) tr = c[i] < c[i - 1];
+                else tr = c[i] < c[i - 1] && c[i] <= c[i + 1];
+            }
+            const unsigned long long b = __ballot(tr);
+            const int at = m + __popcll(b & ((1ull << tid) - 1ull));
+            if (tr && at < mcap) idx[at] = i;
+            m += __popcll(b);
+        }
+        if (tid == 0) s_m = m < mcap ? m : mcap;
+    }
+    __syncthreads();
+    const int m = s_m;
+    for (int i = tid; i < m; i += 256) {
+        const int j = idx[i];
+        const double hv = c[j];
+        h[i] = hv;
+        int k = 0;
+        while (k < n_thr && !(hv < thr[k])) ++k;
+        k0[i] = k;
+        double shift = 0.0;                         // parabolic refinement of the lag; 0 at the edges and where |shift| > 1
+        if (j > 0 && j < n_lags - 1) {
+            const double a = (c[j - 1] + c[j + 1] - 2.0 * c[j]) / 2.0, b = (c[j + 1] - c[j - 1]) / 2.0;
+            shift = -b / (2.0 * a + F_TINY);
+            if (fabs(shift) > 1.0) shift = 0.0;
+        }
+        const double period = (double)(min_p + j) + shift;
+        double bn = rint(bins_per_octave * log2((pitch_sr / period) / f_min));      // np.round: half to even
+        if (!(bn >= 0.0)) bn = 0.0;
+        if (bn > (double)n_bins) bn = (double)n_bins;
+        bin[i] = (int)bn;
+    }
+    __syncthreads();
+    for (int k = tid; k < n_thr; k += 256) {
+        int n = 0;
+        for (int i = 0; i < m; ++i) n += k0[i] <= k ? 1 : 0;
+        nk[k] = n;
+    }
+    __syncthreads();
+    const double e2 = exp(-2.0);
+    for (int i = tid; i < m; i += 256) {            // Boltzmann(2) prior over the troughs below each threshold, Beta mass per threshold
+        double p = 0.0;
+        for (int k = k0[i]; k < n_thr; ++k) {
+            int pos = 0;
+            for (int q = 0; q < i; ++q) pos += k0[q] <= k ? 1 : 0;
+            const int n = nk[k] > 1 ? nk[k] : 1;
+            p += (1.0 - e2) * exp(-2.0 * (double)pos) / (1.0 - exp(-2.0 * (double)n)) * beta[k];
+        }
+        pr[i] = p;
+    }
+    __syncthreads();
+    if (tid == 0 && m > 0) {
+        int g = 0;                                  // the no-trough mass goes to the global minimum (first one), over the thresholds not above it
+        for (int i = 1; i < m; ++i) if (h[i] < h[g]) g = i;
+        double bs = 0.0;
+        for (int k = 0; k < k0[g]; ++k) bs += beta[k];
+        pr[g] += no_trough * bs;
+        for (int i = 0; i < m; ++i)                 // ascending lag: a later trough in the same bin wins; bin n_bins falls into the unvoiced columns
+            if (pr[i] != 0.0 && bin[i] < n_bins) obs[bin[i]] = pr[i];
+    }
+    __syncthreads();
+    if (tid < 64) {
+        double v = 0.0;
+        for (int i = tid; i < n_bins; i += 64) v += obs[i];
+        v = wave_sum_f64(v);
+        if (tid == 0) s_voiced = fmin(1.0, fmax(0.0, v));
+    }
+    __syncthreads();
+    const double unv = log((1.0 - s_voiced) / (double)n_bins + F_TINY);
+    double* o = out + (int64_t)f * 2 * n_bins;
+    for (int i = tid; i < n_bins; i += 256) {
+        o[i] = log(obs[i] + F_TINY);
+        o[n_bins + i] = unv;
+    }
+}
+
+// (value, state) of the larger value; equal values: the lower state (np.argmax's first maximum)
+__device__ __forceinline__ void vit_take(double& v, int& s, double ov, int os) {
+    if (ov > v || (ov == v && os < s)) { v = ov; s = os; }
+}
+
+// One clip per workgroup: the Viterbi pass over 2 n_bins states in add-and-compare form.  State values are double-buffered in LDS, one
+// barrier per frame; backpointers go to HBM; lane 0 backtracks.  A to-state (v, j) scans its predecessors in ascending state index -
+// the voiced block before the unvoiced one, ascending from-bin inside a block - and a candidate replaces the best only on a strict >.
+// States outside the band reach it with log(tiny): max(val) + log(tiny), with the first arg-max of val as predecessor, wins wherever
+// it beats every candidate inside.  (max, arg-max) of a frame's values are reduced while the values are produced and read by the next
+// frame.  Only float64 adds and compares in the host's association: (val[from] + lt), then log_obs + best.
+// Dynamic LDS: val[2][S] | wmax[2][16] (doubles) | warg[2][16] (ints).
+__global__ __launch_bounds__(1024) void k_feat_viterbi(const double* __restrict__ log_obs, const int* __restrict__ first_frame,
+                                                       const int* __restrict__ n_frames, int n_bins, int hw, const double* __restrict__ trans,
+                                                       const double* __restrict__ log_init, double log_tiny, int* __restrict__ ptr,
+                                                       int* __restrict__ states, int states_stride) {
+    extern __shared__ double vsh[];
+    const int S = 2 * n_bins, W = 2 * hw + 1;
+    double* val = vsh;
+    double* wmax = val + 2 * S;
+    int* warg = (int*)(wmax + 32);
+    const int clip = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
+    const int T = n_frames[clip];
+    const int64_t f0 = first_frame[clip];
+    for (int t = 0; t < T; ++t) {
+        double* cur = val + (t & 1) * S;
+        const double* prev = val + ((t & 1) ^ 1) * S;
+        const double* lo = log_obs + (f0 + t) * S;
+        double pmax = -INFINITY;
+        int parg = INT_MAX;
+        if (t > 0)
+            for (int w = 0; w < n_waves; ++w) vit_take(pmax, parg, wmax[((t & 1) ^ 1) * 16 + w], warg[((t & 1) ^ 1) * 16 + w]);
+        const double out_best = pmax + log_tiny;
+        double lbest = -INFINITY;
+        int larg = INT_MAX;
+        for (int s = tid; s < S; s += blockDim.x) {
+            double v;
+            if (t == 0) {
+                v = lo[s] + log_init[s];
+            } else {
+                const int v_to = s >= n_bins ? 1 : 0, j = s - v_to * n_bins;
+                const int o_lo = -hw > -j ? -hw : -j, o_hi = hw < n_bins - 1 - j ? hw : n_bins - 1 - j;
+                double best = -INFINITY;
+                int arg = 0;
+                for (int v_from = 0; v_from < 2; ++v_from) {
+                    const double* tab = trans + ((int64_t)(v_from == v_to ? 0 : 1) * W + (o_lo + hw)) * n_bins + j;
+                    const double* pv = prev + v_from * n_bins + j + o_lo;
+                    for (int o = o_lo; o <= o_hi; ++o, ++pv, tab += n_bins) {
+                        const double cand = *pv + *tab;
+                        if (cand > best) { best = cand; arg = v_from * n_bins + j + o; }
+                    }
+                }
+                if (out_best > best) { best = out_best; arg = parg; }
+                ptr[(f0 + t) * S + s] = arg;
+                v = lo[s] + best;
+            }
+            cur[s] = v;
+            if (v > lbest || larg == INT_MAX) { lbest = v; larg = s; }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) vit_take(lbest, larg, __shfl_xor(lbest, o, 64), __shfl_xor(larg, o, 64));
+        if (lane == 0) { wmax[(t & 1) * 16 + wave] = lbest; warg[(t & 1) * 16 + wave] = larg; }
+        __syncthreads();                            // publishes cur, the wave maxima and (workgroup scope) this frame's backpointers
+    }
+    int* out = states + (int64_t)clip * states_stride;
+    for (int t = T + tid; t < states_stride; t += blockDim.x) out[t] = -1;
+    if (tid == 0 && T > 0) {
+        double fmax_v = -INFINITY;
+        int st = INT_MAX;
+        for (int w = 0; w < n_waves; ++w) vit_take(fmax_v, st, wmax[((T - 1) & 1) * 16 + w], warg[((T - 1) & 1) * 16 + w]);
+        if (st < 0 || st >= S) st = 0;
+        out[T - 1] = st;
+        for (int t = T - 2; t >= 0; --t) {
+            st = ptr[(f0 + t + 1) * S + st];
+            out[t] = st;
+        }
+    }
+}
+
+template <class T>
+int feat_grow(rt_ctx* ctx, T*& p, size_t& cap, size_t need) {
+    if (need <= cap && p) return RT_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    if (need == 0) need = 1;
+    RT_HIP(ctx, hipMalloc((void**)&p, need * sizeof(T)));
+    cap = need;
+    return RT_OK;
+}
+
+// log-obs [n_frames][2 n_bins] of cmnd [n_frames][n_lags], both in HBM, on the context's stream
+int feat_observe(rt_features* s, const double* d_cmnd, int n_frames, int n_lags, int min_p, double* d_logobs) {
+    const int mcap = (n_lags + 1) / 2 + 1;
+    const size_t lds = (size_t)(n_lags + s->pm_bins + 2 * mcap) * 8 + (size_t)(3 * mcap + s->pm_thr) * 4;
+    if (lds > 60 * 1024) return rt_fail(s->ctx, RT_ERR_INVALID, "pitch observation stage: %zu bytes of LDS per frame", lds);
+    hipLaunchKernelGGL(k_feat_observe, dim3(n_frames), dim3(256), lds, s->ctx->stream, d_cmnd, n_lags, min_p, s->pm_bins, s->pm_thr, s->pm_d_thr,
+                       s->pm_d_beta, s->pm_sr, s->pm_fmin, s->pm_bins_per_octave, s->pm_no_trough, d_logobs);
+    return RT_OK;
+}
+
+// state paths [n_clips][stride] (-1 behind a clip's last frame) of the log-obs of n_clips clips laid back to back; d_meta = first frame of
+// every clip, then its frame count
+int feat_viterbi(rt_features* s, const double* d_logobs, const int* d_meta, int n_clips, int* d_ptr, int* d_states, int stride) {
+    const int S = 2 * s->pm_bins, rounds = (S + 1023) / 1024;
+    const int threads = std::min(1024, (((S + rounds - 1) / rounds) + 63) / 64 * 64);
+    const size_t lds = (size_t)(2 * S + 32) * 8 + 32 * 4;
+    hipLaunchKernelGGL(k_feat_viterbi, dim3(n_clips), dim3(threads), lds, s->ctx->stream, d_logobs, d_meta, d_meta + n_clips, s->pm_bins, s->pm_hw,
+                       s->pm_d_trans, s->pm_d_init, s->pm_log_tiny, d_ptr, d_states, stride);
+    return RT_OK;
+}
+
 int feat_tables(rt_features* s) {
     rt_ctx* ctx = s->ctx;
     std::vector<double> c(F_NFFT), sn(F_NFFT);
@@ -312,7 +556,9 @@ int rt_features_destroy(rt_features* s) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (void* p : {(void*)s->d_twc, (void*)s->d_tws, (void*)s->d_melT, (void*)s->d_dct, (void*)s->d_resamp, (void*)s->pcm16k, (void*)s->logmel,
-                    (void*)s->mfcc, (void*)s->cmnd, (void*)s->d_gmax, (void*)s->d_stats, (void*)s->d_lpc})
+                    (void*)s->mfcc, (void*)s->cmnd, (void*)s->d_gmax, (void*)s->d_stats, (void*)s->d_lpc, (void*)s->pm_d_thr, (void*)s->pm_d_beta,
+                    (void*)s->pm_d_trans, (void*)s->pm_d_init, (void*)s->b_pcm, (void*)s->b_logmel, (void*)s->b_mfcc, (void*)s->b_cmnd, (void*)s->b_logobs,
+                    (void*)s->b_ptr, (void*)s->b_states, (void*)s->b_stats, (void*)s->b_lpc, (void*)s->b_gmax, (void*)s->b_meta})
         if (p) (void)hipFree(p);
     delete s;
     return RT_OK;
@@ -378,6 +624,159 @@ int rt_features_extract(rt_features* s, const float* d_pcm, int64_t n_samples, i
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_n_mfcc_frames) *h_n_mfcc_frames = n_frames;
     *h_n_pitch_frames = n_frames;
+    return RT_OK;
+}
+
+int rt_features_set_pitch_model(rt_features* s, int32_t n_bins, int32_t half_width, int32_t n_thresholds, const double* h_thresholds,
+                                const double* h_beta, const double* h_log_trans, const double* h_log_init, double log_tiny, double pitch_sr, double fmin,
+                                int32_t bins_per_semitone, double no_trough_prob) {
+    if (!s || n_bins < 1 || n_bins > 2000 || half_width < 0 || half_width > 4096 || n_thresholds < 1 || n_thresholds > 1024 || !h_thresholds || !h_beta ||
+        !h_log_trans || !h_log_init || !(pitch_sr > 0) || !(fmin > 0) || bins_per_semitone < 1)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_features_set_pitch_model: bad argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->pm_set = false;
+    for (double** p : {&s->pm_d_thr, &s->pm_d_beta, &s->pm_d_trans, &s->pm_d_init}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    const size_t n_trans = (size_t)2 * (2 * half_width + 1) * n_bins;
+    RT_HIP(ctx, hipMalloc((void**)&s->pm_d_thr, (size_t)n_thresholds * 8));
+    RT_HIP(ctx, hipMalloc((void**)&s->pm_d_beta, (size_t)n_thresholds * 8));
+    RT_HIP(ctx, hipMalloc((void**)&s->pm_d_trans, n_trans * 8));
+    RT_HIP(ctx, hipMalloc((void**)&s->pm_d_init, (size_t)2 * n_bins * 8));
+    RT_HIP(ctx, hipMemcpy(s->pm_d_thr, h_thresholds, (size_t)n_thresholds * 8, hipMemcpyHostToDevice));
+    RT_HIP(ctx, hipMemcpy(s->pm_d_beta, h_beta, (size_t)n_thresholds * 8, hipMemcpyHostToDevice));
+    RT_HIP(ctx, hipMemcpy(s->pm_d_trans, h_log_trans, n_trans * 8, hipMemcpyHostToDevice));
+    RT_HIP(ctx, hipMemcpy(s->pm_d_init, h_log_init, (size_t)2 * n_bins * 8, hipMemcpyHostToDevice));
+    s->pm_bins = n_bins; s->pm_hw = half_width; s->pm_thr = n_thresholds;
+    s->pm_log_tiny = log_tiny; s->pm_sr = pitch_sr; s->pm_fmin = fmin; s->pm_bins_per_octave = 12.0 * bins_per_semitone; s->pm_no_trough = no_trough_prob;
+    s->pm_set = true;
+    return RT_OK;
+}
+
+int rt_features_extract_batch(rt_features* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
+                              int32_t min_period, int32_t max_period, int32_t lpc_order, double* h_mfcc_stats26, double* h_lpc, int32_t* h_states,
+                              int32_t cap_frames, int32_t* h_n_pitch_frames) {
+    if (!s || !d_pcm || !n_samples || n_clips < 1 || sample_rate_in < 1000 || !h_mfcc_stats26 || !h_lpc || !h_states || !h_n_pitch_frames || lpc_order < 1 ||
+        lpc_order > LPC_MAX || min_period < 1 || max_period <= min_period || max_period > P_FRAME - P_WIN - 1 || cap_frames < 1)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_features_extract_batch: bad argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (!s->pm_set) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: no pitch model (rt_features_set_pitch_model)");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const bool resample = sample_rate_in != F_SR;
+    if (resample) FT_TRY(feat_resampler(s, sample_rate_in));
+    // every clip's geometry on the host first: nothing is launched for a batch that holds a bad clip
+    std::vector<int64_t> n16(n_clips), pcm_off(n_clips);
+    s->h_meta.assign((size_t)2 * n_clips, 0);
+    int64_t pcm_total = 0, frames_total = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        if (!d_pcm[c] || n_samples[c] < 2) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: clip %d has fewer than two samples", c);
+        n16[c] = resample ? (n_samples[c] * s->rs_L + s->rs_M - 1) / s->rs_M : n_samples[c];
+        if (n16[c] < 2) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: clip %d has fewer than two samples at 16 kHz", c);
+        const int64_t nf = 1 + n16[c] / F_HOP;
+        if (nf > cap_frames) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: clip %d has %lld pitch frames, room for %d", c, (long long)nf, cap_frames);
+        pcm_off[c] = pcm_total;
+        pcm_total += resample ? n16[c] : 0;
+        s->h_meta[c] = (int)frames_total;
+        s->h_meta[n_clips + c] = (int)nf;
+        frames_total += nf;
+        if (frames_total > (int64_t)1 << 20) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: more than 2^20 frames in one batch");
+    }
+    const int n_lags = max_period - min_period + 1, S = 2 * s->pm_bins, F = (int)frames_total;
+    FT_TRY(feat_grow(ctx, s->b_pcm, s->b_pcm_cap, (size_t)pcm_total));
+    FT_TRY(feat_grow(ctx, s->b_logmel, s->b_logmel_cap, (size_t)F * F_MELS));
+    FT_TRY(feat_grow(ctx, s->b_mfcc, s->b_mfcc_cap, (size_t)F * F_MFCC));
+    FT_TRY(feat_grow(ctx, s->b_cmnd, s->b_cmnd_cap, (size_t)F * n_lags));
+    FT_TRY(feat_grow(ctx, s->b_logobs, s->b_logobs_cap, (size_t)F * S));
+    FT_TRY(feat_grow(ctx, s->b_ptr, s->b_ptr_cap, (size_t)F * S));
+    FT_TRY(feat_grow(ctx, s->b_states, s->b_states_cap, (size_t)n_clips * cap_frames));
+    FT_TRY(feat_grow(ctx, s->b_stats, s->b_stats_cap, (size_t)n_clips * 2 * F_MFCC));
+    FT_TRY(feat_grow(ctx, s->b_lpc, s->b_lpc_cap, (size_t)n_clips * (lpc_order + 1)));
+    FT_TRY(feat_grow(ctx, s->b_gmax, s->b_gmax_cap, (size_t)n_clips));
+    FT_TRY(feat_grow(ctx, s->b_meta, s->b_meta_cap, (size_t)2 * n_clips));
+    RT_HIP(ctx, hipMemcpyAsync(s->b_meta, s->h_meta.data(), (size_t)2 * n_clips * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)s->b_gmax, (int)0x80000000, (size_t)n_clips, ctx->stream));
+    // front half: the single-clip call's kernels with the single-clip call's arguments, clip after clip on the stream - every clip's
+    // MFCC statistics, difference function and LPC carry the bits rt_features_extract gives for that clip alone
+    for (int c = 0; c < n_clips; ++c) {
+        const float* src = d_pcm[c];
+        if (resample) {
+            float* dst = s->b_pcm + pcm_off[c];
+            hipLaunchKernelGGL(k_feat_resample, dim3((unsigned)std::min<int64_t>((n16[c] + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_pcm[c], n_samples[c],
+                               dst, n16[c], s->rs_L, s->rs_M, s->rs_taps, s->rs_half, s->d_resamp);
+            src = dst;
+        }
+        const int64_t f0 = s->h_meta[c];
+        const int nf = s->h_meta[n_clips + c];
+        hipLaunchKernelGGL(k_feat_logmel, dim3(nf), dim3(256), (size_t)(3 * F_NFFT + F_BINS) * sizeof(double), ctx->stream, src, n16[c], s->d_twc, s->d_tws,
+                           s->d_melT, s->b_logmel + f0 * F_MELS, s->b_gmax + c);
+        hipLaunchKernelGGL(k_feat_dct, dim3(nf), dim3(64), 0, ctx->stream, s->b_logmel + f0 * F_MELS, s->b_gmax + c, s->d_dct, s->b_mfcc + f0 * F_MFCC);
+        hipLaunchKernelGGL(k_feat_stats, dim3(F_MFCC), dim3(64), 0, ctx->stream, s->b_mfcc + f0 * F_MFCC, nf, s->b_stats + (size_t)c * 2 * F_MFCC);
+        hipLaunchKernelGGL(k_feat_cmnd, dim3(nf), dim3(512), 0, ctx->stream, src, n16[c], min_period, max_period, s->b_cmnd + f0 * n_lags);
+        hipLaunchKernelGGL(k_feat_lpc, dim3(1), dim3(64), 0, ctx->stream, src, n16[c], lpc_order, s->b_lpc + (size_t)c * (lpc_order + 1));
+    }
+    RT_HIP(ctx, hipGetLastError());
+    // back half: one launch each over every frame / every clip of the batch
+    FT_TRY(feat_observe(s, s->b_cmnd, F, n_lags, min_period, s->b_logobs));
+    FT_TRY(feat_viterbi(s, s->b_logobs, s->b_meta, n_clips, s->b_ptr, s->b_states, cap_frames));
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(h_mfcc_stats26, s->b_stats, (size_t)n_clips * 2 * F_MFCC * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(h_lpc, s->b_lpc, (size_t)n_clips * (lpc_order + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(h_states, s->b_states, (size_t)n_clips * cap_frames * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int c = 0; c < n_clips; ++c) h_n_pitch_frames[c] = s->h_meta[n_clips + c];
+    return RT_OK;
+}
+
+int rt_debug_features_observe(rt_features* s, const double* h_cmnd, int32_t n_frames, int32_t n_lags, int32_t min_period, double* h_log_obs) {
+    if (!s || !h_cmnd || !h_log_obs || n_frames < 1 || n_frames > (1 << 20) || n_lags < 2 || n_lags > P_FRAME - P_WIN - 1 || min_period < 1)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_features_observe: bad argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (!s->pm_set) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_observe: no pitch model (rt_features_set_pitch_model)");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const int S = 2 * s->pm_bins;
+    FT_TRY(feat_grow(ctx, s->b_cmnd, s->b_cmnd_cap, (size_t)n_frames * n_lags));
+    FT_TRY(feat_grow(ctx, s->b_logobs, s->b_logobs_cap, (size_t)n_frames * S));
+    RT_HIP(ctx, hipMemcpyAsync(s->b_cmnd, h_cmnd, (size_t)n_frames * n_lags * 8, hipMemcpyHostToDevice, ctx->stream));
+    FT_TRY(feat_observe(s, s->b_cmnd, n_frames, n_lags, min_period, s->b_logobs));
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(h_log_obs, s->b_logobs, (size_t)n_frames * S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+int rt_debug_features_viterbi(rt_features* s, const double* h_log_obs, const int32_t* h_n_frames, int32_t n_clips, int32_t* h_states, int32_t stride) {
+    if (!s || !h_log_obs || !h_n_frames || !h_states || n_clips < 1 || stride < 1)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_features_viterbi: bad argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (!s->pm_set) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_viterbi: no pitch model (rt_features_set_pitch_model)");
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    s->h_meta.assign((size_t)2 * n_clips, 0);
+    int64_t frames_total = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        if (h_n_frames[c] < 1 || h_n_frames[c] > stride) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_viterbi: clip %d has %d frames, room for %d", c, h_n_frames[c], stride);
+        s->h_meta[c] = (int)frames_total;
+        s->h_meta[n_clips + c] = h_n_frames[c];
+        frames_total += h_n_frames[c];
+        if (frames_total > (int64_t)1 << 20) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_viterbi: more than 2^20 frames");
+    }
+    const int S = 2 * s->pm_bins, F = (int)frames_total;
+    FT_TRY(feat_grow(ctx, s->b_logobs, s->b_logobs_cap, (size_t)F * S));
+    FT_TRY(feat_grow(ctx, s->b_ptr, s->b_ptr_cap, (size_t)F * S));
+    FT_TRY(feat_grow(ctx, s->b_states, s->b_states_cap, (size_t)n_clips * stride));
+    FT_TRY(feat_grow(ctx, s->b_meta, s->b_meta_cap, (size_t)2 * n_clips));
+    RT_HIP(ctx, hipMemcpyAsync(s->b_meta, s->h_meta.data(), (size_t)2 * n_clips * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(s->b_logobs, h_log_obs, (size_t)F * S * 8, hipMemcpyHostToDevice, ctx->stream));
+    FT_TRY(feat_viterbi(s, s->b_logobs, s->b_meta, n_clips, s->b_ptr, s->b_states, stride));
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(h_states, s->b_states, (size_t)n_clips * stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

@@ -4,8 +4,10 @@ The reference's accent-drift classifier scores a 286-dimensional vector per segm
 resemblyzer's 256-d speaker embedding + 13 MFCC means + 13 MFCC standard deviations + F0 mean / std (librosa.pyin) + the first two
 LPC formants, all computed by librosa on a temporary WAV (base_tts.py:821-830).  This module produces the 30 hand-crafted
 dimensions from the waveform in HBM: the per-sample work runs in csrc/features.hip behind ``rt_features_extract`` (resampler,
-MFCC, the pYIN difference function, Burg LPC); what is left for the host is arithmetic on a few kilobytes - pYIN's trough
-statistics and Viterbi pass over the [frames][329] difference function, and the roots of one degree-18 polynomial.
+MFCC, the pYIN difference function, Burg LPC).  The single-clip path (``HandcraftedFeatures.__call__``) finishes pYIN here on the
+host - trough statistics and Viterbi pass over the [frames][329] difference function - and these host functions are the
+definition of the two kernels that do the same for a whole chunk of clips in one native call (``HandcraftedFeatures.batch``,
+``rt_features_extract_batch``): there the host is left with the F0 statistics and the roots of one degree-18 polynomial per clip.
 
 The 256-d embedding is NOT produced: resemblyzer's network is a pretrained checkpoint (no weights offline), and the classifier
 itself is a pickled scikit-learn model this build will not load.  ``make_drift_scorer`` therefore takes the classifier as a
@@ -18,8 +20,9 @@ reference's own quirk of leaving ``librosa.pyin``'s default ``sr=22050`` in plac
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
-from typing import Callable, Optional
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -47,14 +50,66 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_features_destroy.argtypes = [vp]
     lib.rt_features_geometry.argtypes = [i32, C.c_double, C.c_double, C.POINTER(i32), C.POINTER(i32)]
     lib.rt_features_extract.argtypes = [vp, vp, i64, i32, i32, i32, i32, pd, C.POINTER(i32), pd, i32, C.POINTER(i32), pd]
+    lib.rt_features_set_pitch_model.argtypes = [vp, i32, i32, i32, pd, pd, pd, pd, C.c_double, C.c_double, C.c_double, i32, C.c_double]
+    lib.rt_features_extract_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, i32, i32, i32, pd, pd, C.POINTER(i32), i32, C.POINTER(i32)]
+    lib.rt_debug_features_observe.argtypes = [vp, pd, i32, i32, i32, pd]
+    lib.rt_debug_features_viterbi.argtypes = [vp, pd, C.POINTER(i32), i32, C.POINTER(i32), i32]
     _DECLARED = True
 
 
 # ------------------------------------------------------------------------------------------------ pYIN, the host half
+def _thresholds() -> np.ndarray:
+    """The trough thresholds, ascending: the upper edges of N_THRESHOLDS equal bins of [0, 1]."""
+    return np.linspace(0.0, 1.0, N_THRESHOLDS + 1)[1:]
+
+
 def _beta_probs() -> np.ndarray:
     """Prior mass of each threshold bin under Beta(2, 18): I_x(2, 18) = 1 - (1 - x)^18 (1 + 18 x)."""
     x = np.linspace(0.0, 1.0, N_THRESHOLDS + 1)
     return np.diff(1.0 - (1.0 - x) ** 18 * (1.0 + 18.0 * x))
+
+
+def default_n_bins() -> int:
+    return int(math.floor(12 * BINS_PER_SEMITONE * math.log2(FMAX / FMIN))) + 1
+
+
+def default_half_width() -> int:
+    return (int(round(MAX_TRANSITION_RATE * 12 * HOP / PITCH_SR)) * BINS_PER_SEMITONE + 1) // 2
+
+
+@functools.lru_cache(maxsize=4)
+def _transition_tables(n_bins: int, hw: int):
+    """What the Viterbi pass adds and compares, every transcendental evaluated here once (the one source of ``viterbi_banded`` and
+    of the tables ``pitch_model`` uploads): ``srcc`` / ``ok`` [2 hw + 1][n_bins] = the from-bin of (offset, to-bin), clipped, and
+    whether it exists; ``log_trans`` [2][2 hw + 1][n_bins] = log(w_local * p + tiny) for p = stay (0) / switch (1);
+    ``log_init`` [2 n_bins] = log(p_init + tiny); ``neg`` = log(tiny), what the dense matrix holds outside the band.
+    (Cached: callers read the arrays, nobody writes them.)"""
+    tiny = np.finfo(np.float64).tiny
+    j = np.arange(n_bins)
+    # local[i][j] = (hw + 1 - |i - j|) / (hw + 1) / rowsum(i) for |i - j| <= hw
+    lo_i, hi_i = np.maximum(0, j - hw), np.minimum(n_bins - 1, j + hw)
+    tri = lambda d: (hw + 1.0 - np.abs(d)) / (hw + 1.0)                           # noqa: E731
+    rowsum = np.array([tri(np.arange(lo_i[i], hi_i[i] + 1) - i).sum() for i in range(n_bins)])
+    offs = np.arange(-hw, hw + 1)
+    src = j[None, :] + offs[:, None]                                             # [offset][to] = from-bin
+    ok = (src >= 0) & (src < n_bins)
+    srcc = np.clip(src, 0, n_bins - 1)
+    w_local = np.where(ok, tri(offs)[:, None] / rowsum[srcc], 0.0)               # local[from][to]
+    log_trans = np.stack([np.log(w_local * (1.0 - SWITCH_PROB) + tiny), np.log(w_local * SWITCH_PROB + tiny)])
+    p_init = np.zeros(2 * n_bins)
+    p_init[n_bins:] = 1.0 / n_bins
+    return srcc, ok, log_trans, np.log(p_init + tiny), np.log(tiny)
+
+
+def pitch_model(n_bins: Optional[int] = None, hw: Optional[int] = None) -> dict:
+    """The tables of pYIN's back half as ``rt_features_set_pitch_model`` takes them (float64, C order), built with the numpy
+    expressions the host functions use: ``thresholds`` / ``beta`` [N_THRESHOLDS], ``log_trans`` [2][2 hw + 1][n_bins],
+    ``log_init`` [2 n_bins], ``log_tiny``."""
+    n_bins = default_n_bins() if n_bins is None else int(n_bins)
+    hw = default_half_width() if hw is None else int(hw)
+    _, _, log_trans, log_init, neg = _transition_tables(n_bins, hw)
+    return {"n_bins": n_bins, "half_width": hw, "thresholds": np.ascontiguousarray(_thresholds()), "beta": np.ascontiguousarray(_beta_probs()),
+            "log_trans": np.ascontiguousarray(log_trans), "log_init": np.ascontiguousarray(log_init), "log_tiny": float(neg)}
 
 
 def observation_log_probs(cmnd: np.ndarray, min_period: int, n_bins: int) -> np.ndarray:
@@ -62,7 +117,7 @@ def observation_log_probs(cmnd: np.ndarray, min_period: int, n_bins: int) -> np.
     cumulative-mean-normalised difference function [frames][lags]: troughs, thresholds below each trough, Boltzmann(2) prior over
     the troughs under a threshold, Beta(2, 18) prior over the thresholds, parabolic refinement of the trough's lag."""
     T, n_lags = cmnd.shape
-    thr = np.linspace(0.0, 1.0, N_THRESHOLDS + 1)[1:]
+    thr = _thresholds()
     beta = _beta_probs()
     tiny = np.finfo(np.float64).tiny
     obs = np.zeros((T, 2 * n_bins))
@@ -98,38 +153,24 @@ def observation_log_probs(cmnd: np.ndarray, min_period: int, n_bins: int) -> np.
     return np.log(obs + tiny)
 
 
-def viterbi_banded(log_obs: np.ndarray, n_bins: int) -> np.ndarray:
+def viterbi_banded(log_obs: np.ndarray, n_bins: int, hw: Optional[int] = None) -> np.ndarray:
     """Most likely state path of pyin's HMM: 2 x n_bins states, pitch transitions a triangle over +-hw bins (row-normalised at the
     edges), voicing kept with probability 0.99.  The transition matrix is never formed: the best predecessor of (voicing v, bin j)
     is searched over the 2 x (2 hw + 1) states that can reach it, lowest state index first on ties (np.argmax's rule on the dense
-    matrix, which oracle/features.py builds)."""
+    matrix, which oracle/features.py builds).  This is the definition of csrc/features.hip k_feat_viterbi."""
     T = log_obs.shape[0]
-    hw = (int(round(MAX_TRANSITION_RATE * 12 * HOP / PITCH_SR)) * BINS_PER_SEMITONE + 1) // 2
-    tiny = np.finfo(np.float64).tiny
+    srcc, ok, log_trans, log_init, neg = _transition_tables(n_bins, default_half_width() if hw is None else int(hw))
     j = np.arange(n_bins)
-    # local[i][j] = (hw + 1 - |i - j|) / (hw + 1) / rowsum(i) for |i - j| <= hw
-    lo_i, hi_i = np.maximum(0, j - hw), np.minimum(n_bins - 1, j + hw)
-    tri = lambda d: (hw + 1.0 - np.abs(d)) / (hw + 1.0)                           # noqa: E731
-    rowsum = np.array([tri(np.arange(lo_i[i], hi_i[i] + 1) - i).sum() for i in range(n_bins)])
-    offs = np.arange(-hw, hw + 1)
-    src = j[None, :] + offs[:, None]                                             # [offset][to] = from-bin
-    ok = (src >= 0) & (src < n_bins)
-    srcc = np.clip(src, 0, n_bins - 1)
-    w_local = np.where(ok, tri(offs)[:, None] / rowsum[srcc], 0.0)               # local[from][to]
     S = 2 * n_bins
-    val = np.full(S, -np.inf)
     ptr = np.zeros((T, S), dtype=np.int64)
-    p_init = np.zeros(S)
-    p_init[n_bins:] = 1.0 / n_bins
-    val = log_obs[0] + np.log(p_init + tiny)
-    neg = np.log(tiny)                                                            # log(0 + tiny): what the dense matrix holds outside the band
+    val = log_obs[0] + log_init
     for t in range(1, T):
         new = np.empty(S)
         for v_to in (0, 1):
             best = np.full(n_bins, -np.inf)
             arg = np.zeros(n_bins, dtype=np.int64)
             for v_from in (0, 1):                                                 # ascending state index: voiced block first
-                lt = np.log(w_local * (1.0 - SWITCH_PROB if v_from == v_to else SWITCH_PROB) + tiny)
+                lt = log_trans[0 if v_from == v_to else 1]
                 cand = np.where(ok, val[v_from * n_bins + srcc] + lt, -np.inf)    # [offset][to]
                 k = np.argmax(cand, axis=0)                                       # first maximum = lowest from-bin
                 c = cand[k, j]
@@ -152,13 +193,19 @@ def viterbi_banded(log_obs: np.ndarray, n_bins: int) -> np.ndarray:
     return states
 
 
-def f0_from_cmnd(cmnd: np.ndarray, min_period: int) -> np.ndarray:
-    """F0 per frame (NaN = unvoiced) from the difference function: the back half of librosa.pyin."""
-    n_bins = int(math.floor(12 * BINS_PER_SEMITONE * math.log2(FMAX / FMIN))) + 1
-    states = viterbi_banded(observation_log_probs(np.asarray(cmnd, dtype=np.float64), min_period, n_bins), n_bins)
+def f0_from_states(states: np.ndarray, n_bins: int) -> np.ndarray:
+    """F0 per frame (NaN = unvoiced) of a state path: bin b of either voicing is FMIN 2^(b / (12 bins per semitone))."""
+    states = np.asarray(states, dtype=np.int64)
     f0 = FMIN * 2.0 ** ((states % n_bins) / (12.0 * BINS_PER_SEMITONE))
     f0[states >= n_bins] = np.nan
     return f0
+
+
+def f0_from_cmnd(cmnd: np.ndarray, min_period: int) -> np.ndarray:
+    """F0 per frame (NaN = unvoiced) from the difference function: the back half of librosa.pyin."""
+    n_bins = default_n_bins()
+    states = viterbi_banded(observation_log_probs(np.asarray(cmnd, dtype=np.float64), min_period, n_bins), n_bins)
+    return f0_from_states(states, n_bins)
 
 
 def formants_from_lpc(a: np.ndarray):
@@ -184,6 +231,7 @@ class HandcraftedFeatures:
         if self.lib.rt_features_geometry(PITCH_SR, FMIN, FMAX, C.byref(lo), C.byref(hi)) != 0:
             raise ValueError("rt_features_geometry refused the pitch range")
         self.min_period, self.max_period = int(lo.value), int(hi.value)
+        self.n_bins: Optional[int] = None                                         # set with the pitch model (batched path)
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -209,6 +257,67 @@ class HandcraftedFeatures:
                        "rt_features_extract")
         return np.array(stats, dtype=np.float64), cmnd[: npf.value], np.array(lpc, dtype=np.float64)
 
+    # ---- the batched path: one native call and one host synchronisation per chunk of clips, pYIN's back half on the device
+    def set_pitch_model(self, model: Optional[dict] = None) -> None:
+        """Upload the tables of pYIN's back half (``pitch_model()``; the real geometry unless a test hands in its own)."""
+        m = pitch_model() if model is None else model
+        pd = C.POINTER(C.c_double)
+        arr = {k: np.ascontiguousarray(m[k], dtype=np.float64) for k in ("thresholds", "beta", "log_trans", "log_init")}
+        if arr["log_trans"].shape != (2, 2 * m["half_width"] + 1, m["n_bins"]) or arr["log_init"].shape != (2 * m["n_bins"],) or \
+                arr["thresholds"].shape != arr["beta"].shape:
+            raise ValueError("pitch model tables do not have the shapes of pitch_model()")
+        self.ctx.check(self.lib.rt_features_set_pitch_model(
+            self.handle, int(m["n_bins"]), int(m["half_width"]), int(arr["thresholds"].shape[0]), arr["thresholds"].ctypes.data_as(pd),
+            arr["beta"].ctypes.data_as(pd), arr["log_trans"].ctypes.data_as(pd), arr["log_init"].ctypes.data_as(pd), float(m["log_tiny"]),
+            float(PITCH_SR), float(FMIN), int(BINS_PER_SEMITONE), float(NO_TROUGH_PROB)), "rt_features_set_pitch_model")
+        self.n_bins = int(m["n_bins"])
+
+    def _extract_batch(self, audios: Sequence, sample_rate: int):
+        """(mfcc statistics [n][26], lpc [n][order + 1], state paths: n arrays of one state per pitch frame)."""
+        if self.n_bins is None:
+            self.set_pitch_model()
+        dev = f"cuda:{self.ctx.device_ordinal}"
+        xs = []
+        for audio in audios:
+            x = audio if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio, dtype=np.float32))
+            x = x.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if x.numel() < 2:
+                raise ValueError("feature extraction needs at least two samples")
+            xs.append(x)
+        n = len(xs)
+        if n == 0:
+            return np.zeros((0, 26)), np.zeros((0, LPC_ORDER + 1)), []
+        torch.cuda.current_stream(torch.device(dev)).synchronize()
+        sr = int(sample_rate)
+        cap = 2 + max(-(-int(x.numel()) * SR // sr) if sr != SR else int(x.numel()) for x in xs) // HOP
+        ptrs = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
+        lens = (C.c_int64 * n)(*[int(x.numel()) for x in xs])
+        stats = np.zeros((n, 26), dtype=np.float64)
+        lpc = np.zeros((n, LPC_ORDER + 1), dtype=np.float64)
+        states = np.zeros((n, cap), dtype=np.int32)
+        npf = (C.c_int32 * n)()
+        pd = C.POINTER(C.c_double)
+        self.ctx.check(self.lib.rt_features_extract_batch(self.handle, ptrs, lens, n, sr, self.min_period, self.max_period, LPC_ORDER,
+                                                          stats.ctypes.data_as(pd), lpc.ctypes.data_as(pd), states.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          cap, npf), "rt_features_extract_batch")
+        return stats, lpc, [states[c, : npf[c]].astype(np.int64) for c in range(n)]
+
+    def f0_states(self, audios: Sequence, sample_rate: int) -> List[np.ndarray]:
+        """The Viterbi state path of every clip (voiced pitch bin b = state b, unvoiced = n_bins + b), decoded on the device."""
+        return self._extract_batch(audios, sample_rate)[2]
+
+    def batch(self, audios: Sequence, sample_rate: int) -> np.ndarray:
+        """``__call__`` for a whole chunk of clips, [n][30]: one native call, one host synchronisation.  The state paths come from
+        the device; the host finishes the F0 statistics and the formants of every clip."""
+        stats, lpc, states = self._extract_batch(audios, sample_rate)
+        out = np.zeros((len(states), 30), dtype=np.float64)
+        for c, st in enumerate(states):
+            f0 = f0_from_states(st, self.n_bins)
+            v = f0[~np.isnan(f0)]
+            f1, f2 = formants_from_lpc(lpc[c])
+            out[c] = np.concatenate([stats[c], [float(v.mean()) if v.size else 0.0, float(v.std()) if v.size else 0.0, f1, f2]])
+        return out
+
     def __call__(self, audio, sample_rate: int) -> np.ndarray:
         """[13 MFCC means | 13 MFCC stds | F0 mean | F0 std | F1 | F2] = elements 256..285 of the reference's feature vector."""
         stats, cmnd, lpc = self.raw(audio, sample_rate)
@@ -223,10 +332,20 @@ def make_drift_scorer(extractor: HandcraftedFeatures, classifier: Callable[[np.n
     """A ``drift_scorer`` hook for the provider (provider.BatchedPipeline): ``(audio tensor, sample_rate) -> probability``.
     ``classifier`` maps the feature vector to the accent-drift probability (the reference's is a pickled scikit-learn model,
     ``predict_proba(...)[0, 1]``); ``embed`` optionally supplies the speaker-embedding dimensions that precede the hand-crafted ones
-    in the reference's layout."""
+    in the reference's layout.  The callable carries ``score.batch(audios, sample_rate) -> list of probabilities``: the features of a
+    whole chunk from one ``extractor.batch`` call, which the provider uses when it validates a chunk."""
     def score(audio: torch.Tensor, sample_rate: int) -> float:
         f = extractor(audio, sample_rate)
         if embed is not None:
             f = np.concatenate([np.asarray(embed(audio, sample_rate), dtype=np.float64).reshape(-1), f])
         return float(classifier(f))
+
+    def batch(audios: Sequence[torch.Tensor], sample_rate: int) -> List[float]:
+        out = []
+        for audio, f in zip(audios, extractor.batch(audios, sample_rate)):
+            if embed is not None:
+                f = np.concatenate([np.asarray(embed(audio, sample_rate), dtype=np.float64).reshape(-1), f])
+            out.append(float(classifier(f)))
+        return out
+    score.batch = batch
     return score

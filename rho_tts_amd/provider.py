@@ -174,7 +174,8 @@ class BatchedPipeline:
                 # RNG stream of a segment = its index in the work list of the whole call: independent of how the list is cut into
                 # batches and of how many ranks share it
                 audios = self._generate_chunk([work[w][2] for w in chunk], [stream_ids[w] for w in chunk], token)
-                for w, a in zip(chunk, audios):
+                drifts = self._chunk_drifts(audios) if self.max_iterations > 1 else None
+                for k, (w, a) in enumerate(zip(chunk, audios)):
                     if a is None:
                         retry.append(w)
                         continue
@@ -185,7 +186,7 @@ class BatchedPipeline:
                         if getattr(self, "auto_sort_good_dir", None) or getattr(self, "auto_sort_bad_dir", None):
                             self._auto_sort_only(a)          # drift detection for auto-sort even without validation retries (:801-818)
                         continue
-                    if self._validate_segment(a, work[w][2], state[w]):
+                    if self._validate_segment(a, work[w][2], state[w], None if drifts is None else drifts[k]):
                         accepted[w] = a                      # valid: this attempt's audio is kept (:859)
                     else:
                         retry.append(w)
@@ -260,10 +261,29 @@ class BatchedPipeline:
     drift_scorer = None        # Callable[[torch.Tensor, int], float]            -> accent-drift probability
     transcriber = None         # Callable[[torch.Tensor, int], Optional[str]]    -> transcription (None = failed)
 
-    def _validate_segment(self, audio: torch.Tensor, text: str, st: dict) -> bool:
+    def _chunk_drifts(self, audios) -> Optional[List[Optional[float]]]:
+        """The drift of every audio of a chunk from ONE call of ``drift_scorer.batch`` (features.make_drift_scorer: one native
+        call and one host synchronisation for the chunk), aligned with ``audios`` (None where there is no audio) - or None when
+        the scorer has no ``batch``, or when the call fails: the per-segment call then decides, segment by segment."""
+        batch = getattr(getattr(self, "drift_scorer", None), "batch", None)
+        have = [a for a in audios if a is not None]
+        if not callable(batch) or not have:
+            return None
+        try:
+            vals = [float(v) for v in batch(have, self.sample_rate)]
+            if len(vals) != len(have):
+                raise RuntimeError(f"drift_scorer.batch returned {len(vals)} scores for {len(have)} segments")
+        except Exception as e:  # noqa: BLE001
+            logger.warning(f"    batched drift scoring failed ({e}); scoring per segment")
+            return None
+        it = iter(vals)
+        return [None if a is None else next(it) for a in audios]
+
+    def _validate_segment(self, audio: torch.Tensor, text: str, st: dict, drift: Optional[float] = None) -> bool:
         """One validation attempt (base_tts.py:821-886), updating the segment's state in the reference's order: drift ->
         auto-sort -> best-by-drift -> text match only if the voice passed.  A validator that raises counts as a failed
-        attempt but keeps what it had already recorded.  Returns True when the attempt is accepted."""
+        attempt but keeps what it had already recorded.  Returns True when the attempt is accepted.  ``drift``: the scorer's value
+        for this audio when the chunk was scored in one call (``_chunk_drifts``); the scorer is then not called again."""
         scorer, transcriber = getattr(self, "drift_scorer", None), getattr(self, "transcriber", None)
         file_based = hasattr(self, "_validate_accent_drift")          # the reference's file-based validators (absent in the host mirror)
         if scorer is None and transcriber is None and not file_based:
@@ -273,7 +293,7 @@ class BatchedPipeline:
         try:
             with (self._validation_input(audio) if need_file else contextlib.nullcontext(None)) as path:
                 if scorer is not None:
-                    drift = float(scorer(audio, self.sample_rate))
+                    drift = float(scorer(audio, self.sample_rate)) if drift is None else float(drift)
                     voice_ok = drift < self.accent_drift_threshold
                 elif file_based:
                     drift, voice_ok = self._validate_accent_drift(path)
