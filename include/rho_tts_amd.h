@@ -405,6 +405,41 @@ RT_API int rt_features_extract_batch(rt_features* f, const float* const* d_pcm, 
                                      int32_t sample_rate_in, int32_t min_period, int32_t max_period, int32_t lpc_order,
                                      double* h_mfcc_stats26, double* h_lpc, int32_t* h_states, int32_t cap_frames, int32_t* h_n_pitch_frames);
 
+/* ------------------------------------------------------------------ speed and pitch control
+ * Stands behind BaseTTS._apply_speed_pitch (base_tts.py:618-650: torchaudio.functional.resample(audio, int(sr * speed), sr), then
+ * torchaudio.functional.pitch_shift(audio, sr, steps)) for one mono clip in HBM: float32 in, float32 out, every intermediate in
+ * float64.  The resampler (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) evaluates its taps per output sample instead of
+ * materialising torchaudio's [new][orig + 2 width] filter bank; the pitch stage is STFT (512, hop 128, periodic Hann, reflect-padded
+ * centre) -> phase vocoder at `rate`, phase accumulated in float64 -> inverse STFT over the window envelope -> resampler -> crop or
+ * zero-pad to the length the stage was given.  Definition: torchaudio 2.x's algorithm in exact arithmetic (tests/speed_pitch_ref.py);
+ * parity with the package is UNPINNED (not installable offline).
+ *
+ * EVERY integer decision is the host's: rt_speedpitch_plan carries them (rho_tts_amd/speedpitch.py plan() computes them with
+ * torchaudio's own Python expressions) and the device decides no length.  rt_speedpitch_apply therefore only enqueues kernels on the
+ * context's stream: no device-to-host copy, no synchronisation (a workspace that has to grow is reallocated first; workspaces never
+ * shrink).  The plan is checked against what integer arithmetic can re-derive (coprime rates, the filter half-width, the resampled
+ * lengths, the frame count) and the float-derived counts against `rate`; an inconsistent plan, or out_capacity below the result's
+ * length, is RT_ERR_INVALID and nothing is written.
+ *   speed stage (do_speed): g = gcd(int(sr * speed), sr), s_o = int(sr * speed) / g, s_n = sr / g, s_width = ceil(6 s_o / (0.99
+ *     min(s_o, s_n))), s_len = ceil(s_n n_in / s_o); s_o == s_n (equal rates): the stage copies
+ *   L: samples behind the speed stage (n_in without it) = samples written to d_out
+ *   pitch stage (do_pitch, L >= 257): rate = 2^(-steps / 12), nf = 1 + L / 128 input frames, n_out = ceil(nf / rate) output frames,
+ *     ls = round(L / rate) stretched samples, resampled by p_o : p_n = int(sr / rate) : sr reduced, p_width, p_len as above */
+typedef struct rt_speedpitch rt_speedpitch;
+typedef struct rt_speedpitch_plan {
+    int32_t do_speed, do_pitch;
+    int64_t s_o, s_n, s_width, s_len;
+    int64_t L;
+    int64_t nf, n_out, ls;
+    int64_t p_o, p_n, p_width, p_len;
+    double  rate;
+} rt_speedpitch_plan;
+RT_API int rt_speedpitch_create(rt_ctx* ctx, rt_speedpitch** out);
+RT_API int rt_speedpitch_destroy(rt_speedpitch* sp);
+/* d_in [n_in] and d_out [out_capacity >= plan->L] are distinct float32 buffers in HBM. */
+RT_API int rt_speedpitch_apply(rt_speedpitch* sp, const float* d_in, int64_t n_in, const rt_speedpitch_plan* plan, float* d_out,
+                               int64_t out_capacity);
+
 /* Measurement and test entry points (rt_profile_*, rt_debug_*, rt_bench_*) are declared in rho_tts_amd_debug.h: a host binding of
  * the generation path needs none of them. */
 

@@ -22,7 +22,8 @@ CXXFLAGS = ["-std=c++17", "-O3", "-fPIC", "-fvisibility=hidden", f"--offload-arc
             "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 # Translation units whose float results are compared bit-for-bit with the CPU reference
 # must not have mul+add fused behind their back.
-PER_FILE = {"postprocess.hip": ["-ffp-contract=off"], "encoder.hip": ["-ffp-contract=off"], "features.hip": ["-ffp-contract=off"]}
+PER_FILE = {"postprocess.hip": ["-ffp-contract=off"], "encoder.hip": ["-ffp-contract=off"], "features.hip": ["-ffp-contract=off"],
+            "speedpitch.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -606,6 +606,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         self.sound_decay_threshold = sound_decay_threshold
         self._engine = None
         self._ctx = None
+        self._speed_pitch = None                               # speedpitch.SpeedPitch, made by the first call that needs it
         self._lock = threading.RLock()
         self._voice_key = None
         # decode-schedule figures of this instance's engine calls, accumulated until cleared: kept / launched row-frames
@@ -630,6 +631,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             if self._engine is None:
                 from .engine import Engine
                 if self._ctx is not None:
+                    self._close_speed_pitch()                  # (it lives on the context that goes away here)
                     self._ctx.close()
                     self._ctx = None
                 self._engine = Engine(self.model_path, self._device_ordinal(), max_batch=max(1, min(64, int(self.batch_size))))
@@ -858,12 +860,30 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             except Exception as e:  # noqa: BLE001  (as the reference: a failed segment is skipped, base_tts.py:1166-1168)
                 logger.warning(f"Segment {seg_idx + 1} failed: {e}")
 
+    def _apply_speed_pitch(self, audio: torch.Tensor, speed: float, pitch_semitones: float) -> torch.Tensor:
+        """``BaseTTS._apply_speed_pitch`` (base_tts.py:618-650) on the GPU, without torchaudio: the resampler and the phase-vocoder
+        pitch shift of csrc/speedpitch.hip (speedpitch.py), on this provider's context.  Reached only with ``speed != 1`` or
+        ``pitch_semitones != 0`` (generate / stream test that first, base_tts.py:1020)."""
+        if speed == 1.0 and pitch_semitones == 0.0:
+            return audio
+        with self._lock:
+            if self._speed_pitch is None:                      # (released with the context it is made on: _load_engine, close)
+                from .speedpitch import SpeedPitch
+                self._speed_pitch = SpeedPitch(self._native_ctx())
+            return self._speed_pitch(audio, speed, pitch_semitones, sample_rate=self.sample_rate)
+
+    def _close_speed_pitch(self) -> None:
+        if self._speed_pitch is not None:
+            self._speed_pitch.close()
+            self._speed_pitch = None
+
     @property
     def sample_rate(self) -> int:
         return 24000 if self._engine is None else self._engine.cfg.sample_rate
 
     def close(self) -> None:
         with self._lock:
+            self._close_speed_pitch()                          # (before the context it lives on)
             if self._engine is not None:
                 self._engine.close()
                 self._engine = None
