@@ -355,6 +355,18 @@ RT_API int rt_stt_set_suppress(rt_stt* s, const int32_t* h_ids, int32_t n);
  * prefix of the FIRST window, for tests. */
 RT_API int rt_stt_transcribe(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, int32_t* h_tokens, int32_t max_tokens,
                              int32_t* h_n_tokens, float* d_first_logits);
+/* n_clips clips in one call: d_pcm[i] holds n_samples[i] floats in HBM, all at sample_rate_in; h_tokens [n_clips][max_tokens_per_clip]
+ * and h_n_tokens [n_clips] receive per clip exactly the ids rt_stt_transcribe gives for it alone with max_tokens =
+ * max_tokens_per_clip (size a row for ceil(seconds / chunk_seconds) * cfg.max_new_tokens).  Every clip is cut into chunk_seconds
+ * windows as there, and the windows of all clips - 32 at a time - go through the front end, the encoder and the greedy decode
+ * together: one launch per stage for the group, and one device-to-host read and one stream synchronisation per decode step
+ * whatever the number of clips.  The group's buffers (78.7 MB per window measured at Whisper-tiny dimensions) are allocated by the
+ * first batched call and only grow; a handle that never batches never pays for them, and one whose allocation failed (out of memory) holds no
+ * group and allocates again at the next batched call.  n_clips == 0: nothing to do, RT_OK.
+ * RT_ERR_INVALID: a null pointer for a clip with samples, a negative length, max_tokens_per_clip < 1.  A clip of zero samples is
+ * one window of silence, as in rt_stt_transcribe. */
+RT_API int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
+                                   int32_t* h_tokens, int32_t max_tokens_per_clip, int32_t* h_n_tokens);
 /* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM. */
 RT_API int rt_stt_log_mel(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, float* d_mel);
 RT_API int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, float* d_states);

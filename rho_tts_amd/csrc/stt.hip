@@ -12,6 +12,10 @@
 // keep hi + lo planes and attention / LayerNorm run in float32: the token ids must equal the float32 oracle's (greedy argmax over
 // 51865 logits), which plain bf16 activations would not guarantee.  The model is tiny (39 M parameters); nothing here is on the
 // hot path of generation - it runs once per validated segment - so the kernels are the simple forms.
+//
+// rt_stt_transcribe_batch runs the same kernels over a whole validation chunk: the windows of all clips, STT_GROUP at a time, are
+// the rows of every launch (group siblings of the front-end kernels, one cache slot per window, the decode bookkeeping in
+// k_stt_pick), and a clip's ids are bit for bit the ids it gets alone.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -45,20 +49,39 @@ __global__ void k_stt_bf16_to_f32(const bf16_t* __restrict__ x, int64_t n, float
 
 // y[n] = sum_j x[base(n) + j - half] h[phase(n)][j]: polyphase windowed-sinc resampler, sr_in / sr_out = M / L in lowest terms,
 // base = floor(n M / L), phase = (n M) mod L; samples outside [0, n_in) are zero.  float64 accumulation in tap order.
+__device__ __forceinline__ float resample_at(const float* __restrict__ x, int64_t n_in, int64_t n, int L, int M, int taps, int half,
+                                             const float* __restrict__ h) {
+    const int64_t num = n * M;
+    const int64_t base = num / L;
+    const int phase = (int)(num % L);
+    const float* hp = h + (int64_t)phase * taps;
+    double acc = 0.0;
+    for (int j = 0; j < taps; ++j) {
+        const int64_t t = base + j - half;
+        if (t >= 0 && t < n_in) acc += (double)x[t] * (double)hp[j];
+    }
+    return (float)acc;
+}
 __global__ void k_resample(const float* __restrict__ x, int64_t n_in, float* __restrict__ y, int64_t n_out, int L, int M, int taps, int half,
                            const float* __restrict__ h) {
-    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_out; n += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t num = n * M;
-        const int64_t base = num / L;
-        const int phase = (int)(num % L);
-        const float* hp = h + (int64_t)phase * taps;
-        double acc = 0.0;
-        for (int j = 0; j < taps; ++j) {
-            const int64_t t = base + j - half;
-            if (t >= 0 && t < n_in) acc += (double)x[t] * (double)hp[j];
-        }
-        y[n] = (float)acc;
-    }
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_out; n += (int64_t)gridDim.x * blockDim.x)
+        y[n] = resample_at(x, n_in, n, L, M, taps, half, h);
+}
+
+// One window of a group, as the front-end kernels of rt_stt_transcribe_batch see it (a small device table, one entry per window)
+struct SttWin {
+    const float* pcm_in;    // the window's samples at the input rate
+    const float* pcm16;     // ... at cfg.sample_rate: its row of the resampler's output, or pcm_in itself when the rates agree
+    int64_t n_in, n16;      // samples at the input rate / at cfg.sample_rate (at most one chunk)
+    int32_t n_comp, pad;    // log-mel frames that can see audio; the rest hold the constant of silence
+};
+// the resampler over a group: blockIdx.y = window, its output row at y + window * y_stride
+__global__ void k_resample_group(const SttWin* __restrict__ wins, float* __restrict__ y, int64_t y_stride, int L, int M, int taps, int half,
+                                 const float* __restrict__ h) {
+    const SttWin w = wins[blockIdx.y];
+    float* yw = y + (int64_t)blockIdx.y * y_stride;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < w.n16; n += (int64_t)gridDim.x * blockDim.x)
+        yw[n] = resample_at(w.pcm_in, w.n_in, n, L, M, taps, half, h);
 }
 
 // One frame per workgroup: the frame's 400 samples of the (zero-padded to 30 s, reflect-padded by n_fft / 2 at both ends) signal
@@ -66,16 +89,15 @@ __global__ void k_resample(const float* __restrict__ x, int64_t n_in, float* __r
 // power spectrum, mel filters, log10(max(., 1e-10)).  logspec is [frames][n_mels]; gmax receives the maximum (ordered-int atomic).
 __device__ __forceinline__ int f32_ordered(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
 __device__ __forceinline__ float ordered_f32(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-__global__ __launch_bounds__(256) void k_logmel_frames(const float* __restrict__ pcm, int64_t n_valid, int64_t n_padded, int n_fft, int hop, int n_bins,
-                                                       int n_mels, const double* __restrict__ twc, const double* __restrict__ tws,
-                                                       const float* __restrict__ window, const float* __restrict__ melT /*[n_bins][n_mels]*/,
-                                                       float* __restrict__ logspec, int* __restrict__ gmax) {
-    extern __shared__ double sh[];                       // xw[n_fft] | c[n_fft] | s[n_fft] | power[n_bins]
+__device__ __forceinline__ void logmel_frame(double* sh /* xw[n_fft] | c[n_fft] | s[n_fft] | power[n_bins] */, const float* __restrict__ pcm, int64_t n_valid,
+                                             int64_t n_padded, int f, int n_fft, int hop, int n_bins, int n_mels, const double* __restrict__ twc,
+                                             const double* __restrict__ tws, const float* __restrict__ window, const float* __restrict__ melT,
+                                             float* __restrict__ logspec, int* __restrict__ gmax) {
     double* xw = sh;
     double* tc = sh + n_fft;
     double* ts = tc + n_fft;
     double* pw = ts + n_fft;
-    const int f = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int64_t start = (int64_t)f * hop - n_fft / 2;
     for (int n = tid; n < n_fft; n += blockDim.x) {
         int64_t t = start + n;
@@ -110,20 +132,45 @@ __global__ __launch_bounds__(256) void k_logmel_frames(const float* __restrict__
     best = wave_max_f32(best);
     if ((tid & 63) == 0 && best > -INFINITY) atomicMax(gmax, f32_ordered(best));
 }
+__global__ __launch_bounds__(256) void k_logmel_frames(const float* __restrict__ pcm, int64_t n_valid, int64_t n_padded, int n_fft, int hop, int n_bins,
+                                                       int n_mels, const double* __restrict__ twc, const double* __restrict__ tws,
+                                                       const float* __restrict__ window, const float* __restrict__ melT /*[n_bins][n_mels]*/,
+                                                       float* __restrict__ logspec, int* __restrict__ gmax) {
+    extern __shared__ double sh[];
+    logmel_frame(sh, pcm, n_valid, n_padded, blockIdx.x, n_fft, hop, n_bins, n_mels, twc, tws, window, melT, logspec, gmax);
+}
+// the frames of a group: blockIdx = (frame, window); window b's features at logspec + b * spec_stride, its maximum in gmax[b]
+__global__ __launch_bounds__(256) void k_logmel_frames_group(const SttWin* __restrict__ wins, int64_t n_padded, int n_fft, int hop, int n_bins, int n_mels,
+                                                             const double* __restrict__ twc, const double* __restrict__ tws,
+                                                             const float* __restrict__ window, const float* __restrict__ melT,
+                                                             float* __restrict__ logspec, int64_t spec_stride, int* __restrict__ gmax) {
+    extern __shared__ double sh[];
+    const SttWin w = wins[blockIdx.y];
+    if ((int)blockIdx.x >= w.n_comp) return;              // (uniform over the workgroup)
+    logmel_frame(sh, w.pcm16, w.n16, n_padded, blockIdx.x, n_fft, hop, n_bins, n_mels, twc, tws, window, melT, logspec + (int64_t)blockIdx.y * spec_stride,
+                 gmax + blockIdx.y);
+}
 // logspec[f][m] <- (max(v, gmax - 8) + 4) / 4; frames >= n_frames_audio hold the value of silence, log10(1e-10) = -10
-__global__ void k_logmel_finish(float* __restrict__ logspec, int64_t n_total, int64_t n_computed, const int* __restrict__ gmax) {
+__device__ __forceinline__ void logmel_finish(float* __restrict__ logspec, int64_t n_total, int64_t n_computed, const int* __restrict__ gmax) {
     const float mx = fmaxf(ordered_f32(*gmax), n_computed < n_total ? -10.f : -INFINITY);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_total; i += (int64_t)gridDim.x * blockDim.x) {
         const float v = i < n_computed ? logspec[i] : -10.f;
         logspec[i] = (fmaxf(v, mx - 8.0f) + 4.0f) / 4.0f;
     }
 }
+__global__ void k_logmel_finish(float* __restrict__ logspec, int64_t n_total, int64_t n_computed, const int* __restrict__ gmax) {
+    logmel_finish(logspec, n_total, n_computed, gmax);
+}
+__global__ void k_logmel_finish_group(const SttWin* __restrict__ wins, float* __restrict__ logspec, int64_t n_total, int n_mels, const int* __restrict__ gmax) {
+    logmel_finish(logspec + (int64_t)blockIdx.y * n_total, n_total, (int64_t)wins[blockIdx.y].n_comp * n_mels, gmax + blockIdx.y);
+}
 
-// LayerNorm with bias over the last dimension, float32 in and out, one workgroup per row (two-pass: mean, then variance)
-__global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, int D, const float* __restrict__ w, const float* __restrict__ b, float eps,
-                                                   float* __restrict__ out) {
+// LayerNorm with bias over the last dimension, float32 in and out, one workgroup per row (two-pass: mean, then variance); input
+// rows lie ldx elements apart (the last prefix row of every window of a group), output rows are dense
+__global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, int64_t ldx, int D, const float* __restrict__ w, const float* __restrict__ b,
+                                                   float eps, float* __restrict__ out) {
     __shared__ float sh[4];
-    const float* r = x + (int64_t)blockIdx.x * D;
+    const float* r = x + (int64_t)blockIdx.x * ldx;
     float s = 0.f;
     for (int i = threadIdx.x; i < D; i += 256) s += r[i];
     s = wave_sum_f32(s);
@@ -141,18 +188,18 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, 
     for (int i = threadIdx.x; i < D; i += 256) o[i] = (r[i] - mean) * inv * w[i] + b[i];
 }
 
-// x[r][:] = token_embedding[tok[r]] (bf16) + position_embedding[pos0 + r] (f32)
-__global__ void k_stt_embed(const bf16_t* __restrict__ tok_emb, const float* __restrict__ pos_emb, const int32_t* __restrict__ tok, int pos0, int D,
+// x[r][:] = token_embedding[tok[r]] (bf16) + position_embedding[pos0 + r % per] (f32): `per` consecutive rows per window
+__global__ void k_stt_embed(const bf16_t* __restrict__ tok_emb, const float* __restrict__ pos_emb, const int32_t* __restrict__ tok, int pos0, int per, int D,
                             float* __restrict__ x) {
     const int r = blockIdx.x;
     const int64_t t = tok[r];
-    for (int i = threadIdx.x; i < D; i += blockDim.x) x[(int64_t)r * D + i] = bf16_to_f32(tok_emb[t * D + i]) + pos_emb[(int64_t)(pos0 + r) * D + i];
+    const int64_t pos = pos0 + r % per;
+    for (int i = threadIdx.x; i < D; i += blockDim.x) x[(int64_t)r * D + i] = bf16_to_f32(tok_emb[t * D + i]) + pos_emb[pos * D + i];
 }
 
 // greedy choice over one row of logits: the largest value among the tokens the mask allows (bit 0: never, bit 1: not as the first
-// generated token), lowest index on ties; the winner is written to out[0] and appended to seq[*n_seq]
-__global__ __launch_bounds__(1024) void k_stt_argmax(const float* __restrict__ logits, int V, const uint8_t* __restrict__ mask, int first_step,
-                                                     int32_t* __restrict__ out) {
+// generated token), lowest index on ties, NaNs never; thread 0 of the 1024-thread workgroup returns the winner
+__device__ __forceinline__ int stt_argmax_row(const float* __restrict__ logits, int V, const uint8_t* __restrict__ mask, int first_step) {
     __shared__ float sv[16];
     __shared__ int si[16];
     float best = -INFINITY;
@@ -174,7 +221,32 @@ __global__ __launch_bounds__(1024) void k_stt_argmax(const float* __restrict__ l
     if (threadIdx.x == 0) {
         for (int w = 1; w < 16; ++w)
             if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        out[0] = bi == 0x7fffffff ? 0 : bi;
+    }
+    return bi == 0x7fffffff ? 0 : bi;
+}
+// the single clip's step: the winner is written to out[0], the next input token
+__global__ __launch_bounds__(1024) void k_stt_argmax(const float* __restrict__ logits, int V, const uint8_t* __restrict__ mask, int first_step,
+                                                     int32_t* __restrict__ out) {
+    const int tok = stt_argmax_row(logits, V, mask, first_step);
+    if (threadIdx.x == 0) out[0] = tok;
+}
+// A group's step, one workgroup per window: the winner of row b becomes the row's next input token; unless the row has ended it is
+// appended to the row's log - or, if it is end-of-sequence, ends the row and takes it off the live count.  An ended row rides along
+// as a dead row: it keeps writing its own cache slot and its own logits, nothing a live row reads.
+__global__ __launch_bounds__(1024) void k_stt_pick(const float* __restrict__ logits, int V, const uint8_t* __restrict__ mask, int first_step, int eos,
+                                                   int log_cap, int32_t* __restrict__ next_tok, int32_t* __restrict__ log, int32_t* __restrict__ n_log,
+                                                   int32_t* __restrict__ done, int32_t* __restrict__ live) {
+    const int b = blockIdx.x;
+    const int tok = stt_argmax_row(logits + (int64_t)b * V, V, mask, first_step);
+    if (threadIdx.x != 0) return;
+    next_tok[b] = tok;
+    if (done[b]) return;
+    if (tok == eos) {
+        done[b] = 1;
+        atomicSub(live, 1);
+    } else if (n_log[b] < log_cap) {
+        log[(int64_t)b * log_cap + n_log[b]] = tok;
+        n_log[b] += 1;
     }
 }
 
@@ -182,7 +254,40 @@ __global__ void k_stt_fill_i32(int32_t* p, int n, int v, int step) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = v + i * step;
 }
 
+// row i of a group's row tables: slot[i] = i / per (the window), pos[i] = i % per
+__global__ void k_stt_fill_rows(int32_t* __restrict__ slot, int32_t* __restrict__ pos, int n, int per) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { slot[i] = i / per; pos[i] = i % per; }
+}
+// dst[b][i] = src[i], b < reps: the encoder's positions laid under every window of a group
+__global__ void k_stt_repeat(const float* __restrict__ src, int64_t n, int reps, float* __restrict__ dst) {
+    const int64_t total = n * reps;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i % n];
+}
+
 }  // namespace
+
+// Windows of one group of rt_stt_transcribe_batch: the rows of every batched launch.  Compile-time: the group's buffers - about
+// 79 MB per window at Whisper-tiny dimensions - are the price of a larger group.
+constexpr int STT_GROUP = 32;
+
+// The buffers one pass works on: the single clip's (B = 1, allocated by rt_stt_finalize) or a group's (B windows, allocated by
+// the first batched call, grown when a later call needs more windows).  Row tables address the caches per row: encoder row
+// b n_ctx + t is position t of slot b and attends up to n_ctx - 1.
+struct SttBufs {
+    int B = 0;
+    KvCache enc_kv, dec_kv, cross_kv;
+    float *pcm16k = nullptr, *mel = nullptr, *c1 = nullptr, *x = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *ao = nullptr, *ff = nullptr,
+          *enc_out = nullptr, *logits = nullptr;
+    float *dx = nullptr, *dxn = nullptr, *dqkv = nullptr, *dq = nullptr, *dao = nullptr, *dff = nullptr;
+    int32_t *enc_slot = nullptr, *enc_pos = nullptr, *enc_last = nullptr;   // [B n_ctx] (enc_last: n_ctx - 1 throughout, also what decoder rows attend across)
+    int32_t *dec_slot = nullptr, *dec_pos = nullptr;       // [B R] rows of the prefix pass: row b R + i -> slot b, position i
+    int32_t *step_slot = nullptr, *step_pos = nullptr;     // [B] rows of a step pass: slot b, position 0 (+ pos_add)
+    int32_t *d_tok = nullptr, *d_gmax = nullptr;
+    // a group only: the decode bookkeeping k_stt_pick keeps and the window table of the front end
+    int32_t *d_log = nullptr, *d_nlog = nullptr, *d_done = nullptr, *d_live = nullptr;   // [B][max_new_tokens] ids | [B] | [B] | [1], one allocation
+    SttWin* d_wins = nullptr;
+    std::vector<void*> owned;
+};
 
 struct rt_stt {
     rt_ctx* ctx = nullptr;
@@ -190,17 +295,16 @@ struct rt_stt {
     std::vector<SttSlot> slots;
     std::map<std::string, int> by_name;
     bool finalized = false;
-    KvCache enc_kv, dec_kv, cross_kv;
     // front-end constants
     double *d_twc = nullptr, *d_tws = nullptr;
     float *d_window = nullptr, *d_melT = nullptr;
     float* d_resamp = nullptr;        // polyphase filter of the last (sr_in -> cfg.sample_rate) pair
     int rs_in = 0, rs_L = 0, rs_M = 0, rs_taps = 0, rs_half = 0;
-    // workspaces (sized for n_ctx rows)
-    float *pcm16k = nullptr, *mel = nullptr, *c1 = nullptr, *x = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *ao = nullptr, *ff = nullptr,
-          *enc_out = nullptr, *logits = nullptr;
-    float *dx = nullptr, *dxn = nullptr, *dqkv = nullptr, *dq = nullptr, *dao = nullptr, *dff = nullptr;
-    int32_t *pos_seq = nullptr, *pos_last = nullptr, *slot0 = nullptr, *d_tok = nullptr, *d_gmax = nullptr;
+    SttBufs one;                      // the single-clip path: n_ctx rows, one cache slot
+    // the batched path (rt_stt_transcribe_batch): nothing of it exists until the first batched call
+    SttBufs grp;
+    std::vector<SttWin> h_wins;       // host copies of what is uploaded per group (alive until the group's last synchronisation)
+    std::vector<int32_t> h_prefix, h_log;
     uint8_t* d_mask = nullptr;
     std::vector<int32_t> suppress_ids;   // rt_stt_set_suppress: ids never produced (a generation config's `suppress_tokens`)
     std::vector<void*> owned;
@@ -254,20 +358,54 @@ void stt_declare(rt_stt* s) {
 }
 
 template <typename T>
-int stt_alloc(rt_stt* s, size_t n, T** out) {
+int stt_alloc(rt_stt* s, std::vector<void*>& owned, size_t n, T** out) {
     void* p = nullptr;
     RT_HIP(s->ctx, hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)));
-    s->owned.push_back(p);
+    owned.push_back(p);
     *out = (T*)p;
     return RT_OK;
 }
 
-int stt_kv(rt_stt* s, KvCache& kv, int layers, int max_pos) {
+int stt_kv(rt_stt* s, std::vector<void*>& owned, KvCache& kv, int layers, int slots, int max_pos) {
     const rt_stt_config& c = s->cfg;
-    kv.layers = layers; kv.slots = 1; kv.kv_heads = c.heads; kv.max_pos = max_pos; kv.head_dim = c.d_model / c.heads;
+    kv.layers = layers; kv.slots = slots; kv.kv_heads = c.heads; kv.max_pos = max_pos; kv.head_dim = c.d_model / c.heads;
     const size_t n = (size_t)layers * kv.layer_stride();
-    ST_TRY(stt_alloc(s, n, &kv.k)); ST_TRY(stt_alloc(s, n, &kv.v)); ST_TRY(stt_alloc(s, n, &kv.k_lo)); ST_TRY(stt_alloc(s, n, &kv.v_lo));
+    ST_TRY(stt_alloc(s, owned, n, &kv.k)); ST_TRY(stt_alloc(s, owned, n, &kv.v)); ST_TRY(stt_alloc(s, owned, n, &kv.k_lo)); ST_TRY(stt_alloc(s, owned, n, &kv.v_lo));
     for (bf16_t* p : {kv.k, kv.v, kv.k_lo, kv.v_lo}) RT_HIP(s->ctx, hipMemsetAsync(p, 0, n * sizeof(bf16_t), s->ctx->stream));
+    return RT_OK;
+}
+
+// caches, workspaces and encoder row tables of B windows; R = decoder rows per window and pass (the forced prefix, then one)
+int stt_alloc_bufs(rt_stt* s, SttBufs& w, int B, int R) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    const int D = c.d_model, T = c.n_ctx, T2 = 2 * T;
+    const size_t b = (size_t)B, rows = b * T;
+    ST_TRY(stt_kv(s, w.owned, w.enc_kv, c.enc_layers, B, T));
+    ST_TRY(stt_kv(s, w.owned, w.dec_kv, c.dec_layers, B, c.n_text_ctx));
+    ST_TRY(stt_kv(s, w.owned, w.cross_kv, c.dec_layers, B, T));
+    ST_TRY(stt_alloc(s, w.owned, b * c.chunk_seconds * c.sample_rate, &w.pcm16k));
+    ST_TRY(stt_alloc(s, w.owned, b * T2 * c.n_mels, &w.mel));
+    ST_TRY(stt_alloc(s, w.owned, b * T2 * D, &w.c1));
+    ST_TRY(stt_alloc(s, w.owned, rows * D, &w.x)); ST_TRY(stt_alloc(s, w.owned, rows * D, &w.xn)); ST_TRY(stt_alloc(s, w.owned, rows * 3 * D, &w.qkv));
+    ST_TRY(stt_alloc(s, w.owned, rows * D, &w.q)); ST_TRY(stt_alloc(s, w.owned, rows * D, &w.ao)); ST_TRY(stt_alloc(s, w.owned, rows * c.ffn, &w.ff));
+    ST_TRY(stt_alloc(s, w.owned, rows * D, &w.enc_out));
+    ST_TRY(stt_alloc(s, w.owned, b * c.vocab, &w.logits));
+    const size_t r = b * R;
+    ST_TRY(stt_alloc(s, w.owned, r * D, &w.dx)); ST_TRY(stt_alloc(s, w.owned, r * D, &w.dxn)); ST_TRY(stt_alloc(s, w.owned, r * 3 * D, &w.dqkv));
+    ST_TRY(stt_alloc(s, w.owned, r * D, &w.dq)); ST_TRY(stt_alloc(s, w.owned, r * D, &w.dao)); ST_TRY(stt_alloc(s, w.owned, r * c.ffn, &w.dff));
+    const size_t n_last = std::max(rows, r);            // (decoder rows read enc_last too)
+    ST_TRY(stt_alloc(s, w.owned, rows, &w.enc_slot)); ST_TRY(stt_alloc(s, w.owned, rows, &w.enc_pos)); ST_TRY(stt_alloc(s, w.owned, n_last, &w.enc_last));
+    ST_TRY(stt_alloc(s, w.owned, r, &w.dec_slot)); ST_TRY(stt_alloc(s, w.owned, r, &w.dec_pos));
+    ST_TRY(stt_alloc(s, w.owned, b, &w.step_slot)); ST_TRY(stt_alloc(s, w.owned, b, &w.step_pos));
+    ST_TRY(stt_alloc(s, w.owned, r, &w.d_tok)); ST_TRY(stt_alloc(s, w.owned, b, &w.d_gmax));
+    hipLaunchKernelGGL(k_stt_fill_rows, dim3(64), dim3(256), 0, ctx->stream, w.enc_slot, w.enc_pos, (int)rows, T);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(64), dim3(256), 0, ctx->stream, w.enc_last, (int)n_last, T - 1, 0);
+    hipLaunchKernelGGL(k_stt_fill_rows, dim3(1), dim3(256), 0, ctx->stream, w.dec_slot, w.dec_pos, (int)r, R);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, w.step_slot, B, 0, 1);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, w.step_pos, B, 0, 0);
+    RT_HIP(ctx, hipGetLastError());
+    w.B = B;            // (last: a set that an allocation failure left incomplete holds no windows)
     return RT_OK;
 }
 
@@ -277,8 +415,9 @@ int stt_gemm(rt_stt* s, const float* A, int M, const PackedW& W, const float* bi
     GemmEpi e; e.bias = bias; e.act = act; e.residual = residual; e.out_f32 = out; e.ldc = W.N;
     return launch_gemm(s->ctx, a, W, e);
 }
-int stt_ln(rt_stt* s, const float* x, int M, const float* w, const float* b, float* out) {
-    hipLaunchKernelGGL(k_layernorm, dim3(M), dim3(256), 0, s->ctx->stream, x, s->cfg.d_model, w, b, 1e-5f, out);
+// M rows of x, ldx elements apart -> dense rows of out
+int stt_ln(rt_stt* s, const float* x, int64_t ldx, int M, const float* w, const float* b, float* out) {
+    hipLaunchKernelGGL(k_layernorm, dim3(M), dim3(256), 0, s->ctx->stream, x, ldx, s->cfg.d_model, w, b, 1e-5f, out);
     RT_HIP(s->ctx, hipGetLastError());
     return RT_OK;
 }
@@ -316,10 +455,17 @@ int stt_resampler(rt_stt* s, int sr_in) {
     return RT_OK;
 }
 
-// PCM (device, any rate) -> log-mel [frames][n_mels] in s->mel (the mutex is held)
+// frames of a window that can see audio: [f hop - n_fft/2, f hop + n_fft/2) meets [0, n16); the rest are the constant of silence
+int stt_frames_with_audio(const rt_stt_config& c, int64_t n16) {
+    const int n_frames = (int)((int64_t)c.chunk_seconds * c.sample_rate / c.hop);     // 3000 (the last of the 3001 STFT frames is dropped)
+    return n16 <= 0 ? 0 : (int)std::min<int64_t>(n_frames, (n16 + c.n_fft / 2 + c.hop - 1) / c.hop + 1);
+}
+
+// PCM (device, any rate) -> log-mel [frames][n_mels] in s->one.mel (the mutex is held)
 int stt_features(rt_stt* s, const float* d_pcm, int64_t n, int sr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
+    SttBufs& w = s->one;
     const int64_t n_pad = (int64_t)c.chunk_seconds * c.sample_rate;
     const float* src = d_pcm;
     int64_t n16 = n;
@@ -327,96 +473,221 @@ int stt_features(rt_stt* s, const float* d_pcm, int64_t n, int sr) {
         ST_TRY(stt_resampler(s, sr));
         n16 = std::min<int64_t>((n * s->rs_L + s->rs_M - 1) / s->rs_M, n_pad);        // ceil(n L / M), at most 30 s
         if (n16 > 0)
-            hipLaunchKernelGGL(k_resample, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_pcm, n, s->pcm16k, n16,
+            hipLaunchKernelGGL(k_resample, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_pcm, n, w.pcm16k, n16,
                                s->rs_L, s->rs_M, s->rs_taps, s->rs_half, s->d_resamp);
         RT_HIP(ctx, hipGetLastError());
-        src = s->pcm16k;
+        src = w.pcm16k;
     }
     n16 = std::min(n16, n_pad);
-    const int n_frames = (int)(n_pad / c.hop);                      // 3000 (the last of the 3001 STFT frames is dropped)
-    // frames that can see audio: [f hop - n_fft/2, f hop + n_fft/2) meets [0, n16); the rest are the constant of silence
-    int n_comp = (int)std::min<int64_t>(n_frames, (n16 + c.n_fft / 2 + c.hop - 1) / c.hop + 1);
-    if (n16 <= 0) n_comp = 0;
+    const int n_frames = (int)(n_pad / c.hop);
+    const int n_comp = stt_frames_with_audio(c, n16);
     const int n_bins = c.n_fft / 2 + 1;
     const int init = (int)0x80000000;                               // below every ordered float
-    RT_HIP(ctx, hipMemcpyAsync(s->d_gmax, &init, 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(w.d_gmax, &init, 4, hipMemcpyHostToDevice, ctx->stream));
     if (n_comp > 0) {
         const size_t lds = (size_t)(3 * c.n_fft + n_bins) * sizeof(double);
         hipLaunchKernelGGL(k_logmel_frames, dim3(n_comp), dim3(256), lds, ctx->stream, src, n16, n_pad, c.n_fft, c.hop, n_bins, c.n_mels, s->d_twc,
-                           s->d_tws, s->d_window, s->d_melT, s->mel, s->d_gmax);
+                           s->d_tws, s->d_window, s->d_melT, w.mel, w.d_gmax);
         RT_HIP(ctx, hipGetLastError());
     }
     const int64_t tot = (int64_t)n_frames * c.n_mels;
-    hipLaunchKernelGGL(k_logmel_finish, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 2048)), dim3(256), 0, ctx->stream, s->mel, tot,
-                       (int64_t)n_comp * c.n_mels, s->d_gmax);
+    hipLaunchKernelGGL(k_logmel_finish, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 2048)), dim3(256), 0, ctx->stream, w.mel, tot,
+                       (int64_t)n_comp * c.n_mels, w.d_gmax);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
 
-// one pre-LN layer over M rows of x (in place).  self-attention over cache `kv` (rows are written at wpos, attend up to apos);
-// cross = the decoder's encoder-attention block between the two
-int stt_layer(rt_stt* s, const std::string& p, float* x, float* xn, float* qkv, float* q, float* ao, float* ff, int M, KvCache& kv, int layer,
-              const int32_t* wpos, const int32_t* apos, int pos_add, bool cross) {
+// One window of the input of a batched call
+struct SttSpan { int clip; const float* pcm; int64_t n; };
+
+// The front end of a group: B windows (device pointers at rate sr) -> log-mel [B][frames][n_mels] in s->grp.mel, one launch per
+// stage for the whole group.  Per frame and per sample the arithmetic of stt_features (shared device functions).
+int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
-    const int H = c.heads, d = c.d_model / c.heads;
-    ST_TRY(stt_ln(s, x, M, SVEC(s, p + ".ln1_w"), SVEC(s, p + ".ln1_b"), xn));
+    SttBufs& w = s->grp;
+    const int64_t n_pad = (int64_t)c.chunk_seconds * c.sample_rate;
+    const bool resample = sr != c.sample_rate;
+    if (resample) ST_TRY(stt_resampler(s, sr));
+    s->h_wins.assign(B, SttWin{});
+    int64_t max16 = 0;
+    int max_comp = 0;
+    for (int b = 0; b < B; ++b) {
+        SttWin& h = s->h_wins[b];
+        h.pcm_in = spans[b].pcm;
+        h.n_in = spans[b].n;
+        h.n16 = std::min<int64_t>(resample ? (h.n_in * s->rs_L + s->rs_M - 1) / s->rs_M : h.n_in, n_pad);
+        h.pcm16 = resample ? w.pcm16k + (size_t)b * n_pad : h.pcm_in;
+        h.n_comp = stt_frames_with_audio(c, h.n16);
+        max16 = std::max(max16, h.n16);
+        max_comp = std::max(max_comp, h.n_comp);
+    }
+    RT_HIP(ctx, hipMemcpyAsync(w.d_wins, s->h_wins.data(), (size_t)B * sizeof(SttWin), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, w.d_gmax, B, (int)0x80000000, 0);    // below every ordered float
+    RT_HIP(ctx, hipGetLastError());
+    if (resample && max16 > 0) {
+        hipLaunchKernelGGL(k_resample_group, dim3((unsigned)std::min<int64_t>((max16 + 255) / 256, 4096), B), dim3(256), 0, ctx->stream, w.d_wins, w.pcm16k,
+                           n_pad, s->rs_L, s->rs_M, s->rs_taps, s->rs_half, s->d_resamp);
+        RT_HIP(ctx, hipGetLastError());
+    }
+    const int n_frames = (int)(n_pad / c.hop), n_bins = c.n_fft / 2 + 1;
+    const int64_t tot = (int64_t)n_frames * c.n_mels;
+    if (max_comp > 0) {
+        const size_t lds = (size_t)(3 * c.n_fft + n_bins) * sizeof(double);
+        hipLaunchKernelGGL(k_logmel_frames_group, dim3(max_comp, B), dim3(256), lds, ctx->stream, w.d_wins, n_pad, c.n_fft, c.hop, n_bins, c.n_mels,
+                           s->d_twc, s->d_tws, s->d_window, s->d_melT, w.mel, tot, w.d_gmax);
+        RT_HIP(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_logmel_finish_group, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 2048), B), dim3(256), 0, ctx->stream, w.d_wins, w.mel, tot,
+                       c.n_mels, w.d_gmax);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// one pre-LN layer over M rows of x (in place).  self-attention over cache `kv` (row r is written at slot[r], wpos[r] + pos_add and
+// attends up to apos[r]); cross = the decoder's encoder-attention block between the two, over the row's slot of w.cross_kv
+int stt_layer(rt_stt* s, SttBufs& w, const std::string& p, float* x, float* xn, float* qkv, float* q, float* ao, float* ff, int M, KvCache& kv, int layer,
+              const int32_t* slot, const int32_t* wpos, const int32_t* apos, int pos_add, bool cross) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    const int H = c.heads, d = c.d_model / c.heads, D = c.d_model;
+    ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln1_w"), SVEC(s, p + ".ln1_b"), xn));
     ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".wqkv"), SVEC(s, p + ".bqkv"), ACT_NONE, nullptr, qkv));
-    ST_TRY(launch_qkv_post(ctx, qkv, 1, M, H, H, d, nullptr, nullptr, 0.f, nullptr, nullptr, s->slot0, wpos, pos_add, q, kv, layer));
-    ST_TRY(launch_attention(ctx, q, M, H, H, d, s->slot0, apos, apos == wpos ? pos_add : 0, 0, kv, layer, nullptr, nullptr, 0, ao));
+    ST_TRY(launch_qkv_post(ctx, qkv, 1, M, H, H, d, nullptr, nullptr, 0.f, nullptr, nullptr, slot, wpos, pos_add, q, kv, layer));
+    ST_TRY(launch_attention(ctx, q, M, H, H, d, slot, apos, apos == wpos ? pos_add : 0, 0, kv, layer, nullptr, nullptr, 0, ao));
     ST_TRY(stt_gemm(s, ao, M, SPW(s, p + ".wo"), SVEC(s, p + ".bo"), ACT_NONE, x, x));
     if (cross) {
-        ST_TRY(stt_ln(s, x, M, SVEC(s, p + ".lnc_w"), SVEC(s, p + ".lnc_b"), xn));
+        ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".lnc_w"), SVEC(s, p + ".lnc_b"), xn));
         ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".cwq"), SVEC(s, p + ".cbq"), ACT_NONE, nullptr, q));
-        ST_TRY(launch_attention(ctx, q, M, H, H, d, s->slot0, s->pos_last, 0, 0, s->cross_kv, layer, nullptr, nullptr, 0, ao));
+        ST_TRY(launch_attention(ctx, q, M, H, H, d, slot, w.enc_last, 0, 0, w.cross_kv, layer, nullptr, nullptr, 0, ao));
         ST_TRY(stt_gemm(s, ao, M, SPW(s, p + ".cwo"), SVEC(s, p + ".cbo"), ACT_NONE, x, x));
     }
-    ST_TRY(stt_ln(s, x, M, SVEC(s, p + ".ln2_w"), SVEC(s, p + ".ln2_b"), xn));
+    ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln2_w"), SVEC(s, p + ".ln2_b"), xn));
     ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".fc1"), SVEC(s, p + ".fc1_b"), ACT_GELU, nullptr, ff));
     ST_TRY(stt_gemm(s, ff, M, SPW(s, p + ".fc2"), SVEC(s, p + ".fc2_b"), ACT_NONE, x, x));
     return RT_OK;
 }
 
-// log-mel in s->mel -> encoder states in s->enc_out [n_ctx][D], and the decoder's cross-attention K/V caches
-int stt_encode(rt_stt* s) {
+// log-mel of B windows in w.mel -> encoder states in w.enc_out [B][n_ctx][D], and the decoder's cross-attention K/V caches.
+// Every launch runs over the B windows' rows; the convolutions' taps stop at a window's ends (rows_out / rows_in).
+int stt_encode(rt_stt* s, SttBufs& w, int B) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int D = c.d_model, T2 = 2 * c.n_ctx, T = c.n_ctx;
     {   // conv1: k = 3, pad 1, GELU, on [T2][n_mels]
-        GemmA a; a.ptr = s->mel; a.is_f32 = 1; a.split = 1; a.M = T2; a.Cin = c.n_mels; a.taps = 3; a.tap_stride = 1; a.tap_offset = -1; a.rows_out = T2; a.rows_in = T2;
-        GemmEpi e; e.bias = SVEC(s, "enc.conv1_b"); e.act = ACT_GELU; e.out_f32 = s->c1; e.ldc = D;
+        GemmA a; a.ptr = w.mel; a.is_f32 = 1; a.split = 1; a.M = (int64_t)B * T2; a.Cin = c.n_mels; a.taps = 3; a.tap_stride = 1; a.tap_offset = -1; a.rows_out = T2; a.rows_in = T2;
+        GemmEpi e; e.bias = SVEC(s, "enc.conv1_b"); e.act = ACT_GELU; e.out_f32 = w.c1; e.ldc = D;
         ST_TRY(launch_gemm(ctx, a, SPW(s, "enc.conv1"), e));
     }
     {   // conv2: k = 3, stride 2, pad 1, GELU, + positions.  Over rows [x[2t], x[2t+1]] it is the 2-tap GEMM (row t-1, row t) with the
         // weight laid out as [0 | W0 | W1 | W2]
-        GemmA a; a.ptr = s->c1; a.is_f32 = 1; a.split = 1; a.M = T; a.Cin = 2 * D; a.taps = 2; a.tap_stride = 1; a.tap_offset = -1; a.rows_out = T; a.rows_in = T;
-        GemmEpi e; e.bias = SVEC(s, "enc.conv2_b"); e.act = ACT_GELU; e.residual = SVEC(s, "enc.pos"); e.out_f32 = s->x; e.ldc = D;
+        GemmA a; a.ptr = w.c1; a.is_f32 = 1; a.split = 1; a.M = (int64_t)B * T; a.Cin = 2 * D; a.taps = 2; a.tap_stride = 1; a.tap_offset = -1; a.rows_out = T; a.rows_in = T;
+        GemmEpi e; e.bias = SVEC(s, "enc.conv2_b"); e.act = ACT_GELU; e.residual = SVEC(s, "enc.pos"); e.out_f32 = w.x; e.ldc = D;
+        if (B > 1) {    // the residual is read per output row: the positions are laid under every window first, and updated in place
+            hipLaunchKernelGGL(k_stt_repeat, dim3(1024), dim3(256), 0, ctx->stream, SVEC(s, "enc.pos"), (int64_t)T * D, B, w.x);
+            RT_HIP(ctx, hipGetLastError());
+            e.residual = w.x;
+        }
         ST_TRY(launch_gemm(ctx, a, SPW(s, "enc.conv2"), e));
     }
+    const int M = B * T;
     for (int i = 0; i < c.enc_layers; ++i)
-        ST_TRY(stt_layer(s, "enc.l" + std::to_string(i), s->x, s->xn, s->qkv, s->q, s->ao, s->ff, T, s->enc_kv, i, s->pos_seq, s->pos_last, 0, false));
-    ST_TRY(stt_ln(s, s->x, T, SVEC(s, "enc.ln_w"), SVEC(s, "enc.ln_b"), s->enc_out));
+        ST_TRY(stt_layer(s, w, "enc.l" + std::to_string(i), w.x, w.xn, w.qkv, w.q, w.ao, w.ff, M, w.enc_kv, i, w.enc_slot, w.enc_pos, w.enc_last, 0, false));
+    ST_TRY(stt_ln(s, w.x, D, M, SVEC(s, "enc.ln_w"), SVEC(s, "enc.ln_b"), w.enc_out));
     // cross-attention K / V of every decoder layer (k_proj has no bias: its half of cbkv is zero)
     for (int i = 0; i < c.dec_layers; ++i) {
         const std::string p = "dec.l" + std::to_string(i);
-        ST_TRY(stt_gemm(s, s->enc_out, T, SPW(s, p + ".cwkv"), SVEC(s, p + ".cbkv"), ACT_NONE, nullptr, s->qkv));
-        ST_TRY(launch_qkv_post(ctx, s->qkv, 1, T, 0, c.heads, D / c.heads, nullptr, nullptr, 0.f, nullptr, nullptr, s->slot0, s->pos_seq, 0, s->q, s->cross_kv, i));
+        ST_TRY(stt_gemm(s, w.enc_out, M, SPW(s, p + ".cwkv"), SVEC(s, p + ".cbkv"), ACT_NONE, nullptr, w.qkv));
+        ST_TRY(launch_qkv_post(ctx, w.qkv, 1, M, 0, c.heads, D / c.heads, nullptr, nullptr, 0.f, nullptr, nullptr, w.enc_slot, w.enc_pos, 0, w.q, w.cross_kv, i));
     }
     return RT_OK;
 }
 
-// M decoder rows (tokens d_tok[0..M) at positions pos0 ..) -> logits of the LAST row in s->logits
-int stt_decode_rows(rt_stt* s, int M, int pos0) {
+// B x per decoder rows (tokens w.d_tok, row r = window r / per at position pos0 + r % per; slot / pos: its row tables) -> logits of
+// the LAST row of every window in w.logits [B][vocab]
+int stt_decode_rows(rt_stt* s, SttBufs& w, int B, int per, int pos0, const int32_t* slot, const int32_t* pos) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
-    const int D = c.d_model;
+    const int D = c.d_model, M = B * per;
     SttSlot* tok = stt_find(s, "dec.tok");
-    hipLaunchKernelGGL(k_stt_embed, dim3(M), dim3(128), 0, ctx->stream, tok->tbl, SVEC(s, "dec.pos"), s->d_tok, pos0, D, s->dx);
+    hipLaunchKernelGGL(k_stt_embed, dim3(M), dim3(128), 0, ctx->stream, tok->tbl, SVEC(s, "dec.pos"), w.d_tok, pos0, per, D, w.dx);
     RT_HIP(ctx, hipGetLastError());
     for (int i = 0; i < c.dec_layers; ++i)
-        ST_TRY(stt_layer(s, "dec.l" + std::to_string(i), s->dx, s->dxn, s->dqkv, s->dq, s->dao, s->dff, M, s->dec_kv, i, s->pos_seq, s->pos_seq, pos0, true));
-    ST_TRY(stt_ln(s, s->dx + (size_t)(M - 1) * D, 1, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), s->dxn));
-    ST_TRY(stt_gemm(s, s->dxn, 1, tok->pw, nullptr, ACT_NONE, nullptr, s->logits));
+        ST_TRY(stt_layer(s, w, "dec.l" + std::to_string(i), w.dx, w.dxn, w.dqkv, w.dq, w.dao, w.dff, M, w.dec_kv, i, slot, pos, pos, pos0, true));
+    ST_TRY(stt_ln(s, w.dx + (size_t)(per - 1) * D, (int64_t)per * D, B, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), w.dxn));
+    ST_TRY(stt_gemm(s, w.dxn, B, tok->pw, nullptr, ACT_NONE, nullptr, w.logits));
+    return RT_OK;
+}
+
+// The group's buffers for B windows: allocated by the first batched call, replaced by larger ones when a call needs more windows.
+// The new set is built aside and becomes s->grp only when every allocation has succeeded; after a failure (a full group is 2.5 GB
+// beside the TTS model) the handle holds no group at all - B = 0, every pointer null - and the next batched call allocates again.
+int stt_group_reserve(rt_stt* s, int B) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    if (s->grp.B >= B) return RT_OK;
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (void* p : s->grp.owned) (void)hipFree(p);
+    s->grp = SttBufs{};
+    SttBufs nw;
+    const size_t b = (size_t)B, P = (size_t)c.n_prefix;
+    auto build = [&]() -> int {
+        ST_TRY(stt_alloc(s, nw.owned, b * c.max_new_tokens + 2 * b + 1, &nw.d_log));
+        nw.d_nlog = nw.d_log + b * c.max_new_tokens;
+        nw.d_done = nw.d_nlog + b;
+        nw.d_live = nw.d_done + b;
+        ST_TRY(stt_alloc(s, nw.owned, b, &nw.d_wins));
+        return stt_alloc_bufs(s, nw, B, (int)P);
+    };
+    const int rc = build();
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);         // (the fills and memsets already launched on the partial set)
+        for (void* p : nw.owned) (void)hipFree(p);
+        (void)hipGetLastError();                         // (the failed call's sticky error must not surface at a later launch check)
+        return rc;
+    }
+    s->grp = std::move(nw);
+    s->h_prefix.resize(b * P);
+    for (size_t i = 0; i < b * P; ++i) s->h_prefix[i] = c.prefix[i % P];
+    return RT_OK;
+}
+
+// Greedy decode of the B encoded windows of the group: ids[b] = what the single-clip loop generates for window b with the full
+// budget.  One device-to-host read (the live count) and one synchronisation per step for the whole group; the logs come back once.
+int stt_decode_group(rt_stt* s, int B, std::vector<std::vector<int32_t>>& ids) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    SttBufs& w = s->grp;
+    const int P = c.n_prefix, cap = c.max_new_tokens;
+    RT_HIP(ctx, hipMemcpyAsync(w.d_tok, s->h_prefix.data(), (size_t)B * P * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(w.d_nlog, 0, (size_t)2 * w.B * 4, ctx->stream));            // log lengths and done flags
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, w.d_live, 1, B, 0);
+    ST_TRY(stt_decode_rows(s, w, B, P, 0, w.dec_slot, w.dec_pos));
+    const int budget = std::min(cap, c.n_text_ctx - P);
+    for (int step = 0; step < budget; ++step) {
+        hipLaunchKernelGGL(k_stt_pick, dim3(B), dim3(1024), 0, ctx->stream, w.logits, c.vocab, s->d_mask, step == 0 ? 1 : 0, c.eos_id, cap, w.d_tok, w.d_log,
+                           w.d_nlog, w.d_done, w.d_live);
+        RT_HIP(ctx, hipGetLastError());
+        int32_t live = 0;
+        RT_HIP(ctx, hipMemcpyAsync(&live, w.d_live, 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (live <= 0) break;
+        if (step + 1 < budget) ST_TRY(stt_decode_rows(s, w, B, 1, P + step, w.step_slot, w.step_pos));
+    }
+    const size_t n_log = (size_t)w.B * cap;             // (the lengths lie behind the logs of all w.B rows: one copy)
+    s->h_log.resize(n_log + w.B);
+    RT_HIP(ctx, hipMemcpyAsync(s->h_log.data(), w.d_log, s->h_log.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ids.assign(B, {});
+    for (int b = 0; b < B; ++b) ids[b].assign(s->h_log.begin() + (size_t)b * cap, s->h_log.begin() + (size_t)b * cap + s->h_log[n_log + b]);
+    return RT_OK;
+}
+
+// argument rules shared by the batched entry points: null for a clip with samples, a negative length
+int stt_check_clips(const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips) {
+    if (n_clips < 0 || (n_clips > 0 && (!d_pcm || !n_samples))) return RT_ERR_INVALID;
+    for (int i = 0; i < n_clips; ++i)
+        if (n_samples[i] < 0 || (n_samples[i] > 0 && !d_pcm[i])) return RT_ERR_INVALID;
     return RT_OK;
 }
 
@@ -454,7 +725,8 @@ int rt_stt_destroy(rt_stt* s) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& sl : s->slots) { if (sl.raw) (void)hipFree(sl.raw); if (sl.raw2) (void)hipFree(sl.raw2); }
-    for (void* p : s->owned) (void)hipFree(p);
+    for (auto* owned : {&s->owned, &s->one.owned, &s->grp.owned})
+        for (void* p : *owned) (void)hipFree(p);
     if (s->d_resamp) (void)hipFree(s->d_resamp);
     delete s;
     return RT_OK;
@@ -523,33 +795,14 @@ int rt_stt_finalize(rt_stt* s) {
     for (auto& sl : s->slots)
         if (!sl.set) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_finalize: tensor '%s' was never set", sl.name.c_str());
     const rt_stt_config& c = s->cfg;
-    const int D = c.d_model, T = c.n_ctx, T2 = 2 * T, Tt = c.n_text_ctx;
-    ST_TRY(stt_kv(s, s->enc_kv, c.enc_layers, T));
-    ST_TRY(stt_kv(s, s->dec_kv, c.dec_layers, Tt));
-    ST_TRY(stt_kv(s, s->cross_kv, c.dec_layers, T));
     std::vector<double> tc(c.n_fft), ts(c.n_fft);
     for (int n = 0; n < c.n_fft; ++n) { tc[n] = std::cos(2.0 * M_PI * n / c.n_fft); ts[n] = std::sin(2.0 * M_PI * n / c.n_fft); }
-    ST_TRY(stt_alloc(s, (size_t)c.n_fft, &s->d_twc)); ST_TRY(stt_alloc(s, (size_t)c.n_fft, &s->d_tws));
+    ST_TRY(stt_alloc(s, s->owned, (size_t)c.n_fft, &s->d_twc)); ST_TRY(stt_alloc(s, s->owned, (size_t)c.n_fft, &s->d_tws));
     RT_HIP(ctx, hipMemcpy(s->d_twc, tc.data(), c.n_fft * 8, hipMemcpyHostToDevice));
     RT_HIP(ctx, hipMemcpy(s->d_tws, ts.data(), c.n_fft * 8, hipMemcpyHostToDevice));
     s->d_window = SVEC(s, "fe.window");
     s->d_melT = SVEC(s, "fe.melT");
-    ST_TRY(stt_alloc(s, (size_t)c.chunk_seconds * c.sample_rate, &s->pcm16k));
-    ST_TRY(stt_alloc(s, (size_t)T2 * c.n_mels, &s->mel));
-    ST_TRY(stt_alloc(s, (size_t)T2 * D, &s->c1));
-    ST_TRY(stt_alloc(s, (size_t)T * D, &s->x)); ST_TRY(stt_alloc(s, (size_t)T * D, &s->xn)); ST_TRY(stt_alloc(s, (size_t)T * 3 * D, &s->qkv));
-    ST_TRY(stt_alloc(s, (size_t)T * D, &s->q)); ST_TRY(stt_alloc(s, (size_t)T * D, &s->ao)); ST_TRY(stt_alloc(s, (size_t)T * c.ffn, &s->ff));
-    ST_TRY(stt_alloc(s, (size_t)T * D, &s->enc_out));
-    ST_TRY(stt_alloc(s, (size_t)c.vocab, &s->logits));
-    const int R = 8;                                                  // decoder rows per pass: the forced prefix, then one
-    ST_TRY(stt_alloc(s, (size_t)R * D, &s->dx)); ST_TRY(stt_alloc(s, (size_t)R * D, &s->dxn)); ST_TRY(stt_alloc(s, (size_t)R * 3 * D, &s->dqkv));
-    ST_TRY(stt_alloc(s, (size_t)R * D, &s->dq)); ST_TRY(stt_alloc(s, (size_t)R * D, &s->dao)); ST_TRY(stt_alloc(s, (size_t)R * c.ffn, &s->dff));
-    ST_TRY(stt_alloc(s, (size_t)T, &s->pos_seq)); ST_TRY(stt_alloc(s, (size_t)T, &s->pos_last)); ST_TRY(stt_alloc(s, (size_t)T, &s->slot0));
-    ST_TRY(stt_alloc(s, (size_t)R, &s->d_tok)); ST_TRY(stt_alloc(s, (size_t)1, &s->d_gmax));
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(8), dim3(256), 0, ctx->stream, s->pos_seq, T, 0, 1);
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(8), dim3(256), 0, ctx->stream, s->pos_last, T, T - 1, 0);
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(8), dim3(256), 0, ctx->stream, s->slot0, T, 0, 0);
-    RT_HIP(ctx, hipGetLastError());
+    ST_TRY(stt_alloc_bufs(s, s->one, 1, 8));                         // decoder rows per pass: the forced prefix (at most 8), then one
     // suppression mask: bit 0 = never (ids >= suppress_from except end-of-sequence), bit 1 = not as the first generated token
     std::vector<uint8_t> mask(c.vocab, 0);
     for (int i = 0; i < c.vocab; ++i)
@@ -558,7 +811,7 @@ int rt_stt_finalize(rt_stt* s) {
         if (c.begin_suppress[i] >= 0 && c.begin_suppress[i] < c.vocab) mask[c.begin_suppress[i]] |= 2;
     for (int32_t id : s->suppress_ids)
         if (id >= 0 && id < c.vocab && id != c.eos_id) mask[id] |= 1;
-    ST_TRY(stt_alloc(s, (size_t)c.vocab, &s->d_mask));
+    ST_TRY(stt_alloc(s, s->owned, (size_t)c.vocab, &s->d_mask));
     RT_HIP(ctx, hipMemcpy(s->d_mask, mask.data(), c.vocab, hipMemcpyHostToDevice));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->finalized = true;
@@ -572,7 +825,7 @@ int rt_stt_log_mel(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sam
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_log_mel: not finalized");
     ST_TRY(stt_features(s, d_pcm, n_samples, sample_rate));
-    RT_HIP(ctx, hipMemcpyAsync(d_mel, s->mel, (size_t)2 * s->cfg.n_ctx * s->cfg.n_mels * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_mel, s->one.mel, (size_t)2 * s->cfg.n_ctx * s->cfg.n_mels * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -584,8 +837,8 @@ int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t samp
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_encode: not finalized");
     ST_TRY(stt_features(s, d_pcm, n_samples, sample_rate));
-    ST_TRY(stt_encode(s));
-    RT_HIP(ctx, hipMemcpyAsync(d_states, s->enc_out, (size_t)s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    ST_TRY(stt_encode(s, s->one, 1));
+    RT_HIP(ctx, hipMemcpyAsync(d_states, s->one.enc_out, (size_t)s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -612,6 +865,7 @@ int rt_stt_transcribe(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t 
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe: not finalized");
     const rt_stt_config& c = s->cfg;
+    SttBufs& w = s->one;
     *h_n_tokens = 0;
     const int64_t win = (int64_t)c.chunk_seconds * sample_rate;     // one window, in input samples
     int n = 0;
@@ -619,24 +873,84 @@ int rt_stt_transcribe(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t 
         if (n >= max_tokens) break;
         const int64_t n_w = std::min<int64_t>(win, n_samples - off);
         ST_TRY(stt_features(s, n_w > 0 ? d_pcm + off : d_pcm, n_w, sample_rate));
-        ST_TRY(stt_encode(s));
+        ST_TRY(stt_encode(s, w, 1));
         // forced prefix in one pass, then one token per pass: the host reads each token (end-of-sequence decides when to stop)
-        RT_HIP(ctx, hipMemcpyAsync(s->d_tok, c.prefix, c.n_prefix * 4, hipMemcpyHostToDevice, ctx->stream));
-        ST_TRY(stt_decode_rows(s, c.n_prefix, 0));
-        if (d_first_logits && off == 0) RT_HIP(ctx, hipMemcpyAsync(d_first_logits, s->logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(w.d_tok, c.prefix, c.n_prefix * 4, hipMemcpyHostToDevice, ctx->stream));
+        ST_TRY(stt_decode_rows(s, w, 1, c.n_prefix, 0, w.dec_slot, w.dec_pos));
+        if (d_first_logits && off == 0) RT_HIP(ctx, hipMemcpyAsync(d_first_logits, w.logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
         const int budget = std::min(std::min(max_tokens - n, c.max_new_tokens), c.n_text_ctx - c.n_prefix);
         for (int step = 0; step < budget; ++step) {
-            hipLaunchKernelGGL(k_stt_argmax, dim3(1), dim3(1024), 0, ctx->stream, s->logits, c.vocab, s->d_mask, step == 0 ? 1 : 0, s->d_tok);
+            hipLaunchKernelGGL(k_stt_argmax, dim3(1), dim3(1024), 0, ctx->stream, w.logits, c.vocab, s->d_mask, step == 0 ? 1 : 0, w.d_tok);
             RT_HIP(ctx, hipGetLastError());
             int32_t tok = 0;
-            RT_HIP(ctx, hipMemcpyAsync(&tok, s->d_tok, 4, hipMemcpyDeviceToHost, ctx->stream));
+            RT_HIP(ctx, hipMemcpyAsync(&tok, w.d_tok, 4, hipMemcpyDeviceToHost, ctx->stream));
             RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
             if (tok == c.eos_id) break;
             h_tokens[n++] = tok;
-            if (step + 1 < budget) ST_TRY(stt_decode_rows(s, 1, c.n_prefix + step));
+            if (step + 1 < budget) ST_TRY(stt_decode_rows(s, w, 1, 1, c.n_prefix + step, w.step_slot, w.step_pos));
         }
     }
     *h_n_tokens = n;
+    return RT_OK;
+}
+
+// The windows of all clips are the rows of the batch: every clip is cut as rt_stt_transcribe cuts it, up to STT_GROUP windows go
+// through the front end, the encoder and the greedy decode together, and a clip's ids are its windows' ids joined and cut at the
+// cap.  A window is decoded with the full budget; greedy decoding makes the cut join what the serial loop gives.  A window is
+// left out only when the groups before it already filled its clip's cap.
+int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, int32_t* h_tokens,
+                            int32_t max_tokens_per_clip, int32_t* h_n_tokens) {
+    if (!s || max_tokens_per_clip < 1 || sample_rate < 1000 || stt_check_clips(d_pcm, n_samples, n_clips) || (n_clips > 0 && (!h_tokens || !h_n_tokens)))
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_transcribe_batch: bad argument");
+    if (n_clips == 0) return RT_OK;
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe_batch: not finalized");
+    const rt_stt_config& c = s->cfg;
+    const int64_t win = (int64_t)c.chunk_seconds * sample_rate;     // one window, in input samples
+    std::vector<SttSpan> all;
+    for (int i = 0; i < n_clips; ++i) {
+        h_n_tokens[i] = 0;
+        for (int64_t off = 0; off == 0 || off < n_samples[i]; off += win)
+            all.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off : nullptr, std::min<int64_t>(win, n_samples[i] - off)});
+    }
+    ST_TRY(stt_group_reserve(s, (int)std::min<size_t>(all.size(), STT_GROUP)));
+    std::vector<SttSpan> group;
+    std::vector<std::vector<int32_t>> ids;
+    for (size_t next = 0; next < all.size();) {
+        group.clear();
+        for (; next < all.size() && (int)group.size() < STT_GROUP; ++next)
+            if (h_n_tokens[all[next].clip] < max_tokens_per_clip) group.push_back(all[next]);
+        if (group.empty()) break;
+        const int B = (int)group.size();
+        ST_TRY(stt_features_group(s, group.data(), B, sample_rate));
+        ST_TRY(stt_encode(s, s->grp, B));
+        ST_TRY(stt_decode_group(s, B, ids));
+        for (int b = 0; b < B; ++b) {
+            const int i = group[b].clip;
+            for (int32_t t : ids[b])
+                if (h_n_tokens[i] < max_tokens_per_clip) h_tokens[(size_t)i * max_tokens_per_clip + h_n_tokens[i]++] = t;
+        }
+    }
+    return RT_OK;
+}
+
+int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, float* d_states) {
+    if (!s || !d_states || n_clips < 1 || n_clips > STT_GROUP || sample_rate < 1000 || stt_check_clips(d_pcm, n_samples, n_clips))
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_encode_batch: bad argument (1 .. %d clips)", STT_GROUP);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_encode_batch: not finalized");
+    const int64_t win = (int64_t)s->cfg.chunk_seconds * sample_rate;
+    std::vector<SttSpan> group;
+    for (int i = 0; i < n_clips; ++i) group.push_back({i, d_pcm[i], std::min<int64_t>(win, n_samples[i])});
+    ST_TRY(stt_group_reserve(s, n_clips));
+    ST_TRY(stt_features_group(s, group.data(), n_clips, sample_rate));
+    ST_TRY(stt_encode(s, s->grp, n_clips));
+    RT_HIP(ctx, hipMemcpyAsync(d_states, s->grp.enc_out, (size_t)n_clips * s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

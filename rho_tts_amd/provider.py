@@ -32,6 +32,7 @@ logger = logging.getLogger("rho_tts_amd")
 
 PROVIDER_NAME = "qwen_mi355x"
 BUILTIN_VOICES = ["Chelsie", "Aidan", "Vivian", "Ryan", "Aria", "Ethan", "Luna", "Harper", "James"]
+_NO_TRANSCRIPT = object()      # "no transcript was handed in" (None is a transcript: the transcription failed)
 
 
 class BatchedPipeline:
@@ -175,6 +176,7 @@ class BatchedPipeline:
                 # batches and of how many ranks share it
                 audios = self._generate_chunk([work[w][2] for w in chunk], [stream_ids[w] for w in chunk], token)
                 drifts = self._chunk_drifts(audios) if self.max_iterations > 1 else None
+                texts = self._chunk_texts(audios, drifts) if self.max_iterations > 1 else None
                 for k, (w, a) in enumerate(zip(chunk, audios)):
                     if a is None:
                         retry.append(w)
@@ -186,7 +188,8 @@ class BatchedPipeline:
                         if getattr(self, "auto_sort_good_dir", None) or getattr(self, "auto_sort_bad_dir", None):
                             self._auto_sort_only(a)          # drift detection for auto-sort even without validation retries (:801-818)
                         continue
-                    if self._validate_segment(a, work[w][2], state[w], None if drifts is None else drifts[k]):
+                    if self._validate_segment(a, work[w][2], state[w], None if drifts is None else drifts[k],
+                                              transcript=_NO_TRANSCRIPT if texts is None else texts[k]):
                         accepted[w] = a                      # valid: this attempt's audio is kept (:859)
                     else:
                         retry.append(w)
@@ -279,11 +282,43 @@ class BatchedPipeline:
         it = iter(vals)
         return [None if a is None else next(it) for a in audios]
 
-    def _validate_segment(self, audio: torch.Tensor, text: str, st: dict, drift: Optional[float] = None) -> bool:
+    def _chunk_texts(self, audios, drifts) -> Optional[list]:
+        """The transcript of every segment of a chunk that the per-segment order would transcribe, from ONE call of
+        ``transcriber.batch`` (stt.WhisperTranscriber.batch: one native call for the chunk), aligned with ``audios``
+        (``_NO_TRANSCRIPT`` where the segment is not in the call).  A segment is in the call when it has audio and its voice check
+        is known to pass before the text check: its drift from ``_chunk_drifts`` is below the threshold, or no drift scorer and no
+        file-based drift validator is configured.  Any other segment is decided by the per-segment call, and so is the whole
+        chunk - None - when the transcriber has no ``batch`` or the call fails."""
+        batch = getattr(getattr(self, "transcriber", None), "batch", None)
+        if not callable(batch):
+            return None
+        if getattr(self, "drift_scorer", None) is not None:
+            if drifts is None:
+                return None
+            take = [a is not None and d is not None and float(d) < self.accent_drift_threshold for a, d in zip(audios, drifts)]
+        elif hasattr(self, "_validate_accent_drift"):
+            return None
+        else:
+            take = [a is not None for a in audios]
+        have = [a for a, t in zip(audios, take) if t]
+        if not have:
+            return None
+        try:
+            vals = list(batch(have, self.sample_rate))
+            if len(vals) != len(have):
+                raise RuntimeError(f"transcriber.batch returned {len(vals)} transcripts for {len(have)} segments")
+        except Exception as e:  # noqa: BLE001
+            logger.warning(f"    batched transcription failed ({e}); transcribing per segment")
+            return None
+        it = iter(vals)
+        return [next(it) if t else _NO_TRANSCRIPT for t in take]
+
+    def _validate_segment(self, audio: torch.Tensor, text: str, st: dict, drift: Optional[float] = None, transcript=_NO_TRANSCRIPT) -> bool:
         """One validation attempt (base_tts.py:821-886), updating the segment's state in the reference's order: drift ->
         auto-sort -> best-by-drift -> text match only if the voice passed.  A validator that raises counts as a failed
         attempt but keeps what it had already recorded.  Returns True when the attempt is accepted.  ``drift``: the scorer's value
-        for this audio when the chunk was scored in one call (``_chunk_drifts``); the scorer is then not called again."""
+        for this audio when the chunk was scored in one call (``_chunk_drifts``); the scorer is then not called again.  ``transcript``:
+        likewise the transcriber's text from ``_chunk_texts`` (None is a transcript: "transcription failed")."""
         scorer, transcriber = getattr(self, "drift_scorer", None), getattr(self, "transcriber", None)
         file_based = hasattr(self, "_validate_accent_drift")          # the reference's file-based validators (absent in the host mirror)
         if scorer is None and transcriber is None and not file_based:
@@ -307,7 +342,8 @@ class BatchedPipeline:
                 if voice_ok:
                     if transcriber is not None:
                         from .validation import validate_text_match
-                        text_ok, sim, _ = validate_text_match(transcriber(audio, self.sample_rate), text, self.text_similarity_threshold)
+                        heard = transcriber(audio, self.sample_rate) if transcript is _NO_TRANSCRIPT else transcript
+                        text_ok, sim, _ = validate_text_match(heard, text, self.text_similarity_threshold)
                         st["text_sim"] = sim
                     elif file_based:
                         text_ok, sim, _ = self._validate_text_match(path, text)

@@ -161,6 +161,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_stt_finalize.argtypes = [vp]
     lib.rt_stt_set_suppress.argtypes = [vp, C.POINTER(i32), i32]
     lib.rt_stt_transcribe.argtypes = [vp, vp, i64, i32, C.POINTER(i32), i32, C.POINTER(i32), vp]
+    lib.rt_stt_transcribe_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(i32), i32, C.POINTER(i32)]
     lib.rt_stt_log_mel.argtypes = [vp, vp, i64, i32, vp]
     lib.rt_stt_encode.argtypes = [vp, vp, i64, i32, vp]
     _DECLARED = True
@@ -363,8 +364,7 @@ class NativeSTT:
     def transcribe_ids(self, audio, sample_rate: int, max_tokens: Optional[int] = None, first_logits: bool = False):
         x = self._pcm(audio)
         # audio longer than one chunk is transcribed window by window (rt_stt_transcribe): room for every window's ids
-        windows = max(1, -(-int(x.numel()) // (int(self.cfg.chunk_seconds) * int(sample_rate))))
-        cap = int(max_tokens or windows * self.cfg.max_new_tokens)
+        cap = int(max_tokens or self.windows(x.numel(), sample_rate) * self.cfg.max_new_tokens)
         toks = (C.c_int32 * cap)()
         n = C.c_int32()
         lg = torch.empty(self.cfg.vocab, dtype=torch.float32, device=x.device) if first_logits else None
@@ -372,6 +372,23 @@ class NativeSTT:
                                                   C.byref(n), C.c_void_p(lg.data_ptr()) if lg is not None else None), "rt_stt_transcribe")
         ids = [int(toks[i]) for i in range(n.value)]
         return (ids, lg) if first_logits else ids
+
+    def windows(self, n_samples: int, sample_rate: int) -> int:
+        """``chunk_seconds`` windows a clip of ``n_samples`` is cut into (rt_stt_transcribe: an empty clip is one window of silence)."""
+        return max(1, -(-int(n_samples) // (int(self.cfg.chunk_seconds) * int(sample_rate))))
+
+    def transcribe_ids_batch(self, audios, sample_rate: int, max_tokens: Optional[int] = None) -> List[List[int]]:
+        """The ids of every clip from ONE native call (rt_stt_transcribe_batch): per clip what ``transcribe_ids`` gives for it alone.
+        ``max_tokens`` caps every clip; the default leaves room for every window of the longest clip, so nothing is cut."""
+        xs = [self._pcm(a) for a in audios]
+        n = len(xs)
+        cap = int(max_tokens or max([self.windows(x.numel(), sample_rate) for x in xs] or [1]) * self.cfg.max_new_tokens)
+        ptrs = (C.c_void_p * max(n, 1))(*[x.data_ptr() if x.numel() else None for x in xs])
+        lens = (C.c_int64 * max(n, 1))(*[x.numel() for x in xs])
+        toks = (C.c_int32 * max(n * cap, 1))()
+        counts = (C.c_int32 * max(n, 1))()
+        self.ctx.check(self.lib.rt_stt_transcribe_batch(self.handle, ptrs, lens, n, int(sample_rate), toks, cap, counts), "rt_stt_transcribe_batch")
+        return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)]
 
     def log_mel(self, audio, sample_rate: int) -> torch.Tensor:
         """[n_mels][frames] float32 (the layout of WhisperFeatureExtractor's ``input_features``)."""
@@ -418,11 +435,21 @@ class WhisperTranscriber:
     def ids(self, audio, sample_rate: int) -> List[int]:
         return self.model.transcribe_ids(audio, sample_rate)
 
-    def __call__(self, audio, sample_rate: int) -> Optional[str]:
-        ids = self.ids(audio, sample_rate)
+    def ids_batch(self, audios, sample_rate: int) -> List[List[int]]:
+        return self.model.transcribe_ids_batch(audios, sample_rate)
+
+    def _text(self, ids: List[int]) -> Optional[str]:
         if self.tokenizer is not None:
             return self.tokenizer.decode(ids, skip_special_tokens=True).strip()
         return " ".join(f"<{i}>" for i in ids)
+
+    def __call__(self, audio, sample_rate: int) -> Optional[str]:
+        return self._text(self.ids(audio, sample_rate))
+
+    def batch(self, audios, sample_rate: int) -> List[Optional[str]]:
+        """The texts of a chunk of segments from one native call (the provider's ``_chunk_texts``): per clip what ``__call__``
+        returns for it."""
+        return [self._text(ids) for ids in self.ids_batch(audios, sample_rate)]
 
     def close(self) -> None:
         self.model.close()
