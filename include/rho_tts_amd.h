@@ -452,6 +452,37 @@ RT_API int rt_speedpitch_destroy(rt_speedpitch* sp);
 RT_API int rt_speedpitch_apply(rt_speedpitch* sp, const float* d_in, int64_t n_in, const rt_speedpitch_plan* plan, float* d_out,
                                int64_t out_capacity);
 
+/* ------------------------------------------------------------------ drift classifier: forest inference from exported tables
+ * Stands behind validation/classifier/__init__.py:115-118 (`model.predict_proba(x)[0][1]` of the pickled scikit-learn model): a
+ * CalibratedClassifierCV of random forests with one isotonic calibrator each - or a bare forest - as plain arrays, which
+ * rho_tts_amd/forest.py documents, exports (export_sklearn), validates and DEFINES the arithmetic of (predict_host).  All indices count
+ * through the whole model:
+ *   h_forest_first [n_forests + 1]: forest c owns the trees h_forest_first[c] .. h_forest_first[c + 1] - 1 (1 .. 64 forests);
+ *   h_tree_first [n_trees + 1]: tree t owns the nodes h_tree_first[t] .. h_tree_first[t + 1] - 1, its root first;
+ *   h_node_feature [n_nodes]: the split feature, -1 for a leaf; h_node_value: the float64 threshold of a split node / the class-1
+ *     fraction of a leaf; h_node_right: the right child of a split node, -1 for a leaf.  The left child of node k is k + 1;
+ *   h_iso_first [n_calibrators + 1], h_iso_x, h_iso_y: the knots of calibrator c (= forest c's); n_calibrators = n_forests, or 0 for
+ *     a single uncalibrated forest.
+ * rt_forest_set_model re-checks on the host what keeps the kernels in bounds and every walk finite - contiguous non-empty ranges, every
+ * child behind its parent and inside its own tree, split features below n_features, finite values, leaf fractions in [0, 1], strictly
+ * increasing knots, at most 64 levels - and returns RT_ERR_INVALID before anything is uploaded when a condition fails (the model set
+ * before stays).  It uploads once and may be called again to replace the model.
+ * rt_forest_predict: h_x [n_rows][n_features] float64 -> h_prob [n_rows] float64, bit-equal to predict_host row by row whatever else
+ * shares the call: features rounded to float32 and compared as doubles (`x <= threshold` goes left), a forest's leaf fractions summed
+ * in tree order and divided by the tree count, clipped to the calibrator's knots and interpolated with np.interp's arithmetic, the
+ * calibrated values summed in order and divided by their count.  One host-to-device copy, two launches, one device-to-host copy and
+ * one stream synchronisation on the context's stream, whatever n_rows is; workspaces belong to the handle and only grow.
+ * n_rows == 0: RT_OK, nothing touched.  RT_ERR_INVALID with no launch: no model set, n_rows < 0, a feature that is NaN, infinite or
+ * beyond float32's range. */
+typedef struct rt_forest rt_forest;
+RT_API int rt_forest_create(rt_ctx* ctx, rt_forest** out);
+RT_API int rt_forest_destroy(rt_forest* f);
+RT_API int rt_forest_set_model(rt_forest* f, int32_t n_features, int32_t n_forests, const int32_t* h_forest_first, int32_t n_trees,
+                               const int32_t* h_tree_first, int32_t n_nodes, const int32_t* h_node_feature, const int32_t* h_node_right,
+                               const double* h_node_value, int32_t n_calibrators, const int32_t* h_iso_first, const double* h_iso_x,
+                               const double* h_iso_y);
+RT_API int rt_forest_predict(rt_forest* f, const double* h_x, int32_t n_rows, double* h_prob);
+
 /* Measurement and test entry points (rt_profile_*, rt_debug_*, rt_bench_*) are declared in rho_tts_amd_debug.h: a host binding of
  * the generation path needs none of them. */
 

@@ -11,7 +11,8 @@ definition of the two kernels that do the same for a whole chunk of clips in one
 
 The 256-d embedding is NOT produced: resemblyzer's network is a pretrained checkpoint (no weights offline), and the classifier
 itself is a pickled scikit-learn model this build will not load.  ``make_drift_scorer`` therefore takes the classifier as a
-callable on the 30 dimensions (or on whatever vector the caller assembles around them).
+callable on the 30 dimensions (or on whatever vector the caller assembles around them); ``make_forest_scorer`` takes it as a
+``forest.DriftForest`` - the same model exported to plain arrays, evaluated on the GPU for a whole chunk in one call.
 
 Definitions: librosa 0.10's defaults as the reference calls them, restated (oracle/features.py says which) - including the
 reference's own quirk of leaving ``librosa.pyin``'s default ``sr=22050`` in place for 16-kHz audio, so that every F0 is
@@ -347,5 +348,40 @@ def make_drift_scorer(extractor: HandcraftedFeatures, classifier: Callable[[np.n
                 f = np.concatenate([np.asarray(embed(audio, sample_rate), dtype=np.float64).reshape(-1), f])
             out.append(float(classifier(f)))
         return out
+    score.batch = batch
+    return score
+
+
+def make_forest_scorer(extractor: HandcraftedFeatures, forest, embed: Optional[Callable[[Sequence[torch.Tensor], int], np.ndarray]] = None
+                       ) -> Callable[[torch.Tensor, int], float]:
+    """A ``drift_scorer`` hook whose classifier runs on the GPU too (forest.DriftForest): ``score.batch(audios, sample_rate)`` makes ONE
+    ``extractor.batch`` call and then ONE ``forest.predict`` call for the whole chunk, and the single-clip form ``score(audio,
+    sample_rate)`` is the same path with one row.  ``embed`` is a BATCH callable ``(audios, sample_rate) -> [n][k]`` for the
+    speaker-embedding dimensions, which come first in the reference's layout (trainer.py:61-65): embedding, then the 30 hand-crafted
+    features.  ``k + 30`` must be the forest's width, checked here: k is 0 without ``embed``, and ``embed.dim`` where the callable
+    carries one; a callable without it can only be held to its width at its first call.  The ``ValueError`` names the sizes."""
+    width = int(forest.n_features)
+    if embed is None and width != 30:
+        raise ValueError(f"the classifier takes {width} features, the extractor gives 30: {width - 30} embedding dimensions are needed (embed=...)")
+    k = None if embed is None else getattr(embed, "dim", None)
+    if embed is not None and (width <= 30 or (k is not None and int(k) + 30 != width)):
+        raise ValueError(f"the classifier takes {width} features, the extractor gives 30 and the embedding {'some' if k is None else int(k)}: "
+                         f"{width} != 30 + {'k' if k is None else int(k)}")
+
+    def batch(audios: Sequence[torch.Tensor], sample_rate: int) -> List[float]:
+        audios = list(audios)
+        if not audios:
+            return []
+        f = np.asarray(extractor.batch(audios, sample_rate), dtype=np.float64).reshape(len(audios), -1)
+        if embed is not None:
+            e = np.asarray(embed(audios, sample_rate), dtype=np.float64)
+            if e.ndim != 2 or e.shape[0] != len(audios) or e.shape[1] + f.shape[1] != width:
+                raise ValueError(f"embed returned an array of shape {e.shape} for {len(audios)} clips: the classifier takes {width} features, "
+                                 f"{f.shape[1]} of them hand-crafted, so it needs [{len(audios)}][{width - f.shape[1]}]")
+            f = np.concatenate([e, f], axis=1)
+        return [float(p) for p in forest.predict(f)]
+
+    def score(audio: torch.Tensor, sample_rate: int) -> float:
+        return batch([audio], sample_rate)[0]
     score.batch = batch
     return score

@@ -643,6 +643,10 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         self._engine = None
         self._ctx = None
         self._speed_pitch = None                               # speedpitch.SpeedPitch, made by the first call that needs it
+        self._drift_scorer = None                              # the caller's drift_scorer, if one was set
+        self._drift_native = None                              # (HandcraftedFeatures, DriftForest, scorer) built from drift_model_path
+        self.drift_embed = None                                # batch callable (audios, sample_rate) -> [n][k]: the embedding dimensions
+        self.drift_optimal_threshold: Optional[float] = None   # the exported file's metadata, known once the file is loaded
         self._lock = threading.RLock()
         self._voice_key = None
         # decode-schedule figures of this instance's engine calls, accumulated until cleared: kept / launched row-frames
@@ -667,7 +671,8 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             if self._engine is None:
                 from .engine import Engine
                 if self._ctx is not None:
-                    self._close_speed_pitch()                  # (it lives on the context that goes away here)
+                    self._close_speed_pitch()                  # (they live on the context that goes away here)
+                    self._close_drift()
                     self._ctx.close()
                     self._ctx = None
                 self._engine = Engine(self.model_path, self._device_ordinal(), max_batch=max(1, min(64, int(self.batch_size))))
@@ -913,13 +918,71 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             self._speed_pitch.close()
             self._speed_pitch = None
 
+    # ---------------------------------------------------------------- drift validation from an exported classifier
+    @property
+    def drift_scorer(self):
+        """The tensor-level drift hook (BatchedPipeline): the caller's when one was set; else, when ``drift_model_path`` names an
+        exported classifier (``.npz``, tools/export_drift_classifier.py), the native one - feature extractor and forest on this
+        provider's context, built at first use; else None, and nothing changes."""
+        if self._drift_scorer is not None or not self.drift_model_path:
+            return self._drift_scorer
+        return self._native_drift_scorer()
+
+    @drift_scorer.setter
+    def drift_scorer(self, scorer) -> None:
+        self._drift_scorer = scorer
+
+    def _native_drift_scorer(self):
+        """HandcraftedFeatures + DriftForest + make_forest_scorer for ``drift_model_path``.  A configuration that cannot work is a
+        ``ValueError`` at first use, never a silently skipped check.  ``accent_drift_threshold`` stays the caller's: the file's
+        ``optimal_threshold`` is metadata, as in the reference, offered as ``drift_optimal_threshold``."""
+        with self._lock:
+            if self._drift_native is not None:
+                return self._drift_native[2]
+            path = str(self.drift_model_path)
+            if not path.lower().endswith(".npz"):
+                raise ValueError(f"drift_model_path = {path!r}: this provider never unpickles a model.  Export the classifier once with "
+                                 "`python tools/export_drift_classifier.py IN.pkl OUT.npz` and point drift_model_path at the .npz")
+            from . import forest as F
+            from .features import HandcraftedFeatures, make_forest_scorer
+            tables = F.load(path)
+            width = int(tables["n_features"])
+            if width != F.HANDCRAFTED and self.drift_embed is None:
+                raise ValueError(f"drift_model_path = {path!r} takes {width} features: the {width - F.HANDCRAFTED} dimensions in front of the "
+                                 f"{F.HANDCRAFTED} hand-crafted ones are the speaker embedding, which this provider does not compute - set "
+                                 "drift_embed to a batch callable (audios, sample_rate) -> [n][k]")
+            if width == F.HANDCRAFTED and self.drift_embed is not None:
+                raise ValueError(f"drift_model_path = {path!r} takes {width} features, all hand-crafted: drift_embed has no place in it")
+            ctx = self._native_ctx()
+            ex = forest = None
+            try:
+                ex = HandcraftedFeatures(ctx)
+                forest = F.DriftForest(ctx, tables)
+                scorer = make_forest_scorer(ex, forest, self.drift_embed)
+            except Exception:
+                for h in (forest, ex):
+                    if h is not None:
+                        h.close()
+                raise
+            self._drift_native = (ex, forest, scorer)
+            self.drift_optimal_threshold = float(tables["optimal_threshold"])
+            return scorer
+
+    def _close_drift(self) -> None:
+        if self._drift_native is not None:
+            ex, forest, _ = self._drift_native
+            self._drift_native = None
+            forest.close()
+            ex.close()
+
     @property
     def sample_rate(self) -> int:
         return 24000 if self._engine is None else self._engine.cfg.sample_rate
 
     def close(self) -> None:
         with self._lock:
-            self._close_speed_pitch()                          # (before the context it lives on)
+            self._close_speed_pitch()                          # (before the context they live on)
+            self._close_drift()
             if self._engine is not None:
                 self._engine.close()
                 self._engine = None
