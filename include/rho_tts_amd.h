@@ -367,6 +367,19 @@ RT_API int rt_stt_transcribe(rt_stt* s, const float* d_pcm, int64_t n_samples, i
  * one window of silence, as in rt_stt_transcribe. */
 RT_API int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
                                    int32_t* h_tokens, int32_t max_tokens_per_clip, int32_t* h_n_tokens);
+/* rt_stt_transcribe_batch decoded by beam search of width beam_size (1 .. 8; the rule: DESIGN.md section 5 - Whisper's published
+ * BeamSearchDecoder with faster-whisper's defaults, patience 1 and length penalty 1, which is what the reference's
+ * model.transcribe(path, language="en") runs with at width 5).  Per window: up to beam_size live hypotheses with cumulative
+ * float32 log-probabilities (log-softmax over the whole vocabulary of the logits masked as for the greedy rule), beam_size + 1
+ * candidates per hypothesis and step, a finished list of beam_size entries; the result is the entry with the largest
+ * score / (ids + 1).  beam_size == 1 gives the ids of rt_stt_transcribe_batch.  floor(32 / beam_size) windows make a group, whose
+ * decoder rows are windows x beams; a clip's ids and score do not depend on the other clips of the call.  Every window of a clip is
+ * decoded and max_tokens cuts the joined ids.  h_scores (optional) [n_clips]: the clip's average log-probability per emitted token,
+ * end-of-sequence counted: sum of its windows' cumulative log-probabilities / sum of (ids + 1).  The decoder side of the beam rows
+ * (two self-attention caches, logits) is allocated by the first beam call and only grows.  RT_ERR_INVALID: the argument rules of
+ * rt_stt_transcribe_batch, and a beam_size outside 1 .. 8. */
+RT_API int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
+                                  int32_t beam_size, int32_t* h_tokens, int32_t max_tokens, int32_t* h_n_tokens, float* h_scores);
 /* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM. */
 RT_API int rt_stt_log_mel(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, float* d_mel);
 RT_API int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, float* d_states);

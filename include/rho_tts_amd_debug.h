@@ -102,6 +102,23 @@ RT_API int rt_debug_features_viterbi(rt_features* f, const double* h_log_obs, co
 RT_API int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
                                      float* d_states);
 
+/* The two kernels of the beam path on their own (tests/test_stt_beam_kernel_gpu.py).
+ * rt_debug_stt_beam_step: one step of the rule on logits the caller supplies (HBM, float32, [n_windows * row_stride][cfg.vocab]; beam j
+ *   of window w is row w * row_stride + j; row_stride is `beam`, or 1 for the step behind the prefix) with the handle's masks and
+ *   end-of-sequence id.  In, per row w * beam + j: the beams' cumulative scores; per window: live beams, finished entries so far, done
+ *   flag.  Out, per row: next token and parent ROW (-1 where the step wrote none), the new scores, the finished list's beams and
+ *   scores (entry k of window w at w * beam + k; the entries from h_n_finished[w] on are this step's); per window: live beams, finished
+ *   entries, done flag; and the number of windows still decoding.  n_windows * beam <= 32.
+ * rt_debug_stt_beam_reorder: fills the four planes of a cache [layers][rows][heads][max_pos][head_dim] with the 16-bit pattern
+ *   (i * 40503 + plane * 12289) & 0x7fff (i: the element's index in its plane) and those of a second one with 0xbeef, gathers row
+ *   h_src[r]'s positions [0, len) into row r of the second, and returns all eight planes in h_planes. */
+RT_API int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_stride, const float* h_scores_in, int32_t n_windows, int32_t beam,
+                                  const int32_t* h_n_live, const int32_t* h_n_finished, const int32_t* h_done, int32_t first_step, int32_t step,
+                                  int32_t* h_next_tok, int32_t* h_parent, float* h_scores_out, int32_t* h_n_live_out, int32_t* h_fin_beam,
+                                  float* h_fin_score, int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows);
+RT_API int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src,
+                                     int32_t len, uint16_t* h_planes);
+
 /* A/B switches for measurements and tests (process-wide; the defaults are the fast path).  One row per switch, as in the table
  * they are generated from (rho_tts_amd/csrc/knobs.h: defaults, accepted ranges, measurement notes).  A code that no row accepts is
  * refused with RT_ERR_INVALID and changes nothing.  `code`:

@@ -16,6 +16,10 @@
 // rt_stt_transcribe_batch runs the same kernels over a whole validation chunk: the windows of all clips, STT_GROUP at a time, are
 // the rows of every launch (group siblings of the front-end kernels, one cache slot per window, the decode bookkeeping in
 // k_stt_pick), and a clip's ids are bit for bit the ids it gets alone.
+//
+// rt_stt_transcribe_beam decodes the same windows by beam search (the reference's transcriber runs faster-whisper's default, width
+// 5): decoder rows are windows x beams, k_stt_beam_select keeps the hypotheses on the device and k_stt_beam_reorder hands a row the
+// self-attention cache of the row it continues; the call also returns each clip's average log-probability per emitted token.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -264,6 +268,206 @@ __global__ void k_stt_repeat(const float* __restrict__ src, int64_t n, int reps,
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) dst[i] = src[i % n];
 }
 
+// ---------------------------------------------------------------------------------------------- beam search (rt_stt_transcribe_beam)
+// The decoding rule: per window up to B live beams with cumulative float32 log-probabilities and a finished
+// list of at most B entries.  Decoder rows are windows x beams: row w B + j is beam j of window w.
+constexpr int STT_BEAM_MAX = 8;
+constexpr int STT_CAND = STT_BEAM_MAX + 1;              // candidates a beam contributes per step: B + 1 <= 9
+constexpr int STT_NO_ID = 0x7fffffff;
+constexpr int STT_SEL_U = 4;                            // logits a thread of k_stt_beam_select requests per round trip
+
+// the order of one row's candidates: the larger log-probability first, the lower id on ties (NaNs never enter)
+__device__ __forceinline__ bool cand_before(float v, int i, float ov, int oi) { return v > ov || (v == ov && i < oi); }
+
+// The beam bookkeeping of a group, one int32 allocation of `R` rows (R >= windows x B): what k_stt_beam_select keeps and the host
+// reads once when the group is decoded.  Finished entry k of window w sits at w B + k.
+struct SttBeamBook {
+    int32_t *next_tok, *src;         // [R] the row's next input token | the row (of this step) it continues
+    float* score;                    // [R] cumulative log-probability of the row's beam
+    int32_t *n_live, *n_fin, *done;  // [R], per window: live beams | finished entries | 1 once the finished list is full
+    int32_t *fin_step, *fin_beam;    // [R] a finished entry: the step it ended at and the beam (of that step) it extends
+    float* fin_score;                // [R]
+    int32_t* live;                   // [1] windows of the group still decoding
+    int32_t *bp_tok, *bp_par;        // [steps][R] back-pointers: the token a row took at a step and the beam it came from
+    int R;
+};
+
+// One step of the rule, one workgroup per window.  Per live row: the masked maximum, sum exp(x - max) (per thread in index order,
+// butterfly per wave, the 16 wave sums in wave order: a row's log-probabilities do not depend on what else is in the launch), then
+// every thread's 9 best (lp, id) in registers, merged through LDS into the row's B + 1 best.  Then wave 0 ranks the window's
+// <= 72 candidates by (score descending, beam, id) and thread 0 walks them: end-of-sequence candidates enter the finished list
+// while it has room, the others become the next beams until B are taken.  logits row of beam j: w row_stride + j (the step behind
+// the prefix has one row per window: row_stride 1, one live beam).
+__global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restrict__ logits, int V, int row_stride, const uint8_t* __restrict__ mask,
+                                                          int first_step, int eos, int B, int step, SttBeamBook bk) {
+    __shared__ float red_v[16];
+    __shared__ int red_i[16];
+    __shared__ float c_score[STT_BEAM_MAX * STT_CAND];
+    __shared__ int c_tok[STT_BEAM_MAX * STT_CAND], c_beam[STT_BEAM_MAX * STT_CAND], c_sorted[STT_BEAM_MAX * STT_CAND];
+    const int w = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    if (bk.done[w]) return;                                // (uniform: a completed window rides along untouched)
+    const int nl = min(bk.n_live[w], B), K = B + 1;
+    const uint8_t bad = first_step ? 3 : 1;
+    for (int j = 0; j < nl; ++j) {
+        const float* x = logits + ((int64_t)w * row_stride + j) * V;
+        // every pass asks for STT_SEL_U logits and mask bytes of the thread at once, unconditionally (clamped indices): one round trip
+        // per 4 elements instead of one per element behind a per-lane branch (8 would spill at 1024 threads)
+        float m = -INFINITY;
+        for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+            float xv[STT_SEL_U];
+            int mk[STT_SEL_U];
+#pragma unroll
+            for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+            for (int u = 0; u < STT_SEL_U; ++u)
+                if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] > m) m = xv[u];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if ((tid & 63) == 0) red_v[wave] = m;
+        __syncthreads();
+        m = red_v[0];
+        for (int k = 1; k < 16; ++k) m = fmaxf(m, red_v[k]);
+        __syncthreads();
+        float sum = 0.f;
+        for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+            float xv[STT_SEL_U];
+            int mk[STT_SEL_U];
+#pragma unroll
+            for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+            for (int u = 0; u < STT_SEL_U; ++u)
+                if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] == xv[u]) sum += expf(xv[u] - m);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+        if ((tid & 63) == 0) red_v[wave] = sum;
+        __syncthreads();
+        sum = red_v[0];
+        for (int k = 1; k < 16; ++k) sum += red_v[k];
+        __syncthreads();
+        const float lse = m + logf(sum);
+        float cv[STT_CAND];
+        int ci[STT_CAND];
+#pragma unroll
+        for (int k = 0; k < STT_CAND; ++k) { cv[k] = -INFINITY; ci[k] = STT_NO_ID; }
+        for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+            float xv[STT_SEL_U];
+            int mk[STT_SEL_U];
+#pragma unroll
+            for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+            for (int u = 0; u < STT_SEL_U; ++u) {
+                const int i = base + 1024 * u;
+                const float lp = xv[u] - lse;
+                if (i >= V || (mk[u] & bad) || !(lp == lp) || !cand_before(lp, i, cv[STT_CAND - 1], ci[STT_CAND - 1])) continue;
+                cv[STT_CAND - 1] = lp; ci[STT_CAND - 1] = i;
+#pragma unroll
+                for (int k = STT_CAND - 1; k > 0; --k)
+                    if (cand_before(cv[k], ci[k], cv[k - 1], ci[k - 1])) {
+                        const float tv = cv[k]; cv[k] = cv[k - 1]; cv[k - 1] = tv;
+                        const int ti = ci[k]; ci[k] = ci[k - 1]; ci[k - 1] = ti;
+                    }
+            }
+        }
+        const float s_j = bk.score[w * B + j];
+        for (int r = 0; r < K; ++r) {
+            float bv = cv[0];
+            int bi = ci[0];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (cand_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+            }
+            if ((tid & 63) == 0) { red_v[wave] = bv; red_i[wave] = bi; }
+            __syncthreads();
+            bv = red_v[0]; bi = red_i[0];
+            for (int k = 1; k < 16; ++k)
+                if (cand_before(red_v[k], red_i[k], bv, bi)) { bv = red_v[k]; bi = red_i[k]; }
+            if (bi != STT_NO_ID && bi == ci[0]) {            // the winner's owner (ids are unique in a row) drops it
+#pragma unroll
+                for (int k = 0; k + 1 < STT_CAND; ++k) { cv[k] = cv[k + 1]; ci[k] = ci[k + 1]; }
+                cv[STT_CAND - 1] = -INFINITY; ci[STT_CAND - 1] = STT_NO_ID;
+            }
+            if (tid == 0) {
+                const bool some = bi != STT_NO_ID && bv > -INFINITY;
+                c_score[j * K + r] = some ? s_j + bv : -INFINITY;
+                c_tok[j * K + r] = bi;
+                c_beam[j * K + r] = j;
+            }
+            __syncthreads();
+        }
+    }
+    const int n = nl * K;
+    if (wave == 0)
+        for (int c = tid; c < n; c += 64) {
+            int rank = 0;
+            for (int o = 0; o < n; ++o) {
+                const bool before = c_score[o] > c_score[c] ||
+                                    (c_score[o] == c_score[c] && (c_beam[o] < c_beam[c] || (c_beam[o] == c_beam[c] && (c_tok[o] < c_tok[c] || (c_tok[o] == c_tok[c] && o < c)))));
+                rank += before ? 1 : 0;
+            }
+            c_sorted[rank] = c;
+        }
+    __syncthreads();
+    if (tid != 0) return;
+    int nb = 0, nf = bk.n_fin[w];
+    for (int c = 0; c < n && nb < B; ++c) {
+        const int id = c_sorted[c];
+        const float sc = c_score[id];
+        if (!(sc > -INFINITY)) break;                      // (behind the last candidate a row could offer)
+        if (c_tok[id] == eos) {
+            if (nf < B) { bk.fin_step[w * B + nf] = step; bk.fin_beam[w * B + nf] = c_beam[id]; bk.fin_score[w * B + nf] = sc; ++nf; }
+        } else {
+            const int row = w * B + nb;
+            bk.next_tok[row] = c_tok[id];
+            bk.src[row] = w * B + c_beam[id];
+            bk.score[row] = sc;
+            bk.bp_tok[(int64_t)step * bk.R + row] = c_tok[id];
+            bk.bp_par[(int64_t)step * bk.R + row] = c_beam[id];
+            ++nb;
+        }
+    }
+    for (int i = nb; i < B; ++i) bk.src[w * B + i] = w * B + i;     // rows without a beam continue themselves (nothing reads them)
+    bk.n_fin[w] = nf;
+    bk.n_live[w] = nb;
+    if (nf >= B || nb == 0) {
+        bk.done[w] = 1;
+        atomicSub(bk.live, 1);
+    }
+}
+
+// The four planes of a decoder self-attention cache
+struct SttKvPlanes { const bf16_t* src[4]; bf16_t* dst[4]; };
+// Row r of the next step continues row src[r] of this one: positions [0, len) of every (layer, head) of cache slot src[r] are
+// copied into slot r of the OTHER cache (two rows may swap parents, and two children of one parent diverge at the next position).
+// blockIdx = (head, row, layer); a copy is len x head_dim contiguous bf16, moved 16 bytes per thread.
+__global__ __launch_bounds__(256) void k_stt_beam_reorder(SttKvPlanes p, const int32_t* __restrict__ src, int slots, int heads, int max_pos, int head_dim, int len) {
+    const int h = blockIdx.x, r = blockIdx.y, l = blockIdx.z;
+    const int from = src[r];
+    if (from < 0 || from >= slots) return;
+    const int64_t per = (int64_t)max_pos * head_dim;
+    const int64_t a = (((int64_t)l * slots + from) * heads + h) * per, b = (((int64_t)l * slots + r) * heads + h) * per;
+    const int n16 = len * head_dim / 8;                    // (head_dim is a multiple of 32)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint4* s4 = (const uint4*)(p.src[q] + a);
+        uint4* d4 = (uint4*)(p.dst[q] + b);
+        for (int i = threadIdx.x; i < n16; i += 256) d4[i] = s4[i];
+    }
+}
+
+// rows of the beam path's prefix pass (row w per + i: the window's first beam row as its cache slot, position i, window w) and of its
+// step passes (row r: its own slot, window r / B)
+__global__ void k_stt_fill_beam_rows(int32_t* __restrict__ pre_slot, int32_t* __restrict__ pre_pos, int32_t* __restrict__ pre_win, int n_pre, int per, int B,
+                                     int32_t* __restrict__ row_slot, int32_t* __restrict__ row_win, int n_rows) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < max(n_pre, n_rows); i += gridDim.x * blockDim.x) {
+        if (i < n_pre) { pre_slot[i] = i / per * B; pre_pos[i] = i % per; pre_win[i] = i / per; }
+        if (i < n_rows) { row_slot[i] = i; row_win[i] = i / B; }
+    }
+}
+
 }  // namespace
 
 // Windows of one group of rt_stt_transcribe_batch: the rows of every batched launch.  Compile-time: the group's buffers - about
@@ -289,6 +493,21 @@ struct SttBufs {
     std::vector<void*> owned;
 };
 
+// The decoder side of the beam path (rt_stt_transcribe_beam), for `rows` rows = windows x beams of one group: two self-attention
+// caches used alternately (k_stt_beam_reorder gathers from one into the other), the decoder workspaces and logits per row, row
+// tables and the bookkeeping of k_stt_beam_select.  The encoder side and the cross-attention cache are the group's (s->grp).
+struct SttBeam {
+    int rows = 0;
+    KvCache kv[2];
+    float *dx = nullptr, *dxn = nullptr, *dqkv = nullptr, *dq = nullptr, *dao = nullptr, *dff = nullptr, *logits = nullptr;
+    int32_t *pre_tok = nullptr, *pre_slot = nullptr, *pre_pos = nullptr, *pre_win = nullptr;   // [rows n_prefix] the prefix pass
+    int32_t *row_slot = nullptr, *row_win = nullptr, *row_pos = nullptr, *enc_last = nullptr;  // [rows] a step pass | [rows n_prefix]
+    int32_t* book_mem = nullptr;
+    size_t book_n = 0;
+    SttBeamBook book{};
+    std::vector<void*> owned;
+};
+
 struct rt_stt {
     rt_ctx* ctx = nullptr;
     rt_stt_config cfg{};
@@ -303,6 +522,8 @@ struct rt_stt {
     SttBufs one;                      // the single-clip path: n_ctx rows, one cache slot
     // the batched path (rt_stt_transcribe_batch): nothing of it exists until the first batched call
     SttBufs grp;
+    SttBeam beam;                     // the beam path: nothing of it exists until the first rt_stt_transcribe_beam
+    std::vector<int32_t> h_book;
     std::vector<SttWin> h_wins;       // host copies of what is uploaded per group (alive until the group's last synchronisation)
     std::vector<int32_t> h_prefix, h_log;
     uint8_t* d_mask = nullptr;
@@ -545,9 +766,10 @@ int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
 }
 
 // one pre-LN layer over M rows of x (in place).  self-attention over cache `kv` (row r is written at slot[r], wpos[r] + pos_add and
-// attends up to apos[r]); cross = the decoder's encoder-attention block between the two, over the row's slot of w.cross_kv
+// attends up to apos[r]); cross = the decoder's encoder-attention block between the two, over slot cross_slot[r] of w.cross_kv (the
+// row's own slot when null: beam rows of one window share the window's encoder states)
 int stt_layer(rt_stt* s, SttBufs& w, const std::string& p, float* x, float* xn, float* qkv, float* q, float* ao, float* ff, int M, KvCache& kv, int layer,
-              const int32_t* slot, const int32_t* wpos, const int32_t* apos, int pos_add, bool cross) {
+              const int32_t* slot, const int32_t* wpos, const int32_t* apos, int pos_add, bool cross, const int32_t* cross_slot = nullptr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int H = c.heads, d = c.d_model / c.heads, D = c.d_model;
@@ -559,7 +781,7 @@ int stt_layer(rt_stt* s, SttBufs& w, const std::string& p, float* x, float* xn, 
     if (cross) {
         ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".lnc_w"), SVEC(s, p + ".lnc_b"), xn));
         ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".cwq"), SVEC(s, p + ".cbq"), ACT_NONE, nullptr, q));
-        ST_TRY(launch_attention(ctx, q, M, H, H, d, slot, w.enc_last, 0, 0, w.cross_kv, layer, nullptr, nullptr, 0, ao));
+        ST_TRY(launch_attention(ctx, q, M, H, H, d, cross_slot ? cross_slot : slot, w.enc_last, 0, 0, w.cross_kv, layer, nullptr, nullptr, 0, ao));
         ST_TRY(stt_gemm(s, ao, M, SPW(s, p + ".cwo"), SVEC(s, p + ".cbo"), ACT_NONE, x, x));
     }
     ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln2_w"), SVEC(s, p + ".ln2_b"), xn));
@@ -604,8 +826,8 @@ int stt_encode(rt_stt* s, SttBufs& w, int B) {
 }
 
 // B x per decoder rows (tokens w.d_tok, row r = window r / per at position pos0 + r % per; slot / pos: its row tables) -> logits of
-// the LAST row of every window in w.logits [B][vocab]
-int stt_decode_rows(rt_stt* s, SttBufs& w, int B, int per, int pos0, const int32_t* slot, const int32_t* pos) {
+// the LAST row of every window in w.logits [B][vocab].  cross_slot: the rows' slots of the cross-attention cache (null: `slot`)
+int stt_decode_rows(rt_stt* s, SttBufs& w, int B, int per, int pos0, const int32_t* slot, const int32_t* pos, const int32_t* cross_slot = nullptr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int D = c.d_model, M = B * per;
@@ -613,7 +835,7 @@ int stt_decode_rows(rt_stt* s, SttBufs& w, int B, int per, int pos0, const int32
     hipLaunchKernelGGL(k_stt_embed, dim3(M), dim3(128), 0, ctx->stream, tok->tbl, SVEC(s, "dec.pos"), w.d_tok, pos0, per, D, w.dx);
     RT_HIP(ctx, hipGetLastError());
     for (int i = 0; i < c.dec_layers; ++i)
-        ST_TRY(stt_layer(s, w, "dec.l" + std::to_string(i), w.dx, w.dxn, w.dqkv, w.dq, w.dao, w.dff, M, w.dec_kv, i, slot, pos, pos, pos0, true));
+        ST_TRY(stt_layer(s, w, "dec.l" + std::to_string(i), w.dx, w.dxn, w.dqkv, w.dq, w.dao, w.dff, M, w.dec_kv, i, slot, pos, pos, pos0, true, cross_slot));
     ST_TRY(stt_ln(s, w.dx + (size_t)(per - 1) * D, (int64_t)per * D, B, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), w.dxn));
     ST_TRY(stt_gemm(s, w.dxn, B, tok->pw, nullptr, ACT_NONE, nullptr, w.logits));
     return RT_OK;
@@ -683,6 +905,147 @@ int stt_decode_group(rt_stt* s, int B, std::vector<std::vector<int32_t>>& ids) {
     return RT_OK;
 }
 
+// the bookkeeping of k_stt_beam_select laid over one int32 allocation of R rows and `steps` steps (sizes in SttBeamBook's comments)
+size_t stt_beam_book_words(int R, int steps) { return (size_t)9 * R + 1 + (size_t)2 * steps * R; }
+SttBeamBook stt_beam_book(int32_t* mem, int R, int steps) {
+    SttBeamBook b;
+    int32_t* p = mem;
+    auto take = [&](size_t n) { int32_t* q = p; p += n; return q; };
+    b.next_tok = take(R); b.src = take(R); b.score = (float*)take(R);
+    b.n_live = take(R); b.n_fin = take(R); b.done = take(R);
+    b.fin_step = take(R); b.fin_beam = take(R); b.fin_score = (float*)take(R);
+    b.live = take(1);
+    b.bp_tok = take((size_t)steps * R); b.bp_par = take((size_t)steps * R);
+    b.R = R;
+    return b;
+}
+
+// The beam path's buffers for `rows` decoder rows: allocated by the first beam call, replaced by larger ones when a call needs more
+// rows (as stt_group_reserve: built aside, and after a failure the handle holds none)
+int stt_beam_reserve(rt_stt* s, int rows) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    if (s->beam.rows >= rows) return RT_OK;
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (void* p : s->beam.owned) (void)hipFree(p);
+    s->beam = SttBeam{};
+    SttBeam nb;
+    const size_t r = (size_t)rows, rp = r * c.n_prefix, D = c.d_model;
+    auto build = [&]() -> int {
+        for (KvCache& kv : nb.kv) ST_TRY(stt_kv(s, nb.owned, kv, c.dec_layers, rows, c.n_text_ctx));
+        ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dx)); ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dxn)); ST_TRY(stt_alloc(s, nb.owned, rp * 3 * D, &nb.dqkv));
+        ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dq)); ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dao)); ST_TRY(stt_alloc(s, nb.owned, rp * c.ffn, &nb.dff));
+        ST_TRY(stt_alloc(s, nb.owned, r * c.vocab, &nb.logits));
+        ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_tok)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_slot)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_pos));
+        ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_win)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.enc_last));
+        ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_slot)); ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_win)); ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_pos));
+        nb.book_n = stt_beam_book_words(rows, c.max_new_tokens);
+        ST_TRY(stt_alloc(s, nb.owned, nb.book_n, &nb.book_mem));
+        nb.book = stt_beam_book(nb.book_mem, rows, c.max_new_tokens);
+        hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(256), 0, ctx->stream, nb.enc_last, (int)rp, c.n_ctx - 1, 0);
+        hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, nb.row_pos, rows, 0, 0);
+        RT_HIP(ctx, hipGetLastError());
+        return RT_OK;
+    };
+    const int rc = build();
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void* p : nb.owned) (void)hipFree(p);
+        (void)hipGetLastError();
+        return rc;
+    }
+    nb.rows = rows;
+    s->beam = std::move(nb);
+    return RT_OK;
+}
+
+int stt_beam_reorder(rt_ctx* ctx, const KvCache& from, const KvCache& to, const int32_t* d_src, int rows, int len) {
+    if (len <= 0 || rows <= 0) return RT_OK;
+    SttKvPlanes p{{from.k, from.v, from.k_lo, from.v_lo}, {to.k, to.v, to.k_lo, to.v_lo}};
+    hipLaunchKernelGGL(k_stt_beam_reorder, dim3(from.kv_heads, rows, from.layers), dim3(256), 0, ctx->stream, p, d_src, from.slots, from.kv_heads, from.max_pos,
+                       from.head_dim, std::min(len, from.max_pos));
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// What beam search gives for one window: the ids of the chosen hypothesis, its cumulative log-probability and the tokens it counts
+// (the ids and end-of-sequence)
+struct SttHyp { std::vector<int32_t> ids; float score = 0.f; int count = 1; };
+
+// Beam search (width B) over the nW encoded windows of the group, rows = nW B.  The prefix pass runs one row per window into the
+// cache slot of the window's first beam row; the reorder kernel then fans it out to the window's rows, and after every later
+// step gives row r the cache of the row it continues.  One device-to-host read and one synchronisation per step, as the greedy
+// group; the bookkeeping comes back once, and the host follows the back-pointers of the finished entries.
+int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    SttBeam& bm = s->beam;
+    const int P = c.n_prefix, rows = nW * B, R = bm.rows;
+    const SttBeamBook& bk = bm.book;
+    SttBufs v;                                  // the decoder's view: the beam path's rows over the group's encoder side
+    v.cross_kv = s->grp.cross_kv; v.enc_last = bm.enc_last;
+    v.dx = bm.dx; v.dxn = bm.dxn; v.dqkv = bm.dqkv; v.dq = bm.dq; v.dao = bm.dao; v.dff = bm.dff; v.logits = bm.logits;
+    RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.next_tok, R, c.eos_id, 0);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.src, R, 0, 1);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.n_live, nW, 1, 0);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.live, 1, nW, 0);
+    hipLaunchKernelGGL(k_stt_fill_beam_rows, dim3(1), dim3(256), 0, ctx->stream, bm.pre_slot, bm.pre_pos, bm.pre_win, nW * P, P, B, bm.row_slot, bm.row_win, rows);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(bm.pre_tok, s->h_prefix.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
+    int cur = 0;
+    v.dec_kv = bm.kv[cur]; v.d_tok = bm.pre_tok;
+    ST_TRY(stt_decode_rows(s, v, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
+    const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
+    int steps = 0;
+    for (int step = 0; step < budget; ++step) {
+        hipLaunchKernelGGL(k_stt_beam_select, dim3(nW), dim3(1024), 0, ctx->stream, bm.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0, c.eos_id, B,
+                           step, bk);
+        RT_HIP(ctx, hipGetLastError());
+        steps = step + 1;
+        int32_t live = 0;
+        RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (live <= 0 || step + 1 >= budget) break;
+        ST_TRY(stt_beam_reorder(ctx, bm.kv[cur], bm.kv[cur ^ 1], bk.src, rows, P + step));
+        cur ^= 1;
+        v.dec_kv = bm.kv[cur]; v.d_tok = bk.next_tok;
+        ST_TRY(stt_decode_rows(s, v, rows, 1, P + step, bm.row_slot, bm.row_pos, bm.row_win));
+    }
+    s->h_book.resize(bm.book_n);
+    RT_HIP(ctx, hipMemcpyAsync(s->h_book.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const SttBeamBook h = stt_beam_book(s->h_book.data(), R, c.max_new_tokens);
+    out.assign(nW, SttHyp{});
+    // the tokens of beam `b` as it stood after step t: follow the back-pointers to step 0
+    auto history = [&](int w, int t, int b, std::vector<int32_t>& ids) {
+        ids.assign(t + 1, 0);
+        for (int u = t; u >= 0; --u) {
+            const size_t at = (size_t)u * R + (size_t)w * B + b;
+            ids[u] = h.bp_tok[at];
+            b = h.bp_par[at];
+        }
+    };
+    for (int w = 0; w < nW; ++w) {
+        // the finished list, then - if it has room left - the live beams in order; the largest score / (tokens + 1) wins, the earlier
+        // entry on a tie
+        bool have = false;
+        double best = 0.0;
+        int n_f = std::min(h.n_fin[w], B);
+        auto offer = [&](int t_last, int b, float score) {
+            const int count = t_last + 2;                   // t_last + 1 ids and end-of-sequence
+            const double norm = (double)score / (double)count;
+            if (have && !(norm > best)) return;
+            have = true; best = norm;
+            out[w].score = score; out[w].count = count;
+            if (t_last >= 0) history(w, t_last, b, out[w].ids); else out[w].ids.clear();
+        };
+        for (int k = 0; k < n_f; ++k) offer(h.fin_step[w * B + k] - 1, h.fin_beam[w * B + k], h.fin_score[w * B + k]);
+        for (int i = 0; i < std::min(h.n_live[w], B) && n_f < B; ++i, ++n_f) offer(steps - 1, i, h.score[w * B + i]);
+    }
+    return RT_OK;
+}
+
 // argument rules shared by the batched entry points: null for a clip with samples, a negative length
 int stt_check_clips(const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips) {
     if (n_clips < 0 || (n_clips > 0 && (!d_pcm || !n_samples))) return RT_ERR_INVALID;
@@ -725,7 +1088,7 @@ int rt_stt_destroy(rt_stt* s) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& sl : s->slots) { if (sl.raw) (void)hipFree(sl.raw); if (sl.raw2) (void)hipFree(sl.raw2); }
-    for (auto* owned : {&s->owned, &s->one.owned, &s->grp.owned})
+    for (auto* owned : {&s->owned, &s->one.owned, &s->grp.owned, &s->beam.owned})
         for (void* p : *owned) (void)hipFree(p);
     if (s->d_resamp) (void)hipFree(s->d_resamp);
     delete s;
@@ -934,6 +1297,133 @@ int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const int64_t*
         }
     }
     return RT_OK;
+}
+
+// As rt_stt_transcribe_batch, decoded by beam search: floor(STT_GROUP / beam_size) windows make a group, whose decoder rows are
+// windows x beams.  Every window is decoded (a clip's score counts all of its windows); max_tokens cuts the joined ids.
+int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, int32_t beam_size,
+                           int32_t* h_tokens, int32_t max_tokens, int32_t* h_n_tokens, float* h_scores) {
+    if (!s || max_tokens < 1 || sample_rate < 1000 || beam_size < 1 || beam_size > STT_BEAM_MAX || stt_check_clips(d_pcm, n_samples, n_clips) ||
+        (n_clips > 0 && (!h_tokens || !h_n_tokens)))
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_transcribe_beam: bad argument (beam_size 1 .. %d)", STT_BEAM_MAX);
+    if (n_clips == 0) return RT_OK;
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe_beam: not finalized");
+    const rt_stt_config& c = s->cfg;
+    const int64_t win = (int64_t)c.chunk_seconds * sample_rate;     // one window, in input samples
+    std::vector<SttSpan> all;
+    for (int i = 0; i < n_clips; ++i) {
+        h_n_tokens[i] = 0;
+        for (int64_t off = 0; off == 0 || off < n_samples[i]; off += win)
+            all.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off : nullptr, std::min<int64_t>(win, n_samples[i] - off)});
+    }
+    const size_t per_group = (size_t)(STT_GROUP / beam_size);
+    const int most = (int)std::min(all.size(), per_group);
+    ST_TRY(stt_group_reserve(s, most));
+    ST_TRY(stt_beam_reserve(s, most * beam_size));
+    std::vector<double> sum(n_clips, 0.0);
+    std::vector<int64_t> count(n_clips, 0);
+    std::vector<SttHyp> hyps;
+    for (size_t next = 0; next < all.size(); next += per_group) {
+        const int nW = (int)std::min(per_group, all.size() - next);
+        ST_TRY(stt_features_group(s, all.data() + next, nW, sample_rate));
+        ST_TRY(stt_encode(s, s->grp, nW));
+        ST_TRY(stt_decode_beam_group(s, nW, beam_size, hyps));
+        for (int b = 0; b < nW; ++b) {
+            const int i = all[next + b].clip;
+            for (int32_t t : hyps[b].ids)
+                if (h_n_tokens[i] < max_tokens) h_tokens[(size_t)i * max_tokens + h_n_tokens[i]++] = t;
+            sum[i] += (double)hyps[b].score;
+            count[i] += hyps[b].count;
+        }
+    }
+    if (h_scores)
+        for (int i = 0; i < n_clips; ++i) h_scores[i] = (float)(sum[i] / (double)std::max<int64_t>(count[i], 1));
+    return RT_OK;
+}
+
+int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_stride, const float* h_scores_in, int32_t n_windows, int32_t beam,
+                           const int32_t* h_n_live, const int32_t* h_n_finished, const int32_t* h_done, int32_t first_step, int32_t step,
+                           int32_t* h_next_tok, int32_t* h_parent, float* h_scores_out, int32_t* h_n_live_out, int32_t* h_fin_beam, float* h_fin_score,
+                           int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows) {
+    if (!s || !d_logits || !h_scores_in || !h_n_live || !h_n_finished || !h_done || !h_next_tok || !h_parent || !h_scores_out || !h_n_live_out || !h_fin_beam ||
+        !h_fin_score || !h_n_finished_out || !h_done_out || !h_live_windows || beam < 1 || beam > STT_BEAM_MAX || n_windows < 1 ||
+        n_windows * beam > STT_GROUP || (row_stride != 1 && row_stride != beam) || step < 0 || step >= s->cfg.max_new_tokens)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_beam_step: bad argument (windows x beam <= %d, row_stride 1 or beam)", STT_GROUP);
+    int live = 0;
+    for (int w = 0; w < n_windows; ++w) {
+        if (h_n_live[w] < 0 || h_n_live[w] > std::min(beam, row_stride) || h_n_finished[w] < 0 || h_n_finished[w] > beam)
+            return rt_fail(s->ctx, RT_ERR_INVALID, "rt_debug_stt_beam_step: window %d: live rows or finished entries out of range", w);
+        live += h_done[w] ? 0 : 1;
+    }
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_beam_step: not finalized");
+    const int R = n_windows * beam;
+    ST_TRY(stt_beam_reserve(s, R));
+    SttBeam& bm = s->beam;
+    const SttBeamBook& bk = bm.book;
+    std::vector<int32_t>& hb = s->h_book;
+    hb.assign(bm.book_n, 0);
+    SttBeamBook h = stt_beam_book(hb.data(), bm.rows, s->cfg.max_new_tokens);
+    for (int r = 0; r < R; ++r) { h.score[r] = h_scores_in[r]; h.next_tok[r] = -1; h.src[r] = -1; }
+    for (int w = 0; w < n_windows; ++w) { h.n_live[w] = h_n_live[w]; h.n_fin[w] = h_n_finished[w]; h.done[w] = h_done[w] ? 1 : 0; }
+    *h.live = live;
+    RT_HIP(ctx, hipMemcpyAsync(bm.book_mem, hb.data(), bm.book_n * 4, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_stt_beam_select, dim3(n_windows), dim3(1024), 0, ctx->stream, d_logits, s->cfg.vocab, row_stride, s->d_mask, first_step ? 1 : 0, s->cfg.eos_id,
+                       beam, step, bk);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(hb.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int r = 0; r < R; ++r) {
+        h_next_tok[r] = h.next_tok[r]; h_parent[r] = h.src[r]; h_scores_out[r] = h.score[r];
+        h_fin_beam[r] = h.fin_beam[r]; h_fin_score[r] = h.fin_score[r];
+    }
+    for (int w = 0; w < n_windows; ++w) { h_n_live_out[w] = h.n_live[w]; h_n_finished_out[w] = h.n_fin[w]; h_done_out[w] = h.done[w]; }
+    *h_live_windows = *h.live;
+    return RT_OK;
+}
+
+int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src, int32_t len,
+                              uint16_t* h_planes) {
+    if (!ctx || !h_src || !h_planes || layers < 1 || rows < 1 || rows > STT_GROUP || heads < 1 || max_pos < 1 || head_dim < 32 || head_dim % 32 || len < 0 ||
+        len > max_pos)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_beam_reorder: bad argument");
+    for (int r = 0; r < rows; ++r)
+        if (h_src[r] < 0 || h_src[r] >= rows) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_beam_reorder: src[%d] outside the rows", r);
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)layers * rows * heads * max_pos * head_dim;           // one plane
+    std::vector<uint16_t> host(8 * n);
+    for (int q = 0; q < 4; ++q)
+        for (size_t i = 0; i < n; ++i) {
+            host[q * n + i] = (uint16_t)((i * 40503u + (size_t)q * 12289u) & 0x7fffu);       // the source cache: a value per (plane, layer, row, head, pos, dim)
+            host[(4 + q) * n + i] = 0xbeef;                                                 // the destination: a sentinel
+        }
+    bf16_t* d = nullptr;
+    int32_t* d_src = nullptr;
+    RT_HIP(ctx, hipMalloc((void**)&d, 8 * n * 2));
+    auto run = [&]() -> int {
+        RT_HIP(ctx, hipMalloc((void**)&d_src, (size_t)rows * 4));
+        RT_HIP(ctx, hipMemcpyAsync(d, host.data(), 8 * n * 2, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(d_src, h_src, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        KvCache a, b;
+        a.layers = b.layers = layers; a.slots = b.slots = rows; a.kv_heads = b.kv_heads = heads; a.max_pos = b.max_pos = max_pos; a.head_dim = b.head_dim = head_dim;
+        a.k = d; a.v = d + n; a.k_lo = d + 2 * n; a.v_lo = d + 3 * n;
+        b.k = d + 4 * n; b.v = d + 5 * n; b.k_lo = d + 6 * n; b.v_lo = d + 7 * n;
+        ST_TRY(stt_beam_reorder(ctx, a, b, d_src, rows, len));
+        RT_HIP(ctx, hipMemcpyAsync(h_planes, d, 8 * n * 2, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    if (d_src) (void)hipFree(d_src);
+    return rc;
 }
 
 int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, float* d_states) {

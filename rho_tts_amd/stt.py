@@ -24,6 +24,13 @@ import torch
 from . import _native
 
 DT_BF16, DT_F32 = 0, 1
+MAX_BEAM = 8                  # widest beam of rt_stt_transcribe_beam
+
+
+def check_beam_size(beam_size) -> int:
+    if isinstance(beam_size, bool) or not isinstance(beam_size, (int, np.integer)) or not 1 <= int(beam_size) <= MAX_BEAM:
+        raise ValueError(f"beam_size must be an integer in 1 .. {MAX_BEAM}, got {beam_size!r}")
+    return int(beam_size)
 
 
 @dataclass
@@ -162,6 +169,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_stt_set_suppress.argtypes = [vp, C.POINTER(i32), i32]
     lib.rt_stt_transcribe.argtypes = [vp, vp, i64, i32, C.POINTER(i32), i32, C.POINTER(i32), vp]
     lib.rt_stt_transcribe_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(i32), i32, C.POINTER(i32)]
+    lib.rt_stt_transcribe_beam.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, i32, C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(C.c_float)]
     lib.rt_stt_log_mel.argtypes = [vp, vp, i64, i32, vp]
     lib.rt_stt_encode.argtypes = [vp, vp, i64, i32, vp]
     _DECLARED = True
@@ -390,6 +398,27 @@ class NativeSTT:
         self.ctx.check(self.lib.rt_stt_transcribe_batch(self.handle, ptrs, lens, n, int(sample_rate), toks, cap, counts), "rt_stt_transcribe_batch")
         return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)]
 
+    def transcribe_ids_beam(self, audios, sample_rate: int, beam_size: int, max_tokens: Optional[int] = None) -> Tuple[List[List[int]], List[float]]:
+        """Beam search of width ``beam_size`` (1 .. 8) over every clip from ONE native call (rt_stt_transcribe_beam): the ids, and per
+        clip the average log-probability per emitted token (end-of-sequence counted) of the chosen hypotheses.  A clip's ids and score
+        are what it gets alone; ``beam_size == 1`` gives the ids of ``transcribe_ids_batch``.  ``max_tokens`` caps every clip's ids."""
+        check_beam_size(beam_size)
+        if max_tokens is not None and int(max_tokens) < 1:
+            raise ValueError(f"max_tokens must be at least 1, got {max_tokens!r}")
+        if not getattr(self, "handle", None):
+            raise ValueError("transcribe_ids_beam: the model is closed")
+        xs = [self._pcm(a) for a in audios]
+        n = len(xs)
+        cap = int(max_tokens or max([self.windows(x.numel(), sample_rate) for x in xs] or [1]) * self.cfg.max_new_tokens)
+        ptrs = (C.c_void_p * max(n, 1))(*[x.data_ptr() if x.numel() else None for x in xs])
+        lens = (C.c_int64 * max(n, 1))(*[x.numel() for x in xs])
+        toks = (C.c_int32 * max(n * cap, 1))()
+        counts = (C.c_int32 * max(n, 1))()
+        scores = (C.c_float * max(n, 1))()
+        self.ctx.check(self.lib.rt_stt_transcribe_beam(self.handle, ptrs, lens, n, int(sample_rate), int(beam_size), toks, cap, counts, scores),
+                       "rt_stt_transcribe_beam")
+        return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)], [float(scores[i]) for i in range(n)]
+
     def log_mel(self, audio, sample_rate: int) -> torch.Tensor:
         """[n_mels][frames] float32 (the layout of WhisperFeatureExtractor's ``input_features``)."""
         x = self._pcm(audio)
@@ -410,9 +439,14 @@ class WhisperTranscriber:
     """``transcriber`` hook of the provider: ``(audio tensor, sample_rate) -> text`` (None = transcription failed), the
     tensor-level stand-in for ``transcribe_audio(path)`` (stt_validator.py:116-148).  ``model_dir``: a local Whisper checkpoint
     (safetensors + config.json + tokenizer.json); without one the model runs on seeded synthetic weights - only when that is asked
-    for explicitly - and the "text" is the generated ids written out, which is all random weights can mean."""
+    for explicitly - and the "text" is the generated ids written out, which is all random weights can mean.  ``beam_size``: 1
+    decodes greedily (the single-clip and the batched call); a larger width sends every call through beam search
+    (``transcribe_ids_beam``; faster-whisper, which the reference transcribes with, defaults to 5), and ``batch_scored`` returns
+    each text with its confidence."""
 
-    def __init__(self, ctx: "_native.Context", model_dir: Optional[str] = None, synthetic: bool = False, cfg: Optional[SttConfig] = None, seed: int = 789):
+    def __init__(self, ctx: "_native.Context", model_dir: Optional[str] = None, synthetic: bool = False, cfg: Optional[SttConfig] = None, seed: int = 789,
+                 beam_size: int = 1):
+        self.beam_size = check_beam_size(beam_size)
         self.tokenizer = None
         dev = f"cuda:{ctx.device_ordinal}"
         if model_dir and os.path.isdir(model_dir) and any(f.endswith(".safetensors") for f in os.listdir(model_dir)):
@@ -433,10 +467,20 @@ class WhisperTranscriber:
         self.model = NativeSTT(ctx, cfg, state)
 
     def ids(self, audio, sample_rate: int) -> List[int]:
+        if self.beam_size > 1:
+            return self.model.transcribe_ids_beam([audio], sample_rate, self.beam_size)[0][0]
         return self.model.transcribe_ids(audio, sample_rate)
 
     def ids_batch(self, audios, sample_rate: int) -> List[List[int]]:
+        if self.beam_size > 1:
+            return self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)[0]
         return self.model.transcribe_ids_batch(audios, sample_rate)
+
+    def batch_scored(self, audios, sample_rate: int) -> List[Tuple[Optional[str], float]]:
+        """The texts of a chunk of segments with their confidence: the average log-probability per emitted token of the chosen
+        hypothesis (0 is certain).  One native call, beam search of the configured width (width 1: the greedy ids, scored)."""
+        ids, scores = self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)
+        return [(self._text(i), s) for i, s in zip(ids, scores)]
 
     def _text(self, ids: List[int]) -> Optional[str]:
         if self.tokenizer is not None:
