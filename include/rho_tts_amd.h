@@ -351,18 +351,20 @@ RT_API int rt_stt_set_suppress(rt_stt* s, const int32_t* h_ids, int32_t n);
  * prefix, end-of-sequence excluded.  Audio longer than one chunk (chunk_seconds, 30 s) is NOT truncated: it is transcribed in
  * consecutive chunk_seconds windows (features, encoder, greedy decode behind the forced prefix per window, at most
  * cfg.max_new_tokens ids each) and the ids are concatenated, at most max_tokens in all - size h_tokens for
- * ceil(seconds / chunk_seconds) * cfg.max_new_tokens.  d_first_logits (optional, HBM, [vocab]): the logits behind the forced
- * prefix of the FIRST window, for tests. */
+ * ceil(seconds / chunk_seconds) * cfg.max_new_tokens.  This is rt_stt_transcribe_batch with one clip: the clip's windows are the
+ * rows of the same launches.  d_first_logits (optional, HBM, [vocab]): the logits behind the forced prefix of the FIRST window,
+ * for tests. */
 RT_API int rt_stt_transcribe(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, int32_t* h_tokens, int32_t max_tokens,
                              int32_t* h_n_tokens, float* d_first_logits);
 /* n_clips clips in one call: d_pcm[i] holds n_samples[i] floats in HBM, all at sample_rate_in; h_tokens [n_clips][max_tokens_per_clip]
- * and h_n_tokens [n_clips] receive per clip exactly the ids rt_stt_transcribe gives for it alone with max_tokens =
+ * and h_n_tokens [n_clips] receive per clip exactly the ids it gets as the only clip of a call (rt_stt_transcribe) with max_tokens =
  * max_tokens_per_clip (size a row for ceil(seconds / chunk_seconds) * cfg.max_new_tokens).  Every clip is cut into chunk_seconds
  * windows as there, and the windows of all clips - 32 at a time - go through the front end, the encoder and the greedy decode
  * together: one launch per stage for the group, and one device-to-host read and one stream synchronisation per decode step
- * whatever the number of clips.  The group's buffers (78.7 MB per window measured at Whisper-tiny dimensions) are allocated by the
- * first batched call and only grow; a handle that never batches never pays for them, and one whose allocation failed (out of memory) holds no
- * group and allocates again at the next batched call.  n_clips == 0: nothing to do, RT_OK.
+ * whatever the number of clips.  The handle holds ONE set of buffers for all rt_stt_* calls (78.7 MB per window measured at
+ * Whisper-tiny dimensions): rt_stt_finalize reserves it for one window, the first call with more windows replaces it by a larger
+ * one and it only grows; a handle that never batches holds one window's, and one whose allocation failed (out of memory) holds
+ * none and allocates again at the next call.  n_clips == 0: nothing to do, RT_OK.
  * RT_ERR_INVALID: a null pointer for a clip with samples, a negative length, max_tokens_per_clip < 1.  A clip of zero samples is
  * one window of silence, as in rt_stt_transcribe. */
 RT_API int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
@@ -380,7 +382,9 @@ RT_API int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const i
  * rt_stt_transcribe_batch, and a beam_size outside 1 .. 8. */
 RT_API int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
                                   int32_t beam_size, int32_t* h_tokens, int32_t max_tokens, int32_t* h_n_tokens, float* h_scores);
-/* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM. */
+/* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM:
+ * row 0 of the same front end and encoder with the clip as its only window.  Of a clip longer than chunk_seconds the first
+ * chunk is kept, and the resampler's taps at its end see the samples behind it. */
 RT_API int rt_stt_log_mel(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, float* d_mel);
 RT_API int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, float* d_states);
 

@@ -96,9 +96,10 @@ RT_API int rt_debug_features_observe(rt_features* f, const double* h_cmnd, int32
 RT_API int rt_debug_features_viterbi(rt_features* f, const double* h_log_obs, const int32_t* h_n_frames, int32_t n_clips, int32_t* h_states,
                                      int32_t stride);
 
-/* The batched speech-to-text path below the ids (tests/test_stt_batch_gpu.py): the first window of n_clips clips (at most one
- * group, 32) through the group's front end and encoder -> d_states [n_clips][n_ctx][d_model] float32 in HBM.  Clip i's states are,
- * bit for bit, what rt_stt_encode gives for that window alone (the first chunk_seconds of the clip, cut as rt_stt_transcribe cuts it). */
+/* The speech-to-text path below the ids with more than one row (tests/test_stt_batch_gpu.py): the first window of n_clips clips (at
+ * most one group, 32) through the front end and encoder -> d_states [n_clips][n_ctx][d_model] float32 in HBM.  Clip i's states
+ * among the n_clips rows are, bit for bit, what rt_stt_encode gives for that window as the only row (the first chunk_seconds of the
+ * clip, cut as rt_stt_transcribe cuts it). */
 RT_API int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
                                      float* d_states);
 

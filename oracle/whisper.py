@@ -27,7 +27,7 @@ import torch
 
 def resample(x: np.ndarray, sr_in: int, sr_out: int, width: float = 6.0, rolloff: float = 0.99) -> np.ndarray:
     """Windowed-sinc resampling, float64: y[n] = sum_t x[t] g(t - n sr_in / sr_out), g = low-pass at rolloff x the lower Nyquist
-    under a Hann window spanning `width` zero crossings (csrc/stt.hip stt_resampler / k_resample, same taps)."""
+    under a Hann window spanning `width` zero crossings (csrc/stt.hip stt_resampler / k_resample_group, same taps)."""
     if sr_in == sr_out:
         return np.asarray(x, dtype=np.float32)
     x = np.asarray(x, dtype=np.float64).reshape(-1)

@@ -76,7 +76,7 @@ constexpr int LPC_MAX = 32, LPC_FRAME = 400;
 __device__ __forceinline__ int ft_ordered(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
 __device__ __forceinline__ float ft_unordered(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
-// y[n] = sum_j x[base(n) + j - half] h[phase(n)][j] (csrc/stt.hip k_resample: the same polyphase filter, float64 accumulation)
+// y[n] = sum_j x[base(n) + j - half] h[phase(n)][j] (csrc/stt.hip k_resample_group: the same polyphase filter, float64 accumulation)
 __global__ void k_feat_resample(const float* __restrict__ x, int64_t n_in, float* __restrict__ y, int64_t n_out, int L, int M, int taps, int half,
                                 const float* __restrict__ h) {
     for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_out; n += (int64_t)gridDim.x * blockDim.x) {

@@ -8,7 +8,7 @@
 //   k_sp_resample  one output sample per thread; the taps h(p, k) = sinc(pi t) cos^2(pi t / 12) base / o, t = (k - width) base / o -
 //                  p base / n, come from this closed form (torchaudio materialises them as a [n][o + 2 width] bank: 726 MB for +4
 //                  semitones at 24 kHz, whose reduced rates are 15119 : 12000) and are summed in ascending k
-//   k_sp_stft      one frame per workgroup: direct 512-point transform from a twiddle table (as k_logmel_frames), magnitude and
+//   k_sp_stft      one frame per workgroup: direct 512-point transform from a twiddle table (as k_logmel_frames_group), magnitude and
 //                  angle of the 257 bins, two zero frames behind the last
 //   k_sp_vocoder   one wave per bin: each lane sums the wrapped phase increments of a contiguous run of output frames, the run
 //                  totals are scanned across the wave, a second pass writes mag (cos, sin) - float64 prefix sums, no atomics

@@ -13,13 +13,17 @@
 // 51865 logits), which plain bf16 activations would not guarantee.  The model is tiny (39 M parameters); nothing here is on the
 // hot path of generation - it runs once per validated segment - so the kernels are the simple forms.
 //
-// rt_stt_transcribe_batch runs the same kernels over a whole validation chunk: the windows of all clips, STT_GROUP at a time, are
-// the rows of every launch (group siblings of the front-end kernels, one cache slot per window, the decode bookkeeping in
-// k_stt_pick), and a clip's ids are bit for bit the ids it gets alone.
+// There is one path.  Every entry point cuts its clips into chunk_seconds windows (stt_cut) and sends them, STT_GROUP at a time, as
+// the rows of every launch: one front-end launch per stage for the group, one cache slot per window, one pick per row and step
+// (k_stt_pick).  rt_stt_transcribe, rt_stt_log_mel and rt_stt_encode are that path with one clip; rt_stt_transcribe_batch is it with
+// a whole validation chunk.  No launch mixes rows, so a clip's values among N rows are bit for bit those it has as the only row.
+// The handle holds one buffer set (SttGroup: an encoder side and a greedy decoder side), reserved for one window at
+// rt_stt_finalize and grown by the first call that needs more windows.
 //
 // rt_stt_transcribe_beam decodes the same windows by beam search (the reference's transcriber runs faster-whisper's default, width
-// 5): decoder rows are windows x beams, k_stt_beam_select keeps the hypotheses on the device and k_stt_beam_reorder hands a row the
-// self-attention cache of the row it continues; the call also returns each clip's average log-probability per emitted token.
+// 5): decoder rows are windows x beams - a decoder side of its own (SttBeam) over the group's encoder side - k_stt_beam_select keeps
+// the hypotheses on the device and k_stt_beam_reorder hands a row the self-attention cache of the row it continues; the call also
+// returns each clip's average log-probability per emitted token.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -66,17 +70,12 @@ __device__ __forceinline__ float resample_at(const float* __restrict__ x, int64_
     }
     return (float)acc;
 }
-__global__ void k_resample(const float* __restrict__ x, int64_t n_in, float* __restrict__ y, int64_t n_out, int L, int M, int taps, int half,
-                           const float* __restrict__ h) {
-    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_out; n += (int64_t)gridDim.x * blockDim.x)
-        y[n] = resample_at(x, n_in, n, L, M, taps, half, h);
-}
 
-// One window of a group, as the front-end kernels of rt_stt_transcribe_batch see it (a small device table, one entry per window)
+// One window of a group, as the front-end kernels see it (a small device table, one entry per window)
 struct SttWin {
     const float* pcm_in;    // the window's samples at the input rate
     const float* pcm16;     // ... at cfg.sample_rate: its row of the resampler's output, or pcm_in itself when the rates agree
-    int64_t n_in, n16;      // samples at the input rate / at cfg.sample_rate (at most one chunk)
+    int64_t n_in, n16;      // samples at the input rate (the taps see all of them) / at cfg.sample_rate (at most one chunk)
     int32_t n_comp, pad;    // log-mel frames that can see audio; the rest hold the constant of silence
 };
 // the resampler over a group: blockIdx.y = window, its output row at y + window * y_stride
@@ -136,17 +135,10 @@ __device__ __forceinline__ void logmel_frame(double* sh /* xw[n_fft] | c[n_fft] 
     best = wave_max_f32(best);
     if ((tid & 63) == 0 && best > -INFINITY) atomicMax(gmax, f32_ordered(best));
 }
-__global__ __launch_bounds__(256) void k_logmel_frames(const float* __restrict__ pcm, int64_t n_valid, int64_t n_padded, int n_fft, int hop, int n_bins,
-                                                       int n_mels, const double* __restrict__ twc, const double* __restrict__ tws,
-                                                       const float* __restrict__ window, const float* __restrict__ melT /*[n_bins][n_mels]*/,
-                                                       float* __restrict__ logspec, int* __restrict__ gmax) {
-    extern __shared__ double sh[];
-    logmel_frame(sh, pcm, n_valid, n_padded, blockIdx.x, n_fft, hop, n_bins, n_mels, twc, tws, window, melT, logspec, gmax);
-}
 // the frames of a group: blockIdx = (frame, window); window b's features at logspec + b * spec_stride, its maximum in gmax[b]
 __global__ __launch_bounds__(256) void k_logmel_frames_group(const SttWin* __restrict__ wins, int64_t n_padded, int n_fft, int hop, int n_bins, int n_mels,
                                                              const double* __restrict__ twc, const double* __restrict__ tws,
-                                                             const float* __restrict__ window, const float* __restrict__ melT,
+                                                             const float* __restrict__ window, const float* __restrict__ melT /*[n_bins][n_mels]*/,
                                                              float* __restrict__ logspec, int64_t spec_stride, int* __restrict__ gmax) {
     extern __shared__ double sh[];
     const SttWin w = wins[blockIdx.y];
@@ -161,9 +153,6 @@ __device__ __forceinline__ void logmel_finish(float* __restrict__ logspec, int64
         const float v = i < n_computed ? logspec[i] : -10.f;
         logspec[i] = (fmaxf(v, mx - 8.0f) + 4.0f) / 4.0f;
     }
-}
-__global__ void k_logmel_finish(float* __restrict__ logspec, int64_t n_total, int64_t n_computed, const int* __restrict__ gmax) {
-    logmel_finish(logspec, n_total, n_computed, gmax);
 }
 __global__ void k_logmel_finish_group(const SttWin* __restrict__ wins, float* __restrict__ logspec, int64_t n_total, int n_mels, const int* __restrict__ gmax) {
     logmel_finish(logspec + (int64_t)blockIdx.y * n_total, n_total, (int64_t)wins[blockIdx.y].n_comp * n_mels, gmax + blockIdx.y);
@@ -201,11 +190,15 @@ __global__ void k_stt_embed(const bf16_t* __restrict__ tok_emb, const float* __r
     for (int i = threadIdx.x; i < D; i += blockDim.x) x[(int64_t)r * D + i] = bf16_to_f32(tok_emb[t * D + i]) + pos_emb[pos * D + i];
 }
 
-// greedy choice over one row of logits: the largest value among the tokens the mask allows (bit 0: never, bit 1: not as the first
-// generated token), lowest index on ties, NaNs never; thread 0 of the 1024-thread workgroup returns the winner
-__device__ __forceinline__ int stt_argmax_row(const float* __restrict__ logits, int V, const uint8_t* __restrict__ mask, int first_step) {
+// A group's greedy step, one 1024-thread workgroup per window: the row's next input token is the largest logit among the tokens the
+// mask allows (bit 0: never, bit 1: not as the first generated token), lowest index on ties, NaNs never.  The host reads the group's
+// tokens once per step and keeps the books; a row that has ended rides along as a dead row: it keeps writing its own cache slot and
+// its own logits, nothing a live row reads.
+__global__ __launch_bounds__(1024) void k_stt_pick(const float* __restrict__ all_logits, int V, const uint8_t* __restrict__ mask, int first_step,
+                                                   int32_t* __restrict__ next_tok) {
     __shared__ float sv[16];
     __shared__ int si[16];
+    const float* logits = all_logits + (int64_t)blockIdx.x * V;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     const uint8_t bad = first_step ? 3 : 1;
@@ -222,36 +215,10 @@ __device__ __forceinline__ int stt_argmax_row(const float* __restrict__ logits, 
     }
     if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = bi; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-    }
-    return bi == 0x7fffffff ? 0 : bi;
-}
-// the single clip's step: the winner is written to out[0], the next input token
-__global__ __launch_bounds__(1024) void k_stt_argmax(const float* __restrict__ logits, int V, const uint8_t* __restrict__ mask, int first_step,
-                                                     int32_t* __restrict__ out) {
-    const int tok = stt_argmax_row(logits, V, mask, first_step);
-    if (threadIdx.x == 0) out[0] = tok;
-}
-// A group's step, one workgroup per window: the winner of row b becomes the row's next input token; unless the row has ended it is
-// appended to the row's log - or, if it is end-of-sequence, ends the row and takes it off the live count.  An ended row rides along
-// as a dead row: it keeps writing its own cache slot and its own logits, nothing a live row reads.
-__global__ __launch_bounds__(1024) void k_stt_pick(const float* __restrict__ logits, int V, const uint8_t* __restrict__ mask, int first_step, int eos,
-                                                   int log_cap, int32_t* __restrict__ next_tok, int32_t* __restrict__ log, int32_t* __restrict__ n_log,
-                                                   int32_t* __restrict__ done, int32_t* __restrict__ live) {
-    const int b = blockIdx.x;
-    const int tok = stt_argmax_row(logits + (int64_t)b * V, V, mask, first_step);
     if (threadIdx.x != 0) return;
-    next_tok[b] = tok;
-    if (done[b]) return;
-    if (tok == eos) {
-        done[b] = 1;
-        atomicSub(live, 1);
-    } else if (n_log[b] < log_cap) {
-        log[(int64_t)b * log_cap + n_log[b]] = tok;
-        n_log[b] += 1;
-    }
+    for (int w = 1; w < 16; ++w)
+        if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+    next_tok[blockIdx.x] = bi == 0x7fffffff ? 0 : bi;
 }
 
 __global__ void k_stt_fill_i32(int32_t* p, int n, int v, int step) {
@@ -470,38 +437,55 @@ __global__ void k_stt_fill_beam_rows(int32_t* __restrict__ pre_slot, int32_t* __
 
 }  // namespace
 
-// Windows of one group of rt_stt_transcribe_batch: the rows of every batched launch.  Compile-time: the group's buffers - about
-// 79 MB per window at Whisper-tiny dimensions - are the price of a larger group.
+// Windows of one group: the rows of every launch.  Compile-time: the group's buffers - about 79 MB per window at Whisper-tiny
+// dimensions - are the price of a larger group.
 constexpr int STT_GROUP = 32;
 
-// The buffers one pass works on: the single clip's (B = 1, allocated by rt_stt_finalize) or a group's (B windows, allocated by
-// the first batched call, grown when a later call needs more windows).  Row tables address the caches per row: encoder row
-// b n_ctx + t is position t of slot b and attends up to n_ctx - 1.
-struct SttBufs {
-    int B = 0;
-    KvCache enc_kv, dec_kv, cross_kv;
-    float *pcm16k = nullptr, *mel = nullptr, *c1 = nullptr, *x = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *ao = nullptr, *ff = nullptr,
-          *enc_out = nullptr, *logits = nullptr;
-    float *dx = nullptr, *dxn = nullptr, *dqkv = nullptr, *dq = nullptr, *dao = nullptr, *dff = nullptr;
-    int32_t *enc_slot = nullptr, *enc_pos = nullptr, *enc_last = nullptr;   // [B n_ctx] (enc_last: n_ctx - 1 throughout, also what decoder rows attend across)
-    int32_t *dec_slot = nullptr, *dec_pos = nullptr;       // [B R] rows of the prefix pass: row b R + i -> slot b, position i
-    int32_t *step_slot = nullptr, *step_pos = nullptr;     // [B] rows of a step pass: slot b, position 0 (+ pos_add)
-    int32_t *d_tok = nullptr, *d_gmax = nullptr;
-    // a group only: the decode bookkeeping k_stt_pick keeps and the window table of the front end
-    int32_t *d_log = nullptr, *d_nlog = nullptr, *d_done = nullptr, *d_live = nullptr;   // [B][max_new_tokens] ids | [B] | [B] | [1], one allocation
+// The workspaces of one pre-LN layer over some rows (stt_layer): [rows][D], qkv [rows][3 D], ff [rows][ffn]
+struct SttWork { float *x = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *ao = nullptr, *ff = nullptr; };
+
+// The encoder side of a group of B windows: front end, encoder, and the cross-attention cache the decoders read.  Row tables address
+// the caches per row: encoder row b n_ctx + t is position t of slot b and attends up to n_ctx - 1.
+struct SttEnc {
+    KvCache kv, cross_kv;
+    float *pcm16k = nullptr, *mel = nullptr, *c1 = nullptr, *out = nullptr;     // out: the encoder states [B][n_ctx][D]
+    SttWork work;
+    int32_t *slot = nullptr, *pos = nullptr, *last = nullptr;                   // [B n_ctx] (last: n_ctx - 1 throughout)
+    int32_t* d_gmax = nullptr;
     SttWin* d_wins = nullptr;
+};
+
+// A decoder side for `rows` rows (greedy: the windows of a group; beam search: windows x beams): the self-attention cache, one slot
+// per row, workspaces for rows x n_prefix rows of a pass, the logits of every row's last position and the tokens a pass reads.
+struct SttDec {
+    KvCache kv;
+    SttWork work;
+    float* logits = nullptr;            // [rows][vocab]
+    int32_t* enc_last = nullptr;        // [rows n_prefix] n_ctx - 1 throughout: how far a row attends across the encoder states
+    const int32_t* tok = nullptr;       // the tokens of the next pass (not owned)
+};
+
+// The one buffer set of the handle: B windows' encoder side and their greedy decoder side, reserved for one window by
+// rt_stt_finalize and replaced by a larger set when a call needs more windows (stt_group_reserve).
+struct SttGroup {
+    int B = 0;
+    SttEnc enc;
+    SttDec dec;
+    int32_t *pre_slot = nullptr, *pre_pos = nullptr;       // [B n_prefix] rows of the prefix pass: row b n_prefix + i -> slot b, position i
+    int32_t *step_slot = nullptr, *step_pos = nullptr;     // [B] rows of a step pass: slot b, position 0 (+ pos_add)
+    int32_t *d_prefix = nullptr, *d_tok = nullptr;         // [B n_prefix] the forced prefix of every window | [B] every row's pick (k_stt_pick)
     std::vector<void*> owned;
 };
 
-// The decoder side of the beam path (rt_stt_transcribe_beam), for `rows` rows = windows x beams of one group: two self-attention
-// caches used alternately (k_stt_beam_reorder gathers from one into the other), the decoder workspaces and logits per row, row
-// tables and the bookkeeping of k_stt_beam_select.  The encoder side and the cross-attention cache are the group's (s->grp).
+// The beam path (rt_stt_transcribe_beam), for `rows` rows = windows x beams of one group: a decoder side, a second self-attention
+// cache (k_stt_beam_reorder gathers from dec.kv into it, then the two swap), row tables and the bookkeeping of k_stt_beam_select.
+// The encoder side and the cross-attention cache are the group's (s->grp.enc).
 struct SttBeam {
     int rows = 0;
-    KvCache kv[2];
-    float *dx = nullptr, *dxn = nullptr, *dqkv = nullptr, *dq = nullptr, *dao = nullptr, *dff = nullptr, *logits = nullptr;
-    int32_t *pre_tok = nullptr, *pre_slot = nullptr, *pre_pos = nullptr, *pre_win = nullptr;   // [rows n_prefix] the prefix pass
-    int32_t *row_slot = nullptr, *row_win = nullptr, *row_pos = nullptr, *enc_last = nullptr;  // [rows] a step pass | [rows n_prefix]
+    SttDec dec;
+    KvCache kv_next;
+    int32_t *pre_slot = nullptr, *pre_pos = nullptr, *pre_win = nullptr;                       // [rows n_prefix] the prefix pass
+    int32_t *row_slot = nullptr, *row_win = nullptr, *row_pos = nullptr;                       // [rows] a step pass
     int32_t* book_mem = nullptr;
     size_t book_n = 0;
     SttBeamBook book{};
@@ -519,13 +503,11 @@ struct rt_stt {
     float *d_window = nullptr, *d_melT = nullptr;
     float* d_resamp = nullptr;        // polyphase filter of the last (sr_in -> cfg.sample_rate) pair
     int rs_in = 0, rs_L = 0, rs_M = 0, rs_taps = 0, rs_half = 0;
-    SttBufs one;                      // the single-clip path: n_ctx rows, one cache slot
-    // the batched path (rt_stt_transcribe_batch): nothing of it exists until the first batched call
-    SttBufs grp;
+    SttGroup grp;                     // every entry point's buffers: one window from rt_stt_finalize on
     SttBeam beam;                     // the beam path: nothing of it exists until the first rt_stt_transcribe_beam
     std::vector<int32_t> h_book;
     std::vector<SttWin> h_wins;       // host copies of what is uploaded per group (alive until the group's last synchronisation)
-    std::vector<int32_t> h_prefix, h_log;
+    std::vector<int32_t> h_tok;
     uint8_t* d_mask = nullptr;
     std::vector<int32_t> suppress_ids;   // rt_stt_set_suppress: ids never produced (a generation config's `suppress_tokens`)
     std::vector<void*> owned;
@@ -596,37 +578,77 @@ int stt_kv(rt_stt* s, std::vector<void*>& owned, KvCache& kv, int layers, int sl
     return RT_OK;
 }
 
-// caches, workspaces and encoder row tables of B windows; R = decoder rows per window and pass (the forced prefix, then one)
-int stt_alloc_bufs(rt_stt* s, SttBufs& w, int B, int R) {
+int stt_alloc_work(rt_stt* s, std::vector<void*>& owned, size_t rows, SttWork& k) {
+    const size_t D = s->cfg.d_model;
+    ST_TRY(stt_alloc(s, owned, rows * D, &k.x)); ST_TRY(stt_alloc(s, owned, rows * D, &k.xn)); ST_TRY(stt_alloc(s, owned, rows * 3 * D, &k.qkv));
+    ST_TRY(stt_alloc(s, owned, rows * D, &k.q)); ST_TRY(stt_alloc(s, owned, rows * D, &k.ao)); ST_TRY(stt_alloc(s, owned, rows * s->cfg.ffn, &k.ff));
+    return RT_OK;
+}
+
+// a decoder side for `rows` rows; a pass runs at most n_prefix rows of each (the forced prefix, then one)
+int stt_alloc_dec(rt_stt* s, std::vector<void*>& owned, int rows, SttDec& d) {
+    const rt_stt_config& c = s->cfg;
+    const size_t rp = (size_t)rows * c.n_prefix;
+    ST_TRY(stt_kv(s, owned, d.kv, c.dec_layers, rows, c.n_text_ctx));
+    ST_TRY(stt_alloc_work(s, owned, rp, d.work));
+    ST_TRY(stt_alloc(s, owned, (size_t)rows * c.vocab, &d.logits));
+    ST_TRY(stt_alloc(s, owned, rp, &d.enc_last));
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(256), 0, s->ctx->stream, d.enc_last, (int)rp, c.n_ctx - 1, 0);
+    RT_HIP(s->ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// the buffer set of B windows
+int stt_alloc_group(rt_stt* s, SttGroup& w, int B) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
-    const int D = c.d_model, T = c.n_ctx, T2 = 2 * T;
-    const size_t b = (size_t)B, rows = b * T;
-    ST_TRY(stt_kv(s, w.owned, w.enc_kv, c.enc_layers, B, T));
-    ST_TRY(stt_kv(s, w.owned, w.dec_kv, c.dec_layers, B, c.n_text_ctx));
-    ST_TRY(stt_kv(s, w.owned, w.cross_kv, c.dec_layers, B, T));
-    ST_TRY(stt_alloc(s, w.owned, b * c.chunk_seconds * c.sample_rate, &w.pcm16k));
-    ST_TRY(stt_alloc(s, w.owned, b * T2 * c.n_mels, &w.mel));
-    ST_TRY(stt_alloc(s, w.owned, b * T2 * D, &w.c1));
-    ST_TRY(stt_alloc(s, w.owned, rows * D, &w.x)); ST_TRY(stt_alloc(s, w.owned, rows * D, &w.xn)); ST_TRY(stt_alloc(s, w.owned, rows * 3 * D, &w.qkv));
-    ST_TRY(stt_alloc(s, w.owned, rows * D, &w.q)); ST_TRY(stt_alloc(s, w.owned, rows * D, &w.ao)); ST_TRY(stt_alloc(s, w.owned, rows * c.ffn, &w.ff));
-    ST_TRY(stt_alloc(s, w.owned, rows * D, &w.enc_out));
-    ST_TRY(stt_alloc(s, w.owned, b * c.vocab, &w.logits));
-    const size_t r = b * R;
-    ST_TRY(stt_alloc(s, w.owned, r * D, &w.dx)); ST_TRY(stt_alloc(s, w.owned, r * D, &w.dxn)); ST_TRY(stt_alloc(s, w.owned, r * 3 * D, &w.dqkv));
-    ST_TRY(stt_alloc(s, w.owned, r * D, &w.dq)); ST_TRY(stt_alloc(s, w.owned, r * D, &w.dao)); ST_TRY(stt_alloc(s, w.owned, r * c.ffn, &w.dff));
-    const size_t n_last = std::max(rows, r);            // (decoder rows read enc_last too)
-    ST_TRY(stt_alloc(s, w.owned, rows, &w.enc_slot)); ST_TRY(stt_alloc(s, w.owned, rows, &w.enc_pos)); ST_TRY(stt_alloc(s, w.owned, n_last, &w.enc_last));
-    ST_TRY(stt_alloc(s, w.owned, r, &w.dec_slot)); ST_TRY(stt_alloc(s, w.owned, r, &w.dec_pos));
+    const int D = c.d_model, T = c.n_ctx, T2 = 2 * T, P = c.n_prefix;
+    const size_t b = (size_t)B, rows = b * T, r = b * P;
+    SttEnc& e = w.enc;
+    ST_TRY(stt_kv(s, w.owned, e.kv, c.enc_layers, B, T));
+    ST_TRY(stt_kv(s, w.owned, e.cross_kv, c.dec_layers, B, T));
+    ST_TRY(stt_alloc(s, w.owned, b * c.chunk_seconds * c.sample_rate, &e.pcm16k));
+    ST_TRY(stt_alloc(s, w.owned, b * T2 * c.n_mels, &e.mel));
+    ST_TRY(stt_alloc(s, w.owned, b * T2 * D, &e.c1));
+    ST_TRY(stt_alloc_work(s, w.owned, rows, e.work));
+    ST_TRY(stt_alloc(s, w.owned, rows * D, &e.out));
+    ST_TRY(stt_alloc(s, w.owned, rows, &e.slot)); ST_TRY(stt_alloc(s, w.owned, rows, &e.pos)); ST_TRY(stt_alloc(s, w.owned, rows, &e.last));
+    ST_TRY(stt_alloc(s, w.owned, b, &e.d_gmax)); ST_TRY(stt_alloc(s, w.owned, b, &e.d_wins));
+    ST_TRY(stt_alloc_dec(s, w.owned, B, w.dec));
+    ST_TRY(stt_alloc(s, w.owned, r, &w.pre_slot)); ST_TRY(stt_alloc(s, w.owned, r, &w.pre_pos));
     ST_TRY(stt_alloc(s, w.owned, b, &w.step_slot)); ST_TRY(stt_alloc(s, w.owned, b, &w.step_pos));
-    ST_TRY(stt_alloc(s, w.owned, r, &w.d_tok)); ST_TRY(stt_alloc(s, w.owned, b, &w.d_gmax));
-    hipLaunchKernelGGL(k_stt_fill_rows, dim3(64), dim3(256), 0, ctx->stream, w.enc_slot, w.enc_pos, (int)rows, T);
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(64), dim3(256), 0, ctx->stream, w.enc_last, (int)n_last, T - 1, 0);
-    hipLaunchKernelGGL(k_stt_fill_rows, dim3(1), dim3(256), 0, ctx->stream, w.dec_slot, w.dec_pos, (int)r, R);
+    ST_TRY(stt_alloc(s, w.owned, r, &w.d_prefix)); ST_TRY(stt_alloc(s, w.owned, b, &w.d_tok));
+    std::vector<int32_t> prefix(r);
+    for (size_t i = 0; i < r; ++i) prefix[i] = c.prefix[i % P];
+    RT_HIP(ctx, hipMemcpy(w.d_prefix, prefix.data(), r * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_stt_fill_rows, dim3(64), dim3(256), 0, ctx->stream, e.slot, e.pos, (int)rows, T);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(64), dim3(256), 0, ctx->stream, e.last, (int)rows, T - 1, 0);
+    hipLaunchKernelGGL(k_stt_fill_rows, dim3(1), dim3(256), 0, ctx->stream, w.pre_slot, w.pre_pos, (int)r, P);
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, w.step_slot, B, 0, 1);
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, w.step_pos, B, 0, 0);
     RT_HIP(ctx, hipGetLastError());
-    w.B = B;            // (last: a set that an allocation failure left incomplete holds no windows)
+    w.B = B;
+    return RT_OK;
+}
+
+// Replaces the buffer set `held` (an SttGroup or an SttBeam) by what `build` allocates.  The new set is built aside and adopted only
+// when every allocation has succeeded; after a failure (a full group is 2.5 GB beside the TTS model) the handle holds no set at all -
+// every pointer null - and the next call allocates again.
+template <typename Set, typename Build>
+int stt_reserve(rt_stt* s, Set& held, Build build) {
+    rt_ctx* ctx = s->ctx;
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (void* p : held.owned) (void)hipFree(p);
+    held = Set{};
+    Set nw;
+    const int rc = build(nw);
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);         // (the fills and memsets already launched on the partial set)
+        for (void* p : nw.owned) (void)hipFree(p);
+        (void)hipGetLastError();                         // (the failed call's sticky error must not surface at a later launch check)
+        return rc;
+    }
+    held = std::move(nw);
     return RT_OK;
 }
 
@@ -682,51 +704,24 @@ int stt_frames_with_audio(const rt_stt_config& c, int64_t n16) {
     return n16 <= 0 ? 0 : (int)std::min<int64_t>(n_frames, (n16 + c.n_fft / 2 + c.hop - 1) / c.hop + 1);
 }
 
-// PCM (device, any rate) -> log-mel [frames][n_mels] in s->one.mel (the mutex is held)
-int stt_features(rt_stt* s, const float* d_pcm, int64_t n, int sr) {
-    rt_ctx* ctx = s->ctx;
-    const rt_stt_config& c = s->cfg;
-    SttBufs& w = s->one;
-    const int64_t n_pad = (int64_t)c.chunk_seconds * c.sample_rate;
-    const float* src = d_pcm;
-    int64_t n16 = n;
-    if (sr != c.sample_rate) {
-        ST_TRY(stt_resampler(s, sr));
-        n16 = std::min<int64_t>((n * s->rs_L + s->rs_M - 1) / s->rs_M, n_pad);        // ceil(n L / M), at most 30 s
-        if (n16 > 0)
-            hipLaunchKernelGGL(k_resample, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_pcm, n, w.pcm16k, n16,
-                               s->rs_L, s->rs_M, s->rs_taps, s->rs_half, s->d_resamp);
-        RT_HIP(ctx, hipGetLastError());
-        src = w.pcm16k;
-    }
-    n16 = std::min(n16, n_pad);
-    const int n_frames = (int)(n_pad / c.hop);
-    const int n_comp = stt_frames_with_audio(c, n16);
-    const int n_bins = c.n_fft / 2 + 1;
-    const int init = (int)0x80000000;                               // below every ordered float
-    RT_HIP(ctx, hipMemcpyAsync(w.d_gmax, &init, 4, hipMemcpyHostToDevice, ctx->stream));
-    if (n_comp > 0) {
-        const size_t lds = (size_t)(3 * c.n_fft + n_bins) * sizeof(double);
-        hipLaunchKernelGGL(k_logmel_frames, dim3(n_comp), dim3(256), lds, ctx->stream, src, n16, n_pad, c.n_fft, c.hop, n_bins, c.n_mels, s->d_twc,
-                           s->d_tws, s->d_window, s->d_melT, w.mel, w.d_gmax);
-        RT_HIP(ctx, hipGetLastError());
-    }
-    const int64_t tot = (int64_t)n_frames * c.n_mels;
-    hipLaunchKernelGGL(k_logmel_finish, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 2048)), dim3(256), 0, ctx->stream, w.mel, tot,
-                       (int64_t)n_comp * c.n_mels, w.d_gmax);
-    RT_HIP(ctx, hipGetLastError());
-    return RT_OK;
-}
-
-// One window of the input of a batched call
+// One window of the input of a call
 struct SttSpan { int clip; const float* pcm; int64_t n; };
 
-// The front end of a group: B windows (device pointers at rate sr) -> log-mel [B][frames][n_mels] in s->grp.mel, one launch per
-// stage for the whole group.  Per frame and per sample the arithmetic of stt_features (shared device functions).
+// Cuts every clip into consecutive chunk_seconds windows of the INPUT (an empty clip is one window of silence); first_only keeps a
+// clip's first window alone
+void stt_cut(const rt_stt_config& c, int sr, const float* const* d_pcm, const int64_t* n_samples, int n_clips, std::vector<SttSpan>& all, bool first_only = false) {
+    const int64_t win = (int64_t)c.chunk_seconds * sr;              // one window, in input samples
+    for (int i = 0; i < n_clips; ++i)
+        for (int64_t off = 0; off == 0 || (off < n_samples[i] && !first_only); off += win)
+            all.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off : nullptr, std::min<int64_t>(win, n_samples[i] - off)});
+}
+
+// The front end of a group: B windows (device pointers at rate sr) -> log-mel [B][frames][n_mels] in s->grp.enc.mel, one launch per
+// stage for the whole group.  The resampler's taps see all spans[b].n samples; at most one chunk of its output is kept.
 int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
-    SttBufs& w = s->grp;
+    SttEnc& w = s->grp.enc;
     const int64_t n_pad = (int64_t)c.chunk_seconds * c.sample_rate;
     const bool resample = sr != c.sample_rate;
     if (resample) ST_TRY(stt_resampler(s, sr));
@@ -765,14 +760,15 @@ int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
     return RT_OK;
 }
 
-// one pre-LN layer over M rows of x (in place).  self-attention over cache `kv` (row r is written at slot[r], wpos[r] + pos_add and
-// attends up to apos[r]); cross = the decoder's encoder-attention block between the two, over slot cross_slot[r] of w.cross_kv (the
-// row's own slot when null: beam rows of one window share the window's encoder states)
-int stt_layer(rt_stt* s, SttBufs& w, const std::string& p, float* x, float* xn, float* qkv, float* q, float* ao, float* ff, int M, KvCache& kv, int layer,
-              const int32_t* slot, const int32_t* wpos, const int32_t* apos, int pos_add, bool cross, const int32_t* cross_slot = nullptr) {
+// one pre-LN layer over M rows of k.x (in place).  self-attention over cache `kv` (row r is written at slot[r], wpos[r] + pos_add and
+// attends up to apos[r]); cross != null: the decoder's encoder-attention block between the two, over slot cross_slot[r] of *cross up
+// to cross_last[r]
+int stt_layer(rt_stt* s, const std::string& p, const SttWork& k, int M, const KvCache& kv, int layer, const int32_t* slot, const int32_t* wpos,
+              const int32_t* apos, int pos_add, const KvCache* cross = nullptr, const int32_t* cross_slot = nullptr, const int32_t* cross_last = nullptr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int H = c.heads, d = c.d_model / c.heads, D = c.d_model;
+    float *x = k.x, *xn = k.xn, *qkv = k.qkv, *q = k.q, *ao = k.ao, *ff = k.ff;
     ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln1_w"), SVEC(s, p + ".ln1_b"), xn));
     ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".wqkv"), SVEC(s, p + ".bqkv"), ACT_NONE, nullptr, qkv));
     ST_TRY(launch_qkv_post(ctx, qkv, 1, M, H, H, d, nullptr, nullptr, 0.f, nullptr, nullptr, slot, wpos, pos_add, q, kv, layer));
@@ -781,7 +777,7 @@ int stt_layer(rt_stt* s, SttBufs& w, const std::string& p, float* x, float* xn, 
     if (cross) {
         ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".lnc_w"), SVEC(s, p + ".lnc_b"), xn));
         ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".cwq"), SVEC(s, p + ".cbq"), ACT_NONE, nullptr, q));
-        ST_TRY(launch_attention(ctx, q, M, H, H, d, cross_slot ? cross_slot : slot, w.enc_last, 0, 0, w.cross_kv, layer, nullptr, nullptr, 0, ao));
+        ST_TRY(launch_attention(ctx, q, M, H, H, d, cross_slot, cross_last, 0, 0, *cross, layer, nullptr, nullptr, 0, ao));
         ST_TRY(stt_gemm(s, ao, M, SPW(s, p + ".cwo"), SVEC(s, p + ".cbo"), ACT_NONE, x, x));
     }
     ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln2_w"), SVEC(s, p + ".ln2_b"), xn));
@@ -790,12 +786,13 @@ int stt_layer(rt_stt* s, SttBufs& w, const std::string& p, float* x, float* xn, 
     return RT_OK;
 }
 
-// log-mel of B windows in w.mel -> encoder states in w.enc_out [B][n_ctx][D], and the decoder's cross-attention K/V caches.
+// log-mel of B windows in w.mel -> encoder states in w.out [B][n_ctx][D], and the decoders' cross-attention K/V cache.
 // Every launch runs over the B windows' rows; the convolutions' taps stop at a window's ends (rows_out / rows_in).
-int stt_encode(rt_stt* s, SttBufs& w, int B) {
+int stt_encode(rt_stt* s, SttEnc& w, int B) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int D = c.d_model, T2 = 2 * c.n_ctx, T = c.n_ctx;
+    const SttWork& k = w.work;
     {   // conv1: k = 3, pad 1, GELU, on [T2][n_mels]
         GemmA a; a.ptr = w.mel; a.is_f32 = 1; a.split = 1; a.M = (int64_t)B * T2; a.Cin = c.n_mels; a.taps = 3; a.tap_stride = 1; a.tap_offset = -1; a.rows_out = T2; a.rows_in = T2;
         GemmEpi e; e.bias = SVEC(s, "enc.conv1_b"); e.act = ACT_GELU; e.out_f32 = w.c1; e.ldc = D;
@@ -804,104 +801,109 @@ int stt_encode(rt_stt* s, SttBufs& w, int B) {
     {   // conv2: k = 3, stride 2, pad 1, GELU, + positions.  Over rows [x[2t], x[2t+1]] it is the 2-tap GEMM (row t-1, row t) with the
         // weight laid out as [0 | W0 | W1 | W2]
         GemmA a; a.ptr = w.c1; a.is_f32 = 1; a.split = 1; a.M = (int64_t)B * T; a.Cin = 2 * D; a.taps = 2; a.tap_stride = 1; a.tap_offset = -1; a.rows_out = T; a.rows_in = T;
-        GemmEpi e; e.bias = SVEC(s, "enc.conv2_b"); e.act = ACT_GELU; e.residual = SVEC(s, "enc.pos"); e.out_f32 = w.x; e.ldc = D;
+        GemmEpi e; e.bias = SVEC(s, "enc.conv2_b"); e.act = ACT_GELU; e.residual = SVEC(s, "enc.pos"); e.out_f32 = k.x; e.ldc = D;
         if (B > 1) {    // the residual is read per output row: the positions are laid under every window first, and updated in place
-            hipLaunchKernelGGL(k_stt_repeat, dim3(1024), dim3(256), 0, ctx->stream, SVEC(s, "enc.pos"), (int64_t)T * D, B, w.x);
+            hipLaunchKernelGGL(k_stt_repeat, dim3(1024), dim3(256), 0, ctx->stream, SVEC(s, "enc.pos"), (int64_t)T * D, B, k.x);
             RT_HIP(ctx, hipGetLastError());
-            e.residual = w.x;
+            e.residual = k.x;
         }
         ST_TRY(launch_gemm(ctx, a, SPW(s, "enc.conv2"), e));
     }
     const int M = B * T;
-    for (int i = 0; i < c.enc_layers; ++i)
-        ST_TRY(stt_layer(s, w, "enc.l" + std::to_string(i), w.x, w.xn, w.qkv, w.q, w.ao, w.ff, M, w.enc_kv, i, w.enc_slot, w.enc_pos, w.enc_last, 0, false));
-    ST_TRY(stt_ln(s, w.x, D, M, SVEC(s, "enc.ln_w"), SVEC(s, "enc.ln_b"), w.enc_out));
+    for (int i = 0; i < c.enc_layers; ++i) ST_TRY(stt_layer(s, "enc.l" + std::to_string(i), k, M, w.kv, i, w.slot, w.pos, w.last, 0));
+    ST_TRY(stt_ln(s, k.x, D, M, SVEC(s, "enc.ln_w"), SVEC(s, "enc.ln_b"), w.out));
     // cross-attention K / V of every decoder layer (k_proj has no bias: its half of cbkv is zero)
     for (int i = 0; i < c.dec_layers; ++i) {
         const std::string p = "dec.l" + std::to_string(i);
-        ST_TRY(stt_gemm(s, w.enc_out, M, SPW(s, p + ".cwkv"), SVEC(s, p + ".cbkv"), ACT_NONE, nullptr, w.qkv));
-        ST_TRY(launch_qkv_post(ctx, w.qkv, 1, M, 0, c.heads, D / c.heads, nullptr, nullptr, 0.f, nullptr, nullptr, w.enc_slot, w.enc_pos, 0, w.q, w.cross_kv, i));
+        ST_TRY(stt_gemm(s, w.out, M, SPW(s, p + ".cwkv"), SVEC(s, p + ".cbkv"), ACT_NONE, nullptr, k.qkv));
+        ST_TRY(launch_qkv_post(ctx, k.qkv, 1, M, 0, c.heads, D / c.heads, nullptr, nullptr, 0.f, nullptr, nullptr, w.slot, w.pos, 0, k.q, w.cross_kv, i));
     }
     return RT_OK;
 }
 
-// B x per decoder rows (tokens w.d_tok, row r = window r / per at position pos0 + r % per; slot / pos: its row tables) -> logits of
-// the LAST row of every window in w.logits [B][vocab].  cross_slot: the rows' slots of the cross-attention cache (null: `slot`)
-int stt_decode_rows(rt_stt* s, SttBufs& w, int B, int per, int pos0, const int32_t* slot, const int32_t* pos, const int32_t* cross_slot = nullptr) {
+// B x per decoder rows (tokens d.tok, row r = window r / per at position pos0 + r % per; slot / pos: its row tables into d.kv) ->
+// logits of the LAST row of every window in d.logits [B][vocab].  cross_slot: the rows' slots of the cross-attention cache `cross`
+int stt_decode_rows(rt_stt* s, const SttDec& d, const KvCache& cross, int B, int per, int pos0, const int32_t* slot, const int32_t* pos, const int32_t* cross_slot) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int D = c.d_model, M = B * per;
+    const SttWork& k = d.work;
     SttSlot* tok = stt_find(s, "dec.tok");
-    hipLaunchKernelGGL(k_stt_embed, dim3(M), dim3(128), 0, ctx->stream, tok->tbl, SVEC(s, "dec.pos"), w.d_tok, pos0, per, D, w.dx);
+    hipLaunchKernelGGL(k_stt_embed, dim3(M), dim3(128), 0, ctx->stream, tok->tbl, SVEC(s, "dec.pos"), d.tok, pos0, per, D, k.x);
     RT_HIP(ctx, hipGetLastError());
-    for (int i = 0; i < c.dec_layers; ++i)
-        ST_TRY(stt_layer(s, w, "dec.l" + std::to_string(i), w.dx, w.dxn, w.dqkv, w.dq, w.dao, w.dff, M, w.dec_kv, i, slot, pos, pos, pos0, true, cross_slot));
-    ST_TRY(stt_ln(s, w.dx + (size_t)(per - 1) * D, (int64_t)per * D, B, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), w.dxn));
-    ST_TRY(stt_gemm(s, w.dxn, B, tok->pw, nullptr, ACT_NONE, nullptr, w.logits));
+    for (int i = 0; i < c.dec_layers; ++i) ST_TRY(stt_layer(s, "dec.l" + std::to_string(i), k, M, d.kv, i, slot, pos, pos, pos0, &cross, cross_slot, d.enc_last));
+    ST_TRY(stt_ln(s, k.x + (size_t)(per - 1) * D, (int64_t)per * D, B, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), k.xn));
+    ST_TRY(stt_gemm(s, k.xn, B, tok->pw, nullptr, ACT_NONE, nullptr, d.logits));
     return RT_OK;
 }
 
-// The group's buffers for B windows: allocated by the first batched call, replaced by larger ones when a call needs more windows.
-// The new set is built aside and becomes s->grp only when every allocation has succeeded; after a failure (a full group is 2.5 GB
-// beside the TTS model) the handle holds no group at all - B = 0, every pointer null - and the next batched call allocates again.
+// The handle's buffer set holds at least B windows: a larger one replaces it when a call needs more (stt_reserve)
 int stt_group_reserve(rt_stt* s, int B) {
+    if (s->grp.B >= B) return RT_OK;
+    return stt_reserve(s, s->grp, [&](SttGroup& nw) { return stt_alloc_group(s, nw, B); });
+}
+
+// Greedy decode of the B encoded windows of the group: ids[b] = the first `budget` ids of window b (forced prefix in one pass, then
+// one token per pass until end-of-sequence).  One device-to-host read (the rows' tokens) and one synchronisation per step for the
+// whole group.  d_first_logits: receives row 0's logits behind the prefix pass.
+int stt_decode_group(rt_stt* s, int B, int budget, std::vector<std::vector<int32_t>>& ids, float* d_first_logits) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
-    if (s->grp.B >= B) return RT_OK;
-    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (void* p : s->grp.owned) (void)hipFree(p);
-    s->grp = SttBufs{};
-    SttBufs nw;
-    const size_t b = (size_t)B, P = (size_t)c.n_prefix;
-    auto build = [&]() -> int {
-        ST_TRY(stt_alloc(s, nw.owned, b * c.max_new_tokens + 2 * b + 1, &nw.d_log));
-        nw.d_nlog = nw.d_log + b * c.max_new_tokens;
-        nw.d_done = nw.d_nlog + b;
-        nw.d_live = nw.d_done + b;
-        ST_TRY(stt_alloc(s, nw.owned, b, &nw.d_wins));
-        return stt_alloc_bufs(s, nw, B, (int)P);
-    };
-    const int rc = build();
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);         // (the fills and memsets already launched on the partial set)
-        for (void* p : nw.owned) (void)hipFree(p);
-        (void)hipGetLastError();                         // (the failed call's sticky error must not surface at a later launch check)
-        return rc;
+    SttGroup& w = s->grp;
+    const int P = c.n_prefix;
+    w.dec.tok = w.d_prefix;
+    ST_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, B, P, 0, w.pre_slot, w.pre_pos, w.pre_slot));
+    if (d_first_logits) RT_HIP(ctx, hipMemcpyAsync(d_first_logits, w.dec.logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    w.dec.tok = w.d_tok;
+    ids.assign(B, {});
+    std::vector<char> done(B, 0);
+    s->h_tok.resize(B);
+    int live = B;
+    for (int step = 0; step < budget; ++step) {
+        hipLaunchKernelGGL(k_stt_pick, dim3(B), dim3(1024), 0, ctx->stream, w.dec.logits, c.vocab, s->d_mask, step == 0 ? 1 : 0, w.d_tok);
+        RT_HIP(ctx, hipGetLastError());
+        RT_HIP(ctx, hipMemcpyAsync(s->h_tok.data(), w.d_tok, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        for (int b = 0; b < B; ++b) {
+            if (done[b]) continue;
+            if (s->h_tok[b] == c.eos_id) { done[b] = 1; --live; }
+            else ids[b].push_back(s->h_tok[b]);
+        }
+        if (live <= 0) break;
+        if (step + 1 < budget) ST_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, B, 1, P + step, w.step_slot, w.step_pos, w.step_slot));
     }
-    s->grp = std::move(nw);
-    s->h_prefix.resize(b * P);
-    for (size_t i = 0; i < b * P; ++i) s->h_prefix[i] = c.prefix[i % P];
     return RT_OK;
 }
 
-// Greedy decode of the B encoded windows of the group: ids[b] = what the single-clip loop generates for window b with the full
-// budget.  One device-to-host read (the live count) and one synchronisation per step for the whole group; the logs come back once.
-int stt_decode_group(rt_stt* s, int B, std::vector<std::vector<int32_t>>& ids) {
-    rt_ctx* ctx = s->ctx;
+// Greedy transcription of n_clips clips, what rt_stt_transcribe (one clip) and rt_stt_transcribe_batch share: up to STT_GROUP
+// windows go through the front end, the encoder and the greedy decode together, and a clip's ids are its windows' ids joined and
+// cut at the cap.  No window is decoded past the cap (it could not contribute more ids); a window is left out only when the groups
+// before it already filled its clip's cap.  d_first_logits: the first window's logits behind the forced prefix.
+int stt_transcribe_greedy(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int n_clips, int sr, int32_t* h_tokens, int cap, int32_t* h_n_tokens,
+                          float* d_first_logits) {
     const rt_stt_config& c = s->cfg;
-    SttBufs& w = s->grp;
-    const int P = c.n_prefix, cap = c.max_new_tokens;
-    RT_HIP(ctx, hipMemcpyAsync(w.d_tok, s->h_prefix.data(), (size_t)B * P * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemsetAsync(w.d_nlog, 0, (size_t)2 * w.B * 4, ctx->stream));            // log lengths and done flags
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, w.d_live, 1, B, 0);
-    ST_TRY(stt_decode_rows(s, w, B, P, 0, w.dec_slot, w.dec_pos));
-    const int budget = std::min(cap, c.n_text_ctx - P);
-    for (int step = 0; step < budget; ++step) {
-        hipLaunchKernelGGL(k_stt_pick, dim3(B), dim3(1024), 0, ctx->stream, w.logits, c.vocab, s->d_mask, step == 0 ? 1 : 0, c.eos_id, cap, w.d_tok, w.d_log,
-                           w.d_nlog, w.d_done, w.d_live);
-        RT_HIP(ctx, hipGetLastError());
-        int32_t live = 0;
-        RT_HIP(ctx, hipMemcpyAsync(&live, w.d_live, 4, hipMemcpyDeviceToHost, ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (live <= 0) break;
-        if (step + 1 < budget) ST_TRY(stt_decode_rows(s, w, B, 1, P + step, w.step_slot, w.step_pos));
+    std::vector<SttSpan> all, group;
+    stt_cut(c, sr, d_pcm, n_samples, n_clips, all);
+    std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
+    ST_TRY(stt_group_reserve(s, (int)std::min<size_t>(all.size(), STT_GROUP)));
+    const int budget = std::min(std::min(c.max_new_tokens, c.n_text_ctx - c.n_prefix), cap);
+    std::vector<std::vector<int32_t>> ids;
+    for (size_t next = 0; next < all.size();) {
+        group.clear();
+        for (; next < all.size() && (int)group.size() < STT_GROUP; ++next)
+            if (h_n_tokens[all[next].clip] < cap) group.push_back(all[next]);
+        if (group.empty()) break;
+        const int B = (int)group.size();
+        ST_TRY(stt_features_group(s, group.data(), B, sr));
+        ST_TRY(stt_encode(s, s->grp.enc, B));
+        ST_TRY(stt_decode_group(s, B, budget, ids, d_first_logits));
+        d_first_logits = nullptr;
+        for (int b = 0; b < B; ++b) {
+            const int i = group[b].clip;
+            for (int32_t t : ids[b])
+                if (h_n_tokens[i] < cap) h_tokens[(size_t)i * cap + h_n_tokens[i]++] = t;
+        }
     }
-    const size_t n_log = (size_t)w.B * cap;             // (the lengths lie behind the logs of all w.B rows: one copy)
-    s->h_log.resize(n_log + w.B);
-    RT_HIP(ctx, hipMemcpyAsync(s->h_log.data(), w.d_log, s->h_log.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ids.assign(B, {});
-    for (int b = 0; b < B; ++b) ids[b].assign(s->h_log.begin() + (size_t)b * cap, s->h_log.begin() + (size_t)b * cap + s->h_log[n_log + b]);
     return RT_OK;
 }
 
@@ -920,43 +922,24 @@ SttBeamBook stt_beam_book(int32_t* mem, int R, int steps) {
     return b;
 }
 
-// The beam path's buffers for `rows` decoder rows: allocated by the first beam call, replaced by larger ones when a call needs more
-// rows (as stt_group_reserve: built aside, and after a failure the handle holds none)
+// The beam path holds at least `rows` decoder rows: allocated by the first beam call, replaced when a call needs more (stt_reserve)
 int stt_beam_reserve(rt_stt* s, int rows) {
-    rt_ctx* ctx = s->ctx;
-    const rt_stt_config& c = s->cfg;
     if (s->beam.rows >= rows) return RT_OK;
-    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (void* p : s->beam.owned) (void)hipFree(p);
-    s->beam = SttBeam{};
-    SttBeam nb;
-    const size_t r = (size_t)rows, rp = r * c.n_prefix, D = c.d_model;
-    auto build = [&]() -> int {
-        for (KvCache& kv : nb.kv) ST_TRY(stt_kv(s, nb.owned, kv, c.dec_layers, rows, c.n_text_ctx));
-        ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dx)); ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dxn)); ST_TRY(stt_alloc(s, nb.owned, rp * 3 * D, &nb.dqkv));
-        ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dq)); ST_TRY(stt_alloc(s, nb.owned, rp * D, &nb.dao)); ST_TRY(stt_alloc(s, nb.owned, rp * c.ffn, &nb.dff));
-        ST_TRY(stt_alloc(s, nb.owned, r * c.vocab, &nb.logits));
-        ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_tok)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_slot)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_pos));
-        ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_win)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.enc_last));
+    return stt_reserve(s, s->beam, [&](SttBeam& nb) -> int {
+        const rt_stt_config& c = s->cfg;
+        const size_t r = (size_t)rows, rp = r * c.n_prefix;
+        ST_TRY(stt_alloc_dec(s, nb.owned, rows, nb.dec));
+        ST_TRY(stt_kv(s, nb.owned, nb.kv_next, c.dec_layers, rows, c.n_text_ctx));
+        ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_slot)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_pos)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_win));
         ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_slot)); ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_win)); ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_pos));
         nb.book_n = stt_beam_book_words(rows, c.max_new_tokens);
         ST_TRY(stt_alloc(s, nb.owned, nb.book_n, &nb.book_mem));
         nb.book = stt_beam_book(nb.book_mem, rows, c.max_new_tokens);
-        hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(256), 0, ctx->stream, nb.enc_last, (int)rp, c.n_ctx - 1, 0);
-        hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, nb.row_pos, rows, 0, 0);
-        RT_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, s->ctx->stream, nb.row_pos, rows, 0, 0);
+        RT_HIP(s->ctx, hipGetLastError());
+        nb.rows = rows;
         return RT_OK;
-    };
-    const int rc = build();
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void* p : nb.owned) (void)hipFree(p);
-        (void)hipGetLastError();
-        return rc;
-    }
-    nb.rows = rows;
-    s->beam = std::move(nb);
-    return RT_OK;
+    });
 }
 
 int stt_beam_reorder(rt_ctx* ctx, const KvCache& from, const KvCache& to, const int32_t* d_src, int rows, int len) {
@@ -982,9 +965,7 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
     SttBeam& bm = s->beam;
     const int P = c.n_prefix, rows = nW * B, R = bm.rows;
     const SttBeamBook& bk = bm.book;
-    SttBufs v;                                  // the decoder's view: the beam path's rows over the group's encoder side
-    v.cross_kv = s->grp.cross_kv; v.enc_last = bm.enc_last;
-    v.dx = bm.dx; v.dxn = bm.dxn; v.dqkv = bm.dqkv; v.dq = bm.dq; v.dao = bm.dao; v.dff = bm.dff; v.logits = bm.logits;
+    const KvCache& cross = s->grp.enc.cross_kv;
     RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.next_tok, R, c.eos_id, 0);
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.src, R, 0, 1);
@@ -992,14 +973,12 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.live, 1, nW, 0);
     hipLaunchKernelGGL(k_stt_fill_beam_rows, dim3(1), dim3(256), 0, ctx->stream, bm.pre_slot, bm.pre_pos, bm.pre_win, nW * P, P, B, bm.row_slot, bm.row_win, rows);
     RT_HIP(ctx, hipGetLastError());
-    RT_HIP(ctx, hipMemcpyAsync(bm.pre_tok, s->h_prefix.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
-    int cur = 0;
-    v.dec_kv = bm.kv[cur]; v.d_tok = bm.pre_tok;
-    ST_TRY(stt_decode_rows(s, v, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
+    bm.dec.tok = s->grp.d_prefix;                // (the forced prefix of every window: the group keeps it)
+    ST_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
     const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
     int steps = 0;
     for (int step = 0; step < budget; ++step) {
-        hipLaunchKernelGGL(k_stt_beam_select, dim3(nW), dim3(1024), 0, ctx->stream, bm.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0, c.eos_id, B,
+        hipLaunchKernelGGL(k_stt_beam_select, dim3(nW), dim3(1024), 0, ctx->stream, bm.dec.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0, c.eos_id, B,
                            step, bk);
         RT_HIP(ctx, hipGetLastError());
         steps = step + 1;
@@ -1007,10 +986,10 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
         RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (live <= 0 || step + 1 >= budget) break;
-        ST_TRY(stt_beam_reorder(ctx, bm.kv[cur], bm.kv[cur ^ 1], bk.src, rows, P + step));
-        cur ^= 1;
-        v.dec_kv = bm.kv[cur]; v.d_tok = bk.next_tok;
-        ST_TRY(stt_decode_rows(s, v, rows, 1, P + step, bm.row_slot, bm.row_pos, bm.row_win));
+        ST_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, P + step));
+        std::swap(bm.dec.kv, bm.kv_next);
+        bm.dec.tok = bk.next_tok;
+        ST_TRY(stt_decode_rows(s, bm.dec, cross, rows, 1, P + step, bm.row_slot, bm.row_pos, bm.row_win));
     }
     s->h_book.resize(bm.book_n);
     RT_HIP(ctx, hipMemcpyAsync(s->h_book.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1088,7 +1067,7 @@ int rt_stt_destroy(rt_stt* s) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& sl : s->slots) { if (sl.raw) (void)hipFree(sl.raw); if (sl.raw2) (void)hipFree(sl.raw2); }
-    for (auto* owned : {&s->owned, &s->one.owned, &s->grp.owned, &s->beam.owned})
+    for (auto* owned : {&s->owned, &s->grp.owned, &s->beam.owned})
         for (void* p : *owned) (void)hipFree(p);
     if (s->d_resamp) (void)hipFree(s->d_resamp);
     delete s;
@@ -1165,7 +1144,7 @@ int rt_stt_finalize(rt_stt* s) {
     RT_HIP(ctx, hipMemcpy(s->d_tws, ts.data(), c.n_fft * 8, hipMemcpyHostToDevice));
     s->d_window = SVEC(s, "fe.window");
     s->d_melT = SVEC(s, "fe.melT");
-    ST_TRY(stt_alloc_bufs(s, s->one, 1, 8));                         // decoder rows per pass: the forced prefix (at most 8), then one
+    ST_TRY(stt_group_reserve(s, 1));                                 // a model that does not fit fails here, and the first call pays no allocation
     // suppression mask: bit 0 = never (ids >= suppress_from except end-of-sequence), bit 1 = not as the first generated token
     std::vector<uint8_t> mask(c.vocab, 0);
     for (int i = 0; i < c.vocab; ++i)
@@ -1187,8 +1166,10 @@ int rt_stt_log_mel(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sam
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_log_mel: not finalized");
-    ST_TRY(stt_features(s, d_pcm, n_samples, sample_rate));
-    RT_HIP(ctx, hipMemcpyAsync(d_mel, s->one.mel, (size_t)2 * s->cfg.n_ctx * s->cfg.n_mels * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    const SttSpan clip{0, d_pcm, n_samples};                         // (uncut: the resampler's taps at the end of the chunk see the samples behind it)
+    ST_TRY(stt_group_reserve(s, 1));
+    ST_TRY(stt_features_group(s, &clip, 1, sample_rate));
+    RT_HIP(ctx, hipMemcpyAsync(d_mel, s->grp.enc.mel, (size_t)2 * s->cfg.n_ctx * s->cfg.n_mels * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -1199,9 +1180,11 @@ int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t samp
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_encode: not finalized");
-    ST_TRY(stt_features(s, d_pcm, n_samples, sample_rate));
-    ST_TRY(stt_encode(s, s->one, 1));
-    RT_HIP(ctx, hipMemcpyAsync(d_states, s->one.enc_out, (size_t)s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    const SttSpan clip{0, d_pcm, n_samples};                         // (uncut, as rt_stt_log_mel)
+    ST_TRY(stt_group_reserve(s, 1));
+    ST_TRY(stt_features_group(s, &clip, 1, sample_rate));
+    ST_TRY(stt_encode(s, s->grp.enc, 1));
+    RT_HIP(ctx, hipMemcpyAsync(d_states, s->grp.enc.out, (size_t)s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -1215,8 +1198,8 @@ int rt_stt_set_suppress(rt_stt* s, const int32_t* h_ids, int32_t n) {
     return RT_OK;
 }
 
-// Audio longer than one chunk is transcribed window by window (consecutive chunk_seconds windows of the INPUT, each through the
-// resampler, the log-mel front-end, the encoder and its own greedy decode behind the forced prefix) and the ids are concatenated:
+// Audio longer than one chunk is transcribed window by window (consecutive chunk_seconds windows of the INPUT, each a row of the
+// resampler, the log-mel front-end, the encoder and the greedy decode behind the forced prefix) and the ids are concatenated:
 // the whole clip is heard, as with the reference's transcribers (faster-whisper walks 30-s windows, stt_validator.py:133-141),
 // though not at their seek positions - those follow timestamp tokens, which the forced <|notimestamps|> prefix rules out.
 int rt_stt_transcribe(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate, int32_t* h_tokens, int32_t max_tokens, int32_t* h_n_tokens,
@@ -1227,40 +1210,10 @@ int rt_stt_transcribe(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t 
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe: not finalized");
-    const rt_stt_config& c = s->cfg;
-    SttBufs& w = s->one;
-    *h_n_tokens = 0;
-    const int64_t win = (int64_t)c.chunk_seconds * sample_rate;     // one window, in input samples
-    int n = 0;
-    for (int64_t off = 0; off == 0 || off < n_samples; off += win) {
-        if (n >= max_tokens) break;
-        const int64_t n_w = std::min<int64_t>(win, n_samples - off);
-        ST_TRY(stt_features(s, n_w > 0 ? d_pcm + off : d_pcm, n_w, sample_rate));
-        ST_TRY(stt_encode(s, w, 1));
-        // forced prefix in one pass, then one token per pass: the host reads each token (end-of-sequence decides when to stop)
-        RT_HIP(ctx, hipMemcpyAsync(w.d_tok, c.prefix, c.n_prefix * 4, hipMemcpyHostToDevice, ctx->stream));
-        ST_TRY(stt_decode_rows(s, w, 1, c.n_prefix, 0, w.dec_slot, w.dec_pos));
-        if (d_first_logits && off == 0) RT_HIP(ctx, hipMemcpyAsync(d_first_logits, w.logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        const int budget = std::min(std::min(max_tokens - n, c.max_new_tokens), c.n_text_ctx - c.n_prefix);
-        for (int step = 0; step < budget; ++step) {
-            hipLaunchKernelGGL(k_stt_argmax, dim3(1), dim3(1024), 0, ctx->stream, w.logits, c.vocab, s->d_mask, step == 0 ? 1 : 0, w.d_tok);
-            RT_HIP(ctx, hipGetLastError());
-            int32_t tok = 0;
-            RT_HIP(ctx, hipMemcpyAsync(&tok, w.d_tok, 4, hipMemcpyDeviceToHost, ctx->stream));
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (tok == c.eos_id) break;
-            h_tokens[n++] = tok;
-            if (step + 1 < budget) ST_TRY(stt_decode_rows(s, w, 1, 1, c.n_prefix + step, w.step_slot, w.step_pos));
-        }
-    }
-    *h_n_tokens = n;
-    return RT_OK;
+    return stt_transcribe_greedy(s, &d_pcm, &n_samples, 1, sample_rate, h_tokens, max_tokens, h_n_tokens, d_first_logits);
 }
 
-// The windows of all clips are the rows of the batch: every clip is cut as rt_stt_transcribe cuts it, up to STT_GROUP windows go
-// through the front end, the encoder and the greedy decode together, and a clip's ids are its windows' ids joined and cut at the
-// cap.  A window is decoded with the full budget; greedy decoding makes the cut join what the serial loop gives.  A window is
-// left out only when the groups before it already filled its clip's cap.
+// The windows of all clips are the rows of the batch (stt_transcribe_greedy): per clip what rt_stt_transcribe gives for it alone
 int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, int32_t* h_tokens,
                             int32_t max_tokens_per_clip, int32_t* h_n_tokens) {
     if (!s || max_tokens_per_clip < 1 || sample_rate < 1000 || stt_check_clips(d_pcm, n_samples, n_clips) || (n_clips > 0 && (!h_tokens || !h_n_tokens)))
@@ -1270,33 +1223,7 @@ int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const int64_t*
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe_batch: not finalized");
-    const rt_stt_config& c = s->cfg;
-    const int64_t win = (int64_t)c.chunk_seconds * sample_rate;     // one window, in input samples
-    std::vector<SttSpan> all;
-    for (int i = 0; i < n_clips; ++i) {
-        h_n_tokens[i] = 0;
-        for (int64_t off = 0; off == 0 || off < n_samples[i]; off += win)
-            all.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off : nullptr, std::min<int64_t>(win, n_samples[i] - off)});
-    }
-    ST_TRY(stt_group_reserve(s, (int)std::min<size_t>(all.size(), STT_GROUP)));
-    std::vector<SttSpan> group;
-    std::vector<std::vector<int32_t>> ids;
-    for (size_t next = 0; next < all.size();) {
-        group.clear();
-        for (; next < all.size() && (int)group.size() < STT_GROUP; ++next)
-            if (h_n_tokens[all[next].clip] < max_tokens_per_clip) group.push_back(all[next]);
-        if (group.empty()) break;
-        const int B = (int)group.size();
-        ST_TRY(stt_features_group(s, group.data(), B, sample_rate));
-        ST_TRY(stt_encode(s, s->grp, B));
-        ST_TRY(stt_decode_group(s, B, ids));
-        for (int b = 0; b < B; ++b) {
-            const int i = group[b].clip;
-            for (int32_t t : ids[b])
-                if (h_n_tokens[i] < max_tokens_per_clip) h_tokens[(size_t)i * max_tokens_per_clip + h_n_tokens[i]++] = t;
-        }
-    }
-    return RT_OK;
+    return stt_transcribe_greedy(s, d_pcm, n_samples, n_clips, sample_rate, h_tokens, max_tokens_per_clip, h_n_tokens, nullptr);
 }
 
 // As rt_stt_transcribe_batch, decoded by beam search: floor(STT_GROUP / beam_size) windows make a group, whose decoder rows are
@@ -1311,14 +1238,9 @@ int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* 
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe_beam: not finalized");
-    const rt_stt_config& c = s->cfg;
-    const int64_t win = (int64_t)c.chunk_seconds * sample_rate;     // one window, in input samples
     std::vector<SttSpan> all;
-    for (int i = 0; i < n_clips; ++i) {
-        h_n_tokens[i] = 0;
-        for (int64_t off = 0; off == 0 || off < n_samples[i]; off += win)
-            all.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off : nullptr, std::min<int64_t>(win, n_samples[i] - off)});
-    }
+    stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, all);
+    std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
     const size_t per_group = (size_t)(STT_GROUP / beam_size);
     const int most = (int)std::min(all.size(), per_group);
     ST_TRY(stt_group_reserve(s, most));
@@ -1329,7 +1251,7 @@ int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* 
     for (size_t next = 0; next < all.size(); next += per_group) {
         const int nW = (int)std::min(per_group, all.size() - next);
         ST_TRY(stt_features_group(s, all.data() + next, nW, sample_rate));
-        ST_TRY(stt_encode(s, s->grp, nW));
+        ST_TRY(stt_encode(s, s->grp.enc, nW));
         ST_TRY(stt_decode_beam_group(s, nW, beam_size, hyps));
         for (int b = 0; b < nW; ++b) {
             const int i = all[next + b].clip;
@@ -1433,13 +1355,12 @@ int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_encode_batch: not finalized");
-    const int64_t win = (int64_t)s->cfg.chunk_seconds * sample_rate;
     std::vector<SttSpan> group;
-    for (int i = 0; i < n_clips; ++i) group.push_back({i, d_pcm[i], std::min<int64_t>(win, n_samples[i])});
+    stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, group, true);
     ST_TRY(stt_group_reserve(s, n_clips));
     ST_TRY(stt_features_group(s, group.data(), n_clips, sample_rate));
-    ST_TRY(stt_encode(s, s->grp, n_clips));
-    RT_HIP(ctx, hipMemcpyAsync(d_states, s->grp.enc_out, (size_t)n_clips * s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    ST_TRY(stt_encode(s, s->grp.enc, n_clips));
+    RT_HIP(ctx, hipMemcpyAsync(d_states, s->grp.enc.out, (size_t)n_clips * s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }

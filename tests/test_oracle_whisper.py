@@ -21,6 +21,27 @@ def clip(seconds, sr, seed):
     return (x + 0.01 * g.standard_normal(t.shape[0])).astype(np.float32)
 
 
+def boundary_clip(cfg, sr=24000):
+    """1.5 chunks at `sr`, silent for 25 ms before the chunk boundary and large in the ten samples just behind it: the resampler's
+    taps for the chunk's last output samples reach those, so a front end that cut the clip to one chunk BEFORE resampling would hear
+    silence where this one hears the filter's ringing."""
+    x = clip(1.5 * cfg.chunk_seconds, sr, 9).copy()
+    edge = cfg.chunk_seconds * sr
+    x[edge - sr // 40: edge] = 0.0
+    x[edge: edge + 10] = 0.9
+    return x
+
+
+def test_boundary_clip_tells_a_cut_before_the_resampler_from_a_cut_behind_it():
+    """What tests/test_stt_batch_gpu.py::test_long_clip_at_a_non_native_rate relies on: the log-mel of the clip resampled whole and cut
+    to the chunk differs from that of the clip cut to the chunk and then resampled by far more than the GPU test's bound of 1e-4."""
+    cfg = S.tiny_test_config()
+    sr, x = 24000, boundary_clip(cfg)
+    whole = OW.log_mel(cfg, OW.resample(x, sr, cfg.sample_rate))
+    cut = OW.log_mel(cfg, OW.resample(x[: cfg.chunk_seconds * sr], sr, cfg.sample_rate))
+    assert float((whole - cut).abs().max()) > 100 * 1e-4
+
+
 def test_mel_filters_and_window_equal_the_feature_extractors():
     from transformers.audio_utils import mel_filter_bank, window_function
     for n_fft, n_mels in ((400, 80), (400, 16), (512, 128)):

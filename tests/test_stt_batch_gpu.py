@@ -1,8 +1,10 @@
 """Batched on-GPU speech-to-text (rt_stt_transcribe_batch): the windows of all clips of a call are the rows of every launch, and a
 clip's ids in a batch are the ids it gets alone - against transformers' Whisper (oracle/whisper.py) on the clips tests/test_stt_gpu.py
 already holds the single-clip call to, against the single-clip call itself, and, below the ids, bit for bit on the encoder
-states; then the provider's validation loop taking one transcription call per chunk."""
+states; then the provider's validation loop taking one transcription call per chunk.  The single-clip calls are the same path with
+one row: "alone" is the clip as the only row, on buffers a larger call may have grown and written before."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -11,7 +13,7 @@ import torch
 from oracle import whisper as OW
 from rho_tts_amd import _native
 from rho_tts_amd import stt as S
-from tests.test_oracle_whisper import clip
+from tests.test_oracle_whisper import boundary_clip, clip
 
 pytestmark = pytest.mark.gpu
 
@@ -127,6 +129,55 @@ def test_encoder_states_in_a_batch_are_the_bits_of_the_single_call(tiny):
     assert any(len(x) > win for x in clips)
     for i, x in enumerate(clips):
         assert torch.equal(out[i], nat.encode(x[:win], SR)), i   # (a clip longer than a window: its first window, cut as the transcription cuts it)
+
+
+def single_stages(nat, x):
+    ids, first = nat.transcribe_ids(x, SR, first_logits=True)
+    return ids, first, nat.log_mel(x, SR), nat.encode(x, SR)
+
+
+def test_a_grown_group_gives_a_single_clip_the_bits_of_a_fresh_handle(ctx, tiny):
+    """One row over buffers sized and written by ten rows (seven ragged clips, two of them longer than a window): ids, the logits
+    behind the prefix, log-mel and encoder states of a short clip equal those from a handle that has only ever seen that clip."""
+    cfg, state, nat = tiny
+    x = clip(0.9, SR, 4)
+    fresh = S.NativeSTT(ctx, cfg, {k: v.cuda() for k, v in state.items()})
+    try:
+        want = single_stages(fresh, x)
+    finally:
+        fresh.close()
+    clips = ragged_clips()
+    assert len(clips) >= 3 and sum(nat.windows(len(c), SR) for c in clips) == 10 and any(nat.windows(len(c), SR) > 1 for c in clips)
+    assert all(nat.transcribe_ids_batch(clips, SR))
+    got = single_stages(nat, x)
+    assert got[0] == want[0] and len(want[0]) > 0
+    for name, g, w in zip(("first logits", "log-mel", "encoder states"), got[1:], want[1:]):
+        assert torch.equal(g, w), name
+
+
+def test_long_clip_at_a_non_native_rate(tiny):
+    """log_mel / encode of a 3-s clip at 24 kHz on 2-s chunks keep the first chunk of the clip RESAMPLED WHOLE: the taps at the
+    chunk's end see the samples behind it (tests/test_oracle_whisper.py shows that boundary_clip tells the two cuts apart by 0.37
+    against the bound of 1e-4 that tests/test_stt_gpu.py holds the log-mel to).  Bit for bit the values the single-clip kernels
+    gave before they were folded into the batched path (tests/golden/stt_boundary_clip.npz, recorded on an MI355X from the last
+    build that had them)."""
+    cfg, _, nat = tiny
+    x = boundary_clip(cfg, SR)
+    assert len(x) > cfg.chunk_seconds * SR
+    mel, states = nat.log_mel(x, SR).cpu(), nat.encode(x, SR).cpu()
+    err = float((mel - OW.log_mel(cfg, OW.resample(x, SR, cfg.sample_rate))).abs().max())
+    print("log-mel against the oracle", err)
+    assert err < 1e-4
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stt_boundary_clip.npz"))
+    assert np.array_equal(mel.numpy(), g["log_mel"]) and np.array_equal(states.numpy(), g["states"])
+
+
+def test_an_empty_clip_is_one_window_of_silence(tiny):
+    cfg, state, nat = tiny
+    empty = np.zeros(0, dtype=np.float32)
+    ids = nat.transcribe_ids(empty, SR)
+    assert ids == nat.transcribe_ids_batch([empty], SR)[0] == nat.transcribe_ids(np.zeros(cfg.chunk_seconds * SR, dtype=np.float32), SR)
+    assert ids == OW.transcribe_windows(OW.build(cfg, state), cfg, empty, SR) and len(ids) > 0
 
 
 def test_arguments(ctx):
