@@ -401,7 +401,11 @@ RT_API int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32
  *     viterbi_banded of rho_tts_amd/features.py, and run as HIP kernels with that definition in rt_features_extract_batch.
  *   h_lpc [lpc_order + 1] float64: Burg LPC of the pre-emphasised (0.97), symmetric-Hann-windowed 25-ms frame about the middle
  *     sample; the formants are the angles of its roots.
- * Frames: 1 + n16 / 512 for both (n16 = samples at 16 kHz).  Parity with librosa is UNPINNED (not installable offline). */
+ * Frames: 1 + n16 / 512 for both (n16 = samples at 16 kHz).  Parity with librosa is UNPINNED (not installable offline).
+ * rt_features_extract and rt_features_extract_batch are one path (one launch per stage for the clips of the call, one workspace
+ * set per handle): the first is it with one clip and without pYIN's back half, so it needs no pitch model; it skips the
+ * difference function when h_cmnd is NULL.  RT_ERR_INVALID: fewer than two samples, before or after resampling;
+ * RT_ERR_LENGTH: cmnd_cap_frames below the clip's frame count. */
 typedef struct rt_features rt_features;
 RT_API int rt_features_create(rt_ctx* ctx, rt_features** out);
 RT_API int rt_features_destroy(rt_features* f);
@@ -426,10 +430,12 @@ RT_API int rt_features_set_pitch_model(rt_features* f, int32_t n_bins, int32_t h
                                        double pitch_sr, double fmin, int32_t bins_per_semitone, double no_trough_prob);
 /* The whole feature extraction of n_clips waveforms in HBM (d_pcm[c]: n_samples[c] floats at sample_rate_in) in one call, with one
  * stream synchronisation and one set of device-to-host copies whatever n_clips is:
- *   h_mfcc_stats26 [n_clips][26], h_lpc [n_clips][lpc_order + 1]: per clip the bits rt_features_extract gives for it alone;
+ *   h_mfcc_stats26 [n_clips][26], h_lpc [n_clips][lpc_order + 1]: per clip the bits rt_features_extract gives for it alone (the
+ *     same path: no launch mixes clips, and a clip's workgroups do what they do when it is the only clip);
  *   h_states [n_clips][cap_frames] int32: the Viterbi state path of every clip (voiced pitch bin b = state b, unvoiced = n_bins + b;
  *     -1 behind the clip's last frame); h_n_pitch_frames [n_clips] = 1 + n16 / 512.
- * RT_ERR_INVALID: a clip below two samples, cap_frames below a clip's frame count, no pitch model set. */
+ * Every clip is checked on the host before anything is launched.  RT_ERR_INVALID: a clip below two samples, cap_frames below a
+ * clip's frame count, no pitch model set, more than 2^20 frames or 65535 clips in one call. */
 RT_API int rt_features_extract_batch(rt_features* f, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips,
                                      int32_t sample_rate_in, int32_t min_period, int32_t max_period, int32_t lpc_order,
                                      double* h_mfcc_stats26, double* h_lpc, int32_t* h_states, int32_t cap_frames, int32_t* h_n_pitch_frames);

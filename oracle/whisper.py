@@ -13,7 +13,7 @@ Parity status:
     (forced language / task ids, suppressed ids) comes with the download.  No checkpoint is available offline, so the decoding
     rule is restated here: forced prefix, argmax over the ids the suppression rule allows, stop at end-of-sequence.
   * resampler (TTS rate -> 16 kHz): PARITY UNPINNED - the reference's pipeline decodes its temporary WAV through ffmpeg, absent
-    here.  ``resample`` restates the windowed-sinc definition of csrc/stt.hip (stt_resampler) in float64.
+    here.  ``resample`` restates the windowed-sinc definition of csrc/resample.h (resampler_design) in float64.
   * trained weights: none offline; seeded synthetic weights only (the architecture is checked, not the transcription quality).
 """
 from __future__ import annotations
@@ -27,7 +27,7 @@ import torch
 
 def resample(x: np.ndarray, sr_in: int, sr_out: int, width: float = 6.0, rolloff: float = 0.99) -> np.ndarray:
     """Windowed-sinc resampling, float64: y[n] = sum_t x[t] g(t - n sr_in / sr_out), g = low-pass at rolloff x the lower Nyquist
-    under a Hann window spanning `width` zero crossings (csrc/stt.hip stt_resampler / k_resample_group, same taps)."""
+    under a Hann window spanning `width` zero crossings (csrc/resample.h resampler_design / resample_at, same taps)."""
     if sr_in == sr_out:
         return np.asarray(x, dtype=np.float32)
     x = np.asarray(x, dtype=np.float64).reshape(-1)

@@ -69,6 +69,12 @@ inline int rt_hip_status(hipError_t e) {
         }                                                                                          \
     } while (0)
 
+#define RT_TRY(expr)            \
+    do {                        \
+        int _rc = (expr);       \
+        if (_rc) return _rc;    \
+    } while (0)
+
 int rt_ctx_scratch(rt_ctx* ctx, size_t bytes, void** out);  // grows ctx->d_scratch
 int rt_ctx_pinned(rt_ctx* ctx, size_t bytes, void** out);   // grows ctx->h_pinned
 
@@ -153,6 +159,9 @@ __device__ __forceinline__ float wave_max_f32(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// float <-> int with the floats' order (for an integer atomicMax over floats; 0x80000000 lies below every ordered float)
+__device__ __forceinline__ int f32_ordered(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
+__device__ __forceinline__ float ordered_f32(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
 // Fragment-tiled activation layout shared by the decode kernels: a [rows][K] matrix is stored as
 // [row block of 16][k tile of 32][lane = (k octet << 4) | row][8 elements], i.e. exactly the A-operand order of

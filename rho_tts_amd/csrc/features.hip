@@ -3,7 +3,7 @@
 // reference computes with librosa on a temporary WAV - 13 MFCCs per frame, the pYIN difference function, a Burg LPC of the
 // mid-file frame - is computed where the generated segment is, and only a few kilobytes leave the GPU:
 //
-//   PCM at the TTS rate -> windowed-sinc resampler (16 kHz; the resampler of the speech-to-text front-end)
+//   PCM at the TTS rate -> windowed-sinc resampler (16 kHz; resample.h, the resampler of the speech-to-text front-end)
 //     -> MFCC: frames of 2048 (hop 512, zero-padded centre), periodic Hann, 2048-point DFT in float64, power spectrum,
 //        128 slaney mel filters, 10 log10 (floor 1e-10), max - 80 dB floor, DCT-II (orthonormal) rows 0..12 -> mean and
 //        standard deviation of every coefficient over the frames (26 numbers)
@@ -16,6 +16,13 @@
 //     -> LPC: pre-emphasis 0.97 in float32, 400-sample symmetric-Hann frame about the middle sample, Burg's recursion in
 //        float64 -> order + 1 coefficients (their roots - an 18 x 18 eigenproblem - are taken on the host)
 //
+// There is one path (feat_run).  rt_features_extract is it with one clip and no back half, rt_features_extract_batch with a whole
+// validation chunk: a small device table (FeatClip, one entry per clip) tells every kernel where a clip's samples and frames are, and
+// each stage is ONE launch for the call - blockIdx.y (blockIdx.x for the per-clip kernels k_feat_stats and k_feat_lpc) is the clip,
+// the grid is sized by the longest clip and the rows past a clip's own count return at once.  No launch mixes clips and every
+// workgroup does for its clip what it does when the clip is alone, so a clip's bits do not depend on its neighbours or on the entry
+// point (tests/test_features_bits_gpu.py holds both to recorded bits).  The handle holds one workspace set, grown on demand.
+//
 // Nothing here is on the hot path of generation (one call per validated segment, ~0.3 ms of GPU time for 3.5 s of audio), so
 // the kernels are the simple forms: direct DFT and direct difference sums in float64, one workgroup per frame.
 // PARITY UNPINNED (librosa absent): the definitions are those of oracle/features.py, which restates librosa 0.10's defaults.
@@ -25,6 +32,18 @@
 #include <vector>
 
 #include "kernels.h"
+#include "resample.h"
+
+// One clip of a call, as the kernels see it (a small device table, one entry per clip; rt_debug_features_viterbi fills it with null audio)
+struct FeatClip {
+    const float* pcm_in;    // the clip's samples at the input rate
+    const float* pcm16;     // ... at 16 kHz: its stretch of the resampler's output, or pcm_in itself when the rates agree
+    int64_t n_in, n16;
+    int32_t first, frames;  // first frame of the clip in the frame-major workspaces of the call, and its frame count
+};
+
+template <class T>
+struct FeatBuf { T* p = nullptr; size_t cap = 0; };
 
 struct rt_features {
     rt_ctx* ctx = nullptr;
@@ -32,33 +51,20 @@ struct rt_features {
     double *d_twc = nullptr, *d_tws = nullptr;     // cos / sin(2 pi n / 2048)
     float* d_melT = nullptr;                       // [1025][128]
     double* d_dct = nullptr;                       // [13][128]
-    float* d_resamp = nullptr;
-    int rs_in = 0, rs_L = 0, rs_M = 0, rs_taps = 0, rs_half = 0;
-    // workspaces (grown on demand)
-    float* pcm16k = nullptr;
-    size_t pcm_cap = 0;
-    float* logmel = nullptr;                       // [frames][128]
-    double* mfcc = nullptr;                        // [frames][13]
-    double* cmnd = nullptr;                        // [frames][lags]
-    size_t frame_cap = 0;
-    int* d_gmax = nullptr;
-    double *d_stats = nullptr, *d_lpc = nullptr;   // [26], [order + 1]
+    Resampler rs;                                  // (sample_rate_in -> 16 kHz) of the last call that needed one
     // pYIN's back half (rt_features_set_pitch_model): every table comes from the host, so the device compares and adds the host's bits
     bool pm_set = false;
     int pm_bins = 0, pm_hw = 0, pm_thr = 0;
     double *pm_d_thr = nullptr, *pm_d_beta = nullptr;          // [n_thresholds] each
     double *pm_d_trans = nullptr, *pm_d_init = nullptr;        // [2][2 hw + 1][n_bins] (stay, switch), [2 n_bins]
     double pm_log_tiny = 0.0, pm_sr = 0.0, pm_fmin = 0.0, pm_bins_per_octave = 0.0, pm_no_trough = 0.0;
-    // workspaces of the batched path (rt_features_extract_batch and the two stage hooks), sized by the batch, grown on demand
-    float* b_pcm = nullptr;                        // every clip at 16 kHz, back to back
-    float* b_logmel = nullptr;                     // [frames of the batch][128]
-    double *b_mfcc = nullptr, *b_cmnd = nullptr, *b_logobs = nullptr;    // [frames][13], [frames][lags], [frames][2 n_bins]
-    int *b_ptr = nullptr, *b_states = nullptr;     // Viterbi backpointers [frames][2 n_bins], state paths [clips][stride]
-    double *b_stats = nullptr, *b_lpc = nullptr;   // [clips][26], [clips][order + 1]
-    int *b_gmax = nullptr, *b_meta = nullptr;      // [clips], first frame | frame count per clip [2][clips]
-    size_t b_pcm_cap = 0, b_logmel_cap = 0, b_mfcc_cap = 0, b_cmnd_cap = 0, b_logobs_cap = 0, b_ptr_cap = 0, b_states_cap = 0, b_stats_cap = 0,
-           b_lpc_cap = 0, b_gmax_cap = 0, b_meta_cap = 0;
-    std::vector<int> h_meta;
+    // the one workspace set (every entry point), sized by the call, grown on demand (feat_grow); "frames" = those of all clips of the call
+    FeatBuf<float> pcm, logmel;                    // every clip at 16 kHz, back to back; [frames][128]
+    FeatBuf<double> mfcc, cmnd, logobs;            // [frames][13], [frames][lags], [frames][2 n_bins]
+    FeatBuf<int> ptr, states, gmax;                // Viterbi backpointers [frames][2 n_bins], state paths [clips][stride], [clips]
+    FeatBuf<double> stats, lpc;                    // [clips][26], [clips][order + 1]
+    FeatBuf<FeatClip> clips;                       // the clip table of the call, and its host copy
+    std::vector<FeatClip> h_clips;
 };
 
 namespace {
@@ -67,35 +73,29 @@ constexpr int F_SR = 16000, F_NFFT = 2048, F_HOP = 512, F_BINS = F_NFFT / 2 + 1,
 constexpr int P_FRAME = 2048, P_WIN = 1024, P_HOP = 512;
 constexpr int LPC_MAX = 32, LPC_FRAME = 400;
 
-#define FT_TRY(expr)            \
-    do {                        \
-        int _rc = (expr);       \
-        if (_rc) return _rc;    \
-    } while (0)
+// Every front-half kernel begins with its clip's entry of the table: blockIdx.y (blockIdx.x in the two per-clip kernels) is the clip,
+// and a frame past the clip's own count returns at once, uniformly over the workgroup.  Behind that each body is what it is for a
+// clip alone: the same loads and sums in the same order.
 
-__device__ __forceinline__ int ft_ordered(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float ft_unordered(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-// y[n] = sum_j x[base(n) + j - half] h[phase(n)][j] (csrc/stt.hip k_resample_group: the same polyphase filter, float64 accumulation)
-__global__ void k_feat_resample(const float* __restrict__ x, int64_t n_in, float* __restrict__ y, int64_t n_out, int L, int M, int taps, int half,
-                                const float* __restrict__ h) {
-    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < n_out; n += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t num = n * M, base = num / L;
-        const float* hp = h + (num % L) * taps;
-        double acc = 0.0;
-        for (int j = 0; j < taps; ++j) {
-            const int64_t t = base + j - half;
-            if (t >= 0 && t < n_in) acc += (double)x[t] * (double)hp[j];
-        }
-        y[n] = (float)acc;
-    }
+// The resampler (resample.h) over the clips of a call; with a resampler every pcm16 lies in the handle's own buffer, and this is its writer
+__global__ void k_feat_resample(const FeatClip* __restrict__ clips, int L, int M, int taps, int half, const float* __restrict__ h) {
+    const FeatClip c = clips[blockIdx.y];
+    float* y = const_cast<float*>(c.pcm16);
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < c.n16; n += (int64_t)gridDim.x * blockDim.x)
+        y[n] = resample_at(c.pcm_in, c.n_in, n, L, M, taps, half, h);
 }
 
 // One MFCC frame per workgroup: frame f covers samples [f hop - 1024, f hop + 1024) of the signal (zeros outside), times the periodic
-// Hann window; bin k on thread k (+ 256 i): direct DFT with the twiddle index k n mod 2048; mel filters; 10 log10.
-__global__ __launch_bounds__(256) void k_feat_logmel(const float* __restrict__ pcm, int64_t n, const double* __restrict__ twc, const double* __restrict__ tws,
+// Hann window; bin k on thread k (+ 256 i): direct DFT with the twiddle index k n mod 2048; mel filters; 10 log10.  gmax is [clips].
+__global__ __launch_bounds__(256) void k_feat_logmel(const FeatClip* __restrict__ clips, const double* __restrict__ twc, const double* __restrict__ tws,
                                                      const float* __restrict__ melT, float* __restrict__ logmel, int* __restrict__ gmax) {
     extern __shared__ double fsh[];               // xw[2048] | c[2048] | s[2048] | power[1025]
+    const FeatClip clip = clips[blockIdx.y];
+    if ((int)blockIdx.x >= clip.frames) return;
+    const float* __restrict__ pcm = clip.pcm16;
+    const int64_t n = clip.n16;
+    logmel += (int64_t)clip.first * F_MELS;
+    gmax += blockIdx.y;
     double* xw = fsh;
     double* tc = fsh + F_NFFT;
     double* ts = tc + F_NFFT;
@@ -130,23 +130,31 @@ __global__ __launch_bounds__(256) void k_feat_logmel(const float* __restrict__ p
         best = fmaxf(best, v);
     }
     best = wave_max_f32(best);
-    if ((tid & 63) == 0 && best > -INFINITY) atomicMax(gmax, ft_ordered(best));
+    if ((tid & 63) == 0 && best > -INFINITY) atomicMax(gmax, f32_ordered(best));
 }
 
 // mfcc[f][c] = sum_m dct[c][m] max(logmel[f][m], gmax - 80): one frame per workgroup of 64 threads (13 of them busy: tiny)
-__global__ __launch_bounds__(64) void k_feat_dct(const float* __restrict__ logmel, const int* __restrict__ gmax, const double* __restrict__ dct,
-                                                 double* __restrict__ mfcc) {
+__global__ __launch_bounds__(64) void k_feat_dct(const FeatClip* __restrict__ clips, const float* __restrict__ logmel, const int* __restrict__ gmax,
+                                                 const double* __restrict__ dct, double* __restrict__ mfcc) {
+    const FeatClip clip = clips[blockIdx.y];
+    if ((int)blockIdx.x >= clip.frames) return;
+    logmel += (int64_t)clip.first * F_MELS;
+    mfcc += (int64_t)clip.first * F_MFCC;
+    gmax += blockIdx.y;
     const int f = blockIdx.x, c = threadIdx.x;
     if (c >= F_MFCC) return;
-    const float floor_db = ft_unordered(*gmax) - 80.0f;
+    const float floor_db = ordered_f32(*gmax) - 80.0f;
     double acc = 0.0;
     for (int m = 0; m < F_MELS; ++m) acc += dct[c * F_MELS + m] * (double)fmaxf(logmel[(int64_t)f * F_MELS + m], floor_db);
     mfcc[(int64_t)f * F_MFCC + c] = acc;
 }
 
-// stats[c] = mean over the frames, stats[13 + c] = population standard deviation (np.std, ddof 0); one wave per coefficient
-__global__ __launch_bounds__(64) void k_feat_stats(const double* __restrict__ mfcc, int n_frames, double* __restrict__ stats) {
-    const int c = blockIdx.x, lane = threadIdx.x;
+// stats[c] = mean over the frames, stats[13 + c] = population standard deviation (np.std, ddof 0); one wave per (clip, coefficient)
+__global__ __launch_bounds__(64) void k_feat_stats(const FeatClip* __restrict__ clips, const double* __restrict__ mfcc, double* __restrict__ stats) {
+    const int n_frames = clips[blockIdx.x].frames;
+    mfcc += (int64_t)clips[blockIdx.x].first * F_MFCC;
+    stats += (int64_t)blockIdx.x * 2 * F_MFCC;
+    const int c = blockIdx.y, lane = threadIdx.x;
     double s = 0.0;
     for (int f = lane; f < n_frames; f += 64) s += mfcc[(int64_t)f * F_MFCC + c];
     const double mean = wave_sum_f64(s) / (double)n_frames;
@@ -158,9 +166,14 @@ __global__ __launch_bounds__(64) void k_feat_stats(const double* __restrict__ mf
 
 // One pitch frame per workgroup: x = samples [f hop - 1024, f hop + 1024) (zeros outside); d(tau) = sum_{j=1..1024} (x[j] - x[j+tau])^2
 // for tau = 1 .. max_p (thread tau), prefix mean of d over 1 .. tau, out[f][tau - min_p] = d(tau) / (mean + tiny).
-__global__ __launch_bounds__(512) void k_feat_cmnd(const float* __restrict__ pcm, int64_t n, int min_p, int max_p, double* __restrict__ out) {
+__global__ __launch_bounds__(512) void k_feat_cmnd(const FeatClip* __restrict__ clips, int min_p, int max_p, double* __restrict__ out) {
     __shared__ double x[P_FRAME];
     __shared__ double d[1024 + 1];
+    const FeatClip clip = clips[blockIdx.y];
+    if ((int)blockIdx.x >= clip.frames) return;
+    const float* __restrict__ pcm = clip.pcm16;
+    const int64_t n = clip.n16;
+    out += (int64_t)clip.first * (max_p - min_p + 1);
     const int f = blockIdx.x, tid = threadIdx.x;
     const int64_t start = (int64_t)f * P_HOP - P_FRAME / 2;
     for (int i = tid; i < P_FRAME; i += 512) {
@@ -184,8 +197,11 @@ __global__ __launch_bounds__(512) void k_feat_cmnd(const float* __restrict__ pcm
 }
 
 // Burg's recursion (Marple) on the pre-emphasised, symmetric-Hann-windowed 25-ms frame about the middle sample; one wave.
-__global__ __launch_bounds__(64) void k_feat_lpc(const float* __restrict__ pcm, int64_t n, int order, double* __restrict__ a_out) {
+__global__ __launch_bounds__(64) void k_feat_lpc(const FeatClip* __restrict__ clips, int order, double* __restrict__ a_out) {
     __shared__ double fwd[LPC_FRAME], bwd[LPC_FRAME], a[LPC_MAX + 1], prev[LPC_MAX + 1];
+    const float* __restrict__ pcm = clips[blockIdx.x].pcm16;
+    const int64_t n = clips[blockIdx.x].n16;
+    a_out += (int64_t)blockIdx.x * (order + 1);
     const int lane = threadIdx.x;
     const int64_t c = n / 2;
     const int64_t lo = c - LPC_FRAME / 2 > 0 ? c - LPC_FRAME / 2 : 0, hi = c + LPC_FRAME / 2 < n ? c + LPC_FRAME / 2 : n;
@@ -370,18 +386,17 @@ __device__ __forceinline__ void vit_take(double& v, int& s, double ov, int os) {
 // it beats every candidate inside.  (max, arg-max) of a frame's values are reduced while the values are produced and read by the next
 // frame.  Only float64 adds and compares in the host's association: (val[from] + lt), then log_obs + best.
 // Dynamic LDS: val[2][S] | wmax[2][16] (doubles) | warg[2][16] (ints).
-__global__ __launch_bounds__(1024) void k_feat_viterbi(const double* __restrict__ log_obs, const int* __restrict__ first_frame,
-                                                       const int* __restrict__ n_frames, int n_bins, int hw, const double* __restrict__ trans,
-                                                       const double* __restrict__ log_init, double log_tiny, int* __restrict__ ptr,
-                                                       int* __restrict__ states, int states_stride) {
+__global__ __launch_bounds__(1024) void k_feat_viterbi(const double* __restrict__ log_obs, const FeatClip* __restrict__ clips, int n_bins, int hw,
+                                                       const double* __restrict__ trans, const double* __restrict__ log_init, double log_tiny,
+                                                       int* __restrict__ ptr, int* __restrict__ states, int states_stride) {
     extern __shared__ double vsh[];
     const int S = 2 * n_bins, W = 2 * hw + 1;
     double* val = vsh;
     double* wmax = val + 2 * S;
     int* warg = (int*)(wmax + 32);
     const int clip = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
-    const int T = n_frames[clip];
-    const int64_t f0 = first_frame[clip];
+    const int T = clips[clip].frames;
+    const int64_t f0 = clips[clip].first;
     for (int t = 0; t < T; ++t) {
         double* cur = val + (t & 1) * S;
         const double* prev = val + ((t & 1) ^ 1) * S;
@@ -438,13 +453,13 @@ __global__ __launch_bounds__(1024) void k_feat_viterbi(const double* __restrict_
 }
 
 template <class T>
-int feat_grow(rt_ctx* ctx, T*& p, size_t& cap, size_t need) {
-    if (need <= cap && p) return RT_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
+int feat_grow(rt_ctx* ctx, FeatBuf<T>& b, size_t need) {
+    if (need <= b.cap && b.p) return RT_OK;
+    if (b.p) (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
     if (need == 0) need = 1;
-    RT_HIP(ctx, hipMalloc((void**)&p, need * sizeof(T)));
-    cap = need;
+    RT_HIP(ctx, hipMalloc((void**)&b.p, need * sizeof(T)));
+    b.cap = need;
     return RT_OK;
 }
 
@@ -458,14 +473,14 @@ int feat_observe(rt_features* s, const double* d_cmnd, int n_frames, int n_lags,
     return RT_OK;
 }
 
-// state paths [n_clips][stride] (-1 behind a clip's last frame) of the log-obs of n_clips clips laid back to back; d_meta = first frame of
-// every clip, then its frame count
-int feat_viterbi(rt_features* s, const double* d_logobs, const int* d_meta, int n_clips, int* d_ptr, int* d_states, int stride) {
+// state paths [n_clips][stride] (-1 behind a clip's last frame) of the log-obs of n_clips clips laid back to back; the clip table
+// gives every clip's first frame and frame count
+int feat_viterbi(rt_features* s, const double* d_logobs, const FeatClip* d_clips, int n_clips, int* d_ptr, int* d_states, int stride) {
     const int S = 2 * s->pm_bins, rounds = (S + 1023) / 1024;
     const int threads = std::min(1024, (((S + rounds - 1) / rounds) + 63) / 64 * 64);
     const size_t lds = (size_t)(2 * S + 32) * 8 + 32 * 4;
-    hipLaunchKernelGGL(k_feat_viterbi, dim3(n_clips), dim3(threads), lds, s->ctx->stream, d_logobs, d_meta, d_meta + n_clips, s->pm_bins, s->pm_hw,
-                       s->pm_d_trans, s->pm_d_init, s->pm_log_tiny, d_ptr, d_states, stride);
+    hipLaunchKernelGGL(k_feat_viterbi, dim3(n_clips), dim3(threads), lds, s->ctx->stream, d_logobs, d_clips, s->pm_bins, s->pm_hw, s->pm_d_trans,
+                       s->pm_d_init, s->pm_log_tiny, d_ptr, d_states, stride);
     return RT_OK;
 }
 
@@ -495,9 +510,6 @@ int feat_tables(rt_features* s) {
     RT_HIP(ctx, hipMalloc((void**)&s->d_tws, F_NFFT * 8));
     RT_HIP(ctx, hipMalloc((void**)&s->d_melT, melT.size() * 4));
     RT_HIP(ctx, hipMalloc((void**)&s->d_dct, dct.size() * 8));
-    RT_HIP(ctx, hipMalloc((void**)&s->d_gmax, 4));
-    RT_HIP(ctx, hipMalloc((void**)&s->d_stats, 2 * F_MFCC * 8));
-    RT_HIP(ctx, hipMalloc((void**)&s->d_lpc, (LPC_MAX + 1) * 8));
     RT_HIP(ctx, hipMemcpy(s->d_twc, c.data(), F_NFFT * 8, hipMemcpyHostToDevice));
     RT_HIP(ctx, hipMemcpy(s->d_tws, sn.data(), F_NFFT * 8, hipMemcpyHostToDevice));
     RT_HIP(ctx, hipMemcpy(s->d_melT, melT.data(), melT.size() * 4, hipMemcpyHostToDevice));
@@ -505,30 +517,80 @@ int feat_tables(rt_features* s) {
     return RT_OK;
 }
 
-// the speech-to-text front-end's resampler (csrc/stt.hip stt_resampler: same taps, same float32 table)
-int feat_resampler(rt_features* s, int sr_in) {
-    if (s->rs_in == sr_in && s->d_resamp) return RT_OK;
-    int a = sr_in, b = F_SR;
-    while (b) { const int t = a % b; a = b; b = t; }
-    const int L = F_SR / a, M = sr_in / a;
-    const double width = 6.0, rolloff = 0.99, base = std::min(sr_in, F_SR) * rolloff;
-    const int half = (int)std::ceil(width * sr_in / base), taps = 2 * half + 1;
-    std::vector<float> h((size_t)L * taps);
-    for (int p = 0; p < L; ++p)
-        for (int j = 0; j < taps; ++j) {
-            const double t = ((double)(j - half) - (double)p / L) * base / sr_in;
-            double v = 0.0;
-            if (std::fabs(t) < width) {
-                const double w = std::cos(t * M_PI / width / 2.0);
-                v = (t == 0.0 ? 1.0 : std::sin(M_PI * t) / (M_PI * t)) * w * w * base / sr_in;
-            }
-            h[(size_t)p * taps + j] = (float)v;
-        }
-    if (s->d_resamp) (void)hipFree(s->d_resamp);
-    s->d_resamp = nullptr;
-    RT_HIP(s->ctx, hipMalloc((void**)&s->d_resamp, h.size() * 4));
-    RT_HIP(s->ctx, hipMemcpy(s->d_resamp, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    s->rs_in = sr_in; s->rs_L = L; s->rs_M = M; s->rs_taps = taps; s->rs_half = half;
+// the clip table of the call (s->h_clips) to the device, on the context's stream
+int feat_upload_clips(rt_features* s) {
+    RT_TRY(feat_grow(s->ctx, s->clips, s->h_clips.size()));
+    RT_HIP(s->ctx, hipMemcpyAsync(s->clips.p, s->h_clips.data(), s->h_clips.size() * sizeof(FeatClip), hipMemcpyHostToDevice, s->ctx->stream));
+    return RT_OK;
+}
+
+// The one extraction path: the front half of n_clips clips - one launch per stage - and, with states_stride > 0, pYIN's back half.
+// It leaves stats [clips][26], lpc [clips][order + 1], cmnd [frames][lags] (want_cmnd) and the state paths [clips][states_stride] in the
+// workspaces and every clip's frame count in s->h_clips, enqueued on the context's stream: the caller copies out what it returns and
+// synchronises.  A clip of more than cap_frames frames ends the call with cap_status, as every refusal does before anything is launched.
+int feat_run(rt_features* s, const char* who, const float* const* d_pcm, const int64_t* n_samples, int n_clips, int sr_in, int min_p, int max_p, int order,
+             bool want_cmnd, int states_stride, int cap_frames, int cap_status) {
+    rt_ctx* ctx = s->ctx;
+    const bool resample = sr_in != F_SR, want_states = states_stride > 0;
+    if (resample) RT_TRY(resampler_design(ctx, s->rs, sr_in, F_SR));
+    if (n_clips > 65535) return rt_fail(ctx, RT_ERR_INVALID, "%s: more than 65535 clips in one call", who);      // (the clip is a grid's y)
+    s->h_clips.assign((size_t)n_clips, FeatClip{});
+    int64_t pcm_total = 0, frames_total = 0, max16 = 0, max_frames = 0;
+    for (int c = 0; c < n_clips; ++c) {
+        FeatClip& h = s->h_clips[c];
+        if (!d_pcm[c] || n_samples[c] < 2) return rt_fail(ctx, RT_ERR_INVALID, "%s: clip %d has fewer than two samples", who, c);
+        h.pcm_in = d_pcm[c];
+        h.n_in = n_samples[c];
+        h.n16 = resample ? s->rs.n_out(h.n_in) : h.n_in;
+        if (h.n16 < 2) return rt_fail(ctx, RT_ERR_INVALID, "%s: clip %d has fewer than two samples at 16 kHz", who, c);
+        // centre-padded framing: 1 + n // hop frames for both the MFCC and the pitch front end (same frame and hop lengths)
+        const int64_t nf = 1 + h.n16 / F_HOP;
+        if (nf > cap_frames) return rt_fail(ctx, cap_status, "%s: clip %d has %lld pitch frames, room for %d", who, c, (long long)nf, cap_frames);
+        h.first = (int)frames_total;
+        h.frames = (int)nf;
+        pcm_total += resample ? h.n16 : 0;
+        frames_total += nf;
+        max16 = std::max(max16, h.n16);
+        max_frames = std::max(max_frames, nf);
+        if (want_states && frames_total > (int64_t)1 << 20) return rt_fail(ctx, RT_ERR_INVALID, "%s: more than 2^20 frames in one batch", who);
+    }
+    const int n_lags = max_p - min_p + 1, S = 2 * s->pm_bins;
+    const size_t F = (size_t)frames_total;
+    if (resample) RT_TRY(feat_grow(ctx, s->pcm, (size_t)pcm_total));
+    RT_TRY(feat_grow(ctx, s->logmel, F * F_MELS));
+    RT_TRY(feat_grow(ctx, s->mfcc, F * F_MFCC));
+    if (want_cmnd) RT_TRY(feat_grow(ctx, s->cmnd, F * n_lags));
+    RT_TRY(feat_grow(ctx, s->stats, (size_t)n_clips * 2 * F_MFCC));
+    RT_TRY(feat_grow(ctx, s->lpc, (size_t)n_clips * (order + 1)));
+    RT_TRY(feat_grow(ctx, s->gmax, (size_t)n_clips));
+    if (want_states) {
+        RT_TRY(feat_grow(ctx, s->logobs, F * S));
+        RT_TRY(feat_grow(ctx, s->ptr, F * S));
+        RT_TRY(feat_grow(ctx, s->states, (size_t)n_clips * states_stride));
+    }
+    int64_t off = 0;
+    for (FeatClip& h : s->h_clips) {
+        h.pcm16 = resample ? s->pcm.p + off : h.pcm_in;
+        off += resample ? h.n16 : 0;
+    }
+    RT_TRY(feat_upload_clips(s));
+    RT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)s->gmax.p, (int)0x80000000, (size_t)n_clips, ctx->stream));      // below every ordered float
+    const dim3 frames((unsigned)max_frames, n_clips);
+    if (resample)
+        hipLaunchKernelGGL(k_feat_resample, dim3((unsigned)std::min<int64_t>((max16 + 255) / 256, 4096), n_clips), dim3(256), 0, ctx->stream, s->clips.p,
+                           s->rs.L, s->rs.M, s->rs.taps, s->rs.half, s->rs.d_h);
+    hipLaunchKernelGGL(k_feat_logmel, frames, dim3(256), (size_t)(3 * F_NFFT + F_BINS) * sizeof(double), ctx->stream, s->clips.p, s->d_twc, s->d_tws, s->d_melT,
+                       s->logmel.p, s->gmax.p);
+    hipLaunchKernelGGL(k_feat_dct, frames, dim3(64), 0, ctx->stream, s->clips.p, s->logmel.p, s->gmax.p, s->d_dct, s->mfcc.p);
+    hipLaunchKernelGGL(k_feat_stats, dim3(n_clips, F_MFCC), dim3(64), 0, ctx->stream, s->clips.p, s->mfcc.p, s->stats.p);
+    if (want_cmnd) hipLaunchKernelGGL(k_feat_cmnd, frames, dim3(512), 0, ctx->stream, s->clips.p, min_p, max_p, s->cmnd.p);
+    hipLaunchKernelGGL(k_feat_lpc, dim3(n_clips), dim3(64), 0, ctx->stream, s->clips.p, order, s->lpc.p);
+    RT_HIP(ctx, hipGetLastError());
+    if (want_states) {                              // one launch each over every frame / every clip of the call
+        RT_TRY(feat_observe(s, s->cmnd.p, (int)F, n_lags, min_p, s->logobs.p));
+        RT_TRY(feat_viterbi(s, s->logobs.p, s->clips.p, n_clips, s->ptr.p, s->states.p, states_stride));
+        RT_HIP(ctx, hipGetLastError());
+    }
     return RT_OK;
 }
 
@@ -555,10 +617,9 @@ int rt_features_destroy(rt_features* s) {
     CtxLock g(ctx);
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : {(void*)s->d_twc, (void*)s->d_tws, (void*)s->d_melT, (void*)s->d_dct, (void*)s->d_resamp, (void*)s->pcm16k, (void*)s->logmel,
-                    (void*)s->mfcc, (void*)s->cmnd, (void*)s->d_gmax, (void*)s->d_stats, (void*)s->d_lpc, (void*)s->pm_d_thr, (void*)s->pm_d_beta,
-                    (void*)s->pm_d_trans, (void*)s->pm_d_init, (void*)s->b_pcm, (void*)s->b_logmel, (void*)s->b_mfcc, (void*)s->b_cmnd, (void*)s->b_logobs,
-                    (void*)s->b_ptr, (void*)s->b_states, (void*)s->b_stats, (void*)s->b_lpc, (void*)s->b_gmax, (void*)s->b_meta})
+    for (void* p : {(void*)s->d_twc, (void*)s->d_tws, (void*)s->d_melT, (void*)s->d_dct, (void*)s->rs.d_h, (void*)s->pm_d_thr, (void*)s->pm_d_beta,
+                    (void*)s->pm_d_trans, (void*)s->pm_d_init, (void*)s->pcm.p, (void*)s->logmel.p, (void*)s->mfcc.p, (void*)s->cmnd.p, (void*)s->logobs.p,
+                    (void*)s->ptr.p, (void*)s->states.p, (void*)s->stats.p, (void*)s->lpc.p, (void*)s->gmax.p, (void*)s->clips.p})
         if (p) (void)hipFree(p);
     delete s;
     return RT_OK;
@@ -580,47 +641,13 @@ int rt_features_extract(rt_features* s, const float* d_pcm, int64_t n_samples, i
     rt_ctx* ctx = s->ctx;
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    const float* src = d_pcm;
-    int64_t n16 = n_samples;
-    if (sample_rate_in != F_SR) {
-        FT_TRY(feat_resampler(s, sample_rate_in));
-        n16 = (n_samples * s->rs_L + s->rs_M - 1) / s->rs_M;
-        if ((size_t)n16 > s->pcm_cap) {
-            if (s->pcm16k) (void)hipFree(s->pcm16k);
-            s->pcm16k = nullptr; s->pcm_cap = 0;
-            RT_HIP(ctx, hipMalloc((void**)&s->pcm16k, (size_t)n16 * 4));
-            s->pcm_cap = (size_t)n16;
-        }
-        hipLaunchKernelGGL(k_feat_resample, dim3((unsigned)std::min<int64_t>((n16 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_pcm, n_samples, s->pcm16k,
-                           n16, s->rs_L, s->rs_M, s->rs_taps, s->rs_half, s->d_resamp);
-        RT_HIP(ctx, hipGetLastError());
-        src = s->pcm16k;
-    }
-    if (n16 < 2) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract: fewer than two samples at 16 kHz");
-    // centre-padded framing: 1 + n // hop frames for both the MFCC and the pitch front end (same frame and hop lengths)
-    const int n_frames = 1 + (int)(n16 / F_HOP);
-    const int n_lags = max_period - min_period + 1;
-    if (h_cmnd && cmnd_cap_frames < n_frames) return rt_fail(ctx, RT_ERR_LENGTH, "rt_features_extract: %d pitch frames, room for %d", n_frames, cmnd_cap_frames);
-    if ((size_t)n_frames > s->frame_cap) {
-        for (void* p : {(void*)s->logmel, (void*)s->mfcc, (void*)s->cmnd}) if (p) (void)hipFree(p);
-        s->logmel = nullptr; s->mfcc = nullptr; s->cmnd = nullptr; s->frame_cap = 0;
-        RT_HIP(ctx, hipMalloc((void**)&s->logmel, (size_t)n_frames * F_MELS * 4));
-        RT_HIP(ctx, hipMalloc((void**)&s->mfcc, (size_t)n_frames * F_MFCC * 8));
-        RT_HIP(ctx, hipMalloc((void**)&s->cmnd, (size_t)n_frames * (P_FRAME - P_WIN) * 8));
-        s->frame_cap = (size_t)n_frames;
-    }
-    const int init = (int)0x80000000;
-    RT_HIP(ctx, hipMemcpyAsync(s->d_gmax, &init, 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_feat_logmel, dim3(n_frames), dim3(256), (size_t)(3 * F_NFFT + F_BINS) * sizeof(double), ctx->stream, src, n16, s->d_twc, s->d_tws,
-                       s->d_melT, s->logmel, s->d_gmax);
-    hipLaunchKernelGGL(k_feat_dct, dim3(n_frames), dim3(64), 0, ctx->stream, s->logmel, s->d_gmax, s->d_dct, s->mfcc);
-    hipLaunchKernelGGL(k_feat_stats, dim3(F_MFCC), dim3(64), 0, ctx->stream, s->mfcc, n_frames, s->d_stats);
-    if (h_cmnd) hipLaunchKernelGGL(k_feat_cmnd, dim3(n_frames), dim3(512), 0, ctx->stream, src, n16, min_period, max_period, s->cmnd);
-    hipLaunchKernelGGL(k_feat_lpc, dim3(1), dim3(64), 0, ctx->stream, src, n16, lpc_order, s->d_lpc);
-    RT_HIP(ctx, hipGetLastError());
-    RT_HIP(ctx, hipMemcpyAsync(h_mfcc_stats26, s->d_stats, 2 * F_MFCC * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (h_cmnd) RT_HIP(ctx, hipMemcpyAsync(h_cmnd, s->cmnd, (size_t)n_frames * n_lags * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(h_lpc, s->d_lpc, (size_t)(lpc_order + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    // one clip, no back half; without h_cmnd the difference function is not computed and any frame count fits
+    RT_TRY(feat_run(s, "rt_features_extract", &d_pcm, &n_samples, 1, sample_rate_in, min_period, max_period, lpc_order, h_cmnd != nullptr, 0,
+                    h_cmnd ? cmnd_cap_frames : INT_MAX, RT_ERR_LENGTH));
+    const int n_frames = s->h_clips[0].frames, n_lags = max_period - min_period + 1;
+    RT_HIP(ctx, hipMemcpyAsync(h_mfcc_stats26, s->stats.p, 2 * F_MFCC * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (h_cmnd) RT_HIP(ctx, hipMemcpyAsync(h_cmnd, s->cmnd.p, (size_t)n_frames * n_lags * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(h_lpc, s->lpc.p, (size_t)(lpc_order + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (h_n_mfcc_frames) *h_n_mfcc_frames = n_frames;
     *h_n_pitch_frames = n_frames;
@@ -667,68 +694,13 @@ int rt_features_extract_batch(rt_features* s, const float* const* d_pcm, const i
     CtxLock g(ctx);
     if (!s->pm_set) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: no pitch model (rt_features_set_pitch_model)");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    const bool resample = sample_rate_in != F_SR;
-    if (resample) FT_TRY(feat_resampler(s, sample_rate_in));
-    // every clip's geometry on the host first: nothing is launched for a batch that holds a bad clip
-    std::vector<int64_t> n16(n_clips), pcm_off(n_clips);
-    s->h_meta.assign((size_t)2 * n_clips, 0);
-    int64_t pcm_total = 0, frames_total = 0;
-    for (int c = 0; c < n_clips; ++c) {
-        if (!d_pcm[c] || n_samples[c] < 2) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: clip %d has fewer than two samples", c);
-        n16[c] = resample ? (n_samples[c] * s->rs_L + s->rs_M - 1) / s->rs_M : n_samples[c];
-        if (n16[c] < 2) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: clip %d has fewer than two samples at 16 kHz", c);
-        const int64_t nf = 1 + n16[c] / F_HOP;
-        if (nf > cap_frames) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: clip %d has %lld pitch frames, room for %d", c, (long long)nf, cap_frames);
-        pcm_off[c] = pcm_total;
-        pcm_total += resample ? n16[c] : 0;
-        s->h_meta[c] = (int)frames_total;
-        s->h_meta[n_clips + c] = (int)nf;
-        frames_total += nf;
-        if (frames_total > (int64_t)1 << 20) return rt_fail(ctx, RT_ERR_INVALID, "rt_features_extract_batch: more than 2^20 frames in one batch");
-    }
-    const int n_lags = max_period - min_period + 1, S = 2 * s->pm_bins, F = (int)frames_total;
-    FT_TRY(feat_grow(ctx, s->b_pcm, s->b_pcm_cap, (size_t)pcm_total));
-    FT_TRY(feat_grow(ctx, s->b_logmel, s->b_logmel_cap, (size_t)F * F_MELS));
-    FT_TRY(feat_grow(ctx, s->b_mfcc, s->b_mfcc_cap, (size_t)F * F_MFCC));
-    FT_TRY(feat_grow(ctx, s->b_cmnd, s->b_cmnd_cap, (size_t)F * n_lags));
-    FT_TRY(feat_grow(ctx, s->b_logobs, s->b_logobs_cap, (size_t)F * S));
-    FT_TRY(feat_grow(ctx, s->b_ptr, s->b_ptr_cap, (size_t)F * S));
-    FT_TRY(feat_grow(ctx, s->b_states, s->b_states_cap, (size_t)n_clips * cap_frames));
-    FT_TRY(feat_grow(ctx, s->b_stats, s->b_stats_cap, (size_t)n_clips * 2 * F_MFCC));
-    FT_TRY(feat_grow(ctx, s->b_lpc, s->b_lpc_cap, (size_t)n_clips * (lpc_order + 1)));
-    FT_TRY(feat_grow(ctx, s->b_gmax, s->b_gmax_cap, (size_t)n_clips));
-    FT_TRY(feat_grow(ctx, s->b_meta, s->b_meta_cap, (size_t)2 * n_clips));
-    RT_HIP(ctx, hipMemcpyAsync(s->b_meta, s->h_meta.data(), (size_t)2 * n_clips * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)s->b_gmax, (int)0x80000000, (size_t)n_clips, ctx->stream));
-    // front half: the single-clip call's kernels with the single-clip call's arguments, clip after clip on the stream - every clip's
-    // MFCC statistics, difference function and LPC carry the bits rt_features_extract gives for that clip alone
-    for (int c = 0; c < n_clips; ++c) {
-        const float* src = d_pcm[c];
-        if (resample) {
-            float* dst = s->b_pcm + pcm_off[c];
-            hipLaunchKernelGGL(k_feat_resample, dim3((unsigned)std::min<int64_t>((n16[c] + 255) / 256, 4096)), dim3(256), 0, ctx->stream, d_pcm[c], n_samples[c],
-                               dst, n16[c], s->rs_L, s->rs_M, s->rs_taps, s->rs_half, s->d_resamp);
-            src = dst;
-        }
-        const int64_t f0 = s->h_meta[c];
-        const int nf = s->h_meta[n_clips + c];
-        hipLaunchKernelGGL(k_feat_logmel, dim3(nf), dim3(256), (size_t)(3 * F_NFFT + F_BINS) * sizeof(double), ctx->stream, src, n16[c], s->d_twc, s->d_tws,
-                           s->d_melT, s->b_logmel + f0 * F_MELS, s->b_gmax + c);
-        hipLaunchKernelGGL(k_feat_dct, dim3(nf), dim3(64), 0, ctx->stream, s->b_logmel + f0 * F_MELS, s->b_gmax + c, s->d_dct, s->b_mfcc + f0 * F_MFCC);
-        hipLaunchKernelGGL(k_feat_stats, dim3(F_MFCC), dim3(64), 0, ctx->stream, s->b_mfcc + f0 * F_MFCC, nf, s->b_stats + (size_t)c * 2 * F_MFCC);
-        hipLaunchKernelGGL(k_feat_cmnd, dim3(nf), dim3(512), 0, ctx->stream, src, n16[c], min_period, max_period, s->b_cmnd + f0 * n_lags);
-        hipLaunchKernelGGL(k_feat_lpc, dim3(1), dim3(64), 0, ctx->stream, src, n16[c], lpc_order, s->b_lpc + (size_t)c * (lpc_order + 1));
-    }
-    RT_HIP(ctx, hipGetLastError());
-    // back half: one launch each over every frame / every clip of the batch
-    FT_TRY(feat_observe(s, s->b_cmnd, F, n_lags, min_period, s->b_logobs));
-    FT_TRY(feat_viterbi(s, s->b_logobs, s->b_meta, n_clips, s->b_ptr, s->b_states, cap_frames));
-    RT_HIP(ctx, hipGetLastError());
-    RT_HIP(ctx, hipMemcpyAsync(h_mfcc_stats26, s->b_stats, (size_t)n_clips * 2 * F_MFCC * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(h_lpc, s->b_lpc, (size_t)n_clips * (lpc_order + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(h_states, s->b_states, (size_t)n_clips * cap_frames * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_TRY(feat_run(s, "rt_features_extract_batch", d_pcm, n_samples, n_clips, sample_rate_in, min_period, max_period, lpc_order, true, cap_frames, cap_frames,
+                    RT_ERR_INVALID));
+    RT_HIP(ctx, hipMemcpyAsync(h_mfcc_stats26, s->stats.p, (size_t)n_clips * 2 * F_MFCC * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(h_lpc, s->lpc.p, (size_t)n_clips * (lpc_order + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(h_states, s->states.p, (size_t)n_clips * cap_frames * 4, hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int c = 0; c < n_clips; ++c) h_n_pitch_frames[c] = s->h_meta[n_clips + c];
+    for (int c = 0; c < n_clips; ++c) h_n_pitch_frames[c] = s->h_clips[c].frames;
     return RT_OK;
 }
 
@@ -740,12 +712,12 @@ int rt_debug_features_observe(rt_features* s, const double* h_cmnd, int32_t n_fr
     if (!s->pm_set) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_observe: no pitch model (rt_features_set_pitch_model)");
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const int S = 2 * s->pm_bins;
-    FT_TRY(feat_grow(ctx, s->b_cmnd, s->b_cmnd_cap, (size_t)n_frames * n_lags));
-    FT_TRY(feat_grow(ctx, s->b_logobs, s->b_logobs_cap, (size_t)n_frames * S));
-    RT_HIP(ctx, hipMemcpyAsync(s->b_cmnd, h_cmnd, (size_t)n_frames * n_lags * 8, hipMemcpyHostToDevice, ctx->stream));
-    FT_TRY(feat_observe(s, s->b_cmnd, n_frames, n_lags, min_period, s->b_logobs));
+    RT_TRY(feat_grow(ctx, s->cmnd, (size_t)n_frames * n_lags));
+    RT_TRY(feat_grow(ctx, s->logobs, (size_t)n_frames * S));
+    RT_HIP(ctx, hipMemcpyAsync(s->cmnd.p, h_cmnd, (size_t)n_frames * n_lags * 8, hipMemcpyHostToDevice, ctx->stream));
+    RT_TRY(feat_observe(s, s->cmnd.p, n_frames, n_lags, min_period, s->logobs.p));
     RT_HIP(ctx, hipGetLastError());
-    RT_HIP(ctx, hipMemcpyAsync(h_log_obs, s->b_logobs, (size_t)n_frames * S * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(h_log_obs, s->logobs.p, (size_t)n_frames * S * 8, hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
@@ -757,25 +729,24 @@ int rt_debug_features_viterbi(rt_features* s, const double* h_log_obs, const int
     CtxLock g(ctx);
     if (!s->pm_set) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_viterbi: no pitch model (rt_features_set_pitch_model)");
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    s->h_meta.assign((size_t)2 * n_clips, 0);
+    s->h_clips.assign((size_t)n_clips, FeatClip{});                 // the clip table with null audio: frames alone
     int64_t frames_total = 0;
     for (int c = 0; c < n_clips; ++c) {
         if (h_n_frames[c] < 1 || h_n_frames[c] > stride) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_viterbi: clip %d has %d frames, room for %d", c, h_n_frames[c], stride);
-        s->h_meta[c] = (int)frames_total;
-        s->h_meta[n_clips + c] = h_n_frames[c];
+        s->h_clips[c].first = (int)frames_total;
+        s->h_clips[c].frames = h_n_frames[c];
         frames_total += h_n_frames[c];
         if (frames_total > (int64_t)1 << 20) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_features_viterbi: more than 2^20 frames");
     }
     const int S = 2 * s->pm_bins, F = (int)frames_total;
-    FT_TRY(feat_grow(ctx, s->b_logobs, s->b_logobs_cap, (size_t)F * S));
-    FT_TRY(feat_grow(ctx, s->b_ptr, s->b_ptr_cap, (size_t)F * S));
-    FT_TRY(feat_grow(ctx, s->b_states, s->b_states_cap, (size_t)n_clips * stride));
-    FT_TRY(feat_grow(ctx, s->b_meta, s->b_meta_cap, (size_t)2 * n_clips));
-    RT_HIP(ctx, hipMemcpyAsync(s->b_meta, s->h_meta.data(), (size_t)2 * n_clips * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(s->b_logobs, h_log_obs, (size_t)F * S * 8, hipMemcpyHostToDevice, ctx->stream));
-    FT_TRY(feat_viterbi(s, s->b_logobs, s->b_meta, n_clips, s->b_ptr, s->b_states, stride));
+    RT_TRY(feat_grow(ctx, s->logobs, (size_t)F * S));
+    RT_TRY(feat_grow(ctx, s->ptr, (size_t)F * S));
+    RT_TRY(feat_grow(ctx, s->states, (size_t)n_clips * stride));
+    RT_TRY(feat_upload_clips(s));
+    RT_HIP(ctx, hipMemcpyAsync(s->logobs.p, h_log_obs, (size_t)F * S * 8, hipMemcpyHostToDevice, ctx->stream));
+    RT_TRY(feat_viterbi(s, s->logobs.p, s->clips.p, n_clips, s->ptr.p, s->states.p, stride));
     RT_HIP(ctx, hipGetLastError());
-    RT_HIP(ctx, hipMemcpyAsync(h_states, s->b_states, (size_t)n_clips * stride * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(h_states, s->states.p, (size_t)n_clips * stride * 4, hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }

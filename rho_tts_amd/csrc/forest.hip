@@ -152,12 +152,6 @@ void forest_free_model(rt_forest* f) {
     f->set = false;
 }
 
-#define FO_TRY(expr)            \
-    do {                        \
-        int _rc = (expr);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -206,12 +200,12 @@ int rt_forest_set_model(rt_forest* f, int32_t n_features, int32_t n_forests, con
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     forest_free_model(f);                                  // (a failed upload leaves the handle without a model)
     const size_t n_knots = (size_t)h_iso_first[n_calibrators];
-    FO_TRY(forest_upload(ctx, f->d_nodes, nodes.data(), nodes.size()));
-    FO_TRY(forest_upload(ctx, f->d_tree_first, h_tree_first, (size_t)n_trees + 1));
-    FO_TRY(forest_upload(ctx, f->d_forest_first, h_forest_first, (size_t)n_forests + 1));
-    FO_TRY(forest_upload(ctx, f->d_iso_first, h_iso_first, (size_t)n_calibrators + 1));
-    FO_TRY(forest_upload(ctx, f->d_iso_x, h_iso_x, n_knots));
-    FO_TRY(forest_upload(ctx, f->d_iso_y, h_iso_y, n_knots));
+    RT_TRY(forest_upload(ctx, f->d_nodes, nodes.data(), nodes.size()));
+    RT_TRY(forest_upload(ctx, f->d_tree_first, h_tree_first, (size_t)n_trees + 1));
+    RT_TRY(forest_upload(ctx, f->d_forest_first, h_forest_first, (size_t)n_forests + 1));
+    RT_TRY(forest_upload(ctx, f->d_iso_first, h_iso_first, (size_t)n_calibrators + 1));
+    RT_TRY(forest_upload(ctx, f->d_iso_x, h_iso_x, n_knots));
+    RT_TRY(forest_upload(ctx, f->d_iso_y, h_iso_y, n_knots));
     f->n_features = n_features; f->n_forests = n_forests; f->n_trees = n_trees; f->n_nodes = n_nodes; f->n_cal = n_calibrators;
     f->max_depth = depth;
     f->set = true;
@@ -237,9 +231,9 @@ int rt_forest_predict(rt_forest* f, const double* h_x, int32_t n_rows, double* h
     }
     if (!forest_features_to_f32(h_x, (int64_t)n_el, f->h_x))
         return rt_fail(ctx, RT_ERR_INVALID, "rt_forest_predict: a feature is NaN, infinite or beyond float32's range");   // before any launch
-    FO_TRY(forest_grow(ctx, f->d_x, f->d_x_cap, n_el));
-    FO_TRY(forest_grow(ctx, f->d_leaf, f->leaf_cap, (size_t)n_pairs));
-    FO_TRY(forest_grow(ctx, f->d_prob, f->prob_cap, (size_t)n_rows));
+    RT_TRY(forest_grow(ctx, f->d_x, f->d_x_cap, n_el));
+    RT_TRY(forest_grow(ctx, f->d_leaf, f->leaf_cap, (size_t)n_pairs));
+    RT_TRY(forest_grow(ctx, f->d_prob, f->prob_cap, (size_t)n_rows));
     RT_HIP(ctx, hipMemcpyAsync(f->d_x, f->h_x, n_el * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     const unsigned blocks = (unsigned)std::min<long long>((n_pairs + 255) / 256, 4096);
     hipLaunchKernelGGL(k_forest_walk, dim3(blocks), dim3(256), 0, ctx->stream, f->d_nodes, f->d_tree_first, f->d_x, f->n_features, f->n_trees, n_pairs,

@@ -98,12 +98,6 @@ struct rt_model {
     int prefix_slot() const { return cfg.max_batch; }
 };
 
-#define RT_TRY(expr)            \
-    do {                        \
-        int _rc = (expr);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
 
 namespace rtm {
 

@@ -209,12 +209,6 @@ int sp_grow(rt_ctx* ctx, T*& p, size_t& cap, size_t need) {
     return RT_OK;
 }
 
-#define SP_TRY(expr)            \
-    do {                        \
-        int _rc = (expr);       \
-        if (_rc) return _rc;    \
-    } while (0)
-
 int64_t sp_gcd(int64_t a, int64_t b) {
     while (b) { const int64_t t = a % b; a = b; b = t; }
     return a;
@@ -311,12 +305,12 @@ int rt_speedpitch_apply(rt_speedpitch* s, const float* d_in, int64_t n_in, const
         return RT_OK;
     }
     const int nf = (int)p->nf, n_out = (int)p->n_out;
-    if (speed) SP_TRY(sp_grow(ctx, s->mid, s->mid_cap, (size_t)L));
-    SP_TRY(sp_grow(ctx, s->mag, s->mag_cap, (size_t)SP_BINS * (nf + 2)));
-    SP_TRY(sp_grow(ctx, s->ang, s->ang_cap, (size_t)SP_BINS * (nf + 2)));
-    SP_TRY(sp_grow(ctx, s->spec, s->spec_cap, (size_t)n_out * SP_BINS * 2));
-    SP_TRY(sp_grow(ctx, s->frames, s->frames_cap, (size_t)n_out * SP_NFFT));
-    SP_TRY(sp_grow(ctx, s->stretch, s->stretch_cap, (size_t)p->ls));
+    if (speed) RT_TRY(sp_grow(ctx, s->mid, s->mid_cap, (size_t)L));
+    RT_TRY(sp_grow(ctx, s->mag, s->mag_cap, (size_t)SP_BINS * (nf + 2)));
+    RT_TRY(sp_grow(ctx, s->ang, s->ang_cap, (size_t)SP_BINS * (nf + 2)));
+    RT_TRY(sp_grow(ctx, s->spec, s->spec_cap, (size_t)n_out * SP_BINS * 2));
+    RT_TRY(sp_grow(ctx, s->frames, s->frames_cap, (size_t)n_out * SP_NFFT));
+    RT_TRY(sp_grow(ctx, s->stretch, s->stretch_cap, (size_t)p->ls));
     if (speed) {
         sp_launch_resample<float, double>(st, d_in, n_in, s->mid, L, L, p->s_o, p->s_n, p->s_width);
         hipLaunchKernelGGL(k_sp_stft<double>, dim3(nf + 2), dim3(256), 0, st, s->mid, L, nf, s->d_twc, s->d_tws, s->mag, s->ang);

@@ -3,7 +3,7 @@
 // model.  Stands behind validation/stt/stt_validator.py:42-148 (model load, transcribe_audio; the reference's own fallback is
 // transformers' Whisper, :85-107) and the temp-WAV round trip of base_tts.py:821-830.
 //
-//   PCM at the TTS rate -> windowed-sinc resampler (16 kHz) -> log-mel front-end (400-point DFT per frame in float64, 80 slaney mel
+//   PCM at the TTS rate -> windowed-sinc resampler (16 kHz; resample.h) -> log-mel front-end (400-point DFT per frame in float64, 80 slaney mel
 //   filters, log10, (max - 8) floor, (x + 4) / 4: WhisperFeatureExtractor) -> 2 convs (GELU) + sinusoidal positions -> pre-LN
 //   encoder (bidirectional attention over 1500 positions) -> decoder (causal self-attention + cross-attention, KV caches) ->
 //   tied LM head -> greedy token ids after the forced prefix.
@@ -29,14 +29,9 @@
 #include <map>
 
 #include "kernels.h"
+#include "resample.h"
 
 namespace {
-
-#define ST_TRY(expr)            \
-    do {                        \
-        int _rc = (expr);       \
-        if (_rc) return _rc;    \
-    } while (0)
 
 enum SttKind { S_GEMM = 0, S_VEC = 1, S_TABLE = 2 };
 struct SttSlot {
@@ -53,22 +48,6 @@ struct SttSlot {
 
 __global__ void k_stt_bf16_to_f32(const bf16_t* __restrict__ x, int64_t n, float* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = bf16_to_f32(x[i]);
-}
-
-// y[n] = sum_j x[base(n) + j - half] h[phase(n)][j]: polyphase windowed-sinc resampler, sr_in / sr_out = M / L in lowest terms,
-// base = floor(n M / L), phase = (n M) mod L; samples outside [0, n_in) are zero.  float64 accumulation in tap order.
-__device__ __forceinline__ float resample_at(const float* __restrict__ x, int64_t n_in, int64_t n, int L, int M, int taps, int half,
-                                             const float* __restrict__ h) {
-    const int64_t num = n * M;
-    const int64_t base = num / L;
-    const int phase = (int)(num % L);
-    const float* hp = h + (int64_t)phase * taps;
-    double acc = 0.0;
-    for (int j = 0; j < taps; ++j) {
-        const int64_t t = base + j - half;
-        if (t >= 0 && t < n_in) acc += (double)x[t] * (double)hp[j];
-    }
-    return (float)acc;
 }
 
 // One window of a group, as the front-end kernels see it (a small device table, one entry per window)
@@ -90,8 +69,6 @@ __global__ void k_resample_group(const SttWin* __restrict__ wins, float* __restr
 // One frame per workgroup: the frame's 400 samples of the (zero-padded to 30 s, reflect-padded by n_fft / 2 at both ends) signal
 // times the periodic Hann window, a direct DFT in float64 (bin k on thread k, twiddles from a 400-entry table: index k n mod 400),
 // power spectrum, mel filters, log10(max(., 1e-10)).  logspec is [frames][n_mels]; gmax receives the maximum (ordered-int atomic).
-__device__ __forceinline__ int f32_ordered(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float ordered_f32(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 __device__ __forceinline__ void logmel_frame(double* sh /* xw[n_fft] | c[n_fft] | s[n_fft] | power[n_bins] */, const float* __restrict__ pcm, int64_t n_valid,
                                              int64_t n_padded, int f, int n_fft, int hop, int n_bins, int n_mels, const double* __restrict__ twc,
                                              const double* __restrict__ tws, const float* __restrict__ window, const float* __restrict__ melT,
@@ -501,8 +478,7 @@ struct rt_stt {
     // front-end constants
     double *d_twc = nullptr, *d_tws = nullptr;
     float *d_window = nullptr, *d_melT = nullptr;
-    float* d_resamp = nullptr;        // polyphase filter of the last (sr_in -> cfg.sample_rate) pair
-    int rs_in = 0, rs_L = 0, rs_M = 0, rs_taps = 0, rs_half = 0;
+    Resampler rs;                     // polyphase filter of the last (sr_in -> cfg.sample_rate) pair (resample.h)
     SttGroup grp;                     // every entry point's buffers: one window from rt_stt_finalize on
     SttBeam beam;                     // the beam path: nothing of it exists until the first rt_stt_transcribe_beam
     std::vector<int32_t> h_book;
@@ -573,15 +549,15 @@ int stt_kv(rt_stt* s, std::vector<void*>& owned, KvCache& kv, int layers, int sl
     const rt_stt_config& c = s->cfg;
     kv.layers = layers; kv.slots = slots; kv.kv_heads = c.heads; kv.max_pos = max_pos; kv.head_dim = c.d_model / c.heads;
     const size_t n = (size_t)layers * kv.layer_stride();
-    ST_TRY(stt_alloc(s, owned, n, &kv.k)); ST_TRY(stt_alloc(s, owned, n, &kv.v)); ST_TRY(stt_alloc(s, owned, n, &kv.k_lo)); ST_TRY(stt_alloc(s, owned, n, &kv.v_lo));
+    RT_TRY(stt_alloc(s, owned, n, &kv.k)); RT_TRY(stt_alloc(s, owned, n, &kv.v)); RT_TRY(stt_alloc(s, owned, n, &kv.k_lo)); RT_TRY(stt_alloc(s, owned, n, &kv.v_lo));
     for (bf16_t* p : {kv.k, kv.v, kv.k_lo, kv.v_lo}) RT_HIP(s->ctx, hipMemsetAsync(p, 0, n * sizeof(bf16_t), s->ctx->stream));
     return RT_OK;
 }
 
 int stt_alloc_work(rt_stt* s, std::vector<void*>& owned, size_t rows, SttWork& k) {
     const size_t D = s->cfg.d_model;
-    ST_TRY(stt_alloc(s, owned, rows * D, &k.x)); ST_TRY(stt_alloc(s, owned, rows * D, &k.xn)); ST_TRY(stt_alloc(s, owned, rows * 3 * D, &k.qkv));
-    ST_TRY(stt_alloc(s, owned, rows * D, &k.q)); ST_TRY(stt_alloc(s, owned, rows * D, &k.ao)); ST_TRY(stt_alloc(s, owned, rows * s->cfg.ffn, &k.ff));
+    RT_TRY(stt_alloc(s, owned, rows * D, &k.x)); RT_TRY(stt_alloc(s, owned, rows * D, &k.xn)); RT_TRY(stt_alloc(s, owned, rows * 3 * D, &k.qkv));
+    RT_TRY(stt_alloc(s, owned, rows * D, &k.q)); RT_TRY(stt_alloc(s, owned, rows * D, &k.ao)); RT_TRY(stt_alloc(s, owned, rows * s->cfg.ffn, &k.ff));
     return RT_OK;
 }
 
@@ -589,10 +565,10 @@ int stt_alloc_work(rt_stt* s, std::vector<void*>& owned, size_t rows, SttWork& k
 int stt_alloc_dec(rt_stt* s, std::vector<void*>& owned, int rows, SttDec& d) {
     const rt_stt_config& c = s->cfg;
     const size_t rp = (size_t)rows * c.n_prefix;
-    ST_TRY(stt_kv(s, owned, d.kv, c.dec_layers, rows, c.n_text_ctx));
-    ST_TRY(stt_alloc_work(s, owned, rp, d.work));
-    ST_TRY(stt_alloc(s, owned, (size_t)rows * c.vocab, &d.logits));
-    ST_TRY(stt_alloc(s, owned, rp, &d.enc_last));
+    RT_TRY(stt_kv(s, owned, d.kv, c.dec_layers, rows, c.n_text_ctx));
+    RT_TRY(stt_alloc_work(s, owned, rp, d.work));
+    RT_TRY(stt_alloc(s, owned, (size_t)rows * c.vocab, &d.logits));
+    RT_TRY(stt_alloc(s, owned, rp, &d.enc_last));
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(256), 0, s->ctx->stream, d.enc_last, (int)rp, c.n_ctx - 1, 0);
     RT_HIP(s->ctx, hipGetLastError());
     return RT_OK;
@@ -605,19 +581,19 @@ int stt_alloc_group(rt_stt* s, SttGroup& w, int B) {
     const int D = c.d_model, T = c.n_ctx, T2 = 2 * T, P = c.n_prefix;
     const size_t b = (size_t)B, rows = b * T, r = b * P;
     SttEnc& e = w.enc;
-    ST_TRY(stt_kv(s, w.owned, e.kv, c.enc_layers, B, T));
-    ST_TRY(stt_kv(s, w.owned, e.cross_kv, c.dec_layers, B, T));
-    ST_TRY(stt_alloc(s, w.owned, b * c.chunk_seconds * c.sample_rate, &e.pcm16k));
-    ST_TRY(stt_alloc(s, w.owned, b * T2 * c.n_mels, &e.mel));
-    ST_TRY(stt_alloc(s, w.owned, b * T2 * D, &e.c1));
-    ST_TRY(stt_alloc_work(s, w.owned, rows, e.work));
-    ST_TRY(stt_alloc(s, w.owned, rows * D, &e.out));
-    ST_TRY(stt_alloc(s, w.owned, rows, &e.slot)); ST_TRY(stt_alloc(s, w.owned, rows, &e.pos)); ST_TRY(stt_alloc(s, w.owned, rows, &e.last));
-    ST_TRY(stt_alloc(s, w.owned, b, &e.d_gmax)); ST_TRY(stt_alloc(s, w.owned, b, &e.d_wins));
-    ST_TRY(stt_alloc_dec(s, w.owned, B, w.dec));
-    ST_TRY(stt_alloc(s, w.owned, r, &w.pre_slot)); ST_TRY(stt_alloc(s, w.owned, r, &w.pre_pos));
-    ST_TRY(stt_alloc(s, w.owned, b, &w.step_slot)); ST_TRY(stt_alloc(s, w.owned, b, &w.step_pos));
-    ST_TRY(stt_alloc(s, w.owned, r, &w.d_prefix)); ST_TRY(stt_alloc(s, w.owned, b, &w.d_tok));
+    RT_TRY(stt_kv(s, w.owned, e.kv, c.enc_layers, B, T));
+    RT_TRY(stt_kv(s, w.owned, e.cross_kv, c.dec_layers, B, T));
+    RT_TRY(stt_alloc(s, w.owned, b * c.chunk_seconds * c.sample_rate, &e.pcm16k));
+    RT_TRY(stt_alloc(s, w.owned, b * T2 * c.n_mels, &e.mel));
+    RT_TRY(stt_alloc(s, w.owned, b * T2 * D, &e.c1));
+    RT_TRY(stt_alloc_work(s, w.owned, rows, e.work));
+    RT_TRY(stt_alloc(s, w.owned, rows * D, &e.out));
+    RT_TRY(stt_alloc(s, w.owned, rows, &e.slot)); RT_TRY(stt_alloc(s, w.owned, rows, &e.pos)); RT_TRY(stt_alloc(s, w.owned, rows, &e.last));
+    RT_TRY(stt_alloc(s, w.owned, b, &e.d_gmax)); RT_TRY(stt_alloc(s, w.owned, b, &e.d_wins));
+    RT_TRY(stt_alloc_dec(s, w.owned, B, w.dec));
+    RT_TRY(stt_alloc(s, w.owned, r, &w.pre_slot)); RT_TRY(stt_alloc(s, w.owned, r, &w.pre_pos));
+    RT_TRY(stt_alloc(s, w.owned, b, &w.step_slot)); RT_TRY(stt_alloc(s, w.owned, b, &w.step_pos));
+    RT_TRY(stt_alloc(s, w.owned, r, &w.d_prefix)); RT_TRY(stt_alloc(s, w.owned, b, &w.d_tok));
     std::vector<int32_t> prefix(r);
     for (size_t i = 0; i < r; ++i) prefix[i] = c.prefix[i % P];
     RT_HIP(ctx, hipMemcpy(w.d_prefix, prefix.data(), r * 4, hipMemcpyHostToDevice));
@@ -665,39 +641,6 @@ int stt_ln(rt_stt* s, const float* x, int64_t ldx, int M, const float* w, const 
     return RT_OK;
 }
 
-// windowed-sinc resampling filter (Hann window over `width` zero crossings of the low-pass at rolloff x the lower Nyquist): the
-// definition rho_tts_amd/stt.py restates in NumPy for the tests (oracle: parity unpinned - the reference's pipeline decodes its
-// temporary WAV through ffmpeg)
-int stt_resampler(rt_stt* s, int sr_in) {
-    if (s->rs_in == sr_in && s->d_resamp) return RT_OK;
-    const int sr_out = s->cfg.sample_rate;
-    int a = sr_in, b = sr_out;
-    while (b) { const int t = a % b; a = b; b = t; }
-    const int L = sr_out / a, M = sr_in / a;
-    const double width = 6.0, rolloff = 0.99;
-    const double base = std::min(sr_in, sr_out) * rolloff;          // cut-off (both sides) in Hz x 2
-    const int half = (int)std::ceil(width * sr_in / base);
-    const int taps = 2 * half + 1;
-    std::vector<float> h((size_t)L * taps);
-    for (int p = 0; p < L; ++p)
-        for (int j = 0; j < taps; ++j) {
-            // time (in input samples) from tap j of phase p to the output instant: t = (j - half) - p / L
-            const double t = ((double)(j - half) - (double)p / L) * base / sr_in;
-            double v = 0.0;
-            if (std::fabs(t) < width) {
-                const double w = std::cos(t * M_PI / width / 2.0);
-                const double sinc = t == 0.0 ? 1.0 : std::sin(M_PI * t) / (M_PI * t);
-                v = sinc * w * w * base / sr_in;
-            }
-            h[(size_t)p * taps + j] = (float)v;
-        }
-    if (s->d_resamp) (void)hipFree(s->d_resamp);
-    RT_HIP(s->ctx, hipMalloc((void**)&s->d_resamp, h.size() * 4));
-    RT_HIP(s->ctx, hipMemcpy(s->d_resamp, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    s->rs_in = sr_in; s->rs_L = L; s->rs_M = M; s->rs_taps = taps; s->rs_half = half;
-    return RT_OK;
-}
-
 // frames of a window that can see audio: [f hop - n_fft/2, f hop + n_fft/2) meets [0, n16); the rest are the constant of silence
 int stt_frames_with_audio(const rt_stt_config& c, int64_t n16) {
     const int n_frames = (int)((int64_t)c.chunk_seconds * c.sample_rate / c.hop);     // 3000 (the last of the 3001 STFT frames is dropped)
@@ -724,7 +667,7 @@ int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
     SttEnc& w = s->grp.enc;
     const int64_t n_pad = (int64_t)c.chunk_seconds * c.sample_rate;
     const bool resample = sr != c.sample_rate;
-    if (resample) ST_TRY(stt_resampler(s, sr));
+    if (resample) RT_TRY(resampler_design(ctx, s->rs, sr, c.sample_rate));
     s->h_wins.assign(B, SttWin{});
     int64_t max16 = 0;
     int max_comp = 0;
@@ -732,7 +675,7 @@ int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
         SttWin& h = s->h_wins[b];
         h.pcm_in = spans[b].pcm;
         h.n_in = spans[b].n;
-        h.n16 = std::min<int64_t>(resample ? (h.n_in * s->rs_L + s->rs_M - 1) / s->rs_M : h.n_in, n_pad);
+        h.n16 = std::min<int64_t>(resample ? s->rs.n_out(h.n_in) : h.n_in, n_pad);
         h.pcm16 = resample ? w.pcm16k + (size_t)b * n_pad : h.pcm_in;
         h.n_comp = stt_frames_with_audio(c, h.n16);
         max16 = std::max(max16, h.n16);
@@ -743,7 +686,7 @@ int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
     RT_HIP(ctx, hipGetLastError());
     if (resample && max16 > 0) {
         hipLaunchKernelGGL(k_resample_group, dim3((unsigned)std::min<int64_t>((max16 + 255) / 256, 4096), B), dim3(256), 0, ctx->stream, w.d_wins, w.pcm16k,
-                           n_pad, s->rs_L, s->rs_M, s->rs_taps, s->rs_half, s->d_resamp);
+                           n_pad, s->rs.L, s->rs.M, s->rs.taps, s->rs.half, s->rs.d_h);
         RT_HIP(ctx, hipGetLastError());
     }
     const int n_frames = (int)(n_pad / c.hop), n_bins = c.n_fft / 2 + 1;
@@ -769,20 +712,20 @@ int stt_layer(rt_stt* s, const std::string& p, const SttWork& k, int M, const Kv
     const rt_stt_config& c = s->cfg;
     const int H = c.heads, d = c.d_model / c.heads, D = c.d_model;
     float *x = k.x, *xn = k.xn, *qkv = k.qkv, *q = k.q, *ao = k.ao, *ff = k.ff;
-    ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln1_w"), SVEC(s, p + ".ln1_b"), xn));
-    ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".wqkv"), SVEC(s, p + ".bqkv"), ACT_NONE, nullptr, qkv));
-    ST_TRY(launch_qkv_post(ctx, qkv, 1, M, H, H, d, nullptr, nullptr, 0.f, nullptr, nullptr, slot, wpos, pos_add, q, kv, layer));
-    ST_TRY(launch_attention(ctx, q, M, H, H, d, slot, apos, apos == wpos ? pos_add : 0, 0, kv, layer, nullptr, nullptr, 0, ao));
-    ST_TRY(stt_gemm(s, ao, M, SPW(s, p + ".wo"), SVEC(s, p + ".bo"), ACT_NONE, x, x));
+    RT_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln1_w"), SVEC(s, p + ".ln1_b"), xn));
+    RT_TRY(stt_gemm(s, xn, M, SPW(s, p + ".wqkv"), SVEC(s, p + ".bqkv"), ACT_NONE, nullptr, qkv));
+    RT_TRY(launch_qkv_post(ctx, qkv, 1, M, H, H, d, nullptr, nullptr, 0.f, nullptr, nullptr, slot, wpos, pos_add, q, kv, layer));
+    RT_TRY(launch_attention(ctx, q, M, H, H, d, slot, apos, apos == wpos ? pos_add : 0, 0, kv, layer, nullptr, nullptr, 0, ao));
+    RT_TRY(stt_gemm(s, ao, M, SPW(s, p + ".wo"), SVEC(s, p + ".bo"), ACT_NONE, x, x));
     if (cross) {
-        ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".lnc_w"), SVEC(s, p + ".lnc_b"), xn));
-        ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".cwq"), SVEC(s, p + ".cbq"), ACT_NONE, nullptr, q));
-        ST_TRY(launch_attention(ctx, q, M, H, H, d, cross_slot, cross_last, 0, 0, *cross, layer, nullptr, nullptr, 0, ao));
-        ST_TRY(stt_gemm(s, ao, M, SPW(s, p + ".cwo"), SVEC(s, p + ".cbo"), ACT_NONE, x, x));
+        RT_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".lnc_w"), SVEC(s, p + ".lnc_b"), xn));
+        RT_TRY(stt_gemm(s, xn, M, SPW(s, p + ".cwq"), SVEC(s, p + ".cbq"), ACT_NONE, nullptr, q));
+        RT_TRY(launch_attention(ctx, q, M, H, H, d, cross_slot, cross_last, 0, 0, *cross, layer, nullptr, nullptr, 0, ao));
+        RT_TRY(stt_gemm(s, ao, M, SPW(s, p + ".cwo"), SVEC(s, p + ".cbo"), ACT_NONE, x, x));
     }
-    ST_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln2_w"), SVEC(s, p + ".ln2_b"), xn));
-    ST_TRY(stt_gemm(s, xn, M, SPW(s, p + ".fc1"), SVEC(s, p + ".fc1_b"), ACT_GELU, nullptr, ff));
-    ST_TRY(stt_gemm(s, ff, M, SPW(s, p + ".fc2"), SVEC(s, p + ".fc2_b"), ACT_NONE, x, x));
+    RT_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln2_w"), SVEC(s, p + ".ln2_b"), xn));
+    RT_TRY(stt_gemm(s, xn, M, SPW(s, p + ".fc1"), SVEC(s, p + ".fc1_b"), ACT_GELU, nullptr, ff));
+    RT_TRY(stt_gemm(s, ff, M, SPW(s, p + ".fc2"), SVEC(s, p + ".fc2_b"), ACT_NONE, x, x));
     return RT_OK;
 }
 
@@ -796,7 +739,7 @@ int stt_encode(rt_stt* s, SttEnc& w, int B) {
     {   // conv1: k = 3, pad 1, GELU, on [T2][n_mels]
         GemmA a; a.ptr = w.mel; a.is_f32 = 1; a.split = 1; a.M = (int64_t)B * T2; a.Cin = c.n_mels; a.taps = 3; a.tap_stride = 1; a.tap_offset = -1; a.rows_out = T2; a.rows_in = T2;
         GemmEpi e; e.bias = SVEC(s, "enc.conv1_b"); e.act = ACT_GELU; e.out_f32 = w.c1; e.ldc = D;
-        ST_TRY(launch_gemm(ctx, a, SPW(s, "enc.conv1"), e));
+        RT_TRY(launch_gemm(ctx, a, SPW(s, "enc.conv1"), e));
     }
     {   // conv2: k = 3, stride 2, pad 1, GELU, + positions.  Over rows [x[2t], x[2t+1]] it is the 2-tap GEMM (row t-1, row t) with the
         // weight laid out as [0 | W0 | W1 | W2]
@@ -807,16 +750,16 @@ int stt_encode(rt_stt* s, SttEnc& w, int B) {
             RT_HIP(ctx, hipGetLastError());
             e.residual = k.x;
         }
-        ST_TRY(launch_gemm(ctx, a, SPW(s, "enc.conv2"), e));
+        RT_TRY(launch_gemm(ctx, a, SPW(s, "enc.conv2"), e));
     }
     const int M = B * T;
-    for (int i = 0; i < c.enc_layers; ++i) ST_TRY(stt_layer(s, "enc.l" + std::to_string(i), k, M, w.kv, i, w.slot, w.pos, w.last, 0));
-    ST_TRY(stt_ln(s, k.x, D, M, SVEC(s, "enc.ln_w"), SVEC(s, "enc.ln_b"), w.out));
+    for (int i = 0; i < c.enc_layers; ++i) RT_TRY(stt_layer(s, "enc.l" + std::to_string(i), k, M, w.kv, i, w.slot, w.pos, w.last, 0));
+    RT_TRY(stt_ln(s, k.x, D, M, SVEC(s, "enc.ln_w"), SVEC(s, "enc.ln_b"), w.out));
     // cross-attention K / V of every decoder layer (k_proj has no bias: its half of cbkv is zero)
     for (int i = 0; i < c.dec_layers; ++i) {
         const std::string p = "dec.l" + std::to_string(i);
-        ST_TRY(stt_gemm(s, w.out, M, SPW(s, p + ".cwkv"), SVEC(s, p + ".cbkv"), ACT_NONE, nullptr, k.qkv));
-        ST_TRY(launch_qkv_post(ctx, k.qkv, 1, M, 0, c.heads, D / c.heads, nullptr, nullptr, 0.f, nullptr, nullptr, w.slot, w.pos, 0, k.q, w.cross_kv, i));
+        RT_TRY(stt_gemm(s, w.out, M, SPW(s, p + ".cwkv"), SVEC(s, p + ".cbkv"), ACT_NONE, nullptr, k.qkv));
+        RT_TRY(launch_qkv_post(ctx, k.qkv, 1, M, 0, c.heads, D / c.heads, nullptr, nullptr, 0.f, nullptr, nullptr, w.slot, w.pos, 0, k.q, w.cross_kv, i));
     }
     return RT_OK;
 }
@@ -831,9 +774,9 @@ int stt_decode_rows(rt_stt* s, const SttDec& d, const KvCache& cross, int B, int
     SttSlot* tok = stt_find(s, "dec.tok");
     hipLaunchKernelGGL(k_stt_embed, dim3(M), dim3(128), 0, ctx->stream, tok->tbl, SVEC(s, "dec.pos"), d.tok, pos0, per, D, k.x);
     RT_HIP(ctx, hipGetLastError());
-    for (int i = 0; i < c.dec_layers; ++i) ST_TRY(stt_layer(s, "dec.l" + std::to_string(i), k, M, d.kv, i, slot, pos, pos, pos0, &cross, cross_slot, d.enc_last));
-    ST_TRY(stt_ln(s, k.x + (size_t)(per - 1) * D, (int64_t)per * D, B, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), k.xn));
-    ST_TRY(stt_gemm(s, k.xn, B, tok->pw, nullptr, ACT_NONE, nullptr, d.logits));
+    for (int i = 0; i < c.dec_layers; ++i) RT_TRY(stt_layer(s, "dec.l" + std::to_string(i), k, M, d.kv, i, slot, pos, pos, pos0, &cross, cross_slot, d.enc_last));
+    RT_TRY(stt_ln(s, k.x + (size_t)(per - 1) * D, (int64_t)per * D, B, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), k.xn));
+    RT_TRY(stt_gemm(s, k.xn, B, tok->pw, nullptr, ACT_NONE, nullptr, d.logits));
     return RT_OK;
 }
 
@@ -852,7 +795,7 @@ int stt_decode_group(rt_stt* s, int B, int budget, std::vector<std::vector<int32
     SttGroup& w = s->grp;
     const int P = c.n_prefix;
     w.dec.tok = w.d_prefix;
-    ST_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, B, P, 0, w.pre_slot, w.pre_pos, w.pre_slot));
+    RT_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, B, P, 0, w.pre_slot, w.pre_pos, w.pre_slot));
     if (d_first_logits) RT_HIP(ctx, hipMemcpyAsync(d_first_logits, w.dec.logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
     w.dec.tok = w.d_tok;
     ids.assign(B, {});
@@ -870,7 +813,7 @@ int stt_decode_group(rt_stt* s, int B, int budget, std::vector<std::vector<int32
             else ids[b].push_back(s->h_tok[b]);
         }
         if (live <= 0) break;
-        if (step + 1 < budget) ST_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, B, 1, P + step, w.step_slot, w.step_pos, w.step_slot));
+        if (step + 1 < budget) RT_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, B, 1, P + step, w.step_slot, w.step_pos, w.step_slot));
     }
     return RT_OK;
 }
@@ -885,7 +828,7 @@ int stt_transcribe_greedy(rt_stt* s, const float* const* d_pcm, const int64_t* n
     std::vector<SttSpan> all, group;
     stt_cut(c, sr, d_pcm, n_samples, n_clips, all);
     std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
-    ST_TRY(stt_group_reserve(s, (int)std::min<size_t>(all.size(), STT_GROUP)));
+    RT_TRY(stt_group_reserve(s, (int)std::min<size_t>(all.size(), STT_GROUP)));
     const int budget = std::min(std::min(c.max_new_tokens, c.n_text_ctx - c.n_prefix), cap);
     std::vector<std::vector<int32_t>> ids;
     for (size_t next = 0; next < all.size();) {
@@ -894,9 +837,9 @@ int stt_transcribe_greedy(rt_stt* s, const float* const* d_pcm, const int64_t* n
             if (h_n_tokens[all[next].clip] < cap) group.push_back(all[next]);
         if (group.empty()) break;
         const int B = (int)group.size();
-        ST_TRY(stt_features_group(s, group.data(), B, sr));
-        ST_TRY(stt_encode(s, s->grp.enc, B));
-        ST_TRY(stt_decode_group(s, B, budget, ids, d_first_logits));
+        RT_TRY(stt_features_group(s, group.data(), B, sr));
+        RT_TRY(stt_encode(s, s->grp.enc, B));
+        RT_TRY(stt_decode_group(s, B, budget, ids, d_first_logits));
         d_first_logits = nullptr;
         for (int b = 0; b < B; ++b) {
             const int i = group[b].clip;
@@ -928,12 +871,12 @@ int stt_beam_reserve(rt_stt* s, int rows) {
     return stt_reserve(s, s->beam, [&](SttBeam& nb) -> int {
         const rt_stt_config& c = s->cfg;
         const size_t r = (size_t)rows, rp = r * c.n_prefix;
-        ST_TRY(stt_alloc_dec(s, nb.owned, rows, nb.dec));
-        ST_TRY(stt_kv(s, nb.owned, nb.kv_next, c.dec_layers, rows, c.n_text_ctx));
-        ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_slot)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_pos)); ST_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_win));
-        ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_slot)); ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_win)); ST_TRY(stt_alloc(s, nb.owned, r, &nb.row_pos));
+        RT_TRY(stt_alloc_dec(s, nb.owned, rows, nb.dec));
+        RT_TRY(stt_kv(s, nb.owned, nb.kv_next, c.dec_layers, rows, c.n_text_ctx));
+        RT_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_slot)); RT_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_pos)); RT_TRY(stt_alloc(s, nb.owned, rp, &nb.pre_win));
+        RT_TRY(stt_alloc(s, nb.owned, r, &nb.row_slot)); RT_TRY(stt_alloc(s, nb.owned, r, &nb.row_win)); RT_TRY(stt_alloc(s, nb.owned, r, &nb.row_pos));
         nb.book_n = stt_beam_book_words(rows, c.max_new_tokens);
-        ST_TRY(stt_alloc(s, nb.owned, nb.book_n, &nb.book_mem));
+        RT_TRY(stt_alloc(s, nb.owned, nb.book_n, &nb.book_mem));
         nb.book = stt_beam_book(nb.book_mem, rows, c.max_new_tokens);
         hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, s->ctx->stream, nb.row_pos, rows, 0, 0);
         RT_HIP(s->ctx, hipGetLastError());
@@ -974,7 +917,7 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
     hipLaunchKernelGGL(k_stt_fill_beam_rows, dim3(1), dim3(256), 0, ctx->stream, bm.pre_slot, bm.pre_pos, bm.pre_win, nW * P, P, B, bm.row_slot, bm.row_win, rows);
     RT_HIP(ctx, hipGetLastError());
     bm.dec.tok = s->grp.d_prefix;                // (the forced prefix of every window: the group keeps it)
-    ST_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
+    RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
     const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
     int steps = 0;
     for (int step = 0; step < budget; ++step) {
@@ -986,10 +929,10 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
         RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (live <= 0 || step + 1 >= budget) break;
-        ST_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, P + step));
+        RT_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, P + step));
         std::swap(bm.dec.kv, bm.kv_next);
         bm.dec.tok = bk.next_tok;
-        ST_TRY(stt_decode_rows(s, bm.dec, cross, rows, 1, P + step, bm.row_slot, bm.row_pos, bm.row_win));
+        RT_TRY(stt_decode_rows(s, bm.dec, cross, rows, 1, P + step, bm.row_slot, bm.row_pos, bm.row_win));
     }
     s->h_book.resize(bm.book_n);
     RT_HIP(ctx, hipMemcpyAsync(s->h_book.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1069,7 +1012,7 @@ int rt_stt_destroy(rt_stt* s) {
     for (auto& sl : s->slots) { if (sl.raw) (void)hipFree(sl.raw); if (sl.raw2) (void)hipFree(sl.raw2); }
     for (auto* owned : {&s->owned, &s->grp.owned, &s->beam.owned})
         for (void* p : *owned) (void)hipFree(p);
-    if (s->d_resamp) (void)hipFree(s->d_resamp);
+    if (s->rs.d_h) (void)hipFree(s->rs.d_h);
     delete s;
     return RT_OK;
 }
@@ -1101,7 +1044,7 @@ int rt_stt_set_tensor(rt_stt* s, const char* name, const void* data, int32_t dty
     const void* d_src = data;
     if (!on_device) {
         void* stage = nullptr;
-        ST_TRY(rt_ctx_scratch(ctx, (size_t)n * esz, &stage));
+        RT_TRY(rt_ctx_scratch(ctx, (size_t)n * esz, &stage));
         RT_HIP(ctx, hipMemcpyAsync(stage, data, (size_t)n * esz, hipMemcpyHostToDevice, ctx->stream));
         d_src = stage;
     }
@@ -1110,7 +1053,7 @@ int rt_stt_set_tensor(rt_stt* s, const char* name, const void* data, int32_t dty
     if (sl->kind == S_GEMM || sl->kind == S_TABLE) {
         void** packed = sl->kind == S_GEMM ? &sl->raw : &sl->raw2;
         RT_HIP(ctx, hipMalloc(packed, packed_bytes((int)rows, (int)cols)));
-        ST_TRY(launch_pack_weight(ctx, (const bf16_t*)d_src, (int)rows, (int)cols, (bf16_t*)*packed, &sl->pw));
+        RT_TRY(launch_pack_weight(ctx, (const bf16_t*)d_src, (int)rows, (int)cols, (bf16_t*)*packed, &sl->pw));
         if (sl->kind == S_TABLE) {
             RT_HIP(ctx, hipMalloc(&sl->raw, (size_t)n * 2));
             RT_HIP(ctx, hipMemcpyAsync(sl->raw, d_src, (size_t)n * 2, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1139,12 +1082,12 @@ int rt_stt_finalize(rt_stt* s) {
     const rt_stt_config& c = s->cfg;
     std::vector<double> tc(c.n_fft), ts(c.n_fft);
     for (int n = 0; n < c.n_fft; ++n) { tc[n] = std::cos(2.0 * M_PI * n / c.n_fft); ts[n] = std::sin(2.0 * M_PI * n / c.n_fft); }
-    ST_TRY(stt_alloc(s, s->owned, (size_t)c.n_fft, &s->d_twc)); ST_TRY(stt_alloc(s, s->owned, (size_t)c.n_fft, &s->d_tws));
+    RT_TRY(stt_alloc(s, s->owned, (size_t)c.n_fft, &s->d_twc)); RT_TRY(stt_alloc(s, s->owned, (size_t)c.n_fft, &s->d_tws));
     RT_HIP(ctx, hipMemcpy(s->d_twc, tc.data(), c.n_fft * 8, hipMemcpyHostToDevice));
     RT_HIP(ctx, hipMemcpy(s->d_tws, ts.data(), c.n_fft * 8, hipMemcpyHostToDevice));
     s->d_window = SVEC(s, "fe.window");
     s->d_melT = SVEC(s, "fe.melT");
-    ST_TRY(stt_group_reserve(s, 1));                                 // a model that does not fit fails here, and the first call pays no allocation
+    RT_TRY(stt_group_reserve(s, 1));                                 // a model that does not fit fails here, and the first call pays no allocation
     // suppression mask: bit 0 = never (ids >= suppress_from except end-of-sequence), bit 1 = not as the first generated token
     std::vector<uint8_t> mask(c.vocab, 0);
     for (int i = 0; i < c.vocab; ++i)
@@ -1153,7 +1096,7 @@ int rt_stt_finalize(rt_stt* s) {
         if (c.begin_suppress[i] >= 0 && c.begin_suppress[i] < c.vocab) mask[c.begin_suppress[i]] |= 2;
     for (int32_t id : s->suppress_ids)
         if (id >= 0 && id < c.vocab && id != c.eos_id) mask[id] |= 1;
-    ST_TRY(stt_alloc(s, s->owned, (size_t)c.vocab, &s->d_mask));
+    RT_TRY(stt_alloc(s, s->owned, (size_t)c.vocab, &s->d_mask));
     RT_HIP(ctx, hipMemcpy(s->d_mask, mask.data(), c.vocab, hipMemcpyHostToDevice));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->finalized = true;
@@ -1167,8 +1110,8 @@ int rt_stt_log_mel(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t sam
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_log_mel: not finalized");
     const SttSpan clip{0, d_pcm, n_samples};                         // (uncut: the resampler's taps at the end of the chunk see the samples behind it)
-    ST_TRY(stt_group_reserve(s, 1));
-    ST_TRY(stt_features_group(s, &clip, 1, sample_rate));
+    RT_TRY(stt_group_reserve(s, 1));
+    RT_TRY(stt_features_group(s, &clip, 1, sample_rate));
     RT_HIP(ctx, hipMemcpyAsync(d_mel, s->grp.enc.mel, (size_t)2 * s->cfg.n_ctx * s->cfg.n_mels * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
@@ -1181,9 +1124,9 @@ int rt_stt_encode(rt_stt* s, const float* d_pcm, int64_t n_samples, int32_t samp
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_encode: not finalized");
     const SttSpan clip{0, d_pcm, n_samples};                         // (uncut, as rt_stt_log_mel)
-    ST_TRY(stt_group_reserve(s, 1));
-    ST_TRY(stt_features_group(s, &clip, 1, sample_rate));
-    ST_TRY(stt_encode(s, s->grp.enc, 1));
+    RT_TRY(stt_group_reserve(s, 1));
+    RT_TRY(stt_features_group(s, &clip, 1, sample_rate));
+    RT_TRY(stt_encode(s, s->grp.enc, 1));
     RT_HIP(ctx, hipMemcpyAsync(d_states, s->grp.enc.out, (size_t)s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
@@ -1243,16 +1186,16 @@ int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* 
     std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
     const size_t per_group = (size_t)(STT_GROUP / beam_size);
     const int most = (int)std::min(all.size(), per_group);
-    ST_TRY(stt_group_reserve(s, most));
-    ST_TRY(stt_beam_reserve(s, most * beam_size));
+    RT_TRY(stt_group_reserve(s, most));
+    RT_TRY(stt_beam_reserve(s, most * beam_size));
     std::vector<double> sum(n_clips, 0.0);
     std::vector<int64_t> count(n_clips, 0);
     std::vector<SttHyp> hyps;
     for (size_t next = 0; next < all.size(); next += per_group) {
         const int nW = (int)std::min(per_group, all.size() - next);
-        ST_TRY(stt_features_group(s, all.data() + next, nW, sample_rate));
-        ST_TRY(stt_encode(s, s->grp.enc, nW));
-        ST_TRY(stt_decode_beam_group(s, nW, beam_size, hyps));
+        RT_TRY(stt_features_group(s, all.data() + next, nW, sample_rate));
+        RT_TRY(stt_encode(s, s->grp.enc, nW));
+        RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps));
         for (int b = 0; b < nW; ++b) {
             const int i = all[next + b].clip;
             for (int32_t t : hyps[b].ids)
@@ -1285,7 +1228,7 @@ int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_stride,
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_beam_step: not finalized");
     const int R = n_windows * beam;
-    ST_TRY(stt_beam_reserve(s, R));
+    RT_TRY(stt_beam_reserve(s, R));
     SttBeam& bm = s->beam;
     const SttBeamBook& bk = bm.book;
     std::vector<int32_t>& hb = s->h_book;
@@ -1336,7 +1279,7 @@ int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t
         a.layers = b.layers = layers; a.slots = b.slots = rows; a.kv_heads = b.kv_heads = heads; a.max_pos = b.max_pos = max_pos; a.head_dim = b.head_dim = head_dim;
         a.k = d; a.v = d + n; a.k_lo = d + 2 * n; a.v_lo = d + 3 * n;
         b.k = d + 4 * n; b.v = d + 5 * n; b.k_lo = d + 6 * n; b.v_lo = d + 7 * n;
-        ST_TRY(stt_beam_reorder(ctx, a, b, d_src, rows, len));
+        RT_TRY(stt_beam_reorder(ctx, a, b, d_src, rows, len));
         RT_HIP(ctx, hipMemcpyAsync(h_planes, d, 8 * n * 2, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return RT_OK;
@@ -1357,9 +1300,9 @@ int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_encode_batch: not finalized");
     std::vector<SttSpan> group;
     stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, group, true);
-    ST_TRY(stt_group_reserve(s, n_clips));
-    ST_TRY(stt_features_group(s, group.data(), n_clips, sample_rate));
-    ST_TRY(stt_encode(s, s->grp.enc, n_clips));
+    RT_TRY(stt_group_reserve(s, n_clips));
+    RT_TRY(stt_features_group(s, group.data(), n_clips, sample_rate));
+    RT_TRY(stt_encode(s, s->grp.enc, n_clips));
     RT_HIP(ctx, hipMemcpyAsync(d_states, s->grp.enc.out, (size_t)n_clips * s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;

@@ -8,6 +8,7 @@ MFCC, the pYIN difference function, Burg LPC).  The single-clip path (``Handcraf
 host - trough statistics and Viterbi pass over the [frames][329] difference function - and these host functions are the
 definition of the two kernels that do the same for a whole chunk of clips in one native call (``HandcraftedFeatures.batch``,
 ``rt_features_extract_batch``): there the host is left with the F0 statistics and the roots of one degree-18 polynomial per clip.
+Natively the two calls are one path - the single-clip call is the batched one with one clip and without the two back-half kernels.
 
 The 256-d embedding is NOT produced: resemblyzer's network is a pretrained checkpoint (no weights offline), and the classifier
 itself is a pickled scikit-learn model this build will not load.  ``make_drift_scorer`` therefore takes the classifier as a
@@ -239,15 +240,26 @@ class HandcraftedFeatures:
             self.lib.rt_features_destroy(self.handle)
             self.handle = None
 
+    def _stage(self, audios: Sequence, sample_rate: int):
+        """The clips as flat float32 tensors on the context's GPU, written (the current stream is synchronised), and room for the
+        frames of the longest: what both native calls take."""
+        dev = torch.device(f"cuda:{self.ctx.device_ordinal}")
+        xs = []
+        for audio in audios:
+            x = audio if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio, dtype=np.float32))
+            x = x.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if x.numel() < 2:
+                raise ValueError("feature extraction needs at least two samples")
+            xs.append(x)
+        if not xs:
+            return xs, 0
+        torch.cuda.current_stream(dev).synchronize()
+        sr = int(sample_rate)
+        return xs, 2 + max(-(-int(x.numel()) * SR // sr) if sr != SR else int(x.numel()) for x in xs) // HOP
+
     def raw(self, audio, sample_rate: int):
         """(mfcc mean+std [26], cmnd [frames][lags], lpc [order + 1]) - what comes off the GPU."""
-        x = audio if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio, dtype=np.float32))
-        x = x.detach().to(device=f"cuda:{self.ctx.device_ordinal}", dtype=torch.float32).reshape(-1).contiguous()
-        if x.numel() < 2:
-            raise ValueError("feature extraction needs at least two samples")
-        torch.cuda.current_stream(x.device).synchronize()
-        n16 = -(-int(x.numel()) * SR // int(sample_rate)) if int(sample_rate) != SR else int(x.numel())
-        cap = 2 + n16 // HOP
+        (x,), cap = self._stage([audio], sample_rate)
         n_lags = self.max_period - self.min_period + 1
         stats = (C.c_double * 26)()
         cmnd = np.zeros((cap, n_lags), dtype=np.float64)
@@ -277,20 +289,10 @@ class HandcraftedFeatures:
         """(mfcc statistics [n][26], lpc [n][order + 1], state paths: n arrays of one state per pitch frame)."""
         if self.n_bins is None:
             self.set_pitch_model()
-        dev = f"cuda:{self.ctx.device_ordinal}"
-        xs = []
-        for audio in audios:
-            x = audio if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio, dtype=np.float32))
-            x = x.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-            if x.numel() < 2:
-                raise ValueError("feature extraction needs at least two samples")
-            xs.append(x)
+        xs, cap = self._stage(audios, sample_rate)
         n = len(xs)
         if n == 0:
             return np.zeros((0, 26)), np.zeros((0, LPC_ORDER + 1)), []
-        torch.cuda.current_stream(torch.device(dev)).synchronize()
-        sr = int(sample_rate)
-        cap = 2 + max(-(-int(x.numel()) * SR // sr) if sr != SR else int(x.numel()) for x in xs) // HOP
         ptrs = (C.c_void_p * n)(*[x.data_ptr() for x in xs])
         lens = (C.c_int64 * n)(*[int(x.numel()) for x in xs])
         stats = np.zeros((n, 26), dtype=np.float64)
@@ -298,7 +300,7 @@ class HandcraftedFeatures:
         states = np.zeros((n, cap), dtype=np.int32)
         npf = (C.c_int32 * n)()
         pd = C.POINTER(C.c_double)
-        self.ctx.check(self.lib.rt_features_extract_batch(self.handle, ptrs, lens, n, sr, self.min_period, self.max_period, LPC_ORDER,
+        self.ctx.check(self.lib.rt_features_extract_batch(self.handle, ptrs, lens, n, int(sample_rate), self.min_period, self.max_period, LPC_ORDER,
                                                           stats.ctypes.data_as(pd), lpc.ctypes.data_as(pd), states.ctypes.data_as(C.POINTER(C.c_int32)),
                                                           cap, npf), "rt_features_extract_batch")
         return stats, lpc, [states[c, : npf[c]].astype(np.int64) for c in range(n)]

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Drift features of one validation chunk: the per-clip path (HandcraftedFeatures.__call__: difference function off the GPU, pYIN's
-back half on the host, one host synchronisation per clip) against HandcraftedFeatures.batch (one native call, pYIN's back half in
-HIP kernels, one synchronisation per chunk).  32 synthetic voiced clips of 4 s at 24 kHz, in HBM; five alternating pairs in one
-process; both outputs are compared before anything is timed.
+"""Drift features of one validation chunk: the per-clip loop (HandcraftedFeatures.__call__: one native call per clip, difference
+function off the GPU, pYIN's back half on the host, one host synchronisation per clip) against HandcraftedFeatures.batch (one native
+call, one launch per stage for the whole chunk, pYIN's back half in HIP kernels, one synchronisation per chunk).  Both go through the
+same native path and the same workspace set of one handle, alternately - so the loop also exercises a one-clip call after a 32-clip
+one.  32 synthetic voiced clips of 4 s at 24 kHz, in HBM; five alternating pairs in one process; both outputs are compared before
+anything is timed.
     python tools/bench_features.py [n_clips] [seconds]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
