@@ -506,6 +506,43 @@ RT_API int rt_forest_set_model(rt_forest* f, int32_t n_features, int32_t n_fores
                                const double* h_iso_y);
 RT_API int rt_forest_predict(rt_forest* f, const double* h_x, int32_t n_rows, double* h_prob);
 
+/* ------------------------------------------------------------------ speaker embedding: the GE2E encoder
+ * Stands behind resemblyzer's VoiceEncoder.embed_utterance(preprocess_wav(...)) as the reference calls it for the first 256 of the
+ * drift classifier's 286 dimensions (validation/classifier/trainer.py:23-68) and for _compute_speaker_similarity
+ * (base_tts.py:325-346), on the waveform where it lives.  The definition is resemblyzer 0.1.x restated; parity with resemblyzer is
+ * UNPINNED (neither it, webrtcvad, librosa nor pretrained weights are available offline).  Stages, in order:
+ *   resample to 16 kHz (the resampler of the speech-to-text and feature front ends);
+ *   normalize_volume(-30 dBFS, increase_only): rms over the clip in float64; below -30 dBFS the clip is multiplied by
+ *     10^((-30 - 20 log10 rms) / 20).  DEVIATION: rms == 0 leaves the clip unchanged (resemblyzer yields NaN);
+ *   trim_long_silences, ONLY for a clip with voice flags: one 0 / 1 flag per 480-sample window of the 16-kHz clip, which resemblyzer
+ *     takes from webrtcvad (mode 3) and this library from the caller - it restates no VAD.  The clip is cut to a multiple of 480,
+ *     the flags are averaged over 8 windows (3 zeros in front, 4 behind), rounded half to even, dilated by seven ones, and the
+ *     windows whose mask is 1 are kept.  DEVIATION (the default): without flags nothing is cut.  A mask that keeps nothing gives one
+ *     partial of zeros;
+ *   partial utterances (rate 1.3, min_coverage 0.75): n_frames = ceil((n + 1) / 160), partial i = mel frames [77 i, 77 i + 160) for
+ *     77 i < max(1, n_frames - 160 + 77 + 1); the last is dropped when it covers less than 0.75 of its 25600 samples and is not the
+ *     only one; the clip is zero-padded to the last partial's end;
+ *   mel: n_fft 400, hop 160, zero-padded centre, periodic Hann, float64 DFT, power spectrum, 40 slaney filters to 8 kHz, no log;
+ *   torch.nn.LSTM(40, 256, num_layers = 3) from a zero state (gates i, f, g, o; two biases), per partial
+ *     e = relu(W h_T + b), e / |e|; per clip the mean of its partial embeddings, divided by its norm (zero norm: zeros, not NaN).
+ * rt_spk_set_tensor takes float32 host arrays under torch's names - lstm.weight_ih_l{0,1,2} [1024][40 | 256], lstm.weight_hh_l*
+ * [1024][256], lstm.bias_ih_l*, lstm.bias_hh_l* [1024][1], linear.weight [256][256], linear.bias [256][1] - and the two front-end
+ * tables mel.filters [201][40] and mel.window [400][1]; a wrong name or shape or a value that is not finite is RT_ERR_INVALID.
+ * rt_spk_finalize packs and uploads them (RT_ERR_STATE when one is missing); calls before it are RT_ERR_STATE.
+ * rt_spk_embed_batch: n_clips waveforms in HBM (d_pcm[c]: n_samples[c] floats at sample_rate_in) -> h_embed [n_clips][256] float32 and
+ * h_n_partials [n_clips], with one launch per stage (the recurrent stage: one per layer, over tiles of 16 partials from whichever
+ * clips), one stream synchronisation and one set of copies whatever n_clips is.  A clip's bits are the same alone, in any batch
+ * and at any place in it.  h_voice_flags may be NULL (no clip is trimmed) and so may any h_voice_flags[c]; n_voice_flags[c] must
+ * then be the clip's window count n16 / 480.  Every clip is checked on the host before anything is launched.  RT_ERR_INVALID: an
+ * empty clip, a flag count that differs from n16 / 480, more than 65535 clips or 4096 partials in one call. */
+typedef struct rt_spk rt_spk;
+RT_API int rt_spk_create(rt_ctx* ctx, rt_spk** out);
+RT_API int rt_spk_destroy(rt_spk* s);
+RT_API int rt_spk_set_tensor(rt_spk* s, const char* name, const float* h_data, int64_t rows, int64_t cols);
+RT_API int rt_spk_finalize(rt_spk* s);
+RT_API int rt_spk_embed_batch(rt_spk* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
+                              const uint8_t* const* h_voice_flags, const int32_t* n_voice_flags, float* h_embed, int32_t* h_n_partials);
+
 /* Measurement and test entry points (rt_profile_*, rt_debug_*, rt_bench_*) are declared in rho_tts_amd_debug.h: a host binding of
  * the generation path needs none of them. */
 

@@ -96,6 +96,17 @@ RT_API int rt_debug_features_observe(rt_features* f, const double* h_cmnd, int32
 RT_API int rt_debug_features_viterbi(rt_features* f, const double* h_log_obs, const int32_t* h_n_frames, int32_t n_clips, int32_t* h_states,
                                      int32_t stride);
 
+/* The stages of the speaker encoder on their own (tests/test_speaker_embed_gpu.py); the encoder must be finalized.  One stream
+ * synchronisation per call.
+ * rt_debug_spk_mel: one clip in HBM through the front end of rt_spk_embed_batch (resample, volume, optional trim with h_voice_flags
+ *   [n_voice_flags], zero padding to the last partial's end) -> h_mel [frames][40] float32, frames = 1 + padded length / 160
+ *   (RT_ERR_LENGTH above cap_frames), and h_n16 = the 16-kHz length after preprocessing, before the padding.
+ * rt_debug_spk_lstm: h_partials [n_partials][160][40] float32 on the HOST -> h_embed [n_partials][256], the unit-norm embedding of
+ *   every partial (three LSTM layers, projection, ReLU, norm). */
+RT_API int rt_debug_spk_mel(rt_spk* s, const float* d_pcm, int64_t n_samples, int32_t sample_rate_in, const uint8_t* h_voice_flags,
+                            int32_t n_voice_flags, float* h_mel, int32_t cap_frames, int32_t* h_n_frames, int64_t* h_n16);
+RT_API int rt_debug_spk_lstm(rt_spk* s, const float* h_partials, int32_t n_partials, float* h_embed);
+
 /* The speech-to-text path below the ids with more than one row (tests/test_stt_batch_gpu.py): the first window of n_clips clips (at
  * most one group, 32) through the front end and encoder -> d_states [n_clips][n_ctx][d_model] float32 in HBM.  Clip i's states
  * among the n_clips rows are, bit for bit, what rt_stt_encode gives for that window as the only row (the first chunk_seconds of the

@@ -23,7 +23,8 @@ CXXFLAGS = ["-std=c++17", "-O3", "-fPIC", "-fvisibility=hidden", f"--offload-arc
 # Translation units whose float results are compared bit-for-bit with the CPU reference
 # must not have mul+add fused behind their back.
 PER_FILE = {"postprocess.hip": ["-ffp-contract=off"], "encoder.hip": ["-ffp-contract=off"], "features.hip": ["-ffp-contract=off"],
-            "speedpitch.hip": ["-ffp-contract=off"], "forest.hip": ["-ffp-contract=off"]}
+            "speedpitch.hip": ["-ffp-contract=off"], "forest.hip": ["-ffp-contract=off"],
+            "speaker.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -10,10 +10,12 @@ definition of the two kernels that do the same for a whole chunk of clips in one
 ``rt_features_extract_batch``): there the host is left with the F0 statistics and the roots of one degree-18 polynomial per clip.
 Natively the two calls are one path - the single-clip call is the batched one with one clip and without the two back-half kernels.
 
-The 256-d embedding is NOT produced: resemblyzer's network is a pretrained checkpoint (no weights offline), and the classifier
-itself is a pickled scikit-learn model this build will not load.  ``make_drift_scorer`` therefore takes the classifier as a
-callable on the 30 dimensions (or on whatever vector the caller assembles around them); ``make_forest_scorer`` takes it as a
-``forest.DriftForest`` - the same model exported to plain arrays, evaluated on the GPU for a whole chunk in one call.
+The 256-d embedding is produced by ``speaker.SpeakerEmbedder`` (csrc/speaker.hip: resemblyzer's GE2E encoder restated, parity
+unpinned, weights from an exported ``.npz``), not here: an instance is the ``embed`` argument of ``make_forest_scorer``, which puts
+its 256 dimensions in front of the 30.  The classifier itself is a pickled scikit-learn model this build will not load:
+``make_drift_scorer`` takes it as a callable on the 30 dimensions (or on whatever vector the caller assembles around them);
+``make_forest_scorer`` takes it as a ``forest.DriftForest`` - the same model exported to plain arrays, evaluated on the GPU for a
+whole chunk in one call.
 
 Definitions: librosa 0.10's defaults as the reference calls them, restated (oracle/features.py says which) - including the
 reference's own quirk of leaving ``librosa.pyin``'s default ``sr=22050`` in place for 16-kHz audio, so that every F0 is

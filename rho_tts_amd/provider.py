@@ -615,7 +615,8 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
                  max_chars_per_segment: Optional[int] = None, batch_size: int = 32, max_iterations: int = 10,
                  accent_drift_threshold: float = 0.17, text_similarity_threshold: float = 0.85,
                  sound_decay_threshold: float = 0.3, drift_model_path: Optional[str] = None,
-                 phonetic_mapping: Optional[Dict[str, str]] = None):
+                 phonetic_mapping: Optional[Dict[str, str]] = None, speaker_encoder_path: Optional[str] = None,
+                 speaker_similarity: str = "model"):
         # Defaults are QwenTTS.__init__'s (providers/qwen.py:48-66) with ONE deviation: batch_size 32 instead of 5.  The reference
         # stores batch_size and never reads it (qwen.py:59,83), so no behaviour of its can depend on the value; here it is the
         # number of decode rows (BASELINE.json's headline batch).  max_iterations keeps the reference's 10: a caller who swaps
@@ -632,6 +633,17 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         self.voice_cloning = reference_audio is not None
         self.model_path = model_path
         self.drift_model_path = drift_model_path
+        # The GE2E speaker encoder (speaker.SpeakerEmbedder; the .npz of tools/export_speaker_encoder.py).  With it a drift classifier
+        # of 256 + 30 features needs no drift_embed, and speaker_similarity="ge2e" answers _compute_speaker_similarity with the
+        # reference's arithmetic.  Without it (the default) nothing changes.
+        if speaker_similarity not in ("model", "ge2e"):
+            raise ValueError(f"speaker_similarity = {speaker_similarity!r}: 'model' (the talker's own speaker encoder) or 'ge2e'")
+        if speaker_similarity == "ge2e" and not speaker_encoder_path:
+            raise ValueError("speaker_similarity='ge2e' needs speaker_encoder_path (the .npz written by tools/export_speaker_encoder.py)")
+        self.speaker_encoder_path = speaker_encoder_path
+        self.speaker_similarity = speaker_similarity
+        self._speaker_embedder = None                          # speaker.SpeakerEmbedder on this provider's context, made at first use
+        self._ge2e_ref = None                                  # (voice key, unit embedding of the reference clip)
         self._max_chars_explicit = max_chars_per_segment is not None
         self.max_chars_per_segment = max_chars_per_segment if max_chars_per_segment is not None else 1000
         self.batch_size = batch_size
@@ -734,7 +746,11 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         resemblyzer on the CPU and is never called by the reference's own pipeline).  Here both embeddings come from the model's
         OWN speaker encoder on the GPU - the statistics-pooling head of the audio encoder that also conditions the talker
         (rt_voice_encode) - so the score says how close the output is in the space the model itself clones from.  Not comparable
-        in value with resemblyzer's; same range and direction (1 = same voice)."""
+        in value with resemblyzer's; same range and direction (1 = same voice).
+        With ``speaker_similarity="ge2e"`` it is the reference's arithmetic instead: the dot product of the unit GE2E embeddings
+        (speaker.SpeakerEmbedder) of the reference clip and of the output; the reference clip's embedding is cached per voice."""
+        if self.speaker_similarity == "ge2e":
+            return self._ge2e_similarity(wav_tensor)
         eng = self._load_engine()
         with self._lock:
             self._ensure_voice(eng)
@@ -746,6 +762,29 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             _, emb = eng.model.encode_voice(pcm[:cap])
         ref = ref.detach().to(torch.float32).cpu().reshape(-1)
         return float(torch.dot(ref, emb) / (ref.norm() * emb.norm()).clamp_min(1e-12))
+
+    def _ge2e_reference_audio(self):
+        """(samples, sample rate) of the configured reference clip, as the voice cloning reads it."""
+        if not self.reference_audio_path:
+            raise ValueError("speaker similarity needs a cloned voice (reference audio with a Base model)")
+        import wave
+        from .voice import load_audio
+        path = str(self.reference_audio_path)
+        sr = self.sample_rate                                  # (a .npy clip is at the model's rate, as the cloning path takes it)
+        if not path.endswith(".npy"):
+            with wave.open(path, "rb") as wf:
+                sr = int(wf.getframerate())                    # the file's own rate: the encoder's resampler brings it to 16 kHz
+        return torch.from_numpy(load_audio(path, sr)), sr
+
+    def _ge2e_similarity(self, wav_tensor: torch.Tensor) -> float:
+        with self._lock:
+            emb = self._speaker_embed()
+            key = (self.reference_audio_path,)
+            if self._ge2e_ref is None or self._ge2e_ref[0] != key:
+                ref_pcm, ref_sr = self._ge2e_reference_audio()
+                self._ge2e_ref = (key, emb(ref_pcm, ref_sr).astype("float64"))
+            out = emb(wav_tensor.detach().reshape(-1), self.sample_rate).astype("float64")
+            return float(self._ge2e_ref[1] @ out)
 
     def _cut_batches(self, todo: List[int], work, bs: int) -> List[List[int]]:
         """The engine decodes any number of segments on its ``batch_size`` rows with continuous batching (finished rows are handed
@@ -947,7 +986,10 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             from .features import HandcraftedFeatures, make_forest_scorer
             tables = F.load(path)
             width = int(tables["n_features"])
-            if width != F.HANDCRAFTED and self.drift_embed is None:
+            embed = self.drift_embed
+            if embed is None and self.speaker_encoder_path and width != F.HANDCRAFTED:
+                embed = self._speaker_embed()                  # (a list of clips -> [n][256], dim = 256): one embedding call per chunk
+            if width != F.HANDCRAFTED and embed is None:
                 raise ValueError(f"drift_model_path = {path!r} takes {width} features: the {width - F.HANDCRAFTED} dimensions in front of the "
                                  f"{F.HANDCRAFTED} hand-crafted ones are the speaker embedding, which this provider does not compute - set "
                                  "drift_embed to a batch callable (audios, sample_rate) -> [n][k]")
@@ -958,7 +1000,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             try:
                 ex = HandcraftedFeatures(ctx)
                 forest = F.DriftForest(ctx, tables)
-                scorer = make_forest_scorer(ex, forest, self.drift_embed)
+                scorer = make_forest_scorer(ex, forest, embed)
             except Exception:
                 for h in (forest, ex):
                     if h is not None:
@@ -974,6 +1016,19 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             self._drift_native = None
             forest.close()
             ex.close()
+        if self._speaker_embedder is not None:                 # (it lives on the same context)
+            self._speaker_embedder.close()
+            self._speaker_embedder = None
+
+    def _speaker_embed(self):
+        """The GE2E encoder of ``speaker_encoder_path`` on this provider's context, built at first use."""
+        with self._lock:
+            if self._speaker_embedder is None:
+                if not self.speaker_encoder_path:
+                    raise ValueError("no speaker_encoder_path: the GE2E speaker encoder is not configured")
+                from .speaker import SpeakerEmbedder
+                self._speaker_embedder = SpeakerEmbedder(self._native_ctx(), str(self.speaker_encoder_path))
+            return self._speaker_embedder
 
     @property
     def sample_rate(self) -> int:
