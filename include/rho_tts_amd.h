@@ -382,6 +382,55 @@ RT_API int rt_stt_transcribe_batch(rt_stt* s, const float* const* d_pcm, const i
  * rt_stt_transcribe_batch, and a beam_size outside 1 .. 8. */
 RT_API int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
                                   int32_t beam_size, int32_t* h_tokens, int32_t max_tokens, int32_t* h_n_tokens, float* h_scores);
+/* Languages and silence ("language and no-speech").  For one window let z be the float32 logits over the whole
+ * vocabulary behind start-of-transcript ALONE (one decoder row at position 0 over the window's encoder states, nothing suppressed):
+ * the window's language is the configured id with the largest z (lowest id on ties, NaNs never), its probability the softmax of z
+ * over the configured ids, and the no-speech probability softmax(z) over the whole vocabulary at the no-speech id.  A clip's
+ * language is decided on its FIRST window and forced on every window of the clip.
+ * rt_stt_set_languages: the ids position 1 of the forced prefix may take (1 .. 128 of them) and the no-speech id.  Before
+ *   rt_stt_finalize, like rt_stt_set_suppress.  RT_ERR_INVALID: a configured prefix of fewer than two entries, prefix[1] not in the
+ *   list, an id outside the vocabulary.  A handle without languages transcribes as before and refuses the calls below that need them.
+ * rt_stt_detect_language: the first window of every clip through front end, encoder, probe pass and k_stt_probe, 32 windows at a
+ *   time -> per clip the language id, its probability and the no-speech probability (the last two optional). */
+RT_API int rt_stt_set_languages(rt_stt* s, const int32_t* h_lang_ids, int32_t n, int32_t no_speech_id);
+RT_API int rt_stt_detect_language(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
+                                  int32_t* h_lang, float* h_lang_prob, float* h_no_speech);
+/* rt_stt_transcribe_beam with options and a fuller report.  All pointers are host memory.
+ * opts: beam_size 1 .. 8 (1 gives the greedy ids); max_tokens caps every clip's joined ids; h_language [n_clips] or NULL - an entry
+ *   >= 0 forces that configured language id on the clip, -1 detects it; NULL: the handle's prefix, and - unless h_win_no_speech is
+ *   asked for - exactly the launches of rt_stt_transcribe_beam.  The probe pass (one more decoder pass of one row per window, and
+ *   one workgroup per window) runs when a clip detects or h_win_no_speech is given; the windows' prefixes are then written on the
+ *   device, with no host synchronisation before the prefix pass.  With every language given and no h_win_no_speech the prefixes
+ *   are copied in and no launch is added to those of rt_stt_transcribe_beam.
+ * out, per clip: h_tokens [n_clips][max_tokens], h_n_tokens, h_scores (optional) as rt_stt_transcribe_beam; h_language (optional)
+ *   the id at position 1 of the clip's prefix; h_language_prob (optional) its probability where it was detected, 1 where it was given.
+ *   Per window, in clip order, each optional, window_cap entries of room: h_win_clip the owning clip, h_win_n_ids the ids the window
+ *   decoded (before max_tokens cuts the clip's joined ids), h_win_logprob its hypothesis' cumulative log-probability (avg_logprob =
+ *   that / (ids + 1)), h_win_no_speech.  n_windows receives the number of windows.  The silence rule (a window is silent when
+ *   no_speech > threshold and avg_logprob < threshold) is the host's: rho_tts_amd/validation.py.
+ * RT_ERR_INVALID (nothing is launched, the handle stays usable): the argument rules of rt_stt_transcribe_beam; a language entry that
+ *   is neither -1 nor a configured id; h_language or h_win_no_speech on a handle without rt_stt_set_languages; window_cap below the
+ *   number of windows when a per-window array is given.  n_clips == 0: RT_OK, n_windows = 0. */
+typedef struct rt_stt_decode_opts {
+    const int32_t* h_language;
+    int32_t beam_size, max_tokens;
+    int32_t reserved[4];
+} rt_stt_decode_opts;
+typedef struct rt_stt_decode_out {
+    int32_t* h_tokens;
+    int32_t* h_n_tokens;
+    float* h_scores;
+    int32_t* h_language;
+    float* h_language_prob;
+    int32_t* h_win_clip;
+    int32_t* h_win_n_ids;
+    float* h_win_logprob;
+    float* h_win_no_speech;
+    int32_t window_cap, n_windows;
+    int32_t reserved[4];
+} rt_stt_decode_out;
+RT_API int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
+                                const rt_stt_decode_opts* opts, rt_stt_decode_out* out);
 /* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM:
  * row 0 of the same front end and encoder with the clip as its only window.  Of a clip longer than chunk_seconds the first
  * chunk is kept, and the resampler's taps at its end see the samples behind it. */

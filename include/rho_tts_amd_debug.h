@@ -131,6 +131,12 @@ RT_API int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_
 RT_API int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src,
                                      int32_t len, uint16_t* h_planes);
 
+/* k_stt_probe on logits the caller supplies (tests/test_stt_lang_kernel_gpu.py): n_rows (1 .. 32) rows of cfg.vocab float32 in HBM,
+ * row r at d_logits + r * row_stride (row_stride >= cfg.vocab), with the handle's languages and no-speech id (rt_stt_set_languages)
+ * -> per row the language id, its probability among the configured ids, and the no-speech probability. */
+RT_API int rt_debug_stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int32_t n_rows, int32_t* h_lang, float* h_lang_prob,
+                              float* h_no_speech);
+
 /* A/B switches for measurements and tests (process-wide; the defaults are the fast path).  One row per switch, as in the table
  * they are generated from (rho_tts_amd/csrc/knobs.h: defaults, accepted ranges, measurement notes).  A code that no row accepts is
  * refused with RT_ERR_INVALID and changes nothing.  `code`:

@@ -24,6 +24,11 @@
 // 5): decoder rows are windows x beams - a decoder side of its own (SttBeam) over the group's encoder side - k_stt_beam_select keeps
 // the hypotheses on the device and k_stt_beam_reorder hands a row the self-attention cache of the row it continues; the call also
 // returns each clip's average log-probability per emitted token.
+//
+// rt_stt_transcribe_ex is that beam path with a prefix per window: a probe pass (start-of-transcript alone, one row per window, the
+// same stt_decode_rows) in front of the prefix pass, k_stt_probe reads a window's language and no-speech probability off its logits
+// and k_stt_lang_prefix writes position 1 of every window's prefix on the device.  The three older entry points pass the handle's
+// prefix and no probe: their launches are what they were.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -196,6 +201,81 @@ __global__ __launch_bounds__(1024) void k_stt_pick(const float* __restrict__ all
     for (int w = 1; w < 16; ++w)
         if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
     next_tok[blockIdx.x] = bi == 0x7fffffff ? 0 : bi;
+}
+
+// What a window sounds like before anything is forced on it ("language and no-speech"), one 1024-thread
+// workgroup per window over z, the logits behind start-of-transcript alone (no suppression mask): the configured language id with
+// the largest z (lowest id on ties, NaNs never), its softmax over the configured ids, and softmax(z) over the whole vocabulary at
+// the no-speech id.  NaNs take no part in either sum.  Every reduction has a fixed order - the <= 128 language terms one after the
+// other on thread 0, the vocabulary per thread in index order, butterfly per wave, the 16 wave sums in wave order - so a window's
+// three results do not depend on what it is batched with.  Row w of the logits starts at w * row_stride.
+constexpr int STT_LANG_MAX = 128;                      // configured language ids (rt_stt_set_languages)
+constexpr int STT_NO_LANG = 0x7fffffff;
+__global__ __launch_bounds__(1024) void k_stt_probe(const float* __restrict__ all_logits, int64_t row_stride, int V, const int32_t* __restrict__ lang_ids, int n_lang,
+                                                    int no_speech_id, int32_t* __restrict__ out_lang, float* __restrict__ out_lang_prob,
+                                                    float* __restrict__ out_no_speech) {
+    __shared__ float red[16];
+    __shared__ float lz[STT_LANG_MAX];
+    __shared__ int li[STT_LANG_MAX];
+    const float* z = all_logits + (int64_t)blockIdx.x * row_stride;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    if (tid < n_lang) { li[tid] = lang_ids[tid]; lz[tid] = z[li[tid]]; }
+    float m = -INFINITY;
+    for (int i = tid; i < V; i += 1024) { const float v = z[i]; if (v > m) m = v; }                  // (a NaN compares false)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((tid & 63) == 0) red[wave] = m;
+    __syncthreads();
+    m = red[0];
+    for (int k = 1; k < 16; ++k) m = fmaxf(m, red[k]);
+    __syncthreads();
+    float sum = 0.f;
+    for (int i = tid; i < V; i += 1024) { const float v = z[i]; if (v == v) sum += expf(v - m); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if ((tid & 63) == 0) red[wave] = sum;
+    __syncthreads();
+    if (tid != 0) return;
+    sum = red[0];
+    for (int k = 1; k < 16; ++k) sum += red[k];
+    const float zn = z[no_speech_id];
+    out_no_speech[blockIdx.x] = (m > -INFINITY && zn == zn) ? expf(zn - (m + logf(sum))) : 0.f;
+    float best = -INFINITY;
+    int bi = STT_NO_LANG;
+    for (int k = 0; k < n_lang; ++k) {
+        const float v = lz[k];
+        if (v != v) continue;
+        if (bi == STT_NO_LANG || v > best || (v == best && li[k] < bi)) { best = v; bi = li[k]; }
+    }
+    float ls = 0.f;
+    for (int k = 0; k < n_lang; ++k)
+        if (lz[k] == lz[k]) ls += expf(lz[k] - best);
+    int low = li[0];                                       // no language has a number: the lowest configured id, probability 0
+    for (int k = 1; k < n_lang; ++k) low = min(low, li[k]);
+    out_lang[blockIdx.x] = bi == STT_NO_LANG ? low : bi;
+    out_lang_prob[blockIdx.x] = (bi != STT_NO_LANG && best > -INFINITY) ? 1.0f / ls : 0.f;
+}
+
+// The forced prefix of every window of a group, written on the device behind k_stt_probe (no host round trip in between): the
+// handle's prefix with position 1 replaced by the clip's language.  clip_lang[c] >= 0: the id the caller forced on clip c, or the id
+// an earlier group of this call detected on its first window; -1: detect - then win_first[w] is the row, in this group, of the first
+// window of w's clip, whose detected id every window of the clip takes (and clip_lang keeps it for the groups to come).
+__global__ void k_stt_lang_prefix(int nW, int P, const int32_t* __restrict__ base_prefix, const int32_t* __restrict__ win_clip,
+                                  const int32_t* __restrict__ win_first, int32_t* __restrict__ clip_lang, const int32_t* __restrict__ probe_lang,
+                                  int32_t* __restrict__ prefix, int32_t* __restrict__ win_lang) {
+    const int w = threadIdx.x;
+    int lang = 0, clip = 0, first = -1;
+    if (w < nW) {
+        clip = win_clip[w];
+        first = win_first[w];
+        lang = clip_lang[clip];
+        if (lang < 0) lang = first >= 0 ? probe_lang[first] : base_prefix[1];
+    }
+    __syncthreads();                                       // (every read of clip_lang lies before the writes)
+    if (w >= nW) return;
+    if (first == w) clip_lang[clip] = lang;
+    win_lang[w] = lang;
+    for (int i = 0; i < P; ++i) prefix[w * P + i] = i == 1 ? lang : base_prefix[i];
 }
 
 __global__ void k_stt_fill_i32(int32_t* p, int n, int v, int step) {
@@ -486,6 +566,18 @@ struct rt_stt {
     std::vector<int32_t> h_tok;
     uint8_t* d_mask = nullptr;
     std::vector<int32_t> suppress_ids;   // rt_stt_set_suppress: ids never produced (a generation config's `suppress_tokens`)
+    // rt_stt_set_languages: the ids position 1 of the prefix may take and the no-speech id; the device side (one group's worth,
+    // allocated by rt_stt_finalize) of the probe pass, k_stt_probe and k_stt_lang_prefix
+    std::vector<int32_t> lang_ids;
+    int32_t no_speech_id = -1;
+    int32_t* d_lang_ids = nullptr;
+    int32_t* d_sot = nullptr;            // [STT_GROUP] start-of-transcript: the tokens of the probe pass
+    int32_t* d_probe = nullptr;          // [4][STT_GROUP]: detected id | its probability | no-speech probability (float) | the id the prefix took
+    int32_t* d_win_meta = nullptr;       // [2][STT_GROUP]: a window's clip | the row of its clip's first window in this group (-1: none)
+    int32_t* d_lang_prefix = nullptr;    // [STT_GROUP][n_prefix] the windows' forced prefixes (k_stt_lang_prefix)
+    int32_t* d_clip_lang = nullptr;      // [clip_lang_cap] per clip of the call: the forced or detected id, -1 until it is detected
+    int clip_lang_cap = 0;
+    std::vector<int32_t> h_probe, h_meta;
     std::vector<void*> owned;
 };
 
@@ -788,13 +880,14 @@ int stt_group_reserve(rt_stt* s, int B) {
 
 // Greedy decode of the B encoded windows of the group: ids[b] = the first `budget` ids of window b (forced prefix in one pass, then
 // one token per pass until end-of-sequence).  One device-to-host read (the rows' tokens) and one synchronisation per step for the
-// whole group.  d_first_logits: receives row 0's logits behind the prefix pass.
-int stt_decode_group(rt_stt* s, int B, int budget, std::vector<std::vector<int32_t>>& ids, float* d_first_logits) {
+// whole group.  d_prefix [B][n_prefix]: every window's forced prefix (the three greedy entry points pass the handle's own, the same
+// for every window).  d_first_logits: receives row 0's logits behind the prefix pass.
+int stt_decode_group(rt_stt* s, int B, int budget, const int32_t* d_prefix, std::vector<std::vector<int32_t>>& ids, float* d_first_logits) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     SttGroup& w = s->grp;
     const int P = c.n_prefix;
-    w.dec.tok = w.d_prefix;
+    w.dec.tok = d_prefix;
     RT_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, B, P, 0, w.pre_slot, w.pre_pos, w.pre_slot));
     if (d_first_logits) RT_HIP(ctx, hipMemcpyAsync(d_first_logits, w.dec.logits, (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
     w.dec.tok = w.d_tok;
@@ -839,7 +932,7 @@ int stt_transcribe_greedy(rt_stt* s, const float* const* d_pcm, const int64_t* n
         const int B = (int)group.size();
         RT_TRY(stt_features_group(s, group.data(), B, sr));
         RT_TRY(stt_encode(s, s->grp.enc, B));
-        RT_TRY(stt_decode_group(s, B, budget, ids, d_first_logits));
+        RT_TRY(stt_decode_group(s, B, budget, s->grp.d_prefix, ids, d_first_logits));
         d_first_logits = nullptr;
         for (int b = 0; b < B; ++b) {
             const int i = group[b].clip;
@@ -898,11 +991,37 @@ int stt_beam_reorder(rt_ctx* ctx, const KvCache& from, const KvCache& to, const 
 // (the ids and end-of-sequence)
 struct SttHyp { std::vector<int32_t> ids; float score = 0.f; int count = 1; };
 
+// Languages of a group (rt_stt_transcribe_ex): the windows' prefixes are in s->d_lang_prefix already (probe false: every language is
+// given), or the probe pass runs and k_stt_lang_prefix writes them from the group's window table in s->d_win_meta - per window its
+// clip and the row, in this group, of its clip's first window (-1: an earlier group held it; s->d_clip_lang keeps what it detected)
+struct SttLangPlan { bool probe; };
+
+// k_stt_probe over nW rows of logits -> s->d_probe rows 0 .. 2
+int stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int nW) {
+    int32_t* p = s->d_probe;
+    hipLaunchKernelGGL(k_stt_probe, dim3(nW), dim3(1024), 0, s->ctx->stream, d_logits, row_stride, s->cfg.vocab, s->d_lang_ids, (int)s->lang_ids.size(),
+                       s->no_speech_id, p, (float*)(p + STT_GROUP), (float*)(p + 2 * STT_GROUP));
+    RT_HIP(s->ctx, hipGetLastError());
+    return RT_OK;
+}
+// k_stt_lang_prefix over the group's window table (s->d_win_meta: stt_transcribe_beam copies it in while the stream is idle, in
+// front of the group's front end - a copy from pageable memory in the middle of the group would make the host wait for the
+// encoder): s->d_lang_prefix and row 3 of s->d_probe
+int stt_lang_prefix(rt_stt* s, int nW) {
+    rt_ctx* ctx = s->ctx;
+    hipLaunchKernelGGL(k_stt_lang_prefix, dim3(1), dim3(64), 0, ctx->stream, nW, s->cfg.n_prefix, s->grp.d_prefix, s->d_win_meta, s->d_win_meta + STT_GROUP,
+                       s->d_clip_lang, s->d_probe, s->d_lang_prefix, s->d_probe + 3 * STT_GROUP);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
 // Beam search (width B) over the nW encoded windows of the group, rows = nW B.  The prefix pass runs one row per window into the
 // cache slot of the window's first beam row; the reorder kernel then fans it out to the window's rows, and after every later
 // step gives row r the cache of the row it continues.  One device-to-host read and one synchronisation per step, as the greedy
 // group; the bookkeeping comes back once, and the host follows the back-pointers of the finished entries.
-int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
+// lang (null: the handle's prefix for every window, nothing probed - the launches of rt_stt_transcribe_beam): a prefix per window,
+// and whether the probe pass runs to decide it.
+int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, const SttLangPlan* lang = nullptr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     SttBeam& bm = s->beam;
@@ -917,6 +1036,18 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
     hipLaunchKernelGGL(k_stt_fill_beam_rows, dim3(1), dim3(256), 0, ctx->stream, bm.pre_slot, bm.pre_pos, bm.pre_win, nW * P, P, B, bm.row_slot, bm.row_win, rows);
     RT_HIP(ctx, hipGetLastError());
     bm.dec.tok = s->grp.d_prefix;                // (the forced prefix of every window: the group keeps it)
+    if (lang) {
+        // the probe pass: row w is start-of-transcript alone at position 0 of cache slot w, over window w's encoder states (the
+        // prefix pass and the reorder behind it overwrite what it leaves in the cache), then the windows' prefixes on the device.
+        // Every language given and no no-speech probability wanted: no launch is added to those of rt_stt_transcribe_beam
+        if (lang->probe) {
+            bm.dec.tok = s->d_sot;
+            RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, 1, 0, bm.row_slot, bm.row_pos, bm.row_slot));
+            RT_TRY(stt_probe(s, bm.dec.logits, c.vocab, nW));
+            RT_TRY(stt_lang_prefix(s, nW));
+        }
+        bm.dec.tok = s->d_lang_prefix;           // (without a probe every language is given: the caller has copied the prefixes in)
+    }
     RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
     const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
     int steps = 0;
@@ -965,6 +1096,103 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out) {
         for (int k = 0; k < n_f; ++k) offer(h.fin_step[w * B + k] - 1, h.fin_beam[w * B + k], h.fin_score[w * B + k]);
         for (int i = 0; i < std::min(h.n_live[w], B) && n_f < B; ++i, ++n_f) offer(steps - 1, i, h.score[w * B + i]);
     }
+    return RT_OK;
+}
+
+// What rt_stt_transcribe_ex asks for and receives beyond ids and scores (host pointers, null: not asked for).  h_req [n_clips]: a
+// clip's language, a configured id or -1 = detect; null: the handle's prefix, and k_stt_lang_prefix does not run.  probe: the probe
+// pass runs (a clip detects, or the windows' no-speech probabilities are wanted).
+struct SttReport {
+    const int32_t* h_req = nullptr;
+    bool probe = false;
+    int32_t* h_lang = nullptr;
+    float* h_lang_prob = nullptr;
+    int32_t *win_clip = nullptr, *win_n_ids = nullptr;
+    float *win_logprob = nullptr, *win_no_speech = nullptr;
+};
+
+// Beam-search transcription of the windows `all` of n_clips clips, what rt_stt_transcribe_beam (rep == null: the handle's prefix for
+// every window, nothing probed) and rt_stt_transcribe_ex share: floor(STT_GROUP / beam_size) windows make a group.
+int stt_transcribe_beam(rt_stt* s, const std::vector<SttSpan>& all, int n_clips, int sr, int beam_size, int32_t* h_tokens, int max_tokens, int32_t* h_n_tokens,
+                        float* h_scores, const SttReport* rep) {
+    rt_ctx* ctx = s->ctx;
+    std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
+    const size_t per_group = (size_t)(STT_GROUP / beam_size);
+    const int most = (int)std::min(all.size(), per_group);
+    RT_TRY(stt_group_reserve(s, most));
+    RT_TRY(stt_beam_reserve(s, most * beam_size));
+    // a prefix per window: written on the device behind the probe (k_stt_lang_prefix), or - every language given and nothing to
+    // probe - laid out here and copied in, which adds no launch to those of rt_stt_transcribe_beam
+    const bool langs = rep && (rep->h_req || rep->probe), probe = langs && rep->probe;
+    const int P = s->cfg.n_prefix;
+    std::vector<int32_t> win_clip(STT_GROUP), win_first(STT_GROUP), first_at(n_clips, -1);
+    if (probe) {
+        if (s->clip_lang_cap < n_clips) {
+            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            const int cap = std::max(n_clips, 2 * s->clip_lang_cap);
+            RT_TRY(stt_alloc(s, s->owned, (size_t)cap, &s->d_clip_lang));          // (the smaller one stays owned until rt_stt_destroy)
+            s->clip_lang_cap = cap;
+        }
+        // without a request every clip keeps the handle's own language
+        std::vector<int32_t> req(n_clips, s->cfg.prefix[1]);
+        if (rep->h_req) req.assign(rep->h_req, rep->h_req + n_clips);
+        RT_HIP(ctx, hipMemcpy(s->d_clip_lang, req.data(), (size_t)n_clips * 4, hipMemcpyHostToDevice));
+        s->h_probe.resize(4 * STT_GROUP);
+    }
+    std::vector<double> sum(n_clips, 0.0);
+    std::vector<int64_t> count(n_clips, 0);
+    std::vector<SttHyp> hyps;
+    for (size_t next = 0; next < all.size(); next += per_group) {
+        const int nW = (int)std::min(per_group, all.size() - next);
+        if (langs) {                                                    // (the copies first, while the stream is idle)
+            for (int b = 0; b < nW; ++b) {
+                const int i = all[next + b].clip;
+                const bool is_first = next + b == 0 || all[next + b - 1].clip != i;
+                if (is_first) first_at[i] = (int32_t)(next + b);
+                win_clip[b] = i;
+                win_first[b] = first_at[i] >= (int32_t)next ? first_at[i] - (int32_t)next : -1;
+            }
+            s->h_meta.assign((size_t)STT_GROUP * std::max(P, 2), -1);   // (alive until the group's synchronisation)
+            if (probe) {
+                for (int b = 0; b < nW; ++b) { s->h_meta[b] = win_clip[b]; s->h_meta[STT_GROUP + b] = win_first[b]; }
+                RT_HIP(ctx, hipMemcpyAsync(s->d_win_meta, s->h_meta.data(), 2 * STT_GROUP * 4, hipMemcpyHostToDevice, ctx->stream));
+            } else {
+                for (int b = 0; b < nW; ++b)
+                    for (int k = 0; k < P; ++k) s->h_meta[(size_t)b * P + k] = k == 1 ? rep->h_req[win_clip[b]] : s->cfg.prefix[k];
+                RT_HIP(ctx, hipMemcpyAsync(s->d_lang_prefix, s->h_meta.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
+            }
+        }
+        RT_TRY(stt_features_group(s, all.data() + next, nW, sr));
+        RT_TRY(stt_encode(s, s->grp.enc, nW));
+        if (langs) {
+            const SttLangPlan plan{probe};
+            RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps, &plan));
+            if (probe) RT_HIP(ctx, hipMemcpy(s->h_probe.data(), s->d_probe, 4 * STT_GROUP * 4, hipMemcpyDeviceToHost));     // (behind the group's last synchronisation)
+        } else {
+            RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps));
+        }
+        const float* pf = (const float*)s->h_probe.data();
+        for (int b = 0; b < nW; ++b) {
+            const int i = all[next + b].clip;
+            for (int32_t t : hyps[b].ids)
+                if (h_n_tokens[i] < max_tokens) h_tokens[(size_t)i * max_tokens + h_n_tokens[i]++] = t;
+            sum[i] += (double)hyps[b].score;
+            count[i] += hyps[b].count;
+            if (!rep) continue;
+            const size_t at = next + b;
+            if (rep->win_clip) rep->win_clip[at] = i;
+            if (rep->win_n_ids) rep->win_n_ids[at] = (int32_t)hyps[b].ids.size();
+            if (rep->win_logprob) rep->win_logprob[at] = hyps[b].score;
+            if (rep->win_no_speech) rep->win_no_speech[at] = pf[2 * STT_GROUP + b];
+            if (langs ? first_at[i] != (int32_t)at : (at != 0 && all[at - 1].clip == i)) continue;      // the clip's first window: its language
+            // a forced language (or the handle's own) counts as certain, as in the reference's transcribers
+            const bool detected = rep->h_req && rep->h_req[i] < 0;
+            if (rep->h_lang) rep->h_lang[i] = probe ? s->h_probe[3 * STT_GROUP + b] : langs ? rep->h_req[i] : s->cfg.prefix[P > 1 ? 1 : 0];
+            if (rep->h_lang_prob) rep->h_lang_prob[i] = detected ? pf[STT_GROUP + b] : 1.0f;
+        }
+    }
+    if (h_scores)
+        for (int i = 0; i < n_clips; ++i) h_scores[i] = (float)(sum[i] / (double)std::max<int64_t>(count[i], 1));
     return RT_OK;
 }
 
@@ -1098,6 +1326,17 @@ int rt_stt_finalize(rt_stt* s) {
         if (id >= 0 && id < c.vocab && id != c.eos_id) mask[id] |= 1;
     RT_TRY(stt_alloc(s, s->owned, (size_t)c.vocab, &s->d_mask));
     RT_HIP(ctx, hipMemcpy(s->d_mask, mask.data(), c.vocab, hipMemcpyHostToDevice));
+    if (!s->lang_ids.empty()) {                                      // rt_stt_set_languages: one group's worth of the probe's buffers
+        RT_TRY(stt_alloc(s, s->owned, s->lang_ids.size(), &s->d_lang_ids));
+        RT_HIP(ctx, hipMemcpy(s->d_lang_ids, s->lang_ids.data(), s->lang_ids.size() * 4, hipMemcpyHostToDevice));
+        RT_TRY(stt_alloc(s, s->owned, (size_t)STT_GROUP, &s->d_sot));
+        RT_TRY(stt_alloc(s, s->owned, (size_t)4 * STT_GROUP, &s->d_probe));
+        RT_TRY(stt_alloc(s, s->owned, (size_t)2 * STT_GROUP, &s->d_win_meta));
+        RT_TRY(stt_alloc(s, s->owned, (size_t)STT_GROUP * c.n_prefix, &s->d_lang_prefix));
+        RT_HIP(ctx, hipMemsetAsync(s->d_probe, 0, (size_t)4 * STT_GROUP * 4, ctx->stream));
+        hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, s->d_sot, STT_GROUP, c.prefix[0], 0);
+        RT_HIP(ctx, hipGetLastError());
+    }
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->finalized = true;
     return RT_OK;
@@ -1183,29 +1422,111 @@ int rt_stt_transcribe_beam(rt_stt* s, const float* const* d_pcm, const int64_t* 
     if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe_beam: not finalized");
     std::vector<SttSpan> all;
     stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, all);
-    std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
-    const size_t per_group = (size_t)(STT_GROUP / beam_size);
-    const int most = (int)std::min(all.size(), per_group);
-    RT_TRY(stt_group_reserve(s, most));
-    RT_TRY(stt_beam_reserve(s, most * beam_size));
-    std::vector<double> sum(n_clips, 0.0);
-    std::vector<int64_t> count(n_clips, 0);
-    std::vector<SttHyp> hyps;
-    for (size_t next = 0; next < all.size(); next += per_group) {
-        const int nW = (int)std::min(per_group, all.size() - next);
+    return stt_transcribe_beam(s, all, n_clips, sample_rate, beam_size, h_tokens, max_tokens, h_n_tokens, h_scores, nullptr);
+}
+
+int rt_stt_set_languages(rt_stt* s, const int32_t* h_lang_ids, int32_t n, int32_t no_speech_id) {
+    if (!s || !h_lang_ids || n < 1 || n > STT_LANG_MAX) return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_set_languages: bad argument (1 .. %d ids)", STT_LANG_MAX);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_set_languages: call before rt_stt_finalize");
+    const rt_stt_config& c = s->cfg;
+    if (c.n_prefix < 2) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_languages: the forced prefix has no language position (%d entries)", c.n_prefix);
+    if (no_speech_id < 0 || no_speech_id >= c.vocab) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_languages: no-speech id %d outside the vocabulary of %d", no_speech_id, c.vocab);
+    bool own = false;
+    for (int i = 0; i < n; ++i) {
+        if (h_lang_ids[i] < 0 || h_lang_ids[i] >= c.vocab) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_languages: language id %d outside the vocabulary of %d", h_lang_ids[i], c.vocab);
+        own = own || h_lang_ids[i] == c.prefix[1];
+    }
+    if (!own) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_languages: position 1 of the configured prefix (%d) is not among the language ids", c.prefix[1]);
+    s->lang_ids.assign(h_lang_ids, h_lang_ids + n);
+    s->no_speech_id = no_speech_id;
+    return RT_OK;
+}
+
+int rt_stt_detect_language(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, int32_t* h_lang, float* h_lang_prob,
+                           float* h_no_speech) {
+    if (!s || sample_rate < 1000 || stt_check_clips(d_pcm, n_samples, n_clips) || (n_clips > 0 && !h_lang))
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_detect_language: bad argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_detect_language: not finalized");
+    if (s->lang_ids.empty()) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_detect_language: the handle has no languages (rt_stt_set_languages)");
+    if (n_clips == 0) return RT_OK;
+    std::vector<SttSpan> all;
+    stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, all, true);
+    RT_TRY(stt_group_reserve(s, std::min(n_clips, STT_GROUP)));
+    SttGroup& w = s->grp;
+    s->h_probe.resize(4 * STT_GROUP);
+    for (int next = 0; next < n_clips; next += STT_GROUP) {
+        const int nW = std::min(STT_GROUP, n_clips - next);
         RT_TRY(stt_features_group(s, all.data() + next, nW, sample_rate));
-        RT_TRY(stt_encode(s, s->grp.enc, nW));
-        RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps));
+        RT_TRY(stt_encode(s, w.enc, nW));
+        w.dec.tok = s->d_sot;                                   // the probe pass on the greedy decoder side: position 0 of slot b
+        RT_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, nW, 1, 0, w.step_slot, w.step_pos, w.step_slot));
+        RT_TRY(stt_probe(s, w.dec.logits, s->cfg.vocab, nW));
+        RT_HIP(ctx, hipMemcpyAsync(s->h_probe.data(), s->d_probe, 3 * STT_GROUP * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const float* pf = (const float*)s->h_probe.data();
         for (int b = 0; b < nW; ++b) {
-            const int i = all[next + b].clip;
-            for (int32_t t : hyps[b].ids)
-                if (h_n_tokens[i] < max_tokens) h_tokens[(size_t)i * max_tokens + h_n_tokens[i]++] = t;
-            sum[i] += (double)hyps[b].score;
-            count[i] += hyps[b].count;
+            h_lang[next + b] = s->h_probe[b];
+            if (h_lang_prob) h_lang_prob[next + b] = pf[STT_GROUP + b];
+            if (h_no_speech) h_no_speech[next + b] = pf[2 * STT_GROUP + b];
         }
     }
-    if (h_scores)
-        for (int i = 0; i < n_clips; ++i) h_scores[i] = (float)(sum[i] / (double)std::max<int64_t>(count[i], 1));
+    return RT_OK;
+}
+
+int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, const rt_stt_decode_opts* opts,
+                         rt_stt_decode_out* out) {
+    if (!s || !opts || !out || opts->max_tokens < 1 || sample_rate < 1000 || opts->beam_size < 1 || opts->beam_size > STT_BEAM_MAX ||
+        stt_check_clips(d_pcm, n_samples, n_clips) || (n_clips > 0 && (!out->h_tokens || !out->h_n_tokens)) || out->window_cap < 0)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_transcribe_ex: bad argument (beam_size 1 .. %d)", STT_BEAM_MAX);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe_ex: not finalized");
+    out->n_windows = 0;
+    if (n_clips == 0) return RT_OK;
+    SttReport rep;
+    rep.h_req = opts->h_language;
+    rep.h_lang = out->h_language; rep.h_lang_prob = out->h_language_prob;
+    rep.win_clip = out->h_win_clip; rep.win_n_ids = out->h_win_n_ids; rep.win_logprob = out->h_win_logprob; rep.win_no_speech = out->h_win_no_speech;
+    rep.probe = rep.win_no_speech != nullptr;
+    if (rep.h_req)
+        for (int i = 0; i < n_clips; ++i) {
+            const int32_t id = rep.h_req[i];
+            if (id == -1) { rep.probe = true; continue; }
+            if (std::find(s->lang_ids.begin(), s->lang_ids.end(), id) == s->lang_ids.end())
+                return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_ex: clip %d: language %d is neither -1 nor a configured id (rt_stt_set_languages)", i, id);
+        }
+    if ((rep.h_req || rep.probe) && s->lang_ids.empty())
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_ex: languages or no-speech probabilities asked of a handle without rt_stt_set_languages");
+    std::vector<SttSpan> all;
+    stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, all);
+    const bool per_window = rep.win_clip || rep.win_n_ids || rep.win_logprob || rep.win_no_speech;
+    if (per_window && (size_t)out->window_cap < all.size())
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_ex: %zu windows, room for %d", all.size(), out->window_cap);
+    RT_TRY(stt_transcribe_beam(s, all, n_clips, sample_rate, opts->beam_size, out->h_tokens, opts->max_tokens, out->h_n_tokens, out->h_scores, &rep));
+    out->n_windows = (int32_t)all.size();
+    return RT_OK;
+}
+
+int rt_debug_stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int32_t n_rows, int32_t* h_lang, float* h_lang_prob, float* h_no_speech) {
+    if (!s || !d_logits || !h_lang || !h_lang_prob || !h_no_speech || n_rows < 1 || n_rows > STT_GROUP || row_stride < s->cfg.vocab)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_probe: bad argument (1 .. %d rows, row_stride >= vocab)", STT_GROUP);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_probe: not finalized");
+    if (s->lang_ids.empty()) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_probe: the handle has no languages (rt_stt_set_languages)");
+    RT_TRY(stt_probe(s, d_logits, row_stride, n_rows));
+    s->h_probe.resize(4 * STT_GROUP);
+    RT_HIP(ctx, hipMemcpyAsync(s->h_probe.data(), s->d_probe, 3 * STT_GROUP * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const float* pf = (const float*)s->h_probe.data();
+    for (int b = 0; b < n_rows; ++b) { h_lang[b] = s->h_probe[b]; h_lang_prob[b] = pf[STT_GROUP + b]; h_no_speech[b] = pf[2 * STT_GROUP + b]; }
     return RT_OK;
 }
 

@@ -12,6 +12,7 @@ weights of the same architecture serve the parity tests and benchmarks (they tra
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import json
 import math
 import os
@@ -25,6 +26,33 @@ from . import _native
 
 DT_BF16, DT_F32 = 0, 1
 MAX_BEAM = 8                  # widest beam of rt_stt_transcribe_beam
+
+
+# The language codes of Whisper's multilingual vocabulary in id order (tokenization_whisper.py LANGUAGES, the first 99: <|en|> is
+# 50259, <|su|> 50357), and the ids behind them the classic layout fixes: <|nospeech|> (published as <|nocaptions|>) 50362.
+WHISPER_LANGUAGE_CODES = (
+    "en zh de es ru ko fr ja pt tr pl ca nl ar sv it id hi fi vi he uk el ms cs ro da hu ta no th ur hr bg lt la mi ml cy sk te fa lv bn sr az sl kn "
+    "et mk br eu is hy ne mn bs kk sq sw gl mr pa si km sn yo so af oc ka be tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my bo tl mg as tt haw ln ha "
+    "ba jw su").split()
+CLASSIC_FIRST_LANGUAGE_ID, CLASSIC_NO_SPEECH_ID = 50259, 50362
+# the languages the provider advertises (provider_info) -> Whisper's codes
+_PROVIDER_LANGUAGES = {"english": "en", "chinese": "zh", "japanese": "ja", "korean": "ko"}
+
+
+def classic_languages() -> Dict[str, int]:
+    return {code: CLASSIC_FIRST_LANGUAGE_ID + i for i, code in enumerate(WHISPER_LANGUAGE_CODES)}
+
+
+def whisper_language(name: str) -> str:
+    """The Whisper language code of a language as the provider names it ("Chinese" -> "zh", any case); a two-letter code passes."""
+    if not isinstance(name, str):
+        raise ValueError(f"language must be a string, got {name!r}")
+    key = name.strip().lower()
+    if key in _PROVIDER_LANGUAGES:
+        return _PROVIDER_LANGUAGES[key]
+    if len(key) == 2 and key.isalpha():
+        return key
+    raise ValueError(f"unknown language {name!r}: one of {sorted(_PROVIDER_LANGUAGES)} or a two-letter code")
 
 
 def check_beam_size(beam_size) -> int:
@@ -56,11 +84,26 @@ class SttConfig:
     begin_suppress: Tuple[int, ...] = (220, 50257)
     suppress_tokens: Tuple[int, ...] = ()  # further ids never produced (a generation config's `suppress_tokens`)
     max_new_tokens: int = 224
+    # the ids position 1 of the prefix may take, by code ("en" -> 50259), and <|nospeech|>: rt_stt_set_languages (empty: a model
+    # without a language slot - it transcribes with its prefix as it stands, and nothing can be detected)
+    languages: Dict[str, int] = field(default_factory=classic_languages)
+    no_speech_id: int = CLASSIC_NO_SPEECH_ID
+    language: str = "en"                 # the code position 1 of `prefix` stands for
+
+    def with_language(self, code: str) -> "SttConfig":
+        """A copy whose prefix carries ``code`` at position 1."""
+        if code not in self.languages or len(self.prefix) < 2:
+            raise ValueError(f"unknown language {code!r}: the model knows {sorted(self.languages)}")
+        return dataclasses.replace(self, prefix=(self.prefix[0], int(self.languages[code])) + tuple(self.prefix[2:]), language=code)
+
+    def language_code(self, token_id: int) -> Optional[str]:
+        return next((k for k, v in self.languages.items() if v == int(token_id)), None)
 
     @staticmethod
-    def from_hf(js: dict, generation: Optional[dict] = None, preprocessor: Optional[dict] = None) -> "SttConfig":
-        """From a checkpoint directory's ``config.json`` (+ ``generation_config.json`` for the forced prefix and the suppressed
-        ids, + ``preprocessor_config.json`` for the feature extractor), as transformers' ``save_pretrained`` writes them."""
+    def from_hf(js: dict, generation: Optional[dict] = None, preprocessor: Optional[dict] = None, language: str = "en") -> "SttConfig":
+        """From a checkpoint directory's ``config.json`` (+ ``generation_config.json`` for the forced prefix, the language ids and
+        the suppressed ids, + ``preprocessor_config.json`` for the feature extractor), as transformers' ``save_pretrained`` writes
+        them.  ``language``: the code position 1 of the prefix is forced to; a code the checkpoint does not know raises."""
         c = SttConfig()
         c.d_model = js.get("d_model", c.d_model)
         c.heads = js.get("encoder_attention_heads", c.heads)
@@ -99,6 +142,18 @@ class SttConfig:
             c.prefix = (start,) + tuple(int(t) for t in (en, tr, nt) if t is not None)
         elif start != c.prefix[0]:
             c.prefix = (start,)
+        # Language ids and <|nospeech|>: lang_to_id with "<|xx|>" stripped to "xx", and no_timestamps_token_id - 1 as transformers
+        # derives it (generation_whisper.py, WhisperNoSpeechDetection's no_speech_token); without a generation config the classic
+        # multilingual vocabulary has the known layout (the defaults), and any other vocabulary has no language slot this build knows
+        if lang:
+            c.languages = {str(k).strip("<|>"): int(v) for k, v in lang.items() if 0 <= int(v) < c.vocab}
+            c.no_speech_id = int(nts) - 1 if nts is not None and 0 < int(nts) <= c.vocab else -1
+        elif not (start == SttConfig.prefix[0] and c.vocab > CLASSIC_NO_SPEECH_ID):
+            c.languages, c.no_speech_id = {}, -1
+        if language != "en":
+            c = c.with_language(language)
+        elif len(c.prefix) > 1:
+            c.language = c.language_code(c.prefix[1]) or "en"
         if gen.get("begin_suppress_tokens"):
             c.begin_suppress = tuple(int(t) for t in gen["begin_suppress_tokens"] if 0 <= int(t) < c.vocab)[:4]
         # Whisper's vocabularies put every special id (language, task, timestamps) behind end-of-sequence
@@ -111,7 +166,7 @@ class SttConfig:
         return c
 
     @staticmethod
-    def from_dir(model_dir: str) -> "SttConfig":
+    def from_dir(model_dir: str, language: str = "en") -> "SttConfig":
         def read(name):
             path = os.path.join(model_dir, name)
             if not os.path.exists(path):
@@ -121,13 +176,14 @@ class SttConfig:
         js = read("config.json")
         if js is None:
             raise ValueError(f"no config.json in {model_dir!r}")
-        return SttConfig.from_hf(js, read("generation_config.json"), read("preprocessor_config.json"))
+        return SttConfig.from_hf(js, read("generation_config.json"), read("preprocessor_config.json"), language)
 
 
 def tiny_test_config() -> SttConfig:
     """A few-thousand-parameter model of the same topology for quick tests (2-s chunks)."""
     return SttConfig(d_model=64, heads=2, ffn=128, enc_layers=2, dec_layers=2, n_mels=16, n_ctx=100, n_text_ctx=32, vocab=300,
-                     chunk_seconds=2, eos_id=290, prefix=(291, 292, 293), suppress_from=290, begin_suppress=(7, 290), max_new_tokens=12)
+                     chunk_seconds=2, eos_id=290, prefix=(291, 292, 293), suppress_from=290, begin_suppress=(7, 290), max_new_tokens=12,
+                     languages={}, no_speech_id=-1)
 
 
 class RtSttConfig(C.Structure):
@@ -136,6 +192,40 @@ class RtSttConfig(C.Structure):
                 ("n_fft", C.c_int32), ("hop", C.c_int32), ("sample_rate", C.c_int32), ("chunk_seconds", C.c_int32),
                 ("eos_id", C.c_int32), ("n_prefix", C.c_int32), ("prefix", C.c_int32 * 8), ("suppress_from", C.c_int32),
                 ("n_begin_suppress", C.c_int32), ("begin_suppress", C.c_int32 * 4), ("max_new_tokens", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RtSttDecodeOpts(C.Structure):
+    _fields_ = [("h_language", C.POINTER(C.c_int32)), ("beam_size", C.c_int32), ("max_tokens", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RtSttDecodeOut(C.Structure):
+    _fields_ = [("h_tokens", C.POINTER(C.c_int32)), ("h_n_tokens", C.POINTER(C.c_int32)), ("h_scores", C.POINTER(C.c_float)),
+                ("h_language", C.POINTER(C.c_int32)), ("h_language_prob", C.POINTER(C.c_float)), ("h_win_clip", C.POINTER(C.c_int32)),
+                ("h_win_n_ids", C.POINTER(C.c_int32)), ("h_win_logprob", C.POINTER(C.c_float)), ("h_win_no_speech", C.POINTER(C.c_float)),
+                ("window_cap", C.c_int32), ("n_windows", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+@dataclass
+class SttWindow:
+    """One chunk_seconds window of a clip as rt_stt_transcribe_ex reports it."""
+    n_ids: int
+    logprob: float                       # cumulative log-probability of the window's hypothesis, end-of-sequence counted
+    no_speech_prob: float                # NaN where the probe pass did not run
+
+    @property
+    def avg_logprob(self) -> float:
+        return self.logprob / (self.n_ids + 1)
+
+
+@dataclass
+class SttClip:
+    """One clip of ``NativeSTT.transcribe_ids_ex``: ``language`` is the id at position 1 of its prefix, ``language_prob`` its
+    probability among the configured ids where it was detected and 1 where it was given."""
+    ids: List[int]
+    score: float
+    language: int
+    language_prob: float
+    windows: List[SttWindow]
 
 
 def _rt_config(c: SttConfig) -> RtSttConfig:
@@ -170,6 +260,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_stt_transcribe.argtypes = [vp, vp, i64, i32, C.POINTER(i32), i32, C.POINTER(i32), vp]
     lib.rt_stt_transcribe_batch.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(i32), i32, C.POINTER(i32)]
     lib.rt_stt_transcribe_beam.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, i32, C.POINTER(i32), i32, C.POINTER(i32), C.POINTER(C.c_float)]
+    lib.rt_stt_set_languages.argtypes = [vp, C.POINTER(i32), i32, i32]
+    lib.rt_stt_detect_language.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.rt_stt_transcribe_ex.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(RtSttDecodeOpts), C.POINTER(RtSttDecodeOut)]
     lib.rt_stt_log_mel.argtypes = [vp, vp, i64, i32, vp]
     lib.rt_stt_encode.argtypes = [vp, vp, i64, i32, vp]
     _DECLARED = True
@@ -350,6 +443,9 @@ class NativeSTT:
         if cfg.suppress_tokens:
             ids = (C.c_int32 * len(cfg.suppress_tokens))(*[int(t) for t in cfg.suppress_tokens])
             ctx.check(self.lib.rt_stt_set_suppress(self.handle, ids, len(cfg.suppress_tokens)), "rt_stt_set_suppress")
+        if cfg.languages:
+            lang = sorted(int(v) for v in cfg.languages.values())
+            ctx.check(self.lib.rt_stt_set_languages(self.handle, (C.c_int32 * len(lang))(*lang), len(lang), int(cfg.no_speech_id)), "rt_stt_set_languages")
         ctx.check(self.lib.rt_stt_finalize(self.handle), "rt_stt_finalize")
 
     def close(self) -> None:
@@ -419,6 +515,70 @@ class NativeSTT:
                        "rt_stt_transcribe_beam")
         return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)], [float(scores[i]) for i in range(n)]
 
+    def _clips(self, audios):
+        xs = [self._pcm(a) for a in audios]
+        n = len(xs)
+        ptrs = (C.c_void_p * max(n, 1))(*[x.data_ptr() if x.numel() else None for x in xs])
+        lens = (C.c_int64 * max(n, 1))(*[x.numel() for x in xs])
+        return xs, n, ptrs, lens
+
+    def _language_id(self, language) -> int:
+        """A code ("zh"), "auto" / None (-1: detect) or a token id, as an entry of rt_stt_decode_opts.h_language."""
+        if language is None or language == "auto":
+            return -1
+        if isinstance(language, str):
+            if language not in self.cfg.languages:
+                raise ValueError(f"unknown language {language!r}: the model knows {sorted(self.cfg.languages)}")
+            return int(self.cfg.languages[language])
+        return int(language)
+
+    def detect_language(self, audios, sample_rate: int) -> List[Tuple[int, float, float]]:
+        """Per clip (language id, its probability among the configured ids, no-speech probability), decided on the clip's first
+        window (rt_stt_detect_language; the rule: DESIGN.md section 5).  ``cfg.language_code`` gives the code of an id."""
+        if not getattr(self, "handle", None):
+            raise ValueError("detect_language: the model is closed")
+        xs, n, ptrs, lens = self._clips(audios)
+        lang, prob, ns = (C.c_int32 * max(n, 1))(), (C.c_float * max(n, 1))(), (C.c_float * max(n, 1))()
+        self.ctx.check(self.lib.rt_stt_detect_language(self.handle, ptrs, lens, n, int(sample_rate), lang, prob, ns), "rt_stt_detect_language")
+        return [(int(lang[i]), float(prob[i]), float(ns[i])) for i in range(n)]
+
+    def transcribe_ids_ex(self, audios, sample_rate: int, beam_size: int = 1, languages=None, max_tokens: Optional[int] = None,
+                          no_speech: bool = True) -> List[SttClip]:
+        """``transcribe_ids_beam`` with a language per clip and a report per window, from ONE native call (rt_stt_transcribe_ex).
+        ``languages``: None - the configured prefix; one entry for all clips or one per clip: a code, a token id, or "auto" / None /
+        -1 to detect the clip's language on its first window.  ``no_speech``: ask for the windows' no-speech probabilities (the
+        probe pass then runs even when every language is given)."""
+        check_beam_size(beam_size)
+        if max_tokens is not None and int(max_tokens) < 1:
+            raise ValueError(f"max_tokens must be at least 1, got {max_tokens!r}")
+        if not getattr(self, "handle", None):
+            raise ValueError("transcribe_ids_ex: the model is closed")
+        xs, n, ptrs, lens = self._clips(audios)
+        n_win = [self.windows(x.numel(), sample_rate) for x in xs]
+        cap = int(max_tokens or max(n_win or [1]) * self.cfg.max_new_tokens)
+        wcap = sum(n_win)
+        opts, out = RtSttDecodeOpts(), RtSttDecodeOut()
+        opts.beam_size, opts.max_tokens = int(beam_size), cap
+        req = None
+        if languages is not None:
+            each = [languages] * n if isinstance(languages, (str, int, np.integer)) else list(languages)
+            if len(each) != n:
+                raise ValueError(f"{len(each)} languages for {n} clips")
+            req = (C.c_int32 * max(n, 1))(*[self._language_id(v) for v in each])
+            opts.h_language = req
+        i32, f32 = lambda k: (C.c_int32 * max(k, 1))(), lambda k: (C.c_float * max(k, 1))()
+        toks, counts, scores, lang, lprob = i32(n * cap), i32(n), f32(n), i32(n), f32(n)
+        w_clip, w_n, w_lp, w_ns = i32(wcap), i32(wcap), f32(wcap), f32(wcap)
+        out.h_tokens, out.h_n_tokens, out.h_scores, out.h_language, out.h_language_prob = toks, counts, scores, lang, lprob
+        out.h_win_clip, out.h_win_n_ids, out.h_win_logprob, out.window_cap = w_clip, w_n, w_lp, wcap
+        if no_speech:
+            out.h_win_no_speech = w_ns
+        self.ctx.check(self.lib.rt_stt_transcribe_ex(self.handle, ptrs, lens, n, int(sample_rate), C.byref(opts), C.byref(out)), "rt_stt_transcribe_ex")
+        clips = [SttClip([int(toks[i * cap + k]) for k in range(counts[i])], float(scores[i]), int(lang[i]), float(lprob[i]), []) for i in range(n)]
+        for w in range(out.n_windows):
+            clips[w_clip[w]].windows.append(SttWindow(int(w_n[w]), float(w_lp[w]), float(w_ns[w]) if no_speech else float("nan")))
+        return clips
+
     def log_mel(self, audio, sample_rate: int) -> torch.Tensor:
         """[n_mels][frames] float32 (the layout of WhisperFeatureExtractor's ``input_features``)."""
         x = self._pcm(audio)
@@ -435,6 +595,18 @@ class NativeSTT:
         return out
 
 
+@dataclass
+class SttDetail:
+    """One clip of ``WhisperTranscriber.batch_detailed``."""
+    text: Optional[str]
+    ids: List[int]
+    avg_logprob: float                   # over the windows kept (over all of them when none is)
+    language: str                        # the code at position 1 of the clip's prefix
+    language_prob: float                 # its probability where it was detected, 1 where it was given
+    no_speech_prob: float                # the largest of the clip's windows
+    windows_dropped: int                 # windows the silence rule left out
+
+
 class WhisperTranscriber:
     """``transcriber`` hook of the provider: ``(audio tensor, sample_rate) -> text`` (None = transcription failed), the
     tensor-level stand-in for ``transcribe_audio(path)`` (stt_validator.py:116-148).  ``model_dir``: a local Whisper checkpoint
@@ -442,16 +614,25 @@ class WhisperTranscriber:
     for explicitly - and the "text" is the generated ids written out, which is all random weights can mean.  ``beam_size``: 1
     decodes greedily (the single-clip and the batched call); a larger width sends every call through beam search
     (``transcribe_ids_beam``; faster-whisper, which the reference transcribes with, defaults to 5), and ``batch_scored`` returns
-    each text with its confidence."""
+    each text with its confidence.  ``language``: the Whisper code the voice speaks ("en", "zh", ...; ``whisper_language`` maps the
+    provider's names) - it takes position 1 of the forced prefix - or "auto": every clip's language is detected on its first window
+    (``transcribe_ids_ex``).  ``no_speech_threshold`` (None: off; Whisper's transcribers use 0.6) and ``logprob_threshold`` switch the
+    silence rule on (validation.window_is_silent): ``__call__`` and ``batch`` then go through ``transcribe_ids_ex`` and leave out the
+    ids of silent windows, so that a silent clip is "" and not what the decoder makes up."""
+    auto, no_speech_threshold, logprob_threshold = False, None, -1.0
+    _ex = False                          # calls go through transcribe_ids_ex (a detected language, or the silence rule)
 
     def __init__(self, ctx: "_native.Context", model_dir: Optional[str] = None, synthetic: bool = False, cfg: Optional[SttConfig] = None, seed: int = 789,
-                 beam_size: int = 1):
+                 beam_size: int = 1, language: str = "en", no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = -1.0):
         self.beam_size = check_beam_size(beam_size)
+        self.auto = language == "auto"
+        self.no_speech_threshold, self.logprob_threshold = no_speech_threshold, logprob_threshold
+        code = "en" if self.auto else language
         self.tokenizer = None
         dev = f"cuda:{ctx.device_ordinal}"
         if model_dir and os.path.isdir(model_dir) and any(f.endswith(".safetensors") for f in os.listdir(model_dir)):
             if cfg is None:
-                cfg = SttConfig.from_dir(model_dir) if os.path.exists(os.path.join(model_dir, "config.json")) else SttConfig()
+                cfg = SttConfig.from_dir(model_dir, code) if os.path.exists(os.path.join(model_dir, "config.json")) else SttConfig()
             state = load_checkpoint(cfg, model_dir, device=dev)
             tok_path = os.path.join(model_dir, "tokenizer.json")
             if os.path.exists(tok_path):
@@ -463,15 +644,24 @@ class WhisperTranscriber:
         else:
             raise ValueError(f"no local Whisper checkpoint at {model_dir!r} (this build cannot download one); pass synthetic=True for seeded "
                              "random weights of the architecture (parity tests, benchmarks)")
+        if code != cfg.language:
+            cfg = cfg.with_language(code)
+        if (self.auto or no_speech_threshold is not None) and not cfg.languages:
+            raise ValueError("language detection and the silence rule need a model with language ids (SttConfig.languages)")
         self.cfg = cfg
         self.model = NativeSTT(ctx, cfg, state)
+        self._ex = self.auto or no_speech_threshold is not None        # calls that must go through transcribe_ids_ex
 
     def ids(self, audio, sample_rate: int) -> List[int]:
+        if self._ex:
+            return self.batch_detailed([audio], sample_rate)[0].ids
         if self.beam_size > 1:
             return self.model.transcribe_ids_beam([audio], sample_rate, self.beam_size)[0][0]
         return self.model.transcribe_ids(audio, sample_rate)
 
     def ids_batch(self, audios, sample_rate: int) -> List[List[int]]:
+        if self._ex:
+            return [d.ids for d in self.batch_detailed(audios, sample_rate)]
         if self.beam_size > 1:
             return self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)[0]
         return self.model.transcribe_ids_batch(audios, sample_rate)
@@ -479,8 +669,33 @@ class WhisperTranscriber:
     def batch_scored(self, audios, sample_rate: int) -> List[Tuple[Optional[str], float]]:
         """The texts of a chunk of segments with their confidence: the average log-probability per emitted token of the chosen
         hypothesis (0 is certain).  One native call, beam search of the configured width (width 1: the greedy ids, scored)."""
+        if self._ex:
+            return [(d.text, d.avg_logprob) for d in self.batch_detailed(audios, sample_rate)]
         ids, scores = self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)
         return [(self._text(i), s) for i, s in zip(ids, scores)]
+
+    def batch_detailed(self, audios, sample_rate: int) -> List["SttDetail"]:
+        """A chunk of segments from one native call (``transcribe_ids_ex``) with everything it reports: per clip the text and ids
+        with silent windows left out, the language the prefix carried and its probability, the largest no-speech probability of its
+        windows and how many windows the silence rule dropped."""
+        from .validation import window_is_silent
+        clips = self.model.transcribe_ids_ex(audios, sample_rate, self.beam_size, "auto" if self.auto else None)
+        out = []
+        for c in clips:
+            ids, at, kept, dropped = [], 0, [], 0
+            for w in c.windows:
+                own = c.ids[at:at + w.n_ids]                          # (a max_tokens cut leaves the last windows short)
+                at += w.n_ids
+                if window_is_silent(w.no_speech_prob, w.avg_logprob, self.no_speech_threshold, self.logprob_threshold):
+                    dropped += 1
+                else:
+                    ids += own
+                    kept.append(w)
+            over = kept or c.windows
+            avg = sum(w.logprob for w in over) / sum(w.n_ids + 1 for w in over)
+            out.append(SttDetail(self._text(ids), ids, avg, self.cfg.language_code(c.language) or str(c.language),
+                                 c.language_prob, max(w.no_speech_prob for w in c.windows), dropped))
+        return out
 
     def _text(self, ids: List[int]) -> Optional[str]:
         if self.tokenizer is not None:

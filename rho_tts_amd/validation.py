@@ -75,3 +75,15 @@ def validate_text_match(transcribed: Optional[str], expected_text: str, threshol
         return True, 0.0, None
     sim = calculate_text_similarity(expected_text, transcribed)
     return sim >= threshold, sim, transcribed
+
+
+def window_is_silent(no_speech_prob: float, avg_logprob: float, no_speech_threshold: Optional[float] = 0.6, logprob_threshold: Optional[float] = -1.0) -> bool:
+    """The silence rule of Whisper's transcribers for one 30-s window: silent - its ids are dropped - when the no-speech probability
+    is ABOVE ``no_speech_threshold`` and the hypothesis' average log-probability (cumulative log-probability / (ids + 1)) is BELOW
+    ``logprob_threshold``: "probably silence" and "low confidence" together (transformers generation_whisper.py: ``_need_fallback``
+    sets should_skip on exactly this pair; faster-whisper's transcribe.py applies the same test; defaults 0.6 and -1.0).
+    ``no_speech_threshold`` None switches the rule off; ``logprob_threshold`` None leaves the no-speech test alone, as in
+    faster-whisper.  A NaN is never above or below anything: such a window is kept."""
+    if no_speech_threshold is None or not no_speech_prob > no_speech_threshold:
+        return False
+    return logprob_threshold is None or avg_logprob < logprob_threshold
