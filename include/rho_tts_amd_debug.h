@@ -137,6 +137,103 @@ RT_API int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, 
 RT_API int rt_debug_stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int32_t n_rows, int32_t* h_lang, float* h_lang_prob,
                               float* h_no_speech);
 
+/* ------------------------------------------------------------------ row kernels on their own (tests/test_rowops_gpu.py)
+ * Each hook checks its arguments, calls the production launch_* function of rowops.hip (so the launcher's dispatch and its refusals
+ * are under test too), synchronises the stream and returns the status.  All pointers are HBM unless named h_*; matrices are
+ * row-major on both sides.  Kernels that write the fragment-tiled layout (common.h tile_off) are run on tiled copies that the hook
+ * makes FROM the caller's row-major output buffers and copies back, so whatever the kernel leaves alone keeps the caller's bytes;
+ * with raw_tiled = 1 the caller's buffers ARE the tiled ones (16 * ceil(rows / 16) rows of H) and nothing is converted. */
+
+/* launch_add_rmsnorm: x [M][H] += scale .* (sum of n_slabs slabs [n_slabs][M][H] + slab_bias) in place (n_slabs > 0), then
+ * rmsnorm(x) .* w -> out_bf16 / out_f32 [M][H] (either may be NULL; w == NULL: the update alone).  slab_bias, scale [H] optional. */
+RT_API int rt_debug_add_rmsnorm(rt_ctx* ctx, float* d_x, int32_t M, int32_t H, const float* d_slabs, int32_t n_slabs, const float* d_slab_bias,
+                                const float* d_scale, const float* d_w, float eps, void* d_out_bf16, float* d_out_f32);
+/* launch_rowsq: block i reads row src_rows[i] (default i; entries in [0, M)) of x [M][H], or - from block g_first on, when g_table
+ * is set - row g_idx[frame * g_idx_frame_stride + (i - g_first) * g_idx_stride] of the f32 table (a negative index is a row of
+ * zeros; frame = *g_frame_ptr or 0), and writes output row dst_rows[i] (default i; entries in [0, out_rows)):
+ * rowsq [out_rows][rowsq_n] = (sum of squares, 0, ...), x_out [out_rows][H] f32 (optional), a_out [out_rows][H] = bf16(norm_w .* x)
+ * (optional, needs norm_w).  H % 32 == 0 with a tiled output, H % 4 == 0 otherwise. */
+RT_API int rt_debug_rowsq(rt_ctx* ctx, const float* d_x, int32_t M, int32_t H, float* d_rowsq, int32_t rowsq_n, float* d_x_out, void* d_a_out_bf16,
+                          const float* d_norm_w, const int32_t* d_src_rows, const int32_t* d_dst_rows, int32_t out_rows, const float* d_g_table,
+                          const int32_t* d_g_idx, int32_t g_idx_stride, int32_t g_first, const int32_t* d_g_frame_ptr, int64_t g_idx_frame_stride,
+                          int32_t raw_tiled);
+/* launch_norm_tiled_rows: out [M][H] = w .* x * rsqrt(sum(rowsq[row][0 .. rowsq_n)) / H + eps); x [M][H] row-major (the hook tiles it). */
+RT_API int rt_debug_norm_tiled_rows(rt_ctx* ctx, const float* d_x, const float* d_rowsq, int32_t rowsq_n, const float* d_w, float eps, int32_t M,
+                                    int32_t H, float* d_out);
+/* launch_embed_rowsq: row r = add_vec + sum_j table_j[idx[r * idx_stride + j]] over n_src bf16 tables (h_tables: HOST array of
+ * device pointers, h_row_strides: HOST array of row strides in elements; a negative index skips the source), or + row
+ * idx[r * idx_stride] of f32_table [.][H]; idx is moved by *frame_ptr * idx_frame_stride.  Out: x_out [M][H] f32, a_out [M][H] =
+ * bf16(norm_w .* x), rowsq [M][rowsq_n].  frame_inc (== frame_ptr) + arrive (a zeroed counter): the launch also adds 1 to the frame
+ * counter.  qkv_table [.][qkv_n] f32: row idx[r * idx_stride] (negative: row 0) is copied to qkv_out [M][qkv_n]. */
+RT_API int rt_debug_embed_rowsq(rt_ctx* ctx, const void* const* h_tables, const int64_t* h_row_strides, int32_t n_src, const float* d_f32_table,
+                                const int32_t* d_idx, int32_t idx_stride, const int32_t* d_frame_ptr, int64_t idx_frame_stride, int32_t M, int32_t H,
+                                const float* d_add_vec, float* d_rowsq, int32_t rowsq_n, float* d_x_out, void* d_a_out_bf16, const float* d_norm_w,
+                                int32_t* d_frame_inc, uint32_t* d_arrive, const float* d_qkv_table, float* d_qkv_out, int32_t qkv_n,
+                                int32_t raw_tiled);
+/* launch_silu_mul: slabs [n_slabs][M][2 I] (gate columns, then up) -> silu(sum gate) * (sum up) as out_f32 [M][I] if given, else out_bf16.
+ * launch_reduce_slabs: out [M][N] = act(bias + sum of slabs [n_slabs][M][N]), act in {0 none, 1 SiLU, 2 GELU}, to f32 and / or bf16.
+ * launch_f32_to_bf16: n elements, round to nearest even. */
+RT_API int rt_debug_silu_mul(rt_ctx* ctx, const float* d_slabs, int32_t n_slabs, int32_t M, int32_t I, void* d_out_bf16, float* d_out_f32);
+RT_API int rt_debug_reduce_slabs(rt_ctx* ctx, const float* d_slabs, int32_t n_slabs, int64_t M, int32_t N, const float* d_bias, int32_t act,
+                                 float* d_out_f32, void* d_out_bf16);
+RT_API int rt_debug_f32_to_bf16(rt_ctx* ctx, const float* d_x, int64_t n, void* d_out_bf16);
+/* launch_qkv_post: slabs [n_slabs][M][(heads + 2 kv_heads) * d] -> q_out [M][heads][d] f32 (RMSNorm with q_norm_w [d] unless NULL,
+ * rotate-half RoPE with cos / sin [max_pos][d / 2] unless NULL), k / v rows to the caches [slots][kv_heads][max_pos][d] bf16 at
+ * (row_slot[r], row_pos[r] + pos_add + *frame_ptr); k_lo / v_lo (both or neither): the low planes.  The hook reads row_slot /
+ * row_pos back and refuses a row outside the caches. */
+RT_API int rt_debug_qkv_post(rt_ctx* ctx, const float* d_slabs, int32_t n_slabs, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                             const float* d_q_norm_w, const float* d_k_norm_w, float eps, const float* d_cos, const float* d_sin,
+                             const int32_t* d_row_slot, const int32_t* d_row_pos, int32_t pos_add, float* d_q_out, void* d_k, void* d_v,
+                             void* d_k_lo, void* d_v_lo, int32_t slots, int32_t max_pos, const int32_t* d_frame_ptr);
+/* launch_gather_sum: out [M][H] = add_vec + add_rows[add_row_idx[r] (default r; negative: none)] + sum_j table_j[idx[r * idx_stride + j]]
+ * (tables as in rt_debug_embed_rowsq; idx_stride 0 = n_src).  launch_gather_f32: out [M][H] = table[idx[r * idx_stride]], zeros for a
+ * negative index.  Both move idx by *frame_ptr * idx_frame_stride and write f32 and / or bf16. */
+RT_API int rt_debug_gather_sum(rt_ctx* ctx, const void* const* h_tables, const int64_t* h_row_strides, int32_t n_src, const int32_t* d_idx, int32_t M,
+                               int32_t H, const float* d_add_vec, const float* d_add_rows, const int32_t* d_add_row_idx, float* d_out_f32,
+                               void* d_out_bf16, int32_t idx_stride, const int32_t* d_frame_ptr, int64_t idx_frame_stride);
+RT_API int rt_debug_gather_f32(rt_ctx* ctx, const float* d_table, int32_t H, const int32_t* d_idx, int32_t M, float* d_out_f32, void* d_out_bf16,
+                               int32_t idx_stride, const int32_t* d_frame_ptr, int64_t idx_frame_stride);
+/* launch_dwconv_ln: x [B][T][C] f32 -> LayerNorm over C (ln_w, ln_b, eps) of the causal depthwise conv (w [7][C], b [C]) -> out [B][T][C].
+ * launch_code_embed_mean: out [rows][H] = mean over q of table [Q][codebook][H] (bf16) at codes [rows][Q], codes clamped to the codebook.
+ * launch_final_conv: hi / lo bf16 planes [B][T][C], w [7][C], bias [1] -> wav [b * wav_stride + t] = clamp(conv, -1, 1). */
+RT_API int rt_debug_dwconv_ln(rt_ctx* ctx, const float* d_x, int32_t B, int32_t T, int32_t C, const float* d_w, const float* d_b, const float* d_ln_w,
+                              const float* d_ln_b, float eps, float* d_out);
+RT_API int rt_debug_code_embed_mean(rt_ctx* ctx, const void* d_table_bf16, int32_t codebook, int32_t Q, int32_t H, const int32_t* d_codes, int64_t rows,
+                                    float* d_out);
+RT_API int rt_debug_final_conv(rt_ctx* ctx, const void* d_hi, const void* d_lo, int32_t B, int32_t T, int32_t C, const float* d_w, const float* d_bias,
+                               float* d_wav, int64_t wav_stride);
+
+/* rt_debug_gemm's tiled mode (mode 0, split_k 1) with the whole epilogue exposed (tests/test_gemm_epilogue_gpu.py): every field of
+ * the launch's GemmEpi - out = act(acc + bias) * scale + residual (the residual may be out_f32 itself), to f32 / bf16 / hi + lo
+ * planes; out2 = act2(out) (3 SnakeBeta with snake2_a / snake2_ib, 5 ELU) to the same kinds; all outputs [M][ldc], ldc >= N (0 = N).
+ * act: 0 none, 1 SiLU, 2 GELU, 3 SnakeBeta (snake_a, snake_ib), 4 clamp to [-1, 1], 5 ELU.  a_form as rt_debug_gemm's a_is_f32.
+ * d_w2_bf16 [N][N] + e2 (optional): the 1x1 conv behind this conv's SnakeBeta in the same launch, launch_gemm(..., w2, e2).
+ * pair_mode 1 asks conv_pair_fusable first, as the codec decoder does, and returns RT_ERR_UNSUPPORTED where it declines; 2 goes
+ * to launch_gemm directly, whose own refusal is then the status. */
+typedef struct rt_debug_epi {
+    const float* bias;
+    const float* scale;
+    const float* residual;
+    float* out_f32;
+    void* out_bf16;
+    void* out_hi;
+    void* out_lo;
+    const float* snake_a;
+    const float* snake_ib;
+    float* out2_f32;
+    void* out2_bf16;
+    void* out2_hi;
+    void* out2_lo;
+    const float* snake2_a;
+    const float* snake2_ib;
+    int64_t ldc;
+    int32_t act;
+    int32_t act2;
+} rt_debug_epi;
+RT_API int rt_debug_gemm_epi(rt_ctx* ctx, const void* d_a, int32_t a_form, int64_t M, int32_t cin, int32_t taps, int32_t tap_stride, int32_t tap_offset,
+                             int32_t rows_out, int32_t rows_in, const void* d_w_bf16, int32_t N, const rt_debug_epi* e, const void* d_w2_bf16,
+                             const rt_debug_epi* e2, int32_t pair_mode);
+
 /* A/B switches for measurements and tests (process-wide; the defaults are the fast path).  One row per switch, as in the table
  * they are generated from (rho_tts_amd/csrc/knobs.h: defaults, accepted ranges, measurement notes).  A code that no row accepts is
  * refused with RT_ERR_INVALID and changes nothing.  `code`:

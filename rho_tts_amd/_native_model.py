@@ -49,6 +49,13 @@ class RtGenerateArgs(C.Structure):
                 ("d_trace_talker", C.c_void_p), ("d_trace_predictor", C.c_void_p), ("max_rows", C.c_int32)]
 
 
+class RtDebugEpi(C.Structure):
+    """rt_debug_epi (include/rho_tts_amd_debug.h): the tiled GEMM's epilogue as rt_debug_gemm_epi takes it."""
+    _fields_ = [(n, C.c_void_p) for n in ("bias", "scale", "residual", "out_f32", "out_bf16", "out_hi", "out_lo", "snake_a", "snake_ib",
+                                          "out2_f32", "out2_bf16", "out2_hi", "out2_lo", "snake2_a", "snake2_ib")] + \
+               [("ldc", C.c_int64), ("act", C.c_int32), ("act2", C.c_int32)]
+
+
 def declare(lib: C.CDLL) -> None:
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     lib.rt_model_create.argtypes = [vp, C.POINTER(RtModelConfig), C.POINTER(vp)]
@@ -87,6 +94,22 @@ def declare(lib: C.CDLL) -> None:
     lib.rt_debug_attention_fused.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]
     lib.rt_debug_attention_prefill.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.rt_debug_sample.argtypes = [vp, vp, i32, i32, C.POINTER(RtSampling), C.c_uint64, i32, i32, i32, i32, vp, vp]
+    # the row kernels and the tiled GEMM's epilogue on their own (tests/test_rowops_gpu.py, tests/test_gemm_epilogue_gpu.py)
+    pvp, pi64 = C.POINTER(vp), C.POINTER(i64)
+    lib.rt_debug_add_rmsnorm.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, f32, vp, vp]
+    lib.rt_debug_rowsq.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, i64, i32]
+    lib.rt_debug_norm_tiled_rows.argtypes = [vp, vp, vp, i32, vp, f32, i32, i32, vp]
+    lib.rt_debug_embed_rowsq.argtypes = [vp, pvp, pi64, i32, vp, vp, i32, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32]
+    lib.rt_debug_silu_mul.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    lib.rt_debug_reduce_slabs.argtypes = [vp, vp, i32, i64, i32, vp, i32, vp, vp]
+    lib.rt_debug_f32_to_bf16.argtypes = [vp, vp, i64, vp]
+    lib.rt_debug_qkv_post.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp]
+    lib.rt_debug_gather_sum.argtypes = [vp, pvp, pi64, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, i64]
+    lib.rt_debug_gather_f32.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, i64]
+    lib.rt_debug_dwconv_ln.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, f32, vp]
+    lib.rt_debug_code_embed_mean.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp]
+    lib.rt_debug_final_conv.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, i64]
+    lib.rt_debug_gemm_epi.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(RtDebugEpi), vp, C.POINTER(RtDebugEpi), i32]
 
 
 def _stack(d: TransformerDims) -> StackDims:

@@ -353,6 +353,303 @@ int rt_debug_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_t V, co
     return rc;
 }
 
+// ------------------------------------------------------------------ row kernels on their own (rowops.hip through its launchers)
+extern "C++" {
+namespace {
+// frees what a hook allocated, after the stream has drained (every exit of a hook runs it)
+struct DbgBufs {
+    rt_ctx* ctx;
+    std::vector<void*> ptrs;
+    explicit DbgBufs(rt_ctx* c) : ctx(c) {}
+    ~DbgBufs() {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    template <typename T>
+    hipError_t alloc(T** out, size_t bytes) {
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+        if (e == hipSuccess) ptrs.push_back(p);
+        *out = (T*)p;
+        return e;
+    }
+};
+// the device array of bf16 sources from the host arrays of the ABI
+int upload_srcs(rt_ctx* ctx, DbgBufs& bufs, const void* const* h_tables, const int64_t* h_row_strides, int n_src, GatherSrc** out) {
+    *out = nullptr;
+    if (n_src <= 0) return RT_OK;
+    std::vector<GatherSrc> h((size_t)n_src);
+    for (int j = 0; j < n_src; ++j) {
+        if (!h_tables[j]) return rt_fail(ctx, RT_ERR_INVALID, "debug hook: source table %d is null", j);
+        h[j].table = (const bf16_t*)h_tables[j];
+        h[j].row_stride = h_row_strides[j];
+    }
+    RT_HIP(ctx, bufs.alloc(out, sizeof(GatherSrc) * (size_t)n_src));
+    RT_HIP(ctx, hipMemcpy(*out, h.data(), sizeof(GatherSrc) * (size_t)n_src, hipMemcpyHostToDevice));
+    return RT_OK;
+}
+int dbg_finish(rt_ctx* ctx, int rc) {
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (rc) return rc;
+    RT_HIP(ctx, se);
+    return RT_OK;
+}
+// tiled working copies of the caller's row-major [rows][H] outputs (see the header: what the kernel leaves alone keeps its bytes)
+template <typename T>
+int dbg_tile_in(rt_ctx* ctx, DbgBufs& bufs, const T* rows_rm, int rows, int H, T** tiled) {
+    const size_t pad = (size_t)(rows + 15) / 16 * 16;
+    RT_HIP(ctx, bufs.alloc(tiled, pad * H * sizeof(T)));
+    RT_HIP(ctx, hipMemsetAsync(*tiled, 0, pad * H * sizeof(T), ctx->stream));
+    hipLaunchKernelGGL((k_tile_rows<T>), dim3(256), dim3(256), 0, ctx->stream, rows_rm, rows, H, 0, *tiled);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+template <typename T>
+int dbg_tile_out(rt_ctx* ctx, const T* tiled, int rows, int H, T* rows_rm) {
+    hipLaunchKernelGGL((k_untile_rows<T>), dim3(256), dim3(256), 0, ctx->stream, tiled, rows, H, 0, rows_rm);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+int dbg_read_i32(rt_ctx* ctx, const int32_t* d, int n, std::vector<int32_t>& h) {
+    h.assign((size_t)n, 0);
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RT_HIP(ctx, hipMemcpy(h.data(), d, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int rt_debug_add_rmsnorm(rt_ctx* ctx, float* d_x, int32_t M, int32_t H, const float* d_slabs, int32_t n_slabs, const float* d_slab_bias,
+                         const float* d_scale, const float* d_w, float eps, void* d_out_bf16, float* d_out_f32) {
+    if (!ctx || !d_x || M < 1 || H < 1 || n_slabs < 0 || (n_slabs > 0 && !d_slabs))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_add_rmsnorm: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_add_rmsnorm(ctx, d_x, M, H, d_slabs, n_slabs, d_slab_bias, d_scale, d_w, eps, (bf16_t*)d_out_bf16, d_out_f32));
+}
+
+int rt_debug_rowsq(rt_ctx* ctx, const float* d_x, int32_t M, int32_t H, float* d_rowsq, int32_t rowsq_n, float* d_x_out, void* d_a_out_bf16,
+                   const float* d_norm_w, const int32_t* d_src_rows, const int32_t* d_dst_rows, int32_t out_rows, const float* d_g_table,
+                   const int32_t* d_g_idx, int32_t g_idx_stride, int32_t g_first, const int32_t* d_g_frame_ptr, int64_t g_idx_frame_stride,
+                   int32_t raw_tiled) {
+    const bool tiled_out = d_x_out || d_a_out_bf16;
+    if (!ctx || !d_rowsq || M < 1 || rowsq_n < 1 || out_rows < 1 || H < 4 || H % 4 || (tiled_out && H % 32) || (d_a_out_bf16 && !d_norm_w) ||
+        (!d_dst_rows && out_rows < M) || (!d_x && !(d_g_table && g_first == 0)))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_rowsq: bad argument (H %% 4 == 0, H %% 32 == 0 with a tiled output, out_rows >= M without a row map)");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<int32_t> h;
+    if (d_src_rows) {
+        RT_TRY(dbg_read_i32(ctx, d_src_rows, M, h));
+        for (int32_t v : h) if (v < 0 || v >= M) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_rowsq: source row %d outside [0, %d)", v, M);
+    }
+    if (d_dst_rows) {
+        RT_TRY(dbg_read_i32(ctx, d_dst_rows, M, h));
+        for (int32_t v : h) if (v < 0 || v >= out_rows) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_rowsq: output row %d outside [0, %d)", v, out_rows);
+    }
+    DbgBufs bufs(ctx);
+    float* x_t = d_x_out;
+    bf16_t* a_t = (bf16_t*)d_a_out_bf16;
+    if (!raw_tiled) {
+        if (d_x_out) RT_TRY(dbg_tile_in(ctx, bufs, (const float*)d_x_out, out_rows, H, &x_t));
+        if (d_a_out_bf16) RT_TRY(dbg_tile_in(ctx, bufs, (const bf16_t*)d_a_out_bf16, out_rows, H, &a_t));
+    }
+    RowsqGather gt;
+    gt.table = d_g_table; gt.idx = d_g_idx; gt.idx_stride = g_idx_stride; gt.first = g_first; gt.frame_ptr = d_g_frame_ptr; gt.idx_frame_stride = g_idx_frame_stride;
+    int rc = launch_rowsq(ctx, d_x, M, H, d_rowsq, rowsq_n, x_t, a_t, d_norm_w, d_src_rows, d_dst_rows, d_g_table ? &gt : nullptr);
+    if (!rc && !raw_tiled) {
+        if (d_x_out) rc = dbg_tile_out(ctx, (const float*)x_t, out_rows, H, d_x_out);
+        if (!rc && d_a_out_bf16) rc = dbg_tile_out(ctx, (const bf16_t*)a_t, out_rows, H, (bf16_t*)d_a_out_bf16);
+    }
+    return dbg_finish(ctx, rc);
+}
+
+int rt_debug_norm_tiled_rows(rt_ctx* ctx, const float* d_x, const float* d_rowsq, int32_t rowsq_n, const float* d_w, float eps, int32_t M, int32_t H,
+                             float* d_out) {
+    if (!ctx || !d_x || !d_rowsq || !d_w || !d_out || M < 1 || rowsq_n < 1 || H < 32 || H % 32)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_norm_tiled_rows: bad argument (H %% 32 == 0)");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    DbgBufs bufs(ctx);
+    float* x_t = nullptr;
+    RT_TRY(dbg_tile_in(ctx, bufs, d_x, M, H, &x_t));
+    return dbg_finish(ctx, launch_norm_tiled_rows(ctx, x_t, d_rowsq, rowsq_n, d_w, eps, M, H, d_out));
+}
+
+int rt_debug_embed_rowsq(rt_ctx* ctx, const void* const* h_tables, const int64_t* h_row_strides, int32_t n_src, const float* d_f32_table,
+                         const int32_t* d_idx, int32_t idx_stride, const int32_t* d_frame_ptr, int64_t idx_frame_stride, int32_t M, int32_t H,
+                         const float* d_add_vec, float* d_rowsq, int32_t rowsq_n, float* d_x_out, void* d_a_out_bf16, const float* d_norm_w,
+                         int32_t* d_frame_inc, uint32_t* d_arrive, const float* d_qkv_table, float* d_qkv_out, int32_t qkv_n, int32_t raw_tiled) {
+    if (!ctx || !d_idx || M < 1 || H < 32 || H % 32 || n_src < 0 || idx_stride < 1 || (n_src > 0 && (!h_tables || !h_row_strides)) ||
+        (n_src == 0 && !d_f32_table) || !d_x_out || !d_a_out_bf16 || !d_rowsq || rowsq_n < 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_embed_rowsq: bad argument (H %% 32 == 0, a source, all three outputs)");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    DbgBufs bufs(ctx);
+    GatherSrc* srcs = nullptr;
+    if (n_src <= 16) RT_TRY(upload_srcs(ctx, bufs, h_tables, h_row_strides, n_src, &srcs));     // (more: the launcher's refusal)
+    float* x_t = d_x_out;
+    bf16_t* a_t = (bf16_t*)d_a_out_bf16;
+    if (!raw_tiled) {
+        RT_TRY(dbg_tile_in(ctx, bufs, (const float*)d_x_out, M, H, &x_t));
+        RT_TRY(dbg_tile_in(ctx, bufs, (const bf16_t*)d_a_out_bf16, M, H, &a_t));
+    }
+    int rc = launch_embed_rowsq(ctx, srcs, n_src, d_f32_table, d_idx, idx_stride, d_frame_ptr, idx_frame_stride, M, H, d_add_vec, d_rowsq, rowsq_n,
+                                x_t, a_t, d_norm_w, d_frame_inc, (unsigned*)d_arrive, d_qkv_table, d_qkv_out, qkv_n);
+    if (!rc && !raw_tiled) {
+        rc = dbg_tile_out(ctx, (const float*)x_t, M, H, d_x_out);
+        if (!rc) rc = dbg_tile_out(ctx, (const bf16_t*)a_t, M, H, (bf16_t*)d_a_out_bf16);
+    }
+    return dbg_finish(ctx, rc);
+}
+
+int rt_debug_silu_mul(rt_ctx* ctx, const float* d_slabs, int32_t n_slabs, int32_t M, int32_t I, void* d_out_bf16, float* d_out_f32) {
+    if (!ctx || !d_slabs || n_slabs < 1 || M < 1 || I < 1 || (!d_out_bf16 && !d_out_f32)) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_silu_mul: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_silu_mul(ctx, d_slabs, n_slabs, M, I, (bf16_t*)d_out_bf16, d_out_f32));
+}
+
+int rt_debug_reduce_slabs(rt_ctx* ctx, const float* d_slabs, int32_t n_slabs, int64_t M, int32_t N, const float* d_bias, int32_t act, float* d_out_f32,
+                          void* d_out_bf16) {
+    if (!ctx || !d_slabs || n_slabs < 1 || M < 1 || N < 1 || act < ACT_NONE || act > ACT_GELU || (!d_out_bf16 && !d_out_f32))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_reduce_slabs: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_reduce_slabs(ctx, d_slabs, n_slabs, M, N, d_bias, act, d_out_f32, (bf16_t*)d_out_bf16));
+}
+
+int rt_debug_f32_to_bf16(rt_ctx* ctx, const float* d_x, int64_t n, void* d_out_bf16) {
+    if (!ctx || !d_x || !d_out_bf16 || n < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_f32_to_bf16: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_f32_to_bf16(ctx, d_x, n, (bf16_t*)d_out_bf16));
+}
+
+int rt_debug_qkv_post(rt_ctx* ctx, const float* d_slabs, int32_t n_slabs, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                      const float* d_q_norm_w, const float* d_k_norm_w, float eps, const float* d_cos, const float* d_sin, const int32_t* d_row_slot,
+                      const int32_t* d_row_pos, int32_t pos_add, float* d_q_out, void* d_k, void* d_v, void* d_k_lo, void* d_v_lo, int32_t slots,
+                      int32_t max_pos, const int32_t* d_frame_ptr) {
+    if (!ctx || !d_slabs || n_slabs < 1 || M < 1 || heads < 1 || kv_heads < 1 || head_dim < 1 || !d_row_slot || !d_row_pos || !d_q_out || !d_k || !d_v ||
+        !d_k_lo != !d_v_lo || !d_cos != !d_sin || slots < 1 || max_pos < 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_qkv_post: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<int32_t> hs, hp, hf(1, 0);
+    RT_TRY(dbg_read_i32(ctx, d_row_slot, M, hs));
+    RT_TRY(dbg_read_i32(ctx, d_row_pos, M, hp));
+    if (d_frame_ptr) RT_TRY(dbg_read_i32(ctx, d_frame_ptr, 1, hf));
+    for (int r = 0; r < M; ++r) {
+        const int64_t pos = (int64_t)hp[r] + pos_add + hf[0];
+        if (hs[r] < 0 || hs[r] >= slots || pos < 0 || pos >= max_pos)
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_qkv_post: row %d at slot %d position %lld is outside the caches", r, hs[r], (long long)pos);
+    }
+    KvCache kv;
+    kv.k = (bf16_t*)d_k; kv.v = (bf16_t*)d_v; kv.k_lo = (bf16_t*)d_k_lo; kv.v_lo = (bf16_t*)d_v_lo;
+    kv.layers = 1; kv.slots = slots; kv.kv_heads = kv_heads; kv.max_pos = max_pos; kv.head_dim = head_dim;
+    return dbg_finish(ctx, launch_qkv_post(ctx, d_slabs, n_slabs, M, heads, kv_heads, head_dim, d_q_norm_w, d_k_norm_w, eps, d_cos, d_sin, d_row_slot,
+                                           d_row_pos, pos_add, d_q_out, kv, 0, d_frame_ptr));
+}
+
+int rt_debug_gather_sum(rt_ctx* ctx, const void* const* h_tables, const int64_t* h_row_strides, int32_t n_src, const int32_t* d_idx, int32_t M, int32_t H,
+                        const float* d_add_vec, const float* d_add_rows, const int32_t* d_add_row_idx, float* d_out_f32, void* d_out_bf16,
+                        int32_t idx_stride, const int32_t* d_frame_ptr, int64_t idx_frame_stride) {
+    if (!ctx || M < 1 || H < 1 || n_src < 0 || n_src > 64 || idx_stride < 0 || (n_src > 0 && (!h_tables || !h_row_strides || !d_idx)) ||
+        (!d_out_f32 && !d_out_bf16))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gather_sum: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    DbgBufs bufs(ctx);
+    GatherSrc* srcs = nullptr;
+    RT_TRY(upload_srcs(ctx, bufs, h_tables, h_row_strides, n_src, &srcs));
+    return dbg_finish(ctx, launch_gather_sum(ctx, srcs, n_src, d_idx, M, H, d_add_vec, d_add_rows, d_add_row_idx, d_out_f32, (bf16_t*)d_out_bf16,
+                                             idx_stride, d_frame_ptr, idx_frame_stride));
+}
+
+int rt_debug_gather_f32(rt_ctx* ctx, const float* d_table, int32_t H, const int32_t* d_idx, int32_t M, float* d_out_f32, void* d_out_bf16,
+                        int32_t idx_stride, const int32_t* d_frame_ptr, int64_t idx_frame_stride) {
+    if (!ctx || !d_table || !d_idx || M < 1 || H < 1 || idx_stride < 1 || (!d_out_f32 && !d_out_bf16))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gather_f32: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_gather_f32(ctx, d_table, H, d_idx, M, d_out_f32, (bf16_t*)d_out_bf16, idx_stride, d_frame_ptr, idx_frame_stride));
+}
+
+int rt_debug_dwconv_ln(rt_ctx* ctx, const float* d_x, int32_t B, int32_t T, int32_t C, const float* d_w, const float* d_b, const float* d_ln_w,
+                       const float* d_ln_b, float eps, float* d_out) {
+    if (!ctx || !d_x || !d_w || !d_b || !d_ln_w || !d_ln_b || !d_out || B < 1 || T < 1 || C < 1 || (size_t)C * 4 > 64 * 1024)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_dwconv_ln: bad argument (a row of C floats must fit 64 KiB of LDS)");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_dwconv_ln(ctx, d_x, B, T, C, d_w, d_b, d_ln_w, d_ln_b, eps, d_out));
+}
+
+int rt_debug_code_embed_mean(rt_ctx* ctx, const void* d_table_bf16, int32_t codebook, int32_t Q, int32_t H, const int32_t* d_codes, int64_t rows,
+                             float* d_out) {
+    if (!ctx || !d_table_bf16 || !d_codes || !d_out || codebook < 1 || Q < 1 || H < 1 || rows < 1 || rows > 0x7fffffff)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_code_embed_mean: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_code_embed_mean(ctx, (const bf16_t*)d_table_bf16, codebook, Q, H, d_codes, rows, d_out));
+}
+
+int rt_debug_final_conv(rt_ctx* ctx, const void* d_hi, const void* d_lo, int32_t B, int32_t T, int32_t C, const float* d_w, const float* d_bias,
+                        float* d_wav, int64_t wav_stride) {
+    if (!ctx || !d_hi || !d_lo || !d_w || !d_bias || !d_wav || B < 1 || T < 1 || C < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_final_conv: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_final_conv(ctx, (const bf16_t*)d_hi, (const bf16_t*)d_lo, B, T, C, d_w, d_bias, d_wav, wav_stride));
+}
+
+// rt_debug_gemm's tiled mode with the whole GemmEpi exposed, and optionally the fused conv pair
+namespace {
+bool dbg_epi(const rt_debug_epi& s, int N, GemmEpi* e) {
+    e->bias = s.bias; e->scale = s.scale; e->residual = s.residual; e->out_f32 = s.out_f32; e->out_bf16 = (bf16_t*)s.out_bf16;
+    e->act = s.act; e->snake_a = s.snake_a; e->snake_ib = s.snake_ib; e->out2_bf16 = (bf16_t*)s.out2_bf16; e->out2_f32 = s.out2_f32;
+    e->out_hi = (bf16_t*)s.out_hi; e->out_lo = (bf16_t*)s.out_lo; e->out2_hi = (bf16_t*)s.out2_hi; e->out2_lo = (bf16_t*)s.out2_lo;
+    e->snake2_a = s.snake2_a; e->snake2_ib = s.snake2_ib; e->act2 = s.act2; e->ldc = s.ldc > 0 ? s.ldc : N; e->split_k = 1;
+    const bool two = s.out2_f32 || s.out2_bf16 || s.out2_hi || s.out2_lo;
+    // what the kernel would dereference without a test of its own (the plane pairs are the launcher's to refuse)
+    return e->ldc >= N && s.act >= ACT_NONE && s.act <= ACT_ELU && (s.act != ACT_SNAKE || (s.snake_a && s.snake_ib)) &&
+           (!two || s.act2 == ACT_ELU || (s.act2 == ACT_SNAKE && s.snake2_a && s.snake2_ib));
+}
+}  // namespace
+
+int rt_debug_gemm_epi(rt_ctx* ctx, const void* d_a, int32_t a_form, int64_t M, int32_t cin, int32_t taps, int32_t tap_stride, int32_t tap_offset,
+                      int32_t rows_out, int32_t rows_in, const void* d_w_bf16, int32_t N, const rt_debug_epi* e, const void* d_w2_bf16,
+                      const rt_debug_epi* e2, int32_t pair_mode) {
+    if (!ctx || !d_a || !d_w_bf16 || !e || M < 1 || N < 1 || cin < 8 || taps < 1 || a_form < 0 || a_form > 3 || (rows_out > 0 && (rows_in < 1 || M % rows_out)) ||
+        (d_w2_bf16 && (!e2 || (pair_mode != 1 && pair_mode != 2))))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gemm_epi: bad argument");
+    GemmEpi ge, ge2;
+    if (!dbg_epi(*e, N, &ge) || (d_w2_bf16 && !dbg_epi(*e2, N, &ge2)))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gemm_epi: ldc < N, an unknown activation or SnakeBeta without its constants");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    DbgBufs bufs(ctx);
+    const int K = cin * taps;
+    bf16_t *packed = nullptr, *packed2 = nullptr;
+    RT_HIP(ctx, bufs.alloc(&packed, packed_bytes(N, K)));
+    PackedW pw, pw2;
+    RT_TRY(launch_pack_weight(ctx, (const bf16_t*)d_w_bf16, N, K, packed, &pw));
+    GemmA a; a.ptr = d_a; a.is_f32 = a_form == 1 || a_form == 2; a.split = a_form >= 2; a.M = M; a.Cin = cin; a.taps = taps; a.tap_stride = tap_stride;
+    a.tap_offset = tap_offset; a.rows_out = rows_out; a.rows_in = rows_in;
+    if (a_form == 3) {           // operand planes: the bf16 hi plane, then the bf16 lo plane, each [input rows][cin]
+        const int64_t in_rows = rows_out > 0 ? (M / rows_out) * rows_in : M;
+        a.ptr_lo = (const bf16_t*)d_a + in_rows * cin;
+    }
+    int rc;
+    if (d_w2_bf16) {
+        RT_HIP(ctx, bufs.alloc(&packed2, packed_bytes(N, N)));
+        RT_TRY(launch_pack_weight(ctx, (const bf16_t*)d_w2_bf16, N, N, packed2, &pw2));
+        if (pair_mode == 1 && !conv_pair_fusable(a, pw, ge, pw2)) rc = rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_debug_gemm_epi: conv_pair_fusable declines this pair");
+        else rc = launch_gemm(ctx, a, pw, ge, &pw2, &ge2);
+    } else {
+        rc = launch_gemm(ctx, a, pw, ge);
+    }
+    return dbg_finish(ctx, rc);
+}
+
 int rt_debug_tune(int32_t code, int32_t arg) {
     // exclusive: waits until no call is executing on any context (CtxLock holds this lock shared), and a resumable generation in
     // flight keeps the plan it began with - the switch is refused rather than applied under it

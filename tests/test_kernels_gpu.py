@@ -1,6 +1,8 @@
-"""Kernel-level numerics on the GPU through the C ABI's test hooks: each HIP kernel against a
-plain PyTorch float32 reference of the same op (bf16 inputs are exact in float32, so the only
-differences are accumulation order and the final rounding)."""
+"""Kernel-level numerics on the GPU through the C ABI's test hooks: the GEMM cores, every attention
+form and the sampler against a plain PyTorch float32 reference of the same op (bf16 inputs are exact
+in float32, so the only differences are accumulation order and the final rounding).  The row kernels
+of rowops.hip are tested one by one in tests/test_rowops_gpu.py, the epilogue of the tiled GEMM and
+of k_conv_win field by field in tests/test_gemm_epilogue_gpu.py."""
 import ctypes as C
 
 import numpy as np
