@@ -431,6 +431,63 @@ typedef struct rt_stt_decode_out {
 } rt_stt_decode_out;
 RT_API int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
                                 const rt_stt_decode_opts* opts, rt_stt_decode_out* out);
+/* Clips longer than one window by timestamps and seek ("timestamps and seek"), as the reference's transcribers
+ * walk them: every window is decoded WITH timestamp tokens under the step rule (transformers' WhisperTimeStampLogitsProcessor), and
+ * the seek rule (_retrieve_segment) closes segments at timestamp pairs, discards an unfinished tail and starts the clip's next
+ * window at the last closed pair's timestamp, so a word that straddles a boundary is decoded again whole.  No conditioning on
+ * previous text, no temperature fallback.  A round holds one window per unfinished clip; rounds run in groups of
+ * floor(32 / beam_size) windows as rt_stt_transcribe_beam.  A clip's result is what it gets as the only clip of a call.
+ * rt_stt_set_timestamps: timestamp ids [timestamp_begin, timestamp_begin + n_timestamps), n_timestamps = chunk_seconds / 0.02 + 1;
+ *   timestamp_begin - 1 is <|notimestamps|>.  Before rt_stt_finalize.  RT_ERR_INVALID: the vocabulary does not hold the ids, the
+ *   handle's prefix does not end in timestamp_begin - 1, or end-of-sequence is not below it.  In timestamp mode the prefix is the
+ *   handle's without that last entry and the timestamp ids leave the suppress mask - for rt_stt_transcribe_seek only; every other
+ *   entry point is what it is without this call.
+ * opts: beam_size, max_tokens (caps every clip's joined TEXT ids) and h_language as rt_stt_decode_opts; max_initial_timestamp_index
+ *   (-1: no limit): the largest timestamp index a window's first token may take; no_speech_threshold (NaN: the silence rule is off)
+ *   and logprob_threshold (NaN: the no-speech test alone): a window with no_speech > threshold and avg_logprob < threshold
+ *   contributes no segment and is consumed whole.
+ * out, per clip: h_tokens [n_clips][max_tokens] the text ids of the clip's segments joined (timestamps and end-of-sequence stripped,
+ *   discarded tails not included), h_n_tokens, h_scores (optional; sum of the kept windows' cumulative log-probabilities / sum of
+ *   their tokens + 1), h_language, h_language_prob (optional) as rt_stt_decode_out.  max_clip_tokens receives the largest uncut
+ *   number of text ids of a clip.  Per segment, in clip order, each optional, segment_cap entries of room: the owning clip, start
+ *   and end in seconds of the clip and in ticks (one tick = floor(0.02 sample_rate_in) input samples), the number of text ids.  Per
+ *   window, in clip order, each optional, window_cap entries: the owning clip, the start offset in input samples, the ids decoded
+ *   (timestamps counted), the cumulative log-probability, the no-speech probability (NaN when no probe ran), the advance in ticks.
+ *   n_segments / n_windows receive the full counts.  Nothing is written past a cap: when one is too small the call returns
+ *   RT_ERR_LENGTH with the counts a repeat needs.
+ * RT_ERR_INVALID (nothing is launched, the handle stays usable): the argument rules of rt_stt_transcribe_ex; a handle without
+ *   rt_stt_set_timestamps; a cap below 1; the silence rule, h_language or h_win_no_speech on a handle without rt_stt_set_languages. */
+typedef struct rt_stt_seek_opts {
+    const int32_t* h_language;
+    int32_t beam_size, max_tokens;
+    int32_t max_initial_timestamp_index;
+    float no_speech_threshold, logprob_threshold;
+    int32_t reserved[3];
+} rt_stt_seek_opts;
+typedef struct rt_stt_seek_out {
+    int32_t* h_tokens;
+    int32_t* h_n_tokens;
+    float* h_scores;
+    int32_t* h_language;
+    float* h_language_prob;
+    int32_t* h_seg_clip;
+    float* h_seg_start;
+    float* h_seg_end;
+    int32_t* h_seg_start_tick;
+    int32_t* h_seg_end_tick;
+    int32_t* h_seg_n_ids;
+    int32_t* h_win_clip;
+    int64_t* h_win_offset;
+    int32_t* h_win_n_ids;
+    float* h_win_logprob;
+    float* h_win_no_speech;
+    int32_t* h_win_advance;
+    int32_t segment_cap, window_cap, n_segments, n_windows, max_clip_tokens;
+    int32_t reserved[3];
+} rt_stt_seek_out;
+RT_API int rt_stt_set_timestamps(rt_stt* s, int32_t timestamp_begin, int32_t n_timestamps);
+RT_API int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
+                                  const rt_stt_seek_opts* opts, rt_stt_seek_out* out);
 /* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM:
  * row 0 of the same front end and encoder with the clip as its only window.  Of a clip longer than chunk_seconds the first
  * chunk is kept, and the resampler's taps at its end see the samples behind it. */

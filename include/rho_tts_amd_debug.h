@@ -130,6 +130,17 @@ RT_API int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_
                                   float* h_fin_score, int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows);
 RT_API int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src,
                                      int32_t len, uint16_t* h_planes);
+/* rt_debug_stt_beam_step under the timestamp rule (tests/test_stt_seek_kernel_gpu.py; a handle with rt_stt_set_timestamps): the step
+ * as rt_stt_transcribe_seek launches it.  Further in, per row: the history state - h_ts_flags_in bit 0: the row's last generated
+ * token is a timestamp, bit 1: the one before it is (or the history holds fewer than two tokens); h_ts_last_in: the last timestamp
+ * id of the row's history, 0: none - and max_initial_timestamp_index (-1: no limit; it binds when first_step is set).  Further out:
+ * the state of every next beam, derived from its parent row's. */
+RT_API int rt_debug_stt_beam_step_ts(rt_stt* s, const float* d_logits, int32_t row_stride, const float* h_scores_in, int32_t n_windows, int32_t beam,
+                                     const int32_t* h_n_live, const int32_t* h_n_finished, const int32_t* h_done, int32_t first_step, int32_t step,
+                                     int32_t max_initial_timestamp_index, const int32_t* h_ts_flags_in, const int32_t* h_ts_last_in,
+                                     int32_t* h_next_tok, int32_t* h_parent, float* h_scores_out, int32_t* h_n_live_out, int32_t* h_fin_beam,
+                                     float* h_fin_score, int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows,
+                                     int32_t* h_ts_flags_out, int32_t* h_ts_last_out);
 
 /* k_stt_probe on logits the caller supplies (tests/test_stt_lang_kernel_gpu.py): n_rows (1 .. 32) rows of cfg.vocab float32 in HBM,
  * row r at d_logits + r * row_stride (row_stride >= cfg.vocab), with the handle's languages and no-speech id (rt_stt_set_languages)

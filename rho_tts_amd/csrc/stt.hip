@@ -29,6 +29,12 @@
 // same stt_decode_rows) in front of the prefix pass, k_stt_probe reads a window's language and no-speech probability off its logits
 // and k_stt_lang_prefix writes position 1 of every window's prefix on the device.  The three older entry points pass the handle's
 // prefix and no probe: their launches are what they were.
+//
+// rt_stt_transcribe_seek walks a clip longer than a window as the reference's transcriber does ("timestamps and
+// seek"): windows are decoded with timestamp tokens - k_stt_beam_select<true> applies the step rule in the passes the step already
+// makes, from three facts per row kept in the beam book - and the host applies the seek rule to what a group decoded
+// (stt_seek_rule): a round holds one window per unfinished clip at the clip's current offset, and the number of rounds is bounded
+// before the first launch.  Off unless rt_stt_set_timestamps was called; no other entry point changes.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -313,8 +319,16 @@ struct SttBeamBook {
     float* fin_score;                // [R]
     int32_t* live;                   // [1] windows of the group still decoding
     int32_t *bp_tok, *bp_par;        // [steps][R] back-pointers: the token a row took at a step and the beam it came from
+    // [R] timestamp mode (rt_stt_transcribe_seek) only, a row's history state: bit 0 - its last token is a timestamp, bit 1 - the one
+    // before it is (or the history is shorter than two) | the last timestamp id of its history, 0: none.  Written for a next beam from
+    // its parent's, so the state follows a beam through `src`
+    int32_t *ts_flags, *ts_last;
     int R;
 };
+
+// The timestamp rule of a step ("timestamps and seek"): timestamp ids are [t0, t0 + nt), t0 - 1 is
+// <|notimestamps|>; max_initial: the largest timestamp index the first generated token may take, -1: no limit
+struct SttTsRule { int t0, nt, max_initial; };
 
 // One step of the rule, one workgroup per window.  Per live row: the masked maximum, sum exp(x - max) (per thread in index order,
 // butterfly per wave, the 16 wave sums in wave order: a row's log-probabilities do not depend on what else is in the launch), then
@@ -322,9 +336,18 @@ struct SttBeamBook {
 // <= 72 candidates by (score descending, beam, id) and thread 0 walks them: end-of-sequence candidates enter the finished list
 // while it has room, the others become the next beams until B are taken.  logits row of beam j: w row_stride + j (the step behind
 // the prefix has one row per window: row_stride 1, one live beam).
+//
+// TS (rt_stt_transcribe_seek): the same passes apply the timestamp rule.  From the row's history state every id is text, timestamp or
+// barred for this step: text ids are [text_lo, t0 - 1) under the mask, timestamp ids [ts_lo, ts_hi) whatever the mask says.  The
+// maximum pass and the sum pass each form the two parts' figures side by side (same order of reduction per part); timestamps win -
+// every text id is barred - when m_ts + log(s_ts) > m_text, and the row's normaliser follows from the parts that survive.  Thread 0
+// writes a next beam's state from its parent's.  TS == false compiles to the statements the kernel had before the rule existed.
+template <bool TS>
 __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restrict__ logits, int V, int row_stride, const uint8_t* __restrict__ mask,
-                                                          int first_step, int eos, int B, int step, SttBeamBook bk) {
+                                                          int first_step, int eos, int B, int step, SttBeamBook bk, SttTsRule ts) {
     __shared__ float red_v[16];
+    __shared__ float red_w[16];
+    __shared__ int sh_flags[STT_BEAM_MAX], sh_last[STT_BEAM_MAX];
     __shared__ int red_i[16];
     __shared__ float c_score[STT_BEAM_MAX * STT_CAND];
     __shared__ int c_tok[STT_BEAM_MAX * STT_CAND], c_beam[STT_BEAM_MAX * STT_CAND], c_sorted[STT_BEAM_MAX * STT_CAND];
@@ -332,45 +355,109 @@ __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restric
     if (bk.done[w]) return;                                // (uniform: a completed window rides along untouched)
     const int nl = min(bk.n_live[w], B), K = B + 1;
     const uint8_t bad = first_step ? 3 : 1;
+    if constexpr (TS) {
+        if (tid < B) { sh_flags[tid] = bk.ts_flags[w * B + tid]; sh_last[tid] = bk.ts_last[w * B + tid]; }
+        __syncthreads();
+    }
     for (int j = 0; j < nl; ++j) {
         const float* x = logits + ((int64_t)w * row_stride + j) * V;
+        int text_lo = 0, text_hi = 0, ts_lo = 0, ts_hi = 0;
+        if constexpr (TS) {
+            const bool last = sh_flags[j] & 1, pen = sh_flags[j] & 2;
+            const int lts = sh_last[j];
+            text_hi = ts.t0 - 1;                               // <|notimestamps|> never appears
+            ts_lo = ts.t0; ts_hi = min(ts.t0 + ts.nt, V);
+            if (lts > 0) ts_lo = max(ts_lo, (last && !pen) ? lts : lts + 1);      // timestamps do not decrease (nor repeat, outside a pair)
+            if (last && pen) ts_lo = ts_hi;                    // behind a pair (or a lone first timestamp): text
+            if (last && !pen) text_lo = eos;                   // closing a pair: a timestamp or the end
+            if (first_step) {                                  // the first generated token is a timestamp, at most max_initial
+                text_lo = text_hi;
+                if (ts.max_initial >= 0) ts_hi = min(ts_hi, ts.t0 + ts.max_initial + 1);
+            }
+        }
+        // 0: barred, 1: text, 2: timestamp
+        auto kind = [&](int i, int mk) -> int {
+            if (i >= ts_lo && i < ts_hi) return 2;
+            return (i >= text_lo && i < text_hi && !(mk & bad)) ? 1 : 0;
+        };
         // every pass asks for STT_SEL_U logits and mask bytes of the thread at once, unconditionally (clamped indices): one round trip
         // per 4 elements instead of one per element behind a per-lane branch (8 would spill at 1024 threads)
-        float m = -INFINITY;
+        float m = -INFINITY, m2 = -INFINITY;                   // (m2, sum2: the timestamp part, TS only)
         for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
             float xv[STT_SEL_U];
             int mk[STT_SEL_U];
 #pragma unroll
             for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
 #pragma unroll
-            for (int u = 0; u < STT_SEL_U; ++u)
-                if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] > m) m = xv[u];
+            for (int u = 0; u < STT_SEL_U; ++u) {
+                if constexpr (TS) {
+                    const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
+                    if (kd == 1 && xv[u] > m) m = xv[u];
+                    if (kd == 2 && xv[u] > m2) m2 = xv[u];
+                } else {
+                    if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] > m) m = xv[u];
+                }
+            }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
         if ((tid & 63) == 0) red_v[wave] = m;
+        if constexpr (TS) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
+            if ((tid & 63) == 0) red_w[wave] = m2;
+        }
         __syncthreads();
         m = red_v[0];
         for (int k = 1; k < 16; ++k) m = fmaxf(m, red_v[k]);
+        if constexpr (TS) {
+            m2 = red_w[0];
+            for (int k = 1; k < 16; ++k) m2 = fmaxf(m2, red_w[k]);
+        }
         __syncthreads();
-        float sum = 0.f;
+        float sum = 0.f, sum2 = 0.f;
         for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
             float xv[STT_SEL_U];
             int mk[STT_SEL_U];
 #pragma unroll
             for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
 #pragma unroll
-            for (int u = 0; u < STT_SEL_U; ++u)
-                if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] == xv[u]) sum += expf(xv[u] - m);
+            for (int u = 0; u < STT_SEL_U; ++u) {
+                if constexpr (TS) {
+                    const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
+                    if (kd == 1 && xv[u] == xv[u]) sum += expf(xv[u] - m);
+                    if (kd == 2 && xv[u] == xv[u]) sum2 += expf(xv[u] - m2);
+                } else {
+                    if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] == xv[u]) sum += expf(xv[u] - m);
+                }
+            }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
         if ((tid & 63) == 0) red_v[wave] = sum;
+        if constexpr (TS) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o, 64);
+            if ((tid & 63) == 0) red_w[wave] = sum2;
+        }
         __syncthreads();
         sum = red_v[0];
         for (int k = 1; k < 16; ++k) sum += red_v[k];
+        if constexpr (TS) {
+            sum2 = red_w[0];
+            for (int k = 1; k < 16; ++k) sum2 += red_w[k];
+        }
         __syncthreads();
-        const float lse = m + logf(sum);
+        float lse = m + logf(sum);
+        bool text_ok = true;
+        if constexpr (TS) {
+            // the comparison needs no normaliser: logsumexp(timestamps) > max(text) on the raw logits is the same on log-probabilities
+            const bool has_ts = m2 > -INFINITY, has_text = m > -INFINITY;
+            const float lse_ts = has_ts ? m2 + logf(sum2) : -INFINITY;
+            text_ok = has_text && !(lse_ts > m);
+            if (!text_ok) lse = lse_ts;
+            else if (has_ts) { const float mm = fmaxf(m, m2); lse = mm + logf(sum * expf(m - mm) + sum2 * expf(m2 - mm)); }
+        }
         float cv[STT_CAND];
         int ci[STT_CAND];
 #pragma unroll
@@ -384,7 +471,13 @@ __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restric
             for (int u = 0; u < STT_SEL_U; ++u) {
                 const int i = base + 1024 * u;
                 const float lp = xv[u] - lse;
-                if (i >= V || (mk[u] & bad) || !(lp == lp) || !cand_before(lp, i, cv[STT_CAND - 1], ci[STT_CAND - 1])) continue;
+                if constexpr (TS) {
+                    const int kd = i < V ? kind(i, mk[u]) : 0;
+                    if (kd == 0 || (kd == 1 && !text_ok)) continue;
+                } else {
+                    if (i >= V || (mk[u] & bad)) continue;
+                }
+                if (!(lp == lp) || !cand_before(lp, i, cv[STT_CAND - 1], ci[STT_CAND - 1])) continue;
                 cv[STT_CAND - 1] = lp; ci[STT_CAND - 1] = i;
 #pragma unroll
                 for (int k = STT_CAND - 1; k > 0; --k)
@@ -450,6 +543,11 @@ __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restric
             bk.score[row] = sc;
             bk.bp_tok[(int64_t)step * bk.R + row] = c_tok[id];
             bk.bp_par[(int64_t)step * bk.R + row] = c_beam[id];
+            if constexpr (TS) {
+                const bool is_ts = c_tok[id] >= ts.t0;
+                bk.ts_flags[row] = (is_ts ? 1 : 0) | ((first_step || (sh_flags[c_beam[id]] & 1)) ? 2 : 0);
+                bk.ts_last[row] = is_ts ? c_tok[id] : sh_last[c_beam[id]];
+            }
             ++nb;
         }
     }
@@ -578,6 +676,9 @@ struct rt_stt {
     int32_t* d_clip_lang = nullptr;      // [clip_lang_cap] per clip of the call: the forced or detected id, -1 until it is detected
     int clip_lang_cap = 0;
     std::vector<int32_t> h_probe, h_meta;
+    // rt_stt_set_timestamps: timestamp ids [ts_begin, ts_begin + ts_count), 0: not configured (rt_stt_transcribe_seek refuses)
+    int32_t ts_begin = 0, ts_count = 0;
+    int32_t* d_ts_prefix = nullptr;      // [STT_GROUP][n_prefix - 1] the windows' prefixes in timestamp mode (without <|notimestamps|>)
     std::vector<void*> owned;
 };
 
@@ -944,7 +1045,7 @@ int stt_transcribe_greedy(rt_stt* s, const float* const* d_pcm, const int64_t* n
 }
 
 // the bookkeeping of k_stt_beam_select laid over one int32 allocation of R rows and `steps` steps (sizes in SttBeamBook's comments)
-size_t stt_beam_book_words(int R, int steps) { return (size_t)9 * R + 1 + (size_t)2 * steps * R; }
+size_t stt_beam_book_words(int R, int steps) { return (size_t)11 * R + 1 + (size_t)2 * steps * R; }
 SttBeamBook stt_beam_book(int32_t* mem, int R, int steps) {
     SttBeamBook b;
     int32_t* p = mem;
@@ -954,6 +1055,7 @@ SttBeamBook stt_beam_book(int32_t* mem, int R, int steps) {
     b.fin_step = take(R); b.fin_beam = take(R); b.fin_score = (float*)take(R);
     b.live = take(1);
     b.bp_tok = take((size_t)steps * R); b.bp_par = take((size_t)steps * R);
+    b.ts_flags = take(R); b.ts_last = take(R);
     b.R = R;
     return b;
 }
@@ -1007,10 +1109,11 @@ int stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int nW) {
 // k_stt_lang_prefix over the group's window table (s->d_win_meta: stt_transcribe_beam copies it in while the stream is idle, in
 // front of the group's front end - a copy from pageable memory in the middle of the group would make the host wait for the
 // encoder): s->d_lang_prefix and row 3 of s->d_probe
-int stt_lang_prefix(rt_stt* s, int nW) {
+// (timestamp mode: the first P = n_prefix - 1 entries per window, into s->d_ts_prefix)
+int stt_lang_prefix(rt_stt* s, int nW, int P, int32_t* d_out) {
     rt_ctx* ctx = s->ctx;
-    hipLaunchKernelGGL(k_stt_lang_prefix, dim3(1), dim3(64), 0, ctx->stream, nW, s->cfg.n_prefix, s->grp.d_prefix, s->d_win_meta, s->d_win_meta + STT_GROUP,
-                       s->d_clip_lang, s->d_probe, s->d_lang_prefix, s->d_probe + 3 * STT_GROUP);
+    hipLaunchKernelGGL(k_stt_lang_prefix, dim3(1), dim3(64), 0, ctx->stream, nW, P, s->grp.d_prefix, s->d_win_meta, s->d_win_meta + STT_GROUP,
+                       s->d_clip_lang, s->d_probe, d_out, s->d_probe + 3 * STT_GROUP);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -1021,11 +1124,15 @@ int stt_lang_prefix(rt_stt* s, int nW) {
 // group; the bookkeeping comes back once, and the host follows the back-pointers of the finished entries.
 // lang (null: the handle's prefix for every window, nothing probed - the launches of rt_stt_transcribe_beam): a prefix per window,
 // and whether the probe pass runs to decide it.
-int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, const SttLangPlan* lang = nullptr) {
+// ts (null: as ever): timestamp mode - the prefix is the handle's without its last entry (<|notimestamps|>), the windows' prefixes
+// are in s->d_ts_prefix (lang is given), every step applies the timestamp rule (k_stt_beam_select<true>), and the ids that come back
+// hold timestamp ids.
+int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, const SttLangPlan* lang = nullptr, const SttTsRule* ts = nullptr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     SttBeam& bm = s->beam;
-    const int P = c.n_prefix, rows = nW * B, R = bm.rows;
+    const int P = ts ? c.n_prefix - 1 : c.n_prefix, rows = nW * B, R = bm.rows;
+    int32_t* d_win_prefix = ts ? s->d_ts_prefix : s->d_lang_prefix;
     const SttBeamBook& bk = bm.book;
     const KvCache& cross = s->grp.enc.cross_kv;
     RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
@@ -1044,16 +1151,20 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
             bm.dec.tok = s->d_sot;
             RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, 1, 0, bm.row_slot, bm.row_pos, bm.row_slot));
             RT_TRY(stt_probe(s, bm.dec.logits, c.vocab, nW));
-            RT_TRY(stt_lang_prefix(s, nW));
+            RT_TRY(stt_lang_prefix(s, nW, P, d_win_prefix));
         }
-        bm.dec.tok = s->d_lang_prefix;           // (without a probe every language is given: the caller has copied the prefixes in)
+        bm.dec.tok = d_win_prefix;           // (without a probe every language is given: the caller has copied the prefixes in)
     }
     RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
     const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
     int steps = 0;
     for (int step = 0; step < budget; ++step) {
-        hipLaunchKernelGGL(k_stt_beam_select, dim3(nW), dim3(1024), 0, ctx->stream, bm.dec.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0, c.eos_id, B,
-                           step, bk);
+        if (ts)
+            hipLaunchKernelGGL(k_stt_beam_select<true>, dim3(nW), dim3(1024), 0, ctx->stream, bm.dec.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0,
+                               c.eos_id, B, step, bk, *ts);
+        else
+            hipLaunchKernelGGL(k_stt_beam_select<false>, dim3(nW), dim3(1024), 0, ctx->stream, bm.dec.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0,
+                               c.eos_id, B, step, bk, SttTsRule{});
         RT_HIP(ctx, hipGetLastError());
         steps = step + 1;
         int32_t live = 0;
@@ -1193,6 +1304,157 @@ int stt_transcribe_beam(rt_stt* s, const std::vector<SttSpan>& all, int n_clips,
     }
     if (h_scores)
         for (int i = 0; i < n_clips; ++i) h_scores[i] = (float)(sum[i] / (double)std::max<int64_t>(count[i], 1));
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- timestamps and seek (rt_stt_transcribe_seek)
+// A closed segment of one window: start and end in ticks of the window, and its text ids (timestamps stripped)
+struct SttSeg { int start = 0, end = 0; std::vector<int32_t> ids; };
+
+// The seek rule ("timestamps and seek") on one window's hypothesis `seq` (end-of-sequence stripped, timestamp
+// ids are those >= t0): consecutive timestamp pairs close segments; with a single trailing timestamp the window is consumed whole;
+// otherwise the tokens behind the last closed pair are discarded and the next window starts at that pair's timestamp; without any
+// pair the window is one segment, consumed whole.  own: the ticks the window's own samples span; whole: a whole window in ticks.
+// Returns the advance in ticks.
+int stt_seek_rule(const std::vector<int32_t>& seq, int t0, int own, int whole, std::vector<SttSeg>& segs) {
+    const int n = (int)seq.size();
+    auto is_ts = [&](int k) { return seq[k] >= t0; };
+    auto close = [&](int a, int b, int start, int end) {
+        SttSeg g;
+        g.start = start; g.end = end;
+        for (int k = a; k < b; ++k)
+            if (!is_ts(k)) g.ids.push_back(seq[k]);
+        segs.push_back(std::move(g));
+    };
+    std::vector<int> cuts;
+    for (int k = 0; k + 1 < n; ++k)
+        if (is_ts(k) && is_ts(k + 1)) cuts.push_back(k + 1);
+    const bool single = n >= 2 && !is_ts(n - 2) && is_ts(n - 1);
+    if (!cuts.empty()) {
+        if (single) cuts.push_back(n); else cuts.back() += 1;      // (the last slice keeps both timestamps of its pair)
+        int last = 0;
+        for (size_t i = 0; i < cuts.size(); ++i) {
+            const int cur = cuts[i];
+            const bool tail = i + 1 == cuts.size() && !single;
+            close(last, cur, seq[last] - t0, seq[cur - (tail ? 2 : 1)] - t0);
+            last = cur;
+        }
+        return single ? whole : seq[last - 2] - t0;
+    }
+    int end = own;
+    for (int k = n - 1; k >= 0; --k)
+        if (is_ts(k)) { if (seq[k] != t0) end = seq[k] - t0; break; }
+    close(0, n, 0, end);
+    return whole;
+}
+
+// What one decoded window of a seek call leaves behind
+struct SttSeekWin { int clip; int64_t off; int n_ids; float logprob, no_speech; int advance; };
+struct SttSeekSeg { int clip; int64_t start_tick, end_tick; int n_ids; };
+struct SttSeekResult {
+    std::vector<std::vector<int32_t>> ids;               // per clip: the text ids of its segments, joined
+    std::vector<std::vector<SttSeekSeg>> segs;           // per clip, in order
+    std::vector<std::vector<SttSeekWin>> wins;           // per clip, in order
+    std::vector<float> score, lang_prob;
+    std::vector<int32_t> lang;
+};
+
+// The seek loop: a round holds one window per unfinished clip at the clip's current offset (in input samples, a multiple of the
+// tick); rounds go through front end, encoder, optional probe and the beam decode in groups of floor(STT_GROUP / beam_size) windows
+// as stt_transcribe_beam does, and the host applies the silence rule and the seek rule to what a group decoded.  Every round moves
+// every unfinished clip on by at least one tick, so max_rounds - computed before the first launch - bounds the loop.
+int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int n_clips, int sr, const rt_stt_seek_opts& o, bool probe,
+                        SttSeekResult& res) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    const int beam_size = o.beam_size, P = c.n_prefix - 1;
+    const int64_t tick = (int64_t)(0.02 * (double)sr), win = (int64_t)c.chunk_seconds * sr;
+    const int whole = s->ts_count - 1;
+    const SttTsRule rule{s->ts_begin, s->ts_count, o.max_initial_timestamp_index};
+    int64_t max_rounds = 1;
+    for (int i = 0; i < n_clips; ++i) max_rounds = std::max<int64_t>(max_rounds, (n_samples[i] + tick - 1) / tick + 1);
+    const size_t per_group = (size_t)(STT_GROUP / beam_size);
+    const int most = (int)std::min<size_t>((size_t)n_clips, per_group);
+    RT_TRY(stt_group_reserve(s, most));
+    RT_TRY(stt_beam_reserve(s, most * beam_size));
+    if (probe) {
+        if (s->clip_lang_cap < n_clips) {
+            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            const int cap = std::max(n_clips, 2 * s->clip_lang_cap);
+            RT_TRY(stt_alloc(s, s->owned, (size_t)cap, &s->d_clip_lang));
+            s->clip_lang_cap = cap;
+        }
+        std::vector<int32_t> req(n_clips, c.prefix[1]);
+        if (o.h_language) req.assign(o.h_language, o.h_language + n_clips);
+        RT_HIP(ctx, hipMemcpy(s->d_clip_lang, req.data(), (size_t)n_clips * 4, hipMemcpyHostToDevice));
+        s->h_probe.resize(4 * STT_GROUP);
+    }
+    res.ids.assign(n_clips, {}); res.segs.assign(n_clips, {}); res.wins.assign(n_clips, {});
+    res.score.assign(n_clips, 0.f); res.lang_prob.assign(n_clips, 1.f); res.lang.assign(n_clips, c.prefix[P > 1 ? 1 : 0]);
+    std::vector<int64_t> off(n_clips, 0);
+    std::vector<char> done(n_clips, 0);
+    std::vector<double> sum(n_clips, 0.0), sum_all(n_clips, 0.0);
+    std::vector<int64_t> count(n_clips, 0), count_all(n_clips, 0);
+    const bool silence = o.no_speech_threshold == o.no_speech_threshold;
+    std::vector<SttSpan> spans;
+    std::vector<SttHyp> hyps;
+    std::vector<SttSeg> segs;
+    for (int64_t round = 0; round < max_rounds; ++round) {
+        spans.clear();
+        for (int i = 0; i < n_clips; ++i)
+            if (!done[i]) spans.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off[i] : nullptr, std::min<int64_t>(win, n_samples[i] - off[i])});
+        if (spans.empty()) break;
+        for (size_t next = 0; next < spans.size(); next += per_group) {
+            const int nW = (int)std::min(per_group, spans.size() - next);
+            s->h_meta.assign((size_t)STT_GROUP * std::max(c.n_prefix, 2), -1);      // (alive until the group's synchronisation)
+            if (probe) {        // a clip's language is fixed by its first window: round 0 detects, later rounds find it in d_clip_lang
+                for (int b = 0; b < nW; ++b) { s->h_meta[b] = spans[next + b].clip; s->h_meta[STT_GROUP + b] = round == 0 ? b : -1; }
+                RT_HIP(ctx, hipMemcpyAsync(s->d_win_meta, s->h_meta.data(), 2 * STT_GROUP * 4, hipMemcpyHostToDevice, ctx->stream));
+            } else {
+                for (int b = 0; b < nW; ++b)
+                    for (int k = 0; k < P; ++k)
+                        s->h_meta[(size_t)b * P + k] = (k == 1 && o.h_language) ? o.h_language[spans[next + b].clip] : c.prefix[k];
+                RT_HIP(ctx, hipMemcpyAsync(s->d_ts_prefix, s->h_meta.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
+            }
+            RT_TRY(stt_features_group(s, spans.data() + next, nW, sr));
+            RT_TRY(stt_encode(s, s->grp.enc, nW));
+            const SttLangPlan plan{probe};
+            RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps, &plan, &rule));
+            if (probe) RT_HIP(ctx, hipMemcpy(s->h_probe.data(), s->d_probe, 4 * STT_GROUP * 4, hipMemcpyDeviceToHost));
+            const float* pf = (const float*)s->h_probe.data();
+            for (int b = 0; b < nW; ++b) {
+                const SttSpan& sp = spans[next + b];
+                const int i = sp.clip;
+                const SttHyp& h = hyps[b];
+                if (round == 0) {
+                    const bool detected = o.h_language && o.h_language[i] < 0;
+                    res.lang[i] = probe ? s->h_probe[3 * STT_GROUP + b] : o.h_language ? o.h_language[i] : c.prefix[P > 1 ? 1 : 0];
+                    res.lang_prob[i] = detected ? pf[STT_GROUP + b] : 1.0f;
+                }
+                const float ns = probe ? pf[2 * STT_GROUP + b] : NAN;
+                const float avg = h.score / (float)h.count;
+                const bool silent = silence && ns > o.no_speech_threshold && (!(o.logprob_threshold == o.logprob_threshold) || avg < o.logprob_threshold);
+                sum_all[i] += (double)h.score; count_all[i] += h.count;
+                int advance = whole;
+                if (!silent) {
+                    sum[i] += (double)h.score; count[i] += h.count;
+                    segs.clear();
+                    advance = stt_seek_rule(h.ids, s->ts_begin, (int)std::min<int64_t>(whole, sp.n / tick), whole, segs);
+                    const int64_t base = off[i] / tick;
+                    for (const SttSeg& g : segs) {
+                        res.segs[i].push_back({i, base + g.start, base + g.end, (int)g.ids.size()});
+                        res.ids[i].insert(res.ids[i].end(), g.ids.begin(), g.ids.end());
+                    }
+                }
+                if (advance <= 0) advance = whole;                  // (a window that would not move its clip moves it by a whole window)
+                res.wins[i].push_back({i, off[i], (int)h.ids.size(), h.score, ns, advance});
+                off[i] += (int64_t)advance * tick;
+                if (off[i] >= n_samples[i]) done[i] = 1;
+            }
+        }
+    }
+    for (int i = 0; i < n_clips; ++i)
+        res.score[i] = count[i] > 0 ? (float)(sum[i] / (double)count[i]) : (float)(sum_all[i] / (double)std::max<int64_t>(count_all[i], 1));
     return RT_OK;
 }
 
@@ -1337,6 +1599,7 @@ int rt_stt_finalize(rt_stt* s) {
         hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, s->d_sot, STT_GROUP, c.prefix[0], 0);
         RT_HIP(ctx, hipGetLastError());
     }
+    if (s->ts_begin > 0) RT_TRY(stt_alloc(s, s->owned, (size_t)STT_GROUP * c.n_prefix, &s->d_ts_prefix));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->finalized = true;
     return RT_OK;
@@ -1513,6 +1776,90 @@ int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int64_t* n_
     return RT_OK;
 }
 
+int rt_stt_set_timestamps(rt_stt* s, int32_t timestamp_begin, int32_t n_timestamps) {
+    if (!s) return RT_ERR_INVALID;
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_set_timestamps: call before rt_stt_finalize");
+    const rt_stt_config& c = s->cfg;
+    if (timestamp_begin < 1 || n_timestamps < 2 || (int64_t)timestamp_begin + n_timestamps > c.vocab)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_timestamps: the vocabulary of %d does not hold timestamp ids %d .. %lld", c.vocab, timestamp_begin,
+                       (long long)timestamp_begin + n_timestamps - 1);
+    if (c.n_prefix < 2 || c.prefix[c.n_prefix - 1] != timestamp_begin - 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_timestamps: the configured prefix does not end in <|notimestamps|> = %d", timestamp_begin - 1);
+    if (c.eos_id >= timestamp_begin - 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_timestamps: end-of-sequence %d is not below <|notimestamps|>", c.eos_id);
+    s->ts_begin = timestamp_begin;
+    s->ts_count = n_timestamps;
+    return RT_OK;
+}
+
+// Clips of any length by timestamps and seek: stt_transcribe_seek computes the whole result on the host,
+// then it is written out under the caps - nothing past one; RT_ERR_LENGTH with the counts a repeat needs when one is too small.
+int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, const rt_stt_seek_opts* opts,
+                           rt_stt_seek_out* out) {
+    if (!s || !opts || !out || opts->max_tokens < 1 || sample_rate < 1000 || opts->beam_size < 1 || opts->beam_size > STT_BEAM_MAX ||
+        stt_check_clips(d_pcm, n_samples, n_clips) || (n_clips > 0 && (!out->h_tokens || !out->h_n_tokens)) || out->segment_cap < 1 || out->window_cap < 1 ||
+        opts->max_initial_timestamp_index < -1)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_transcribe_seek: bad argument (beam_size 1 .. %d, caps >= 1)", STT_BEAM_MAX);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_transcribe_seek: not finalized");
+    if (s->ts_begin <= 0) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_seek: the handle has no timestamp ids (rt_stt_set_timestamps)");
+    out->n_segments = out->n_windows = out->max_clip_tokens = 0;
+    if (n_clips == 0) return RT_OK;
+    const bool silence = opts->no_speech_threshold == opts->no_speech_threshold;
+    bool probe = out->h_win_no_speech != nullptr || silence;
+    if (opts->h_language)
+        for (int i = 0; i < n_clips; ++i) {
+            const int32_t id = opts->h_language[i];
+            if (id == -1) { probe = true; continue; }
+            if (std::find(s->lang_ids.begin(), s->lang_ids.end(), id) == s->lang_ids.end())
+                return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_seek: clip %d: language %d is neither -1 nor a configured id (rt_stt_set_languages)", i, id);
+        }
+    if ((opts->h_language || probe) && s->lang_ids.empty())
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_seek: languages, no-speech probabilities or the silence rule asked of a handle without rt_stt_set_languages");
+    SttSeekResult res;
+    RT_TRY(stt_transcribe_seek(s, d_pcm, n_samples, n_clips, sample_rate, *opts, probe, res));
+    const double tick_s = (double)(int64_t)(0.02 * (double)sample_rate) / (double)sample_rate;
+    int64_t n_seg = 0, n_win = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        const int n_ids = (int)res.ids[i].size();
+        out->max_clip_tokens = std::max(out->max_clip_tokens, n_ids);
+        out->h_n_tokens[i] = std::min(n_ids, opts->max_tokens);
+        std::copy(res.ids[i].begin(), res.ids[i].begin() + out->h_n_tokens[i], out->h_tokens + (size_t)i * opts->max_tokens);
+        if (out->h_scores) out->h_scores[i] = res.score[i];
+        if (out->h_language) out->h_language[i] = res.lang[i];
+        if (out->h_language_prob) out->h_language_prob[i] = res.lang_prob[i];
+        for (const SttSeekSeg& g : res.segs[i]) {
+            const int64_t at = n_seg++;
+            if (at >= out->segment_cap) continue;
+            if (out->h_seg_clip) out->h_seg_clip[at] = i;
+            if (out->h_seg_start_tick) out->h_seg_start_tick[at] = (int32_t)g.start_tick;
+            if (out->h_seg_end_tick) out->h_seg_end_tick[at] = (int32_t)g.end_tick;
+            if (out->h_seg_start) out->h_seg_start[at] = (float)((double)g.start_tick * tick_s);
+            if (out->h_seg_end) out->h_seg_end[at] = (float)((double)g.end_tick * tick_s);
+            if (out->h_seg_n_ids) out->h_seg_n_ids[at] = g.n_ids;
+        }
+        for (const SttSeekWin& w : res.wins[i]) {
+            const int64_t at = n_win++;
+            if (at >= out->window_cap) continue;
+            if (out->h_win_clip) out->h_win_clip[at] = i;
+            if (out->h_win_offset) out->h_win_offset[at] = w.off;
+            if (out->h_win_n_ids) out->h_win_n_ids[at] = w.n_ids;
+            if (out->h_win_logprob) out->h_win_logprob[at] = w.logprob;
+            if (out->h_win_no_speech) out->h_win_no_speech[at] = w.no_speech;
+            if (out->h_win_advance) out->h_win_advance[at] = w.advance;
+        }
+    }
+    out->n_segments = (int32_t)n_seg;
+    out->n_windows = (int32_t)n_win;
+    if (n_seg > out->segment_cap || n_win > out->window_cap)
+        return rt_fail(ctx, RT_ERR_LENGTH, "rt_stt_transcribe_seek: %lld segments and %lld windows, room for %d and %d", (long long)n_seg, (long long)n_win,
+                       out->segment_cap, out->window_cap);
+    return RT_OK;
+}
+
 int rt_debug_stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int32_t n_rows, int32_t* h_lang, float* h_lang_prob, float* h_no_speech) {
     if (!s || !d_logits || !h_lang || !h_lang_prob || !h_no_speech || n_rows < 1 || n_rows > STT_GROUP || row_stride < s->cfg.vocab)
         return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_probe: bad argument (1 .. %d rows, row_stride >= vocab)", STT_GROUP);
@@ -1530,24 +1877,30 @@ int rt_debug_stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int
     return RT_OK;
 }
 
-int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_stride, const float* h_scores_in, int32_t n_windows, int32_t beam,
-                           const int32_t* h_n_live, const int32_t* h_n_finished, const int32_t* h_done, int32_t first_step, int32_t step,
-                           int32_t* h_next_tok, int32_t* h_parent, float* h_scores_out, int32_t* h_n_live_out, int32_t* h_fin_beam, float* h_fin_score,
-                           int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows) {
+}  // extern "C"
+
+namespace {
+// rt_debug_stt_beam_step, and - ts given - rt_debug_stt_beam_step_ts: the timestamp instantiation with the rows' history state
+// (flags, last timestamp) copied in before the step and out behind it
+int stt_debug_beam_step(const char* who, rt_stt* s, const float* d_logits, int32_t row_stride, const float* h_scores_in, int32_t n_windows, int32_t beam,
+                        const int32_t* h_n_live, const int32_t* h_n_finished, const int32_t* h_done, int32_t first_step, int32_t step,
+                        int32_t* h_next_tok, int32_t* h_parent, float* h_scores_out, int32_t* h_n_live_out, int32_t* h_fin_beam, float* h_fin_score,
+                        int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows, const SttTsRule* ts = nullptr, const int32_t* h_flags_in = nullptr,
+                        const int32_t* h_last_in = nullptr, int32_t* h_flags_out = nullptr, int32_t* h_last_out = nullptr) {
     if (!s || !d_logits || !h_scores_in || !h_n_live || !h_n_finished || !h_done || !h_next_tok || !h_parent || !h_scores_out || !h_n_live_out || !h_fin_beam ||
         !h_fin_score || !h_n_finished_out || !h_done_out || !h_live_windows || beam < 1 || beam > STT_BEAM_MAX || n_windows < 1 ||
         n_windows * beam > STT_GROUP || (row_stride != 1 && row_stride != beam) || step < 0 || step >= s->cfg.max_new_tokens)
-        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_beam_step: bad argument (windows x beam <= %d, row_stride 1 or beam)", STT_GROUP);
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "%s: bad argument (windows x beam <= %d, row_stride 1 or beam)", who, STT_GROUP);
     int live = 0;
     for (int w = 0; w < n_windows; ++w) {
         if (h_n_live[w] < 0 || h_n_live[w] > std::min(beam, row_stride) || h_n_finished[w] < 0 || h_n_finished[w] > beam)
-            return rt_fail(s->ctx, RT_ERR_INVALID, "rt_debug_stt_beam_step: window %d: live rows or finished entries out of range", w);
+            return rt_fail(s->ctx, RT_ERR_INVALID, "%s: window %d: live rows or finished entries out of range", who, w);
         live += h_done[w] ? 0 : 1;
     }
     rt_ctx* ctx = s->ctx;
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
-    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_beam_step: not finalized");
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "%s: not finalized", who);
     const int R = n_windows * beam;
     RT_TRY(stt_beam_reserve(s, R));
     SttBeam& bm = s->beam;
@@ -1556,11 +1909,17 @@ int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_stride,
     hb.assign(bm.book_n, 0);
     SttBeamBook h = stt_beam_book(hb.data(), bm.rows, s->cfg.max_new_tokens);
     for (int r = 0; r < R; ++r) { h.score[r] = h_scores_in[r]; h.next_tok[r] = -1; h.src[r] = -1; }
+    if (ts)
+        for (int r = 0; r < R; ++r) { h.ts_flags[r] = h_flags_in[r]; h.ts_last[r] = h_last_in[r]; }
     for (int w = 0; w < n_windows; ++w) { h.n_live[w] = h_n_live[w]; h.n_fin[w] = h_n_finished[w]; h.done[w] = h_done[w] ? 1 : 0; }
     *h.live = live;
     RT_HIP(ctx, hipMemcpyAsync(bm.book_mem, hb.data(), bm.book_n * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_stt_beam_select, dim3(n_windows), dim3(1024), 0, ctx->stream, d_logits, s->cfg.vocab, row_stride, s->d_mask, first_step ? 1 : 0, s->cfg.eos_id,
-                       beam, step, bk);
+    if (ts)
+        hipLaunchKernelGGL(k_stt_beam_select<true>, dim3(n_windows), dim3(1024), 0, ctx->stream, d_logits, s->cfg.vocab, row_stride, s->d_mask, first_step ? 1 : 0,
+                           s->cfg.eos_id, beam, step, bk, *ts);
+    else
+        hipLaunchKernelGGL(k_stt_beam_select<false>, dim3(n_windows), dim3(1024), 0, ctx->stream, d_logits, s->cfg.vocab, row_stride, s->d_mask, first_step ? 1 : 0,
+                           s->cfg.eos_id, beam, step, bk, SttTsRule{});
     RT_HIP(ctx, hipGetLastError());
     RT_HIP(ctx, hipMemcpyAsync(hb.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1569,8 +1928,34 @@ int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_stride,
         h_fin_beam[r] = h.fin_beam[r]; h_fin_score[r] = h.fin_score[r];
     }
     for (int w = 0; w < n_windows; ++w) { h_n_live_out[w] = h.n_live[w]; h_n_finished_out[w] = h.n_fin[w]; h_done_out[w] = h.done[w]; }
+    if (ts)
+        for (int r = 0; r < R; ++r) { h_flags_out[r] = h.ts_flags[r]; h_last_out[r] = h.ts_last[r]; }
     *h_live_windows = *h.live;
     return RT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_stride, const float* h_scores_in, int32_t n_windows, int32_t beam,
+                           const int32_t* h_n_live, const int32_t* h_n_finished, const int32_t* h_done, int32_t first_step, int32_t step,
+                           int32_t* h_next_tok, int32_t* h_parent, float* h_scores_out, int32_t* h_n_live_out, int32_t* h_fin_beam, float* h_fin_score,
+                           int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows) {
+    return stt_debug_beam_step("rt_debug_stt_beam_step", s, d_logits, row_stride, h_scores_in, n_windows, beam, h_n_live, h_n_finished, h_done, first_step, step,
+                               h_next_tok, h_parent, h_scores_out, h_n_live_out, h_fin_beam, h_fin_score, h_n_finished_out, h_done_out, h_live_windows);
+}
+
+int rt_debug_stt_beam_step_ts(rt_stt* s, const float* d_logits, int32_t row_stride, const float* h_scores_in, int32_t n_windows, int32_t beam,
+                              const int32_t* h_n_live, const int32_t* h_n_finished, const int32_t* h_done, int32_t first_step, int32_t step,
+                              int32_t max_initial_timestamp_index, const int32_t* h_ts_flags_in, const int32_t* h_ts_last_in,
+                              int32_t* h_next_tok, int32_t* h_parent, float* h_scores_out, int32_t* h_n_live_out, int32_t* h_fin_beam, float* h_fin_score,
+                              int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows, int32_t* h_ts_flags_out, int32_t* h_ts_last_out) {
+    if (!s || s->ts_begin <= 0 || !h_ts_flags_in || !h_ts_last_in || !h_ts_flags_out || !h_ts_last_out || max_initial_timestamp_index < -1)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_beam_step_ts: bad argument (a handle with rt_stt_set_timestamps, the rows' history state)");
+    const SttTsRule rule{s->ts_begin, s->ts_count, max_initial_timestamp_index};
+    return stt_debug_beam_step("rt_debug_stt_beam_step_ts", s, d_logits, row_stride, h_scores_in, n_windows, beam, h_n_live, h_n_finished, h_done, first_step, step,
+                               h_next_tok, h_parent, h_scores_out, h_n_live_out, h_fin_beam, h_fin_score, h_n_finished_out, h_done_out, h_live_windows, &rule,
+                               h_ts_flags_in, h_ts_last_in, h_ts_flags_out, h_ts_last_out);
 }
 
 int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src, int32_t len,

@@ -89,6 +89,16 @@ class SttConfig:
     languages: Dict[str, int] = field(default_factory=classic_languages)
     no_speech_id: int = CLASSIC_NO_SPEECH_ID
     language: str = "en"                 # the code position 1 of `prefix` stands for
+    # the first timestamp id, <|notimestamps|> + 1 (None: the vocabulary has no timestamp ids this build knows; from_hf fills it):
+    # rt_stt_set_timestamps, the seek path (transcribe_ids_seek).  The first token of a window is at most this many ticks of 0.02 s in
+    # (1 s, as in openai's and faster-whisper's transcribers; -1: no limit)
+    timestamp_begin: Optional[int] = None
+    max_initial_timestamp_index: int = 50
+
+    @property
+    def n_timestamps(self) -> int:
+        """Timestamp ids of one window: <|0.00|> .. <|chunk_seconds|> in ticks of 0.02 s."""
+        return int(self.chunk_seconds) * 50 + 1
 
     def with_language(self, code: str) -> "SttConfig":
         """A copy whose prefix carries ``code`` at position 1."""
@@ -150,6 +160,9 @@ class SttConfig:
             c.no_speech_id = int(nts) - 1 if nts is not None and 0 < int(nts) <= c.vocab else -1
         elif not (start == SttConfig.prefix[0] and c.vocab > CLASSIC_NO_SPEECH_ID):
             c.languages, c.no_speech_id = {}, -1
+        # timestamp ids follow <|notimestamps|>; the seek path needs the prefix to end in it and the vocabulary to hold them
+        if nts is not None and len(c.prefix) > 1 and c.prefix[-1] == int(nts) and int(nts) + 1 + c.n_timestamps <= c.vocab and c.eos_id < int(nts):
+            c.timestamp_begin = int(nts) + 1
         if language != "en":
             c = c.with_language(language)
         elif len(c.prefix) > 1:
@@ -203,6 +216,60 @@ class RtSttDecodeOut(C.Structure):
                 ("h_language", C.POINTER(C.c_int32)), ("h_language_prob", C.POINTER(C.c_float)), ("h_win_clip", C.POINTER(C.c_int32)),
                 ("h_win_n_ids", C.POINTER(C.c_int32)), ("h_win_logprob", C.POINTER(C.c_float)), ("h_win_no_speech", C.POINTER(C.c_float)),
                 ("window_cap", C.c_int32), ("n_windows", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class RtSttSeekOpts(C.Structure):
+    _fields_ = [("h_language", C.POINTER(C.c_int32)), ("beam_size", C.c_int32), ("max_tokens", C.c_int32), ("max_initial_timestamp_index", C.c_int32),
+                ("no_speech_threshold", C.c_float), ("logprob_threshold", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class RtSttSeekOut(C.Structure):
+    _fields_ = [("h_tokens", C.POINTER(C.c_int32)), ("h_n_tokens", C.POINTER(C.c_int32)), ("h_scores", C.POINTER(C.c_float)),
+                ("h_language", C.POINTER(C.c_int32)), ("h_language_prob", C.POINTER(C.c_float)),
+                ("h_seg_clip", C.POINTER(C.c_int32)), ("h_seg_start", C.POINTER(C.c_float)), ("h_seg_end", C.POINTER(C.c_float)),
+                ("h_seg_start_tick", C.POINTER(C.c_int32)), ("h_seg_end_tick", C.POINTER(C.c_int32)), ("h_seg_n_ids", C.POINTER(C.c_int32)),
+                ("h_win_clip", C.POINTER(C.c_int32)), ("h_win_offset", C.POINTER(C.c_int64)), ("h_win_n_ids", C.POINTER(C.c_int32)),
+                ("h_win_logprob", C.POINTER(C.c_float)), ("h_win_no_speech", C.POINTER(C.c_float)), ("h_win_advance", C.POINTER(C.c_int32)),
+                ("segment_cap", C.c_int32), ("window_cap", C.c_int32), ("n_segments", C.c_int32), ("n_windows", C.c_int32),
+                ("max_clip_tokens", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+@dataclass
+class SttSegment:
+    """One closed segment of a clip (transcribe_ids_seek): start and end in seconds of the clip (and in ticks of 0.02 s, which is what
+    the decoder's timestamp ids count), and its text ids."""
+    start: float
+    end: float
+    ids: List[int]
+    start_tick: int = 0
+    end_tick: int = 0
+    text: Optional[str] = None           # WhisperTranscriber.batch_segments fills it
+
+
+@dataclass
+class SttSeekWindow:
+    """One decoded window of a clip on the seek path: where it started (input samples), what it decoded (timestamp ids counted) and how
+    far it moved the clip on (ticks)."""
+    offset: int
+    n_ids: int
+    logprob: float
+    no_speech_prob: float                # NaN where the probe pass did not run
+    advance: int
+
+    @property
+    def avg_logprob(self) -> float:
+        return self.logprob / (self.n_ids + 1)
+
+
+@dataclass
+class SttSeekClip:
+    """One clip of ``NativeSTT.transcribe_ids_seek``: ``SttClip`` with the closed segments and the windows of the seek path."""
+    ids: List[int]
+    score: float
+    language: int
+    language_prob: float
+    segments: List[SttSegment]
+    windows: List[SttSeekWindow]
 
 
 @dataclass
@@ -263,6 +330,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_stt_set_languages.argtypes = [vp, C.POINTER(i32), i32, i32]
     lib.rt_stt_detect_language.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.rt_stt_transcribe_ex.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(RtSttDecodeOpts), C.POINTER(RtSttDecodeOut)]
+    lib.rt_stt_set_timestamps.argtypes = [vp, i32, i32]
+    lib.rt_stt_transcribe_seek.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(RtSttSeekOpts), C.POINTER(RtSttSeekOut)]
     lib.rt_stt_log_mel.argtypes = [vp, vp, i64, i32, vp]
     lib.rt_stt_encode.argtypes = [vp, vp, i64, i32, vp]
     _DECLARED = True
@@ -446,6 +515,8 @@ class NativeSTT:
         if cfg.languages:
             lang = sorted(int(v) for v in cfg.languages.values())
             ctx.check(self.lib.rt_stt_set_languages(self.handle, (C.c_int32 * len(lang))(*lang), len(lang), int(cfg.no_speech_id)), "rt_stt_set_languages")
+        if cfg.timestamp_begin is not None:
+            ctx.check(self.lib.rt_stt_set_timestamps(self.handle, int(cfg.timestamp_begin), int(cfg.n_timestamps)), "rt_stt_set_timestamps")
         ctx.check(self.lib.rt_stt_finalize(self.handle), "rt_stt_finalize")
 
     def close(self) -> None:
@@ -579,6 +650,82 @@ class NativeSTT:
             clips[w_clip[w]].windows.append(SttWindow(int(w_n[w]), float(w_lp[w]), float(w_ns[w]) if no_speech else float("nan")))
         return clips
 
+    def seek_caps(self, n_samples: Sequence[int], sample_rate: int) -> Tuple[int, int, int]:
+        """(tokens per clip, segments, windows) the first attempt of ``transcribe_ids_seek`` leaves room for.  A repeat costs a whole
+        decode and room costs a few integers, so the guess is generous: per clip twice its fixed-cut windows plus two, and per
+        window the most segments its tokens can close (a segment takes a text id and a timestamp at least).  The call reports what
+        it needed when that is short."""
+        n_win = [2 * self.windows(n, sample_rate) + 2 for n in n_samples]
+        per_window = int(self.cfg.max_new_tokens) // 2 + 1
+        return max(n_win or [1]) * int(self.cfg.max_new_tokens), max(1, sum(n_win) * per_window), max(1, sum(n_win))
+
+    def transcribe_ids_seek(self, audios, sample_rate: int, beam_size: int = 1, languages=None, max_tokens: Optional[int] = None,
+                            max_initial_timestamp_index: Optional[int] = None, no_speech_threshold: Optional[float] = None,
+                            logprob_threshold: Optional[float] = -1.0, no_speech: bool = True, caps: Optional[Tuple[int, int, int]] = None) -> List[SttSeekClip]:
+        """Clips of any length by timestamps and seek (rt_stt_transcribe_seek; the rules: DESIGN.md section 5): per clip the text ids of
+        its closed segments, the segments with their times and the windows the call decoded.  ``languages`` as ``transcribe_ids_ex``;
+        ``max_initial_timestamp_index`` None: the configuration's (-1: no limit); ``no_speech_threshold`` not None switches the silence
+        rule on (validation.window_is_silent): a silent window gives no segment and is consumed whole.  ``caps``: room for (tokens per
+        clip, segments, windows) at the first attempt (default: ``seek_caps``); when one runs out the call is repeated ONCE with the
+        counts the library reported, so a result is never cut - except the ids at an explicit ``max_tokens``."""
+        check_beam_size(beam_size)
+        if max_tokens is not None and int(max_tokens) < 1:
+            raise ValueError(f"max_tokens must be at least 1, got {max_tokens!r}")
+        if not getattr(self, "handle", None):
+            raise ValueError("transcribe_ids_seek: the model is closed")
+        if self.cfg.timestamp_begin is None:
+            raise ValueError("transcribe_ids_seek: the configuration has no timestamp ids (SttConfig.timestamp_begin)")
+        xs, n, ptrs, lens = self._clips(audios)
+        tcap, scap, wcap = caps or self.seek_caps([x.numel() for x in xs], sample_rate)
+        if max_tokens is not None:
+            tcap = int(max_tokens)
+        req = None
+        if languages is not None:
+            each = [languages] * n if isinstance(languages, (str, int, np.integer)) else list(languages)
+            if len(each) != n:
+                raise ValueError(f"{len(each)} languages for {n} clips")
+            req = (C.c_int32 * max(n, 1))(*[self._language_id(v) for v in each])
+        mi = self.cfg.max_initial_timestamp_index if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
+        nan = float("nan")
+        i32, f32 = lambda k: (C.c_int32 * max(k, 1))(), lambda k: (C.c_float * max(k, 1))()
+        for attempt in range(2):
+            opts, out = RtSttSeekOpts(), RtSttSeekOut()
+            opts.beam_size, opts.max_tokens, opts.max_initial_timestamp_index = int(beam_size), int(tcap), int(mi)
+            opts.no_speech_threshold = nan if no_speech_threshold is None else float(no_speech_threshold)
+            opts.logprob_threshold = nan if logprob_threshold is None else float(logprob_threshold)
+            if req is not None:
+                opts.h_language = req
+            toks, counts, scores, lang, lprob = i32(n * tcap), i32(n), f32(n), i32(n), f32(n)
+            g_clip, g_s, g_e, g_st, g_et, g_n = i32(scap), f32(scap), f32(scap), i32(scap), i32(scap), i32(scap)
+            w_clip, w_off, w_n, w_lp, w_ns, w_adv = i32(wcap), (C.c_int64 * max(wcap, 1))(), i32(wcap), f32(wcap), f32(wcap), i32(wcap)
+            out.h_tokens, out.h_n_tokens, out.h_scores, out.h_language, out.h_language_prob = toks, counts, scores, lang, lprob
+            out.h_seg_clip, out.h_seg_start, out.h_seg_end, out.h_seg_start_tick, out.h_seg_end_tick, out.h_seg_n_ids = g_clip, g_s, g_e, g_st, g_et, g_n
+            out.h_win_clip, out.h_win_offset, out.h_win_n_ids, out.h_win_logprob, out.h_win_advance = w_clip, w_off, w_n, w_lp, w_adv
+            if no_speech or no_speech_threshold is not None:
+                out.h_win_no_speech = w_ns
+            out.segment_cap, out.window_cap = int(scap), int(wcap)
+            rc = self.lib.rt_stt_transcribe_seek(self.handle, ptrs, lens, n, int(sample_rate), C.byref(opts), C.byref(out))
+            short = out.n_segments > scap or out.n_windows > wcap or (max_tokens is None and out.max_clip_tokens > tcap)
+            if rc not in (_native.RT_OK, _native.RT_ERR_LENGTH) or not short:
+                self.ctx.check(rc, "rt_stt_transcribe_seek")
+                break
+            if attempt == 1:
+                raise RuntimeError(f"rt_stt_transcribe_seek: length: the repeated call needed {out.n_segments} segments, {out.n_windows} windows and "
+                                   f"{out.max_clip_tokens} ids, not the {scap}, {wcap} and {tcap} it reported before")
+            scap, wcap = max(scap, out.n_segments), max(wcap, out.n_windows)
+            if max_tokens is None:
+                tcap = max(tcap, out.max_clip_tokens)
+        clips = [SttSeekClip([int(toks[i * tcap + k]) for k in range(counts[i])], float(scores[i]), int(lang[i]), float(lprob[i]), [], []) for i in range(n)]
+        at = [0] * n
+        for g in range(out.n_segments):
+            i = g_clip[g]
+            ids = clips[i].ids[at[i]:at[i] + g_n[g]]                  # (an explicit max_tokens leaves the last segments short)
+            at[i] += g_n[g]
+            clips[i].segments.append(SttSegment(float(g_s[g]), float(g_e[g]), ids, int(g_st[g]), int(g_et[g])))
+        for w in range(out.n_windows):
+            clips[w_clip[w]].windows.append(SttSeekWindow(int(w_off[w]), int(w_n[w]), float(w_lp[w]), float(w_ns[w]) if out.h_win_no_speech else nan, int(w_adv[w])))
+        return clips
+
     def log_mel(self, audio, sample_rate: int) -> torch.Tensor:
         """[n_mels][frames] float32 (the layout of WhisperFeatureExtractor's ``input_features``)."""
         x = self._pcm(audio)
@@ -593,6 +740,24 @@ class NativeSTT:
         self.ctx.check(self.lib.rt_stt_encode(self.handle, C.c_void_p(x.data_ptr() if x.numel() else 0), x.numel(), int(sample_rate),
                                               C.c_void_p(out.data_ptr())), "rt_stt_encode")
         return out
+
+
+def join_segment_texts(texts) -> str:
+    """A clip's text from its segments' texts, as the reference joins them: ``" ".join(segment.text ...)`` and a final strip
+    (stt_validator.py:136, :143)."""
+    return " ".join(texts).strip()
+
+
+def check_timestamp_config(cfg: SttConfig, timestamps: bool) -> None:
+    """``WhisperTranscriber(timestamps=True)`` needs a configuration with timestamp ids whose prefix ends in <|notimestamps|>."""
+    if not timestamps:
+        return
+    tb = cfg.timestamp_begin
+    if tb is None:
+        raise ValueError("timestamps=True needs a model with timestamp ids (SttConfig.timestamp_begin)")
+    if not cfg.prefix or cfg.prefix[-1] != tb - 1 or tb + cfg.n_timestamps > cfg.vocab:
+        raise ValueError(f"timestamps=True: the prefix {tuple(cfg.prefix)} must end in <|notimestamps|> = {tb - 1} and the vocabulary of {cfg.vocab} "
+                         f"hold the {cfg.n_timestamps} timestamp ids from {tb} on")
 
 
 @dataclass
@@ -621,9 +786,14 @@ class WhisperTranscriber:
     ids of silent windows, so that a silent clip is "" and not what the decoder makes up."""
     auto, no_speech_threshold, logprob_threshold = False, None, -1.0
     _ex = False                          # calls go through transcribe_ids_ex (a detected language, or the silence rule)
+    timestamps = False                   # calls go through transcribe_ids_seek (the reference's long-form rule; see below)
 
     def __init__(self, ctx: "_native.Context", model_dir: Optional[str] = None, synthetic: bool = False, cfg: Optional[SttConfig] = None, seed: int = 789,
-                 beam_size: int = 1, language: str = "en", no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = -1.0):
+                 beam_size: int = 1, language: str = "en", no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = -1.0,
+                 timestamps: bool = False):
+        """``timestamps``: every call decodes with timestamp tokens and walks a clip longer than one window by seek positions
+        (``transcribe_ids_seek``), as the reference's ``model.transcribe`` does; a clip's text is its segments' texts joined with a
+        space (stt_validator.py:136), and ``batch_segments`` returns them with their times."""
         self.beam_size = check_beam_size(beam_size)
         self.auto = language == "auto"
         self.no_speech_threshold, self.logprob_threshold = no_speech_threshold, logprob_threshold
@@ -648,11 +818,36 @@ class WhisperTranscriber:
             cfg = cfg.with_language(code)
         if (self.auto or no_speech_threshold is not None) and not cfg.languages:
             raise ValueError("language detection and the silence rule need a model with language ids (SttConfig.languages)")
+        self.timestamps = bool(timestamps)
+        check_timestamp_config(cfg, self.timestamps)
         self.cfg = cfg
         self.model = NativeSTT(ctx, cfg, state)
         self._ex = self.auto or no_speech_threshold is not None        # calls that must go through transcribe_ids_ex
 
+    def _seek(self, audios, sample_rate: int) -> List[SttSeekClip]:
+        return self.model.transcribe_ids_seek(audios, sample_rate, self.beam_size, "auto" if self.auto else None,
+                                              no_speech_threshold=self.no_speech_threshold, logprob_threshold=self.logprob_threshold,
+                                              no_speech=bool(self.cfg.languages))
+
+    def _segment_text(self, ids: List[int]) -> str:
+        """One segment's text as the reference's transcriber hands it over (unstripped: the join and the final strip are the caller's)."""
+        if self.tokenizer is not None:
+            return self.tokenizer.decode(ids, skip_special_tokens=True)
+        return " ".join(f"<{i}>" for i in ids)
+
+    def _joined(self, clip: SttSeekClip) -> str:
+        return join_segment_texts(self._segment_text(g.ids) for g in clip.segments)
+
+    def batch_segments(self, audios, sample_rate: int) -> List[List[SttSegment]]:
+        """Per clip its closed segments with start and end in seconds and their texts (``timestamps=True`` only)."""
+        if not self.timestamps:
+            raise ValueError("batch_segments needs WhisperTranscriber(timestamps=True)")
+        clips = self._seek(audios, sample_rate)
+        return [[dataclasses.replace(g, text=self._segment_text(g.ids).strip()) for g in c.segments] for c in clips]
+
     def ids(self, audio, sample_rate: int) -> List[int]:
+        if self.timestamps:
+            return self._seek([audio], sample_rate)[0].ids
         if self._ex:
             return self.batch_detailed([audio], sample_rate)[0].ids
         if self.beam_size > 1:
@@ -660,6 +855,8 @@ class WhisperTranscriber:
         return self.model.transcribe_ids(audio, sample_rate)
 
     def ids_batch(self, audios, sample_rate: int) -> List[List[int]]:
+        if self.timestamps:
+            return [c.ids for c in self._seek(audios, sample_rate)]
         if self._ex:
             return [d.ids for d in self.batch_detailed(audios, sample_rate)]
         if self.beam_size > 1:
@@ -669,6 +866,8 @@ class WhisperTranscriber:
     def batch_scored(self, audios, sample_rate: int) -> List[Tuple[Optional[str], float]]:
         """The texts of a chunk of segments with their confidence: the average log-probability per emitted token of the chosen
         hypothesis (0 is certain).  One native call, beam search of the configured width (width 1: the greedy ids, scored)."""
+        if self.timestamps:
+            return [(self._joined(c), c.score) for c in self._seek(audios, sample_rate)]
         if self._ex:
             return [(d.text, d.avg_logprob) for d in self.batch_detailed(audios, sample_rate)]
         ids, scores = self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)
@@ -679,6 +878,14 @@ class WhisperTranscriber:
         with silent windows left out, the language the prefix carried and its probability, the largest no-speech probability of its
         windows and how many windows the silence rule dropped."""
         from .validation import window_is_silent
+        if self.timestamps:
+            out = []
+            for c in self._seek(audios, sample_rate):
+                dropped = sum(1 for w in c.windows if window_is_silent(w.no_speech_prob, w.avg_logprob, self.no_speech_threshold, self.logprob_threshold))
+                ns = [w.no_speech_prob for w in c.windows if w.no_speech_prob == w.no_speech_prob]
+                out.append(SttDetail(self._joined(c), c.ids, c.score, self.cfg.language_code(c.language) or str(c.language), c.language_prob,
+                                     max(ns) if ns else float("nan"), dropped))
+            return out
         clips = self.model.transcribe_ids_ex(audios, sample_rate, self.beam_size, "auto" if self.auto else None)
         out = []
         for c in clips:
@@ -703,11 +910,15 @@ class WhisperTranscriber:
         return " ".join(f"<{i}>" for i in ids)
 
     def __call__(self, audio, sample_rate: int) -> Optional[str]:
+        if self.timestamps:
+            return self._joined(self._seek([audio], sample_rate)[0])
         return self._text(self.ids(audio, sample_rate))
 
     def batch(self, audios, sample_rate: int) -> List[Optional[str]]:
         """The texts of a chunk of segments from one native call (the provider's ``_chunk_texts``): per clip what ``__call__``
         returns for it."""
+        if self.timestamps:
+            return [self._joined(c) for c in self._seek(audios, sample_rate)]
         return [self._text(ids) for ids in self.ids_batch(audios, sample_rate)]
 
     def close(self) -> None:
