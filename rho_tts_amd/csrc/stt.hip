@@ -35,6 +35,10 @@
 // makes, from three facts per row kept in the beam book - and the host applies the seek rule to what a group decoded
 // (stt_seek_rule): a round holds one window per unfinished clip at the clip's current offset, and the number of rounds is bounded
 // before the first launch.  Off unless rt_stt_set_timestamps was called; no other entry point changes.
+//
+// The three beam entry points run their groups through one driver (stt_run_group) under one plan (SttPlan: the clips' language
+// requests, whether the probe runs, the timestamp rule); what each keeps for itself is how it forms its groups and what it makes of
+// the hypotheses - fixed cuts and joined ids (stt_transcribe_beam), rounds, offsets and the seek rule (stt_transcribe_seek).
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -672,13 +676,14 @@ struct rt_stt {
     int32_t* d_sot = nullptr;            // [STT_GROUP] start-of-transcript: the tokens of the probe pass
     int32_t* d_probe = nullptr;          // [4][STT_GROUP]: detected id | its probability | no-speech probability (float) | the id the prefix took
     int32_t* d_win_meta = nullptr;       // [2][STT_GROUP]: a window's clip | the row of its clip's first window in this group (-1: none)
-    int32_t* d_lang_prefix = nullptr;    // [STT_GROUP][n_prefix] the windows' forced prefixes (k_stt_lang_prefix)
     int32_t* d_clip_lang = nullptr;      // [clip_lang_cap] per clip of the call: the forced or detected id, -1 until it is detected
     int clip_lang_cap = 0;
     std::vector<int32_t> h_probe, h_meta;
     // rt_stt_set_timestamps: timestamp ids [ts_begin, ts_begin + ts_count), 0: not configured (rt_stt_transcribe_seek refuses)
     int32_t ts_begin = 0, ts_count = 0;
-    int32_t* d_ts_prefix = nullptr;      // [STT_GROUP][n_prefix - 1] the windows' prefixes in timestamp mode (without <|notimestamps|>)
+    // [STT_GROUP][n_prefix] a prefix per window (SttPlan; in timestamp mode n_prefix - 1 entries each, without <|notimestamps|>):
+    // allocated by rt_stt_finalize for a handle with languages or timestamps
+    int32_t* d_win_prefix = nullptr;
     std::vector<void*> owned;
 };
 
@@ -1093,10 +1098,19 @@ int stt_beam_reorder(rt_ctx* ctx, const KvCache& from, const KvCache& to, const 
 // (the ids and end-of-sequence)
 struct SttHyp { std::vector<int32_t> ids; float score = 0.f; int count = 1; };
 
-// Languages of a group (rt_stt_transcribe_ex): the windows' prefixes are in s->d_lang_prefix already (probe false: every language is
-// given), or the probe pass runs and k_stt_lang_prefix writes them from the group's window table in s->d_win_meta - per window its
-// clip and the row, in this group, of its clip's first window (-1: an earlier group held it; s->d_clip_lang keeps what it detected)
-struct SttLangPlan { bool probe; };
+// What the windows of a group take in place of the handle's prefix (stt_run_group).  Nothing set: the launches of
+// rt_stt_transcribe_beam - s->grp.d_prefix for every window, nothing probed, no copy.  Otherwise a prefix per window in
+// s->d_win_prefix: laid out on the host and copied in (probe false: every language is given), or written behind the probe pass by
+// k_stt_lang_prefix from the group's window table in s->d_win_meta - per window its clip and the row, in this group, of its clip's
+// first window (-1: an earlier group held it; s->d_clip_lang keeps what it detected).
+struct SttPlan {
+    const int32_t* h_req = nullptr;     // [n_clips] a clip's language, a configured id or -1 = detect; null: the handle's own
+    bool probe = false;                 // the probe pass runs: a clip detects, or the windows' no-speech probabilities are wanted
+    const SttTsRule* ts = nullptr;      // timestamp mode: the prefix without its last entry (<|notimestamps|>), the rule at every step
+    int32_t win_first[STT_GROUP] = {};  // the window table's second column, set per group (the first, a window's clip, is in its span)
+    bool per_window() const { return h_req || probe || ts; }
+    int n_prefix(const rt_stt_config& c) const { return ts ? c.n_prefix - 1 : c.n_prefix; }
+};
 
 // k_stt_probe over nW rows of logits -> s->d_probe rows 0 .. 2
 int stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int nW) {
@@ -1106,15 +1120,30 @@ int stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int nW) {
     RT_HIP(s->ctx, hipGetLastError());
     return RT_OK;
 }
-// k_stt_lang_prefix over the group's window table (s->d_win_meta: stt_transcribe_beam copies it in while the stream is idle, in
-// front of the group's front end - a copy from pageable memory in the middle of the group would make the host wait for the
-// encoder): s->d_lang_prefix and row 3 of s->d_probe
-// (timestamp mode: the first P = n_prefix - 1 entries per window, into s->d_ts_prefix)
-int stt_lang_prefix(rt_stt* s, int nW, int P, int32_t* d_out) {
+// The probe pass over the nW encoded windows of the group on decoder side d: row w is start-of-transcript alone at position 0 of
+// cache slot slot[w] (pos: zeros), over window w's encoder states, then k_stt_probe on its logits.  The greedy side
+// (rt_stt_detect_language) and the beam side run the same kernels at the same shapes: a window's three results are the same bits.
+int stt_probe_pass(rt_stt* s, SttDec& d, const int32_t* slot, const int32_t* pos, int nW) {
+    d.tok = s->d_sot;
+    RT_TRY(stt_decode_rows(s, d, s->grp.enc.cross_kv, nW, 1, 0, slot, pos, slot));
+    return stt_probe(s, d.logits, s->cfg.vocab, nW);
+}
+// k_stt_lang_prefix over the group's window table (s->d_win_meta): the first P entries of every window's prefix into
+// s->d_win_prefix, and row 3 of s->d_probe
+int stt_lang_prefix(rt_stt* s, int nW, int P) {
     rt_ctx* ctx = s->ctx;
     hipLaunchKernelGGL(k_stt_lang_prefix, dim3(1), dim3(64), 0, ctx->stream, nW, P, s->grp.d_prefix, s->d_win_meta, s->d_win_meta + STT_GROUP,
-                       s->d_clip_lang, s->d_probe, d_out, s->d_probe + 3 * STT_GROUP);
+                       s->d_clip_lang, s->d_probe, s->d_win_prefix, s->d_probe + 3 * STT_GROUP);
     RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+// One step of beam search over nW windows: k_stt_beam_select, the timestamp instantiation when a rule is given
+int stt_beam_select(rt_stt* s, const float* d_logits, int row_stride, int nW, int first_step, int B, int step, const SttBeamBook& bk, const SttTsRule* ts) {
+    const rt_stt_config& c = s->cfg;
+    auto* select = ts ? k_stt_beam_select<true> : k_stt_beam_select<false>;
+    hipLaunchKernelGGL(select, dim3(nW), dim3(1024), 0, s->ctx->stream, d_logits, c.vocab, row_stride, s->d_mask, first_step, c.eos_id, B, step, bk,
+                       ts ? *ts : SttTsRule{});
+    RT_HIP(s->ctx, hipGetLastError());
     return RT_OK;
 }
 
@@ -1122,17 +1151,13 @@ int stt_lang_prefix(rt_stt* s, int nW, int P, int32_t* d_out) {
 // cache slot of the window's first beam row; the reorder kernel then fans it out to the window's rows, and after every later
 // step gives row r the cache of the row it continues.  One device-to-host read and one synchronisation per step, as the greedy
 // group; the bookkeeping comes back once, and the host follows the back-pointers of the finished entries.
-// lang (null: the handle's prefix for every window, nothing probed - the launches of rt_stt_transcribe_beam): a prefix per window,
-// and whether the probe pass runs to decide it.
-// ts (null: as ever): timestamp mode - the prefix is the handle's without its last entry (<|notimestamps|>), the windows' prefixes
-// are in s->d_ts_prefix (lang is given), every step applies the timestamp rule (k_stt_beam_select<true>), and the ids that come back
-// hold timestamp ids.
-int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, const SttLangPlan* lang = nullptr, const SttTsRule* ts = nullptr) {
+// plan: the prefix every window takes (SttPlan) and whether the probe pass runs to decide it; in timestamp mode every step applies
+// the timestamp rule (k_stt_beam_select<true>), and the ids that come back hold timestamp ids.
+int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, const SttPlan& plan) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     SttBeam& bm = s->beam;
-    const int P = ts ? c.n_prefix - 1 : c.n_prefix, rows = nW * B, R = bm.rows;
-    int32_t* d_win_prefix = ts ? s->d_ts_prefix : s->d_lang_prefix;
+    const int P = plan.n_prefix(c), rows = nW * B, R = bm.rows;
     const SttBeamBook& bk = bm.book;
     const KvCache& cross = s->grp.enc.cross_kv;
     RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
@@ -1143,29 +1168,21 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
     hipLaunchKernelGGL(k_stt_fill_beam_rows, dim3(1), dim3(256), 0, ctx->stream, bm.pre_slot, bm.pre_pos, bm.pre_win, nW * P, P, B, bm.row_slot, bm.row_win, rows);
     RT_HIP(ctx, hipGetLastError());
     bm.dec.tok = s->grp.d_prefix;                // (the forced prefix of every window: the group keeps it)
-    if (lang) {
-        // the probe pass: row w is start-of-transcript alone at position 0 of cache slot w, over window w's encoder states (the
-        // prefix pass and the reorder behind it overwrite what it leaves in the cache), then the windows' prefixes on the device.
-        // Every language given and no no-speech probability wanted: no launch is added to those of rt_stt_transcribe_beam
-        if (lang->probe) {
-            bm.dec.tok = s->d_sot;
-            RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, 1, 0, bm.row_slot, bm.row_pos, bm.row_slot));
-            RT_TRY(stt_probe(s, bm.dec.logits, c.vocab, nW));
-            RT_TRY(stt_lang_prefix(s, nW, P, d_win_prefix));
+    if (plan.per_window()) {
+        // the probe pass on cache slot w of window w (the prefix pass and the reorder behind it overwrite what it leaves in the
+        // cache), then the windows' prefixes on the device.  Every language given and no no-speech probability wanted: no launch is
+        // added to those of rt_stt_transcribe_beam
+        if (plan.probe) {
+            RT_TRY(stt_probe_pass(s, bm.dec, bm.row_slot, bm.row_pos, nW));
+            RT_TRY(stt_lang_prefix(s, nW, P));
         }
-        bm.dec.tok = d_win_prefix;           // (without a probe every language is given: the caller has copied the prefixes in)
+        bm.dec.tok = s->d_win_prefix;        // (without a probe every language is given: stt_run_group has copied the prefixes in)
     }
     RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
     const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
     int steps = 0;
     for (int step = 0; step < budget; ++step) {
-        if (ts)
-            hipLaunchKernelGGL(k_stt_beam_select<true>, dim3(nW), dim3(1024), 0, ctx->stream, bm.dec.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0,
-                               c.eos_id, B, step, bk, *ts);
-        else
-            hipLaunchKernelGGL(k_stt_beam_select<false>, dim3(nW), dim3(1024), 0, ctx->stream, bm.dec.logits, c.vocab, step == 0 ? 1 : B, s->d_mask, step == 0 ? 1 : 0,
-                               c.eos_id, B, step, bk, SttTsRule{});
-        RT_HIP(ctx, hipGetLastError());
+        RT_TRY(stt_beam_select(s, bm.dec.logits, step == 0 ? 1 : B, nW, step == 0 ? 1 : 0, B, step, bk, plan.ts));
         steps = step + 1;
         int32_t live = 0;
         RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -1210,9 +1227,65 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
     return RT_OK;
 }
 
-// What rt_stt_transcribe_ex asks for and receives beyond ids and scores (host pointers, null: not asked for).  h_req [n_clips]: a
-// clip's language, a configured id or -1 = detect; null: the handle's prefix, and k_stt_lang_prefix does not run.  probe: the probe
-// pass runs (a clip detects, or the windows' no-speech probabilities are wanted).
+// The per-call side of a plan with a probe: s->d_clip_lang holds every clip's request, and the probe's results have a host copy
+int stt_plan_begin(rt_stt* s, const SttPlan& plan, int n_clips) {
+    rt_ctx* ctx = s->ctx;
+    if (!plan.probe) return RT_OK;
+    if (s->clip_lang_cap < n_clips) {
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const int cap = std::max(n_clips, 2 * s->clip_lang_cap);
+        RT_TRY(stt_alloc(s, s->owned, (size_t)cap, &s->d_clip_lang));          // (the smaller one stays owned until rt_stt_destroy)
+        s->clip_lang_cap = cap;
+    }
+    // without a request every clip keeps the handle's own language
+    std::vector<int32_t> req(n_clips, s->cfg.prefix[1]);
+    if (plan.h_req) req.assign(plan.h_req, plan.h_req + n_clips);
+    RT_HIP(ctx, hipMemcpy(s->d_clip_lang, req.data(), (size_t)n_clips * 4, hipMemcpyHostToDevice));
+    s->h_probe.resize(4 * STT_GROUP);
+    return RT_OK;
+}
+
+// What a group reports per window beside its hypothesis: the language its prefix took, that language's probability - the probe's
+// for the window where the clip asked for detection (the clip's own on its first window), 1 where it was given: a forced language
+// (or the handle's own) counts as certain, as in the reference's transcribers - and the no-speech probability (NaN without a probe)
+struct SttWinInfo { int32_t lang; float lang_prob, no_speech; };
+
+// One group through the whole path, what rt_stt_transcribe_beam, rt_stt_transcribe_ex and rt_stt_transcribe_seek share: nW windows
+// at rate sr -> front end, encoder, beam search of width B under the plan.  The group's uploads come first, while the stream is
+// idle: a copy from pageable memory in the middle of the group would make the host wait for the encoder.
+int stt_run_group(rt_stt* s, const SttSpan* spans, int nW, int sr, int B, const SttPlan& plan, std::vector<SttHyp>& hyps, std::vector<SttWinInfo>& info) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    const int P = plan.n_prefix(c);
+    if (plan.per_window()) {
+        s->h_meta.assign((size_t)STT_GROUP * std::max(c.n_prefix, 2), -1);      // (alive until the group's synchronisation)
+        if (plan.probe) {
+            for (int b = 0; b < nW; ++b) { s->h_meta[b] = spans[b].clip; s->h_meta[STT_GROUP + b] = plan.win_first[b]; }
+            RT_HIP(ctx, hipMemcpyAsync(s->d_win_meta, s->h_meta.data(), 2 * STT_GROUP * 4, hipMemcpyHostToDevice, ctx->stream));
+        } else {        // every language is given: laid out here and copied in, which adds no launch to those of rt_stt_transcribe_beam
+            for (int b = 0; b < nW; ++b)
+                for (int k = 0; k < P; ++k) s->h_meta[(size_t)b * P + k] = (k == 1 && plan.h_req) ? plan.h_req[spans[b].clip] : c.prefix[k];
+            RT_HIP(ctx, hipMemcpyAsync(s->d_win_prefix, s->h_meta.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+    }
+    RT_TRY(stt_features_group(s, spans, nW, sr));
+    RT_TRY(stt_encode(s, s->grp.enc, nW));
+    RT_TRY(stt_decode_beam_group(s, nW, B, hyps, plan));
+    if (plan.probe) RT_HIP(ctx, hipMemcpy(s->h_probe.data(), s->d_probe, 4 * STT_GROUP * 4, hipMemcpyDeviceToHost));     // (behind the group's last synchronisation)
+    const float* pf = (const float*)s->h_probe.data();
+    info.resize(nW);
+    for (int b = 0; b < nW; ++b) {
+        const int i = spans[b].clip;
+        const bool detected = plan.h_req && plan.h_req[i] < 0;
+        info[b].lang = plan.probe ? s->h_probe[3 * STT_GROUP + b] : plan.h_req ? plan.h_req[i] : c.prefix[P > 1 ? 1 : 0];
+        info[b].lang_prob = detected ? pf[STT_GROUP + b] : 1.0f;
+        info[b].no_speech = plan.probe ? pf[2 * STT_GROUP + b] : NAN;
+    }
+    return RT_OK;
+}
+
+// What rt_stt_transcribe_ex asks for (h_req, probe: as SttPlan's) and receives beyond ids and scores (host pointers, null: not
+// asked for)
 struct SttReport {
     const int32_t* h_req = nullptr;
     bool probe = false;
@@ -1226,63 +1299,27 @@ struct SttReport {
 // every window, nothing probed) and rt_stt_transcribe_ex share: floor(STT_GROUP / beam_size) windows make a group.
 int stt_transcribe_beam(rt_stt* s, const std::vector<SttSpan>& all, int n_clips, int sr, int beam_size, int32_t* h_tokens, int max_tokens, int32_t* h_n_tokens,
                         float* h_scores, const SttReport* rep) {
-    rt_ctx* ctx = s->ctx;
     std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
     const size_t per_group = (size_t)(STT_GROUP / beam_size);
     const int most = (int)std::min(all.size(), per_group);
     RT_TRY(stt_group_reserve(s, most));
     RT_TRY(stt_beam_reserve(s, most * beam_size));
-    // a prefix per window: written on the device behind the probe (k_stt_lang_prefix), or - every language given and nothing to
-    // probe - laid out here and copied in, which adds no launch to those of rt_stt_transcribe_beam
-    const bool langs = rep && (rep->h_req || rep->probe), probe = langs && rep->probe;
-    const int P = s->cfg.n_prefix;
-    std::vector<int32_t> win_clip(STT_GROUP), win_first(STT_GROUP), first_at(n_clips, -1);
-    if (probe) {
-        if (s->clip_lang_cap < n_clips) {
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const int cap = std::max(n_clips, 2 * s->clip_lang_cap);
-            RT_TRY(stt_alloc(s, s->owned, (size_t)cap, &s->d_clip_lang));          // (the smaller one stays owned until rt_stt_destroy)
-            s->clip_lang_cap = cap;
-        }
-        // without a request every clip keeps the handle's own language
-        std::vector<int32_t> req(n_clips, s->cfg.prefix[1]);
-        if (rep->h_req) req.assign(rep->h_req, rep->h_req + n_clips);
-        RT_HIP(ctx, hipMemcpy(s->d_clip_lang, req.data(), (size_t)n_clips * 4, hipMemcpyHostToDevice));
-        s->h_probe.resize(4 * STT_GROUP);
-    }
+    SttPlan plan;
+    if (rep) { plan.h_req = rep->h_req; plan.probe = rep->probe; }
+    RT_TRY(stt_plan_begin(s, plan, n_clips));
+    std::vector<int32_t> first_at(n_clips, -1);      // a clip's first window, among `all`
     std::vector<double> sum(n_clips, 0.0);
     std::vector<int64_t> count(n_clips, 0);
     std::vector<SttHyp> hyps;
+    std::vector<SttWinInfo> info;
     for (size_t next = 0; next < all.size(); next += per_group) {
         const int nW = (int)std::min(per_group, all.size() - next);
-        if (langs) {                                                    // (the copies first, while the stream is idle)
-            for (int b = 0; b < nW; ++b) {
-                const int i = all[next + b].clip;
-                const bool is_first = next + b == 0 || all[next + b - 1].clip != i;
-                if (is_first) first_at[i] = (int32_t)(next + b);
-                win_clip[b] = i;
-                win_first[b] = first_at[i] >= (int32_t)next ? first_at[i] - (int32_t)next : -1;
-            }
-            s->h_meta.assign((size_t)STT_GROUP * std::max(P, 2), -1);   // (alive until the group's synchronisation)
-            if (probe) {
-                for (int b = 0; b < nW; ++b) { s->h_meta[b] = win_clip[b]; s->h_meta[STT_GROUP + b] = win_first[b]; }
-                RT_HIP(ctx, hipMemcpyAsync(s->d_win_meta, s->h_meta.data(), 2 * STT_GROUP * 4, hipMemcpyHostToDevice, ctx->stream));
-            } else {
-                for (int b = 0; b < nW; ++b)
-                    for (int k = 0; k < P; ++k) s->h_meta[(size_t)b * P + k] = k == 1 ? rep->h_req[win_clip[b]] : s->cfg.prefix[k];
-                RT_HIP(ctx, hipMemcpyAsync(s->d_lang_prefix, s->h_meta.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
-            }
+        for (int b = 0; b < nW; ++b) {
+            const int i = all[next + b].clip;
+            if (next + b == 0 || all[next + b - 1].clip != i) first_at[i] = (int32_t)(next + b);
+            plan.win_first[b] = first_at[i] >= (int32_t)next ? first_at[i] - (int32_t)next : -1;
         }
-        RT_TRY(stt_features_group(s, all.data() + next, nW, sr));
-        RT_TRY(stt_encode(s, s->grp.enc, nW));
-        if (langs) {
-            const SttLangPlan plan{probe};
-            RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps, &plan));
-            if (probe) RT_HIP(ctx, hipMemcpy(s->h_probe.data(), s->d_probe, 4 * STT_GROUP * 4, hipMemcpyDeviceToHost));     // (behind the group's last synchronisation)
-        } else {
-            RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps));
-        }
-        const float* pf = (const float*)s->h_probe.data();
+        RT_TRY(stt_run_group(s, all.data() + next, nW, sr, beam_size, plan, hyps, info));
         for (int b = 0; b < nW; ++b) {
             const int i = all[next + b].clip;
             for (int32_t t : hyps[b].ids)
@@ -1294,12 +1331,10 @@ int stt_transcribe_beam(rt_stt* s, const std::vector<SttSpan>& all, int n_clips,
             if (rep->win_clip) rep->win_clip[at] = i;
             if (rep->win_n_ids) rep->win_n_ids[at] = (int32_t)hyps[b].ids.size();
             if (rep->win_logprob) rep->win_logprob[at] = hyps[b].score;
-            if (rep->win_no_speech) rep->win_no_speech[at] = pf[2 * STT_GROUP + b];
-            if (langs ? first_at[i] != (int32_t)at : (at != 0 && all[at - 1].clip == i)) continue;      // the clip's first window: its language
-            // a forced language (or the handle's own) counts as certain, as in the reference's transcribers
-            const bool detected = rep->h_req && rep->h_req[i] < 0;
-            if (rep->h_lang) rep->h_lang[i] = probe ? s->h_probe[3 * STT_GROUP + b] : langs ? rep->h_req[i] : s->cfg.prefix[P > 1 ? 1 : 0];
-            if (rep->h_lang_prob) rep->h_lang_prob[i] = detected ? pf[STT_GROUP + b] : 1.0f;
+            if (rep->win_no_speech) rep->win_no_speech[at] = info[b].no_speech;
+            if (first_at[i] != (int32_t)at) continue;                   // the clip's first window: its language
+            if (rep->h_lang) rep->h_lang[i] = info[b].lang;
+            if (rep->h_lang_prob) rep->h_lang_prob[i] = info[b].lang_prob;
         }
     }
     if (h_scores)
@@ -1360,37 +1395,27 @@ struct SttSeekResult {
 };
 
 // The seek loop: a round holds one window per unfinished clip at the clip's current offset (in input samples, a multiple of the
-// tick); rounds go through front end, encoder, optional probe and the beam decode in groups of floor(STT_GROUP / beam_size) windows
-// as stt_transcribe_beam does, and the host applies the silence rule and the seek rule to what a group decoded.  Every round moves
+// tick); rounds go through stt_run_group in groups of floor(STT_GROUP / beam_size) windows as stt_transcribe_beam's windows do (the
+// probe, if any, in front of the decode), and the host applies the silence rule and the seek rule to what a group decoded.  Every round moves
 // every unfinished clip on by at least one tick, so max_rounds - computed before the first launch - bounds the loop.
 int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int n_clips, int sr, const rt_stt_seek_opts& o, bool probe,
                         SttSeekResult& res) {
-    rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
-    const int beam_size = o.beam_size, P = c.n_prefix - 1;
+    const int beam_size = o.beam_size;
     const int64_t tick = (int64_t)(0.02 * (double)sr), win = (int64_t)c.chunk_seconds * sr;
     const int whole = s->ts_count - 1;
     const SttTsRule rule{s->ts_begin, s->ts_count, o.max_initial_timestamp_index};
+    SttPlan plan;
+    plan.h_req = o.h_language; plan.probe = probe; plan.ts = &rule;
     int64_t max_rounds = 1;
     for (int i = 0; i < n_clips; ++i) max_rounds = std::max<int64_t>(max_rounds, (n_samples[i] + tick - 1) / tick + 1);
     const size_t per_group = (size_t)(STT_GROUP / beam_size);
     const int most = (int)std::min<size_t>((size_t)n_clips, per_group);
     RT_TRY(stt_group_reserve(s, most));
     RT_TRY(stt_beam_reserve(s, most * beam_size));
-    if (probe) {
-        if (s->clip_lang_cap < n_clips) {
-            RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            const int cap = std::max(n_clips, 2 * s->clip_lang_cap);
-            RT_TRY(stt_alloc(s, s->owned, (size_t)cap, &s->d_clip_lang));
-            s->clip_lang_cap = cap;
-        }
-        std::vector<int32_t> req(n_clips, c.prefix[1]);
-        if (o.h_language) req.assign(o.h_language, o.h_language + n_clips);
-        RT_HIP(ctx, hipMemcpy(s->d_clip_lang, req.data(), (size_t)n_clips * 4, hipMemcpyHostToDevice));
-        s->h_probe.resize(4 * STT_GROUP);
-    }
+    RT_TRY(stt_plan_begin(s, plan, n_clips));
     res.ids.assign(n_clips, {}); res.segs.assign(n_clips, {}); res.wins.assign(n_clips, {});
-    res.score.assign(n_clips, 0.f); res.lang_prob.assign(n_clips, 1.f); res.lang.assign(n_clips, c.prefix[P > 1 ? 1 : 0]);
+    res.score.assign(n_clips, 0.f); res.lang_prob.assign(n_clips, 1.f); res.lang.assign(n_clips, 0);     // (round 0 fills both for every clip)
     std::vector<int64_t> off(n_clips, 0);
     std::vector<char> done(n_clips, 0);
     std::vector<double> sum(n_clips, 0.0), sum_all(n_clips, 0.0);
@@ -1398,6 +1423,7 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
     const bool silence = o.no_speech_threshold == o.no_speech_threshold;
     std::vector<SttSpan> spans;
     std::vector<SttHyp> hyps;
+    std::vector<SttWinInfo> info;
     std::vector<SttSeg> segs;
     for (int64_t round = 0; round < max_rounds; ++round) {
         spans.clear();
@@ -1406,32 +1432,15 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
         if (spans.empty()) break;
         for (size_t next = 0; next < spans.size(); next += per_group) {
             const int nW = (int)std::min(per_group, spans.size() - next);
-            s->h_meta.assign((size_t)STT_GROUP * std::max(c.n_prefix, 2), -1);      // (alive until the group's synchronisation)
-            if (probe) {        // a clip's language is fixed by its first window: round 0 detects, later rounds find it in d_clip_lang
-                for (int b = 0; b < nW; ++b) { s->h_meta[b] = spans[next + b].clip; s->h_meta[STT_GROUP + b] = round == 0 ? b : -1; }
-                RT_HIP(ctx, hipMemcpyAsync(s->d_win_meta, s->h_meta.data(), 2 * STT_GROUP * 4, hipMemcpyHostToDevice, ctx->stream));
-            } else {
-                for (int b = 0; b < nW; ++b)
-                    for (int k = 0; k < P; ++k)
-                        s->h_meta[(size_t)b * P + k] = (k == 1 && o.h_language) ? o.h_language[spans[next + b].clip] : c.prefix[k];
-                RT_HIP(ctx, hipMemcpyAsync(s->d_ts_prefix, s->h_meta.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
-            }
-            RT_TRY(stt_features_group(s, spans.data() + next, nW, sr));
-            RT_TRY(stt_encode(s, s->grp.enc, nW));
-            const SttLangPlan plan{probe};
-            RT_TRY(stt_decode_beam_group(s, nW, beam_size, hyps, &plan, &rule));
-            if (probe) RT_HIP(ctx, hipMemcpy(s->h_probe.data(), s->d_probe, 4 * STT_GROUP * 4, hipMemcpyDeviceToHost));
-            const float* pf = (const float*)s->h_probe.data();
+            // a clip's language is fixed by its first window: round 0 detects, later rounds find it in d_clip_lang
+            for (int b = 0; b < nW; ++b) plan.win_first[b] = round == 0 ? b : -1;
+            RT_TRY(stt_run_group(s, spans.data() + next, nW, sr, beam_size, plan, hyps, info));
             for (int b = 0; b < nW; ++b) {
                 const SttSpan& sp = spans[next + b];
                 const int i = sp.clip;
                 const SttHyp& h = hyps[b];
-                if (round == 0) {
-                    const bool detected = o.h_language && o.h_language[i] < 0;
-                    res.lang[i] = probe ? s->h_probe[3 * STT_GROUP + b] : o.h_language ? o.h_language[i] : c.prefix[P > 1 ? 1 : 0];
-                    res.lang_prob[i] = detected ? pf[STT_GROUP + b] : 1.0f;
-                }
-                const float ns = probe ? pf[2 * STT_GROUP + b] : NAN;
+                if (round == 0) { res.lang[i] = info[b].lang; res.lang_prob[i] = info[b].lang_prob; }
+                const float ns = info[b].no_speech;
                 const float avg = h.score / (float)h.count;
                 const bool silent = silence && ns > o.no_speech_threshold && (!(o.logprob_threshold == o.logprob_threshold) || avg < o.logprob_threshold);
                 sum_all[i] += (double)h.score; count_all[i] += h.count;
@@ -1463,6 +1472,18 @@ int stt_check_clips(const float* const* d_pcm, const int64_t* n_samples, int32_t
     if (n_clips < 0 || (n_clips > 0 && (!d_pcm || !n_samples))) return RT_ERR_INVALID;
     for (int i = 0; i < n_clips; ++i)
         if (n_samples[i] < 0 || (n_samples[i] > 0 && !d_pcm[i])) return RT_ERR_INVALID;
+    return RT_OK;
+}
+
+// The language requests of a call of `who` (null: none): -1 asks for detection - the probe pass then runs, as it does when `probe`
+// comes in set - and any other id must be configured.  wants: what the probe serves in that entry point, for the user's message
+int stt_check_languages(rt_stt* s, const char* who, const char* wants, const int32_t* h_req, int n_clips, bool& probe) {
+    for (int i = 0; h_req && i < n_clips; ++i) {
+        if (h_req[i] == -1) { probe = true; continue; }
+        if (std::find(s->lang_ids.begin(), s->lang_ids.end(), h_req[i]) == s->lang_ids.end())
+            return rt_fail(s->ctx, RT_ERR_INVALID, "%s: clip %d: language %d is neither -1 nor a configured id (rt_stt_set_languages)", who, i, h_req[i]);
+    }
+    if ((h_req || probe) && s->lang_ids.empty()) return rt_fail(s->ctx, RT_ERR_INVALID, "%s: %s asked of a handle without rt_stt_set_languages", who, wants);
     return RT_OK;
 }
 
@@ -1594,12 +1615,11 @@ int rt_stt_finalize(rt_stt* s) {
         RT_TRY(stt_alloc(s, s->owned, (size_t)STT_GROUP, &s->d_sot));
         RT_TRY(stt_alloc(s, s->owned, (size_t)4 * STT_GROUP, &s->d_probe));
         RT_TRY(stt_alloc(s, s->owned, (size_t)2 * STT_GROUP, &s->d_win_meta));
-        RT_TRY(stt_alloc(s, s->owned, (size_t)STT_GROUP * c.n_prefix, &s->d_lang_prefix));
         RT_HIP(ctx, hipMemsetAsync(s->d_probe, 0, (size_t)4 * STT_GROUP * 4, ctx->stream));
         hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, s->d_sot, STT_GROUP, c.prefix[0], 0);
         RT_HIP(ctx, hipGetLastError());
     }
-    if (s->ts_begin > 0) RT_TRY(stt_alloc(s, s->owned, (size_t)STT_GROUP * c.n_prefix, &s->d_ts_prefix));
+    if (!s->lang_ids.empty() || s->ts_begin > 0) RT_TRY(stt_alloc(s, s->owned, (size_t)STT_GROUP * c.n_prefix, &s->d_win_prefix));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->finalized = true;
     return RT_OK;
@@ -1726,9 +1746,7 @@ int rt_stt_detect_language(rt_stt* s, const float* const* d_pcm, const int64_t* 
         const int nW = std::min(STT_GROUP, n_clips - next);
         RT_TRY(stt_features_group(s, all.data() + next, nW, sample_rate));
         RT_TRY(stt_encode(s, w.enc, nW));
-        w.dec.tok = s->d_sot;                                   // the probe pass on the greedy decoder side: position 0 of slot b
-        RT_TRY(stt_decode_rows(s, w.dec, w.enc.cross_kv, nW, 1, 0, w.step_slot, w.step_pos, w.step_slot));
-        RT_TRY(stt_probe(s, w.dec.logits, s->cfg.vocab, nW));
+        RT_TRY(stt_probe_pass(s, w.dec, w.step_slot, w.step_pos, nW));      // on the greedy decoder side: position 0 of slot b
         RT_HIP(ctx, hipMemcpyAsync(s->h_probe.data(), s->d_probe, 3 * STT_GROUP * 4, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const float* pf = (const float*)s->h_probe.data();
@@ -1757,15 +1775,7 @@ int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int64_t* n_
     rep.h_lang = out->h_language; rep.h_lang_prob = out->h_language_prob;
     rep.win_clip = out->h_win_clip; rep.win_n_ids = out->h_win_n_ids; rep.win_logprob = out->h_win_logprob; rep.win_no_speech = out->h_win_no_speech;
     rep.probe = rep.win_no_speech != nullptr;
-    if (rep.h_req)
-        for (int i = 0; i < n_clips; ++i) {
-            const int32_t id = rep.h_req[i];
-            if (id == -1) { rep.probe = true; continue; }
-            if (std::find(s->lang_ids.begin(), s->lang_ids.end(), id) == s->lang_ids.end())
-                return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_ex: clip %d: language %d is neither -1 nor a configured id (rt_stt_set_languages)", i, id);
-        }
-    if ((rep.h_req || rep.probe) && s->lang_ids.empty())
-        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_ex: languages or no-speech probabilities asked of a handle without rt_stt_set_languages");
+    RT_TRY(stt_check_languages(s, "rt_stt_transcribe_ex", "languages or no-speech probabilities", rep.h_req, n_clips, rep.probe));
     std::vector<SttSpan> all;
     stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, all);
     const bool per_window = rep.win_clip || rep.win_n_ids || rep.win_logprob || rep.win_no_speech;
@@ -1810,15 +1820,7 @@ int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* 
     if (n_clips == 0) return RT_OK;
     const bool silence = opts->no_speech_threshold == opts->no_speech_threshold;
     bool probe = out->h_win_no_speech != nullptr || silence;
-    if (opts->h_language)
-        for (int i = 0; i < n_clips; ++i) {
-            const int32_t id = opts->h_language[i];
-            if (id == -1) { probe = true; continue; }
-            if (std::find(s->lang_ids.begin(), s->lang_ids.end(), id) == s->lang_ids.end())
-                return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_seek: clip %d: language %d is neither -1 nor a configured id (rt_stt_set_languages)", i, id);
-        }
-    if ((opts->h_language || probe) && s->lang_ids.empty())
-        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_seek: languages, no-speech probabilities or the silence rule asked of a handle without rt_stt_set_languages");
+    RT_TRY(stt_check_languages(s, "rt_stt_transcribe_seek", "languages, no-speech probabilities or the silence rule", opts->h_language, n_clips, probe));
     SttSeekResult res;
     RT_TRY(stt_transcribe_seek(s, d_pcm, n_samples, n_clips, sample_rate, *opts, probe, res));
     const double tick_s = (double)(int64_t)(0.02 * (double)sample_rate) / (double)sample_rate;
@@ -1914,13 +1916,7 @@ int stt_debug_beam_step(const char* who, rt_stt* s, const float* d_logits, int32
     for (int w = 0; w < n_windows; ++w) { h.n_live[w] = h_n_live[w]; h.n_fin[w] = h_n_finished[w]; h.done[w] = h_done[w] ? 1 : 0; }
     *h.live = live;
     RT_HIP(ctx, hipMemcpyAsync(bm.book_mem, hb.data(), bm.book_n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (ts)
-        hipLaunchKernelGGL(k_stt_beam_select<true>, dim3(n_windows), dim3(1024), 0, ctx->stream, d_logits, s->cfg.vocab, row_stride, s->d_mask, first_step ? 1 : 0,
-                           s->cfg.eos_id, beam, step, bk, *ts);
-    else
-        hipLaunchKernelGGL(k_stt_beam_select<false>, dim3(n_windows), dim3(1024), 0, ctx->stream, d_logits, s->cfg.vocab, row_stride, s->d_mask, first_step ? 1 : 0,
-                           s->cfg.eos_id, beam, step, bk, SttTsRule{});
-    RT_HIP(ctx, hipGetLastError());
+    RT_TRY(stt_beam_select(s, d_logits, row_stride, n_windows, first_step ? 1 : 0, beam, step, bk, ts));
     RT_HIP(ctx, hipMemcpyAsync(hb.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int r = 0; r < R; ++r) {

@@ -484,6 +484,19 @@ def to_native(state: Dict[str, torch.Tensor], c: SttConfig) -> Dict[str, torch.T
     return out
 
 
+def _i32(k: int):
+    return (C.c_int32 * max(k, 1))()
+
+
+def _f32(k: int):
+    return (C.c_float * max(k, 1))()
+
+
+def _clip_ids(toks, counts, n: int, cap: int) -> List[List[int]]:
+    """The ids of ``n`` clips out of ``toks`` [n][cap], ``counts[i]`` of clip i."""
+    return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)]
+
+
 class NativeSTT:
     """One ``rt_stt``: the speech-to-text model in HBM, on the context (GPU, stream) of the TTS engine it validates."""
 
@@ -552,39 +565,14 @@ class NativeSTT:
         """``chunk_seconds`` windows a clip of ``n_samples`` is cut into (rt_stt_transcribe: an empty clip is one window of silence)."""
         return max(1, -(-int(n_samples) // (int(self.cfg.chunk_seconds) * int(sample_rate))))
 
-    def transcribe_ids_batch(self, audios, sample_rate: int, max_tokens: Optional[int] = None) -> List[List[int]]:
-        """The ids of every clip from ONE native call (rt_stt_transcribe_batch): per clip what ``transcribe_ids`` gives for it alone.
-        ``max_tokens`` caps every clip; the default leaves room for every window of the longest clip, so nothing is cut."""
-        xs = [self._pcm(a) for a in audios]
-        n = len(xs)
-        cap = int(max_tokens or max([self.windows(x.numel(), sample_rate) for x in xs] or [1]) * self.cfg.max_new_tokens)
-        ptrs = (C.c_void_p * max(n, 1))(*[x.data_ptr() if x.numel() else None for x in xs])
-        lens = (C.c_int64 * max(n, 1))(*[x.numel() for x in xs])
-        toks = (C.c_int32 * max(n * cap, 1))()
-        counts = (C.c_int32 * max(n, 1))()
-        self.ctx.check(self.lib.rt_stt_transcribe_batch(self.handle, ptrs, lens, n, int(sample_rate), toks, cap, counts), "rt_stt_transcribe_batch")
-        return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)]
-
-    def transcribe_ids_beam(self, audios, sample_rate: int, beam_size: int, max_tokens: Optional[int] = None) -> Tuple[List[List[int]], List[float]]:
-        """Beam search of width ``beam_size`` (1 .. 8) over every clip from ONE native call (rt_stt_transcribe_beam): the ids, and per
-        clip the average log-probability per emitted token (end-of-sequence counted) of the chosen hypotheses.  A clip's ids and score
-        are what it gets alone; ``beam_size == 1`` gives the ids of ``transcribe_ids_batch``.  ``max_tokens`` caps every clip's ids."""
+    # What the batched methods share: the argument checks (before anything touches a device), the clips as pointer and length
+    # arrays, room for every window's ids, the languages as an array
+    def _check(self, who: str, beam_size, max_tokens) -> None:
         check_beam_size(beam_size)
         if max_tokens is not None and int(max_tokens) < 1:
             raise ValueError(f"max_tokens must be at least 1, got {max_tokens!r}")
         if not getattr(self, "handle", None):
-            raise ValueError("transcribe_ids_beam: the model is closed")
-        xs = [self._pcm(a) for a in audios]
-        n = len(xs)
-        cap = int(max_tokens or max([self.windows(x.numel(), sample_rate) for x in xs] or [1]) * self.cfg.max_new_tokens)
-        ptrs = (C.c_void_p * max(n, 1))(*[x.data_ptr() if x.numel() else None for x in xs])
-        lens = (C.c_int64 * max(n, 1))(*[x.numel() for x in xs])
-        toks = (C.c_int32 * max(n * cap, 1))()
-        counts = (C.c_int32 * max(n, 1))()
-        scores = (C.c_float * max(n, 1))()
-        self.ctx.check(self.lib.rt_stt_transcribe_beam(self.handle, ptrs, lens, n, int(sample_rate), int(beam_size), toks, cap, counts, scores),
-                       "rt_stt_transcribe_beam")
-        return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)], [float(scores[i]) for i in range(n)]
+            raise ValueError(f"{who}: the model is closed")
 
     def _clips(self, audios):
         xs = [self._pcm(a) for a in audios]
@@ -592,6 +580,40 @@ class NativeSTT:
         ptrs = (C.c_void_p * max(n, 1))(*[x.data_ptr() if x.numel() else None for x in xs])
         lens = (C.c_int64 * max(n, 1))(*[x.numel() for x in xs])
         return xs, n, ptrs, lens
+
+    def _token_cap(self, n_win: Sequence[int], max_tokens: Optional[int]) -> int:
+        """``max_tokens``, or room for every window (``n_win``: per clip) of the longest clip, so nothing is cut."""
+        return int(max_tokens or max(list(n_win) or [1]) * self.cfg.max_new_tokens)
+
+    def _languages(self, languages, n: int):
+        """``languages`` of a call over ``n`` clips (one entry for all or one per clip) as rt_stt_decode_opts.h_language; None stays None."""
+        if languages is None:
+            return None
+        each = [languages] * n if isinstance(languages, (str, int, np.integer)) else list(languages)
+        if len(each) != n:
+            raise ValueError(f"{len(each)} languages for {n} clips")
+        return (C.c_int32 * max(n, 1))(*[self._language_id(v) for v in each])
+
+    def transcribe_ids_batch(self, audios, sample_rate: int, max_tokens: Optional[int] = None) -> List[List[int]]:
+        """The ids of every clip from ONE native call (rt_stt_transcribe_batch): per clip what ``transcribe_ids`` gives for it alone.
+        ``max_tokens`` caps every clip; the default leaves room for every window of the longest clip, so nothing is cut."""
+        xs, n, ptrs, lens = self._clips(audios)
+        cap = self._token_cap([self.windows(x.numel(), sample_rate) for x in xs], max_tokens)
+        toks, counts = _i32(n * cap), _i32(n)
+        self.ctx.check(self.lib.rt_stt_transcribe_batch(self.handle, ptrs, lens, n, int(sample_rate), toks, cap, counts), "rt_stt_transcribe_batch")
+        return _clip_ids(toks, counts, n, cap)
+
+    def transcribe_ids_beam(self, audios, sample_rate: int, beam_size: int, max_tokens: Optional[int] = None) -> Tuple[List[List[int]], List[float]]:
+        """Beam search of width ``beam_size`` (1 .. 8) over every clip from ONE native call (rt_stt_transcribe_beam): the ids, and per
+        clip the average log-probability per emitted token (end-of-sequence counted) of the chosen hypotheses.  A clip's ids and score
+        are what it gets alone; ``beam_size == 1`` gives the ids of ``transcribe_ids_batch``.  ``max_tokens`` caps every clip's ids."""
+        self._check("transcribe_ids_beam", beam_size, max_tokens)
+        xs, n, ptrs, lens = self._clips(audios)
+        cap = self._token_cap([self.windows(x.numel(), sample_rate) for x in xs], max_tokens)
+        toks, counts, scores = _i32(n * cap), _i32(n), _f32(n)
+        self.ctx.check(self.lib.rt_stt_transcribe_beam(self.handle, ptrs, lens, n, int(sample_rate), int(beam_size), toks, cap, counts, scores),
+                       "rt_stt_transcribe_beam")
+        return _clip_ids(toks, counts, n, cap), [float(scores[i]) for i in range(n)]
 
     def _language_id(self, language) -> int:
         """A code ("zh"), "auto" / None (-1: detect) or a token id, as an entry of rt_stt_decode_opts.h_language."""
@@ -619,33 +641,23 @@ class NativeSTT:
         ``languages``: None - the configured prefix; one entry for all clips or one per clip: a code, a token id, or "auto" / None /
         -1 to detect the clip's language on its first window.  ``no_speech``: ask for the windows' no-speech probabilities (the
         probe pass then runs even when every language is given)."""
-        check_beam_size(beam_size)
-        if max_tokens is not None and int(max_tokens) < 1:
-            raise ValueError(f"max_tokens must be at least 1, got {max_tokens!r}")
-        if not getattr(self, "handle", None):
-            raise ValueError("transcribe_ids_ex: the model is closed")
+        self._check("transcribe_ids_ex", beam_size, max_tokens)
         xs, n, ptrs, lens = self._clips(audios)
         n_win = [self.windows(x.numel(), sample_rate) for x in xs]
-        cap = int(max_tokens or max(n_win or [1]) * self.cfg.max_new_tokens)
-        wcap = sum(n_win)
+        cap, wcap = self._token_cap(n_win, max_tokens), sum(n_win)
         opts, out = RtSttDecodeOpts(), RtSttDecodeOut()
         opts.beam_size, opts.max_tokens = int(beam_size), cap
-        req = None
-        if languages is not None:
-            each = [languages] * n if isinstance(languages, (str, int, np.integer)) else list(languages)
-            if len(each) != n:
-                raise ValueError(f"{len(each)} languages for {n} clips")
-            req = (C.c_int32 * max(n, 1))(*[self._language_id(v) for v in each])
+        req = self._languages(languages, n)
+        if req is not None:
             opts.h_language = req
-        i32, f32 = lambda k: (C.c_int32 * max(k, 1))(), lambda k: (C.c_float * max(k, 1))()
-        toks, counts, scores, lang, lprob = i32(n * cap), i32(n), f32(n), i32(n), f32(n)
-        w_clip, w_n, w_lp, w_ns = i32(wcap), i32(wcap), f32(wcap), f32(wcap)
+        toks, counts, scores, lang, lprob = _i32(n * cap), _i32(n), _f32(n), _i32(n), _f32(n)
+        w_clip, w_n, w_lp, w_ns = _i32(wcap), _i32(wcap), _f32(wcap), _f32(wcap)
         out.h_tokens, out.h_n_tokens, out.h_scores, out.h_language, out.h_language_prob = toks, counts, scores, lang, lprob
         out.h_win_clip, out.h_win_n_ids, out.h_win_logprob, out.window_cap = w_clip, w_n, w_lp, wcap
         if no_speech:
             out.h_win_no_speech = w_ns
         self.ctx.check(self.lib.rt_stt_transcribe_ex(self.handle, ptrs, lens, n, int(sample_rate), C.byref(opts), C.byref(out)), "rt_stt_transcribe_ex")
-        clips = [SttClip([int(toks[i * cap + k]) for k in range(counts[i])], float(scores[i]), int(lang[i]), float(lprob[i]), []) for i in range(n)]
+        clips = [SttClip(ids, float(scores[i]), int(lang[i]), float(lprob[i]), []) for i, ids in enumerate(_clip_ids(toks, counts, n, cap))]
         for w in range(out.n_windows):
             clips[w_clip[w]].windows.append(SttWindow(int(w_n[w]), float(w_lp[w]), float(w_ns[w]) if no_speech else float("nan")))
         return clips
@@ -668,26 +680,16 @@ class NativeSTT:
         rule on (validation.window_is_silent): a silent window gives no segment and is consumed whole.  ``caps``: room for (tokens per
         clip, segments, windows) at the first attempt (default: ``seek_caps``); when one runs out the call is repeated ONCE with the
         counts the library reported, so a result is never cut - except the ids at an explicit ``max_tokens``."""
-        check_beam_size(beam_size)
-        if max_tokens is not None and int(max_tokens) < 1:
-            raise ValueError(f"max_tokens must be at least 1, got {max_tokens!r}")
-        if not getattr(self, "handle", None):
-            raise ValueError("transcribe_ids_seek: the model is closed")
+        self._check("transcribe_ids_seek", beam_size, max_tokens)
         if self.cfg.timestamp_begin is None:
             raise ValueError("transcribe_ids_seek: the configuration has no timestamp ids (SttConfig.timestamp_begin)")
         xs, n, ptrs, lens = self._clips(audios)
         tcap, scap, wcap = caps or self.seek_caps([x.numel() for x in xs], sample_rate)
         if max_tokens is not None:
             tcap = int(max_tokens)
-        req = None
-        if languages is not None:
-            each = [languages] * n if isinstance(languages, (str, int, np.integer)) else list(languages)
-            if len(each) != n:
-                raise ValueError(f"{len(each)} languages for {n} clips")
-            req = (C.c_int32 * max(n, 1))(*[self._language_id(v) for v in each])
+        req = self._languages(languages, n)
         mi = self.cfg.max_initial_timestamp_index if max_initial_timestamp_index is None else int(max_initial_timestamp_index)
         nan = float("nan")
-        i32, f32 = lambda k: (C.c_int32 * max(k, 1))(), lambda k: (C.c_float * max(k, 1))()
         for attempt in range(2):
             opts, out = RtSttSeekOpts(), RtSttSeekOut()
             opts.beam_size, opts.max_tokens, opts.max_initial_timestamp_index = int(beam_size), int(tcap), int(mi)
@@ -695,9 +697,9 @@ class NativeSTT:
             opts.logprob_threshold = nan if logprob_threshold is None else float(logprob_threshold)
             if req is not None:
                 opts.h_language = req
-            toks, counts, scores, lang, lprob = i32(n * tcap), i32(n), f32(n), i32(n), f32(n)
-            g_clip, g_s, g_e, g_st, g_et, g_n = i32(scap), f32(scap), f32(scap), i32(scap), i32(scap), i32(scap)
-            w_clip, w_off, w_n, w_lp, w_ns, w_adv = i32(wcap), (C.c_int64 * max(wcap, 1))(), i32(wcap), f32(wcap), f32(wcap), i32(wcap)
+            toks, counts, scores, lang, lprob = _i32(n * tcap), _i32(n), _f32(n), _i32(n), _f32(n)
+            g_clip, g_s, g_e, g_st, g_et, g_n = _i32(scap), _f32(scap), _f32(scap), _i32(scap), _i32(scap), _i32(scap)
+            w_clip, w_off, w_n, w_lp, w_ns, w_adv = _i32(wcap), (C.c_int64 * max(wcap, 1))(), _i32(wcap), _f32(wcap), _f32(wcap), _i32(wcap)
             out.h_tokens, out.h_n_tokens, out.h_scores, out.h_language, out.h_language_prob = toks, counts, scores, lang, lprob
             out.h_seg_clip, out.h_seg_start, out.h_seg_end, out.h_seg_start_tick, out.h_seg_end_tick, out.h_seg_n_ids = g_clip, g_s, g_e, g_st, g_et, g_n
             out.h_win_clip, out.h_win_offset, out.h_win_n_ids, out.h_win_logprob, out.h_win_advance = w_clip, w_off, w_n, w_lp, w_adv
@@ -715,7 +717,7 @@ class NativeSTT:
             scap, wcap = max(scap, out.n_segments), max(wcap, out.n_windows)
             if max_tokens is None:
                 tcap = max(tcap, out.max_clip_tokens)
-        clips = [SttSeekClip([int(toks[i * tcap + k]) for k in range(counts[i])], float(scores[i]), int(lang[i]), float(lprob[i]), [], []) for i in range(n)]
+        clips = [SttSeekClip(ids, float(scores[i]), int(lang[i]), float(lprob[i]), [], []) for i, ids in enumerate(_clip_ids(toks, counts, n, tcap))]
         at = [0] * n
         for g in range(out.n_segments):
             i = g_clip[g]
@@ -762,14 +764,15 @@ def check_timestamp_config(cfg: SttConfig, timestamps: bool) -> None:
 
 @dataclass
 class SttDetail:
-    """One clip of ``WhisperTranscriber.batch_detailed``."""
+    """One clip of ``WhisperTranscriber.batch_detailed``.  (The defaults stand where a native call reports less: the greedy calls give
+    ids alone, the plain beam call ids and a score - ``WhisperTranscriber._run``; ``batch_detailed`` fills every field.)"""
     text: Optional[str]
     ids: List[int]
-    avg_logprob: float                   # over the windows kept (over all of them when none is)
-    language: str                        # the code at position 1 of the clip's prefix
-    language_prob: float                 # its probability where it was detected, 1 where it was given
-    no_speech_prob: float                # the largest of the clip's windows
-    windows_dropped: int                 # windows the silence rule left out
+    avg_logprob: float = float("nan")    # over the windows kept (over all of them when none is)
+    language: Optional[str] = None       # the code at position 1 of the clip's prefix
+    language_prob: float = float("nan")  # its probability where it was detected, 1 where it was given
+    no_speech_prob: float = float("nan")  # the largest of the clip's windows
+    windows_dropped: int = 0             # windows the silence rule left out
 
 
 class WhisperTranscriber:
@@ -845,38 +848,11 @@ class WhisperTranscriber:
         clips = self._seek(audios, sample_rate)
         return [[dataclasses.replace(g, text=self._segment_text(g.ids).strip()) for g in c.segments] for c in clips]
 
-    def ids(self, audio, sample_rate: int) -> List[int]:
-        if self.timestamps:
-            return self._seek([audio], sample_rate)[0].ids
-        if self._ex:
-            return self.batch_detailed([audio], sample_rate)[0].ids
-        if self.beam_size > 1:
-            return self.model.transcribe_ids_beam([audio], sample_rate, self.beam_size)[0][0]
-        return self.model.transcribe_ids(audio, sample_rate)
-
-    def ids_batch(self, audios, sample_rate: int) -> List[List[int]]:
-        if self.timestamps:
-            return [c.ids for c in self._seek(audios, sample_rate)]
-        if self._ex:
-            return [d.ids for d in self.batch_detailed(audios, sample_rate)]
-        if self.beam_size > 1:
-            return self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)[0]
-        return self.model.transcribe_ids_batch(audios, sample_rate)
-
-    def batch_scored(self, audios, sample_rate: int) -> List[Tuple[Optional[str], float]]:
-        """The texts of a chunk of segments with their confidence: the average log-probability per emitted token of the chosen
-        hypothesis (0 is certain).  One native call, beam search of the configured width (width 1: the greedy ids, scored)."""
-        if self.timestamps:
-            return [(self._joined(c), c.score) for c in self._seek(audios, sample_rate)]
-        if self._ex:
-            return [(d.text, d.avg_logprob) for d in self.batch_detailed(audios, sample_rate)]
-        ids, scores = self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)
-        return [(self._text(i), s) for i, s in zip(ids, scores)]
-
-    def batch_detailed(self, audios, sample_rate: int) -> List["SttDetail"]:
-        """A chunk of segments from one native call (``transcribe_ids_ex``) with everything it reports: per clip the text and ids
-        with silent windows left out, the language the prefix carried and its probability, the largest no-speech probability of its
-        windows and how many windows the silence rule dropped."""
+    def _run(self, audios, sample_rate: int, scored: bool = False, detailed: bool = False, single: bool = False) -> List[SttDetail]:
+        """The one place where the configuration picks the native call; the public methods are projections of what it returns.
+        ``timestamps``: the seek call, whatever is asked.  ``_ex``, or every field asked for (``detailed``): ``transcribe_ids_ex``.
+        Else a width above 1, or a score asked for (``scored``): the beam call (width 1: the greedy ids, scored).  Else greedy:
+        the single-clip call for ``single`` (``audios`` is that clip alone), the batched call otherwise."""
         from .validation import window_is_silent
         if self.timestamps:
             out = []
@@ -886,6 +862,12 @@ class WhisperTranscriber:
                 out.append(SttDetail(self._joined(c), c.ids, c.score, self.cfg.language_code(c.language) or str(c.language), c.language_prob,
                                      max(ns) if ns else float("nan"), dropped))
             return out
+        if not (self._ex or detailed):
+            if self.beam_size > 1 or scored:
+                ids, scores = self.model.transcribe_ids_beam(audios, sample_rate, self.beam_size)
+                return [SttDetail(self._text(i), i, s) for i, s in zip(ids, scores)]
+            ids = [self.model.transcribe_ids(audios[0], sample_rate)] if single else self.model.transcribe_ids_batch(audios, sample_rate)
+            return [SttDetail(self._text(i), i) for i in ids]
         clips = self.model.transcribe_ids_ex(audios, sample_rate, self.beam_size, "auto" if self.auto else None)
         out = []
         for c in clips:
@@ -909,17 +891,30 @@ class WhisperTranscriber:
             return self.tokenizer.decode(ids, skip_special_tokens=True).strip()
         return " ".join(f"<{i}>" for i in ids)
 
+    def ids(self, audio, sample_rate: int) -> List[int]:
+        return self._run([audio], sample_rate, single=True)[0].ids
+
+    def ids_batch(self, audios, sample_rate: int) -> List[List[int]]:
+        return [d.ids for d in self._run(audios, sample_rate)]
+
+    def batch_scored(self, audios, sample_rate: int) -> List[Tuple[Optional[str], float]]:
+        """The texts of a chunk of segments with their confidence: the average log-probability per emitted token of the chosen
+        hypothesis (0 is certain).  One native call, beam search of the configured width (width 1: the greedy ids, scored)."""
+        return [(d.text, d.avg_logprob) for d in self._run(audios, sample_rate, scored=True)]
+
+    def batch_detailed(self, audios, sample_rate: int) -> List[SttDetail]:
+        """A chunk of segments from one native call (``transcribe_ids_ex``) with everything it reports: per clip the text and ids
+        with silent windows left out, the language the prefix carried and its probability, the largest no-speech probability of its
+        windows and how many windows the silence rule dropped."""
+        return self._run(audios, sample_rate, detailed=True)
+
     def __call__(self, audio, sample_rate: int) -> Optional[str]:
-        if self.timestamps:
-            return self._joined(self._seek([audio], sample_rate)[0])
-        return self._text(self.ids(audio, sample_rate))
+        return self._run([audio], sample_rate, single=True)[0].text
 
     def batch(self, audios, sample_rate: int) -> List[Optional[str]]:
         """The texts of a chunk of segments from one native call (the provider's ``_chunk_texts``): per clip what ``__call__``
-        returns for it."""
-        if self.timestamps:
-            return [self._joined(c) for c in self._seek(audios, sample_rate)]
-        return [self._text(ids) for ids in self.ids_batch(audios, sample_rate)]
+        returns for it (in timestamp mode: its segments' texts joined)."""
+        return [d.text for d in self._run(audios, sample_rate)]
 
     def close(self) -> None:
         self.model.close()

@@ -163,6 +163,33 @@ def test_existing_paths_are_what_they_are_without_timestamps(ctx, sets):
         plain.close()
 
 
+def test_timestamps_on_a_handle_without_languages(ctx, sets):
+    """A handle with timestamp ids and no language ids: the seek path without a probe and the plain beam call return the bits of the
+    handle with languages; detection and the silence rule are refused, and the handle answers afterwards."""
+    bare = S.NativeSTT(ctx, dataclasses.replace(CFG, languages={}), {k: v.cuda() for k, v in SC.state_b(CFG).items()})
+
+    def no_probe(c):
+        """The clip with its windows' no-speech probabilities - all NaN, which never compares equal - set aside."""
+        assert c.windows and all(np.isnan(w.no_speech_prob) for w in c.windows)
+        return dataclasses.replace(c, windows=[dataclasses.replace(w, no_speech_prob=0.0) for w in c.windows])
+    try:
+        nat = sets["B"][0]
+        clips = ragged()[:3]
+        kw = dict(max_initial_timestamp_index=25, no_speech=False)
+        for B in (1, 5):
+            got, want = bare.transcribe_ids_seek(clips, SR_IN, B, **kw), nat.transcribe_ids_seek(clips, SR_IN, B, **kw)
+            assert [no_probe(c) for c in got] == [no_probe(c) for c in want]
+            assert all(c.language == CFG.prefix[1] and c.language_prob == 1.0 for c in got)
+            with pytest.raises(ValueError):
+                bare.transcribe_ids_seek(clips, SR_IN, B, "auto", **kw)
+            with pytest.raises(ValueError):
+                bare.transcribe_ids_seek(clips, SR_IN, B, no_speech_threshold=0.6, **kw)
+            assert [no_probe(c) for c in bare.transcribe_ids_seek(clips, SR_IN, B, **kw)] == [no_probe(c) for c in got]
+            assert bare.transcribe_ids_beam(clips, SR_IN, B) == nat.transcribe_ids_beam(clips, SR_IN, B)
+    finally:
+        bare.close()
+
+
 def test_whisper_tiny_dimensions(ctx):
     """51865 ids of which 1501 are timestamps, 30-s windows: a 31-s clip (two rounds) and a 4-s clip at width 1.  A clip is held to
     the reference - ids, segments, offsets, every window's score within 4 E - where the reference's margin meets the constant; on the
