@@ -245,6 +245,34 @@ RT_API int rt_debug_gemm_epi(rt_ctx* ctx, const void* d_a, int32_t a_form, int64
                              int32_t rows_out, int32_t rows_in, const void* d_w_bf16, int32_t N, const rt_debug_epi* e, const void* d_w2_bf16,
                              const rt_debug_epi* e2, int32_t pair_mode);
 
+/* ------------------------------------------------------------------ the conditioning front-end's own kernels (encoder.hip;
+ * tests/test_encoder_kernels_gpu.py).  Each hook checks its pointers, calls the production launch_* function (whose dispatch and
+ * refusals are under test too), synchronises the stream once and returns the status.  All pointers are HBM unless named h_*.
+ *
+ * launch_enc_conv0: pcm [T] -> x [T][C] f32 = bias[c] + sum_k w[c][k] * pcm[t - (K - 1) + k] (zeros in front of the clip; K = the number
+ *   of taps), hi / lo [T][C] = the bf16 operand planes of ELU(x).  C must divide 256.  T = 0 launches nothing.
+ * launch_rvq: the split residual vector quantiser.  sem, aco [T][D]; h_cbT: HOST array of Q device pointers to the TRANSPOSED
+ *   codebooks [D][K] (K entries, K <= 4096; D <= 4096; Q >= 1) -> codes [T][Q]: level 0 quantises sem, levels 1 .. Q - 1 quantise aco
+ *   residually; distances in float32, ascending d, one rounding per operation; the lowest index wins a tie; a row no entry wins
+ *   (a non-finite vector) gets code 0.  d_aco is IN/OUT: on return it holds the residual after the last acoustic level
+ *   (aco - sum of the chosen entries of levels 1 .. Q - 1, subtracted in that order in float32); with Q == 1 it is unchanged.
+ *   T = 0 launches nothing.
+ * launch_stats_pool: x [T][C] -> out [2 C] = (mean over t, sqrt(variance about that mean + 1e-5)), T >= 1.
+ * launch_gemv_f32: y [N] = W [N][K] . x [K] + b (b may be NULL), then max(., 0) when relu is set. */
+RT_API int rt_debug_enc_conv0(rt_ctx* ctx, const float* d_pcm, int64_t T, int32_t C, int32_t K, const float* d_w, const float* d_bias, float* d_x,
+                              void* d_hi, void* d_lo);
+RT_API int rt_debug_rvq(rt_ctx* ctx, const float* d_sem, float* d_aco, int32_t T, int32_t D, int32_t K, int32_t Q, const void* const* h_cbT,
+                        int32_t* d_codes);
+RT_API int rt_debug_stats_pool(rt_ctx* ctx, const float* d_x, int32_t T, int32_t C, float* d_out);
+RT_API int rt_debug_gemv_f32(rt_ctx* ctx, const float* d_W, const float* d_b_or_NULL, const float* d_x, int32_t N, int32_t K, int32_t relu,
+                             float* d_y);
+/* rt_voice_encode (same launches, same codes and speaker vector) that additionally copies the intermediates oracle/encoder.py names
+ * to HOST buffers, each optional: feats, tf [2 F][enc.tf.hidden] (conv features; transformer output), emb [F][enc.tf.hidden] (after
+ * the stride-2 conv), sem, aco [F][enc.vq_dim] (the quantiser's inputs, before it runs), F = *h_n_frames. */
+RT_API int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t n_samples, int32_t max_frames, float* h_feats, float* h_tf,
+                                        float* h_emb, float* h_sem, float* h_aco, int32_t* h_codes, int32_t* h_n_frames,
+                                        float* h_speaker_embed);
+
 /* A/B switches for measurements and tests (process-wide; the defaults are the fast path).  One row per switch, as in the table
  * they are generated from (rho_tts_amd/csrc/knobs.h: defaults, accepted ranges, measurement notes).  A code that no row accepts is
  * refused with RT_ERR_INVALID and changes nothing.  `code`:

@@ -110,6 +110,12 @@ def declare(lib: C.CDLL) -> None:
     lib.rt_debug_code_embed_mean.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp]
     lib.rt_debug_final_conv.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, i64]
     lib.rt_debug_gemm_epi.argtypes = [vp, vp, i32, i64, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(RtDebugEpi), vp, C.POINTER(RtDebugEpi), i32]
+    # the conditioning front-end's kernels and stages (tests/test_encoder_kernels_gpu.py)
+    lib.rt_debug_enc_conv0.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]
+    lib.rt_debug_rvq.argtypes = [vp, vp, vp, i32, i32, i32, i32, pvp, vp]
+    lib.rt_debug_stats_pool.argtypes = [vp, vp, i32, i32, vp]
+    lib.rt_debug_gemv_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    lib.rt_debug_voice_encode_stages.argtypes = [vp, C.POINTER(C.c_float), i64, i32, vp, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32), vp]
 
 
 def _stack(d: TransformerDims) -> StackDims:

@@ -601,6 +601,44 @@ int rt_debug_final_conv(rt_ctx* ctx, const void* d_hi, const void* d_lo, int32_t
     return dbg_finish(ctx, launch_final_conv(ctx, (const bf16_t*)d_hi, (const bf16_t*)d_lo, B, T, C, d_w, d_bias, d_wav, wav_stride));
 }
 
+// ------------------------------------------------------------------ the conditioning front-end's kernels (encoder.hip through its launchers)
+int rt_debug_enc_conv0(rt_ctx* ctx, const float* d_pcm, int64_t T, int32_t C, int32_t K, const float* d_w, const float* d_bias, float* d_x, void* d_hi,
+                       void* d_lo) {
+    if (!ctx || !d_pcm || !d_w || !d_bias || !d_x || !d_hi || !d_lo || T < 0 || K < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_enc_conv0: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_enc_conv0(ctx, d_pcm, T, C, K, d_w, d_bias, d_x, (bf16_t*)d_hi, (bf16_t*)d_lo));
+}
+
+int rt_debug_rvq(rt_ctx* ctx, const float* d_sem, float* d_aco, int32_t T, int32_t D, int32_t K, int32_t Q, const void* const* h_cbT, int32_t* d_codes) {
+    if (!ctx || !d_sem || !d_aco || !d_codes || T < 0 || D < 1 || K < 1 || (Q > 0 && !h_cbT)) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_rvq: bad argument");
+    for (int q = 0; q < Q; ++q)
+        if (!h_cbT[q]) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_rvq: codebook %d is null", q);
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    DbgBufs bufs(ctx);
+    const float** d_cbT = nullptr;
+    if (Q > 0) {
+        RT_HIP(ctx, bufs.alloc(&d_cbT, sizeof(float*) * (size_t)Q));
+        RT_HIP(ctx, hipMemcpy(d_cbT, h_cbT, sizeof(float*) * (size_t)Q, hipMemcpyHostToDevice));
+    }
+    return dbg_finish(ctx, launch_rvq(ctx, d_sem, d_aco, T, D, K, Q, d_cbT, d_codes));
+}
+
+int rt_debug_stats_pool(rt_ctx* ctx, const float* d_x, int32_t T, int32_t C, float* d_out) {
+    if (!ctx || !d_x || !d_out || C < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stats_pool: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_stats_pool(ctx, d_x, T, C, d_out));
+}
+
+int rt_debug_gemv_f32(rt_ctx* ctx, const float* d_W, const float* d_b_or_NULL, const float* d_x, int32_t N, int32_t K, int32_t relu, float* d_y) {
+    if (!ctx || !d_W || !d_x || !d_y || N < 1 || K < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gemv_f32: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    return dbg_finish(ctx, launch_gemv_f32(ctx, d_W, d_b_or_NULL, d_x, N, K, relu, d_y));
+}
+
 // rt_debug_gemm's tiled mode with the whole GemmEpi exposed, and optionally the fused conv pair
 namespace {
 bool dbg_epi(const rt_debug_epi& s, int N, GemmEpi* e) {

@@ -2,7 +2,8 @@
 // and projections of the encoder run on the tiled MFMA GEMM (gemm.hip) in split precision; this file holds what is not a GEMM:
 // the 1-channel input conv, the residual vector quantiser, the statistics pooling and the speaker head's matrix-vector products.
 // Built with -ffp-contract=off: the quantiser's distance has a DEFINED float32 evaluation order (oracle/encoder.py rvq_level)
-// and its argmin is compared bit for bit.
+// and its argmin is compared bit for bit; the first conv's sums are compared bit for bit as well (every kernel here on its own:
+// tests/test_encoder_kernels_gpu.py through the rt_debug_* hooks of debug.hip).
 #include "kernels.h"
 
 namespace {
@@ -144,6 +145,9 @@ __global__ __launch_bounds__(RVQ_T) void k_rvq(const float* __restrict__ sem, fl
                 const int j2 = sh_j[tid][ww];
                 if (d2 < best || (d2 == best && j2 < bj)) { best = d2; bj = j2; }
             }
+            // no entry won (every distance NaN or above 3.4e38: a non-finite vector out of the convolutions): entry 0, so that
+            // neither the residual update below nor an embedding lookup of the code leaves the codebook
+            if (bj < 0 || bj >= K) bj = 0;
             sh_win[tid] = bj;
             if (t0 + tid < T) codes[(int64_t)(t0 + tid) * Q + q] = bj;
         }
@@ -156,7 +160,8 @@ __global__ __launch_bounds__(RVQ_T) void k_rvq(const float* __restrict__ sem, fl
         }
         __syncthreads();
     }
-    for (int i = tid; i < RVQ_FT * D; i += RVQ_T) {
+    if (Q < 2) return;                            // no acoustic level ran: sh_x still holds the semantic vectors, aco stays as it is
+    for (int i = tid; i < RVQ_FT * D; i += RVQ_T) {         // the residual after the last acoustic level
         const int f = i / D, k = i - f * D;
         if (t0 + f < T) aco[(int64_t)(t0 + f) * D + k] = sh_x[i];
     }

@@ -2,6 +2,8 @@
 // the voice prefix through the talker (rt_model_set_voice*: its K/V, computed once per voice and shared by every sequence) and its
 // export / import as a blob (what a data-parallel job broadcasts).  Stands behind the `ref_audio=path` argument the reference hands
 // its model on EVERY call (providers/qwen.py:253-258).
+#include <cmath>
+
 #include "model_internal.h"
 
 using namespace rtm;
@@ -99,11 +101,21 @@ int rt_model_set_voice(rt_model* m, int32_t n_rows, const int32_t* h_text_ids, c
     return set_voice_impl(m, n_rows, h_text_ids, h_codec_ids, h_speaker_row, h_speaker_embed);
 }
 
+// Host buffers (each optional) that additionally receive the intermediates oracle/encoder.py names: rt_debug_voice_encode_stages
+// only - the public entry points pass none.  They are copies out of the buffers the launches use anyway: the launches are the same.
+struct VoiceStages {
+    float* feats = nullptr;            // [Te][He]  conv features, Te = 2 * frames
+    float* tf = nullptr;               // [Te][He]  transformer output
+    float* emb = nullptr;              // [Tf][He]  after the stride-2 conv
+    float* sem = nullptr;              // [Tf][vq_dim] each: the quantiser's inputs
+    float* aco = nullptr;
+};
+
 // ---- conditioning front-end: reference audio -> codes [frames][num_quantizers] + speaker embedding (mutex held by the caller).
 // Channels-last activations; every convolution is an implicit GEMM in split precision (float32 activations fed as hi + lo bf16
 // planes): a k = 2r, stride r conv is the 2-tap GEMM over the clip viewed as [T / r][r * C] rows (causal: taps at t - 1 and t).
 static int voice_encode_impl(rt_model* m, const float* h_pcm, int64_t n_samples, int32_t* h_codes, int32_t max_frames, int32_t* h_n_frames,
-                             float* h_speaker_embed) {
+                             float* h_speaker_embed, const VoiceStages* stages = nullptr) {
     rt_ctx* ctx = m->ctx;
     const rt_model_config& c = m->cfg;
     const rt_encoder_config& e = c.enc;
@@ -114,7 +126,14 @@ static int voice_encode_impl(rt_model* m, const float* h_pcm, int64_t n_samples,
     const int64_t n_frames = std::min<int64_t>(std::min<int64_t>(n_samples / hop, max_frames), e.max_ref_frames);
     if (n_frames < 1) return rt_fail(ctx, RT_ERR_INVALID, "reference audio is shorter than one codec frame (%lld samples per frame)", (long long)hop);
     const int64_t T = n_frames * hop;
+    // a NaN sample makes every distance of its frames NaN, and no codebook entry wins: refuse the clip before anything is launched
+    for (int64_t i = 0; i < T; ++i)
+        if (!std::isfinite(h_pcm[i])) return rt_fail(ctx, RT_ERR_INVALID, "reference audio: sample %lld is not finite", (long long)i);
     pool_release_all(m);
+    auto stage_out = [&](float* h_dst, const float* d_src, size_t n) -> int {
+        if (h_dst) RT_HIP(ctx, hipMemcpyAsync(h_dst, d_src, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        return RT_OK;
+    };
     struct Planes { bf16_t* hi = nullptr; bf16_t* lo = nullptr; };
     auto planes = [&](size_t n, Planes* p) -> int {
         RT_TRY(pool_arr(m, n, &p->hi));
@@ -171,6 +190,7 @@ static int voice_encode_impl(rt_model* m, const float* h_pcm, int64_t n_samples,
         RT_TRY(launch_gemm(ctx, a, W(ci), ep));
     }
     const int Te = (int)Tc;                        // = 2 * n_frames
+    if (stages) RT_TRY(stage_out(stages->feats, feats, (size_t)Te * He));
     // ---- speaker head on the conv features
     float *stats = nullptr, *sh1 = nullptr, *spk = nullptr;
     RT_TRY(pool_arr(m, (size_t)2 * He, &stats));
@@ -194,6 +214,7 @@ static int voice_encode_impl(rt_model* m, const float* h_pcm, int64_t n_samples,
         RT_TRY(alloc_stack_ws(m, e.tf, Te, &w, true));
         RT_TRY(stack_forward(m, m->etf, w, h, Te, d_slot, d_pos, 0, nullptr, hn + 2 * He));
     }
+    if (stages) RT_TRY(stage_out(stages->tf, hn + 2 * He, (size_t)Te * He));
     // ---- stride-2 conv k = 4 with REPLICATE left padding (2 samples = the first row twice), no bias
     RT_HIP(ctx, hipMemcpyAsync(hn, hn + 2 * He, (size_t)He * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipMemcpyAsync(hn + He, hn + 2 * He, (size_t)He * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -217,6 +238,11 @@ static int voice_encode_impl(rt_model* m, const float* h_pcm, int64_t n_samples,
         GemmEpi ep; ep.out_f32 = which ? aco : sem; ep.ldc = e.vq_dim;
         RT_TRY(launch_gemm(ctx, a, PW(m, which ? "enc.vq_aco" : "enc.vq_sem"), ep));
     }
+    if (stages) {
+        RT_TRY(stage_out(stages->emb, emb, (size_t)Tf * He));
+        RT_TRY(stage_out(stages->sem, sem, (size_t)Tf * e.vq_dim));
+        RT_TRY(stage_out(stages->aco, aco, (size_t)Tf * e.vq_dim));          // (before the quantiser turns it into the residual)
+    }
     RT_TRY(launch_rvq(ctx, sem, aco, Tf, e.vq_dim, c.codebook_size, c.num_quantizers, m->d_cbT, d_codes));
     RT_HIP(ctx, hipMemcpyAsync(h_codes, d_codes, (size_t)Tf * c.num_quantizers * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (h_speaker_embed) RT_HIP(ctx, hipMemcpyAsync(h_speaker_embed, spk, (size_t)c.talker.hidden * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -232,6 +258,17 @@ int rt_voice_encode(rt_model* m, const float* h_pcm, int64_t n_samples, int32_t*
     CtxLock g(m->ctx);
     RT_HIP(m->ctx, hipSetDevice(m->ctx->device));
     return voice_encode_impl(m, h_pcm, n_samples, h_codes, max_frames, h_n_frames, h_speaker_embed);
+}
+
+// rt_voice_encode with the intermediates copied out (tests/test_encoder_kernels_gpu.py); declared in rho_tts_amd_debug.h
+int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t n_samples, int32_t max_frames, float* h_feats, float* h_tf, float* h_emb,
+                                 float* h_sem, float* h_aco, int32_t* h_codes, int32_t* h_n_frames, float* h_speaker_embed) {
+    if (!m || !h_pcm || !h_codes || !h_n_frames || max_frames < 1) return rt_fail(m ? m->ctx : nullptr, RT_ERR_INVALID, "rt_debug_voice_encode_stages: null argument");
+    CtxLock g(m->ctx);
+    RT_HIP(m->ctx, hipSetDevice(m->ctx->device));
+    VoiceStages st;
+    st.feats = h_feats; st.tf = h_tf; st.emb = h_emb; st.sem = h_sem; st.aco = h_aco;
+    return voice_encode_impl(m, h_pcm, n_samples, h_codes, max_frames, h_n_frames, h_speaker_embed, &st);
 }
 
 int rt_model_set_voice_pcm(rt_model* m, const float* h_pcm, int64_t n_samples, int32_t n_head_rows, const int32_t* h_text_ids,

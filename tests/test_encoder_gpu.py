@@ -2,7 +2,8 @@
 (oracle/encoder.py - PARITY UNPINNED against qwen-tts, cross-checked against transformers' Mimi in tests/test_oracle_encoder.py).
 
 Codes are integers.  The quantiser kernel evaluates its distances in the oracle's defined float32 order, so given the same
-input vectors its argmin is the oracle's bit for bit (checked directly).  End to end the vectors themselves come out of
+input vectors its argmin is the oracle's bit for bit - checked directly in tests/test_encoder_kernels_gpu.py: the kernel alone on
+the reference's own vectors (ties, near-ties, every instantiation), and on this pipeline's own sem / aco.  End to end the vectors themselves come out of
 MFMA convolutions (float32-faithful split precision, ~1e-6 relative) rather than CPU float32, so a code may differ only where
 two codebook entries are within that noise of each other: the test demands exact equality on the committed clips and, were
 a near-tie ever to flip, that the oracle's two distances differ by < 1e-4 relative (nothing else is accepted)."""
