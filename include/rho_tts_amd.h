@@ -199,7 +199,7 @@ typedef struct rt_model_config {
     int32_t upsample_rates[8];
     int32_t decoder_dim;
     int32_t codec_eos_id;
-    int32_t max_batch;            /* sequences decoded together          */
+    int32_t max_batch;            /* sequences decoded together, 1..128  */
     int32_t max_positions;        /* KV rows per sequence (prompt + frames) */
     int32_t max_codec_frames;     /* frames per sequence one rt_code2wav call may decode */
     int32_t reserved[4];

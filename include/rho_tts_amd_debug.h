@@ -52,9 +52,9 @@ RT_API int rt_debug_attention_planes(rt_ctx* ctx, const float* d_q, int32_t M, i
                                      const int32_t* d_row_slot, const int32_t* d_row_pos, int32_t window, const void* d_k_hi,
                                      const void* d_k_lo, const void* d_v_hi, const void* d_v_lo, int32_t slots, int32_t max_pos,
                                      float* d_out_f32);
-/* The dominant decode kernel on its own (gemm_col.hip k_gemm_col; launched as model_stack.hip launches it: row blocks of <= 64,
+/* The dominant decode kernel on its own (gemm_col.hip k_gemm_col; launched as model_stack.hip launches it: row blocks of <= 64, or ONE launch of 65..128 rows unless rt_debug_tune(3200),
  * production sub-tile split when split = 0).  Row-major operands; the hook converts to / from the fragment-tiled layout.
- *   A [M][K] bf16, W [N][K] bf16 (epi 2: gate rows [0, N/2) then up rows), M <= 64, K % 32 == 0, row_off % 16 == 0
+ *   A [M][K] bf16, W [N][K] bf16 (epi 2: gate rows [0, N/2) then up rows), M <= 128, K % 32 == 0, row_off % 16 == 0
  *   d_rowsq [M][rowsq_n] or NULL: partial sums of squares of the pre-norm row; acc rows are scaled by rsqrt(sum/K + eps)
  *   epi 0 STORE: d_x [M][N] f32 out = scale_row * (A W^T) + bias
  *   epi 1 RESID: d_x [M][N] f32 in/out: x += scale .* (scale_row * (A W^T) + bias); d_next_bf16 [M][N] = bf16(next_norm_w .* x);
@@ -296,7 +296,8 @@ RT_API int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t
  *   1700 + n: queued items (rt_generate with n_items > max_batch) take over finished rows every n frames (n = 1..99, default 4)
  *   1800/1801/1802 narrow-channel (96 / 192) k>1 convs on 128-row tiles / 256-row tiles for long inputs / 256-row tiles always
  *   1900/1901/1902/1903 prompt-prefill GEMMs on the split-K tiled kernel / on k_gemm_mid (automatic, 64 x 64, 128 x 128 tiles)
- *   2000 + n: batches of up to n rows (n = 1..64, default 64) decode on the column-owner path, larger ones on the legacy split-K path
+ *   2000 + n: batches of up to n rows (n = 1..64, default 64) decode on the column-owner path, larger ones of <= 64 rows on the legacy
+ *        split-K path (65..128 rows decode on the column-owner path alone, and only while n stands at 64)
  *   2100/2101 the codec decoder's 96-channel residual units as two launches (k = 7 conv, 1x1 conv) / one fused launch
  *   2200/2201 prompt-prefill attention behind a shared voice prefix on the vector unit / on the matrix cores
  *   2300/2301 decode GEMMs of <= 16 rows on the 32-row / the two-workgroups-per-CU 16-row instantiation
@@ -307,6 +308,7 @@ RT_API int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t
  *   2900/2901 rt_code2wav with / without the residual-stream store of every stage's third unit (no reader) and the waveform copy behind the last conv
  *   3000/3001 the codec decoder's 192-channel residual units as two launches / one fused launch (k = 7 with tap unrolling; 2100 switches both widths off)
  *   3100/3101 predictor passes 2..G-1: layer 0's qkv GEMM launch / its q/k/v row copied from the per-code table built by rt_model_finalize
+ *   3200/3201 generations on 65..128 rows: two 64-row decode GEMM launches per weight matrix / one 128-row launch (same bits)
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
 RT_API int rt_debug_tune(int32_t code, int32_t arg);
@@ -318,7 +320,8 @@ RT_API int rt_bench_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_
                            int64_t* stamps8);
 /* iters back-to-back launches of the decode step's fused attention: M rows at position prefix_len + own_len - 1, the first
  * prefix_len positions read from a shared prefix slot (shared = 1) or from each row's own slot (0), cycling through `layers`
- * cache regions; zeros as operands. */
+ * cache regions; zeros as operands.  M <= 128; above 64 rows the launch is frame-indexed as a decode step's is, and shared | 2
+ * runs the same rows as blocks of 64. */
 RT_API int rt_bench_attention_fused(rt_ctx* ctx, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t prefix_len, int32_t own_len,
                                     int32_t shared, int32_t layers, int32_t iters, double* avg_us);
 RT_API int rt_bench_gemm_skinny(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t split_k, int32_t n_mats, int32_t iters,

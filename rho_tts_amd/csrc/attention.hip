@@ -307,7 +307,10 @@ int attention_any(rt_ctx* ctx, const float* q, int M, int heads, int kv_heads, i
     // (decode steps only - the fused form, or frame-indexed rows: a PROMPT row must be attended with the same wave split,
     //  i.e. the same float32 merge order, whether it is prefilled alone or among 400 rows - a text's audio may not depend on
     //  what it was batched with)
-    const bool wide = (FUSED || f0.frame_ptr) && M * kv_heads <= 512 && kv.max_pos > 64 && (window <= 0 || window > 256);
+    // (frame-indexed launches of 65..128 rows - a decode step on a wide batch - keep the 16-wave split whatever M * kv_heads comes
+    //  to: a row must get the split, i.e. the float32 merge order, it gets alone.  Launches of <= 64 rows are the ones they were.)
+    const bool rows_ok = M * kv_heads <= 512 || (f0.frame_ptr && M > 64 && kv_heads <= 512);
+    const bool wide = (FUSED || f0.frame_ptr) && rows_ok && kv.max_pos > 64 && (window <= 0 || window > 256);
 #define RT_ATT(DD)                                                                                                                   \
     return wide ? dispatch_rep<DD, FUSED, 16>(ctx, rep, grid, q, heads, kv_heads, row_slot, row_pos, pos_add, window, kc, vc, kv.max_pos, out, f) \
                 : dispatch_rep<DD, FUSED, 4>(ctx, rep, grid, q, heads, kv_heads, row_slot, row_pos, pos_add, window, kc, vc, kv.max_pos, out, f)

@@ -171,12 +171,12 @@ int rt_debug_attention_planes(rt_ctx* ctx, const float* d_q, int32_t M, int32_t 
 }
 
 // The column-owner decode GEMM (k_gemm_col) on its own, launched exactly as model_stack.hip's col_gemm launches it (row blocks of
-// 64 / 32, the production sub-tile split unless one is forced).  Row-major operands at the ABI; the hook tiles / un-tiles.
+// 128 / 64 / 32, the production sub-tile split unless one is forced).  Row-major operands at the ABI; the hook tiles / un-tiles.
 int rt_debug_gemm_col(rt_ctx* ctx, const void* d_a_bf16, int32_t M, int32_t K, const void* d_w_bf16, int32_t N, int32_t epi, int32_t split,
                       int32_t row_off, int32_t nt, const float* d_rowsq, int32_t rowsq_n, float eps, const float* d_bias, const float* d_scale,
                       float* d_x, const float* d_next_norm_w, void* d_next_bf16, float* d_rowsq_out, void* d_act_bf16) {
-    if (!ctx || !d_a_bf16 || !d_w_bf16 || M < 1 || M > 64 || K < 32 || K % 32 || N < 1 || row_off < 0 || row_off % 16)
-        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gemm_col: bad argument (1 <= M <= 64, K %% 32 == 0, row_off %% 16 == 0)");
+    if (!ctx || !d_a_bf16 || !d_w_bf16 || M < 1 || M > 128 || K < 32 || K % 32 || N < 1 || row_off < 0 || row_off % 16)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gemm_col: bad argument (1 <= M <= 128, K %% 32 == 0, row_off %% 16 == 0)");
     if (epi < COL_STORE || epi > COL_SILU) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gemm_col: epi %d", epi);
     if ((epi != COL_SILU && !d_x) || (epi == COL_SILU && (!d_act_bf16 || N % 32)) || (epi == COL_RESID && !d_rowsq_out))
         return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_gemm_col: missing output for epilogue %d", epi);
@@ -230,7 +230,7 @@ int rt_debug_gemm_col(rt_ctx* ctx, const void* d_a_bf16, int32_t M, int32_t K, c
         DBG_HIP(hipMemsetAsync(act_t, 0, (size_t)rows * No * 2, ctx->stream));
         c.out_bf16 = act_t;
     }
-    const int blk = g_col_rows64 ? 64 : 32;
+    const int blk = (M > 64 && g_col_rows128) ? 128 : (g_col_rows64 ? 64 : 32);   // (65..128 rows: what a generation that wide launches)
     for (int r0 = 0; r0 < M && !rc; r0 += blk) {                 // model_stack.hip col_gemm
         ColArgs a = c;
         a.M = std::min(blk, M - r0);
@@ -741,7 +741,7 @@ int rt_bench_gemm_skinny(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t s
 // Back-to-back launches of the column-owner GEMM over n_mats weight matrices (> 512 MB in total => HBM-cold).
 int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_norm, int32_t epi, int32_t n_mats, int32_t iters,
                       double* avg_us, int64_t* stamps8) {
-    if (!ctx || !avg_us || M < 1 || M > 64 || N < 64 || K < 16 || K % 16 || n_mats < 1 || iters < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_bench_gemm_col: bad argument");
+    if (!ctx || !avg_us || M < 1 || M > 128 || N < 64 || K < 16 || K % 16 || n_mats < 1 || iters < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_bench_gemm_col: bad argument");
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pb = packed_bytes(N, K);
@@ -750,16 +750,17 @@ int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_no
     float *out = nullptr, *rowsq = nullptr, *rowsq_out = nullptr, *normw = nullptr;
     bf16_t* act = nullptr;
     RT_HIP(ctx, hipMalloc((void**)&wbuf, pb * n_mats));
-    RT_HIP(ctx, hipMalloc(&a, (size_t)64 * K * 4));
-    RT_HIP(ctx, hipMalloc((void**)&out, (size_t)64 * N * 4));
-    RT_HIP(ctx, hipMalloc((void**)&act, (size_t)64 * N * 2));
-    RT_HIP(ctx, hipMalloc((void**)&rowsq, (size_t)64 * 512 * 4));
-    RT_HIP(ctx, hipMalloc((void**)&rowsq_out, (size_t)64 * (N / 4 + 4) * 4));
+    const size_t R = M > 64 ? 128 : 64;      // rows the buffers hold (whole 32-row blocks of the tiled ones)
+    RT_HIP(ctx, hipMalloc(&a, R * K * 4));
+    RT_HIP(ctx, hipMalloc((void**)&out, R * N * 4));
+    RT_HIP(ctx, hipMalloc((void**)&act, R * N * 2));
+    RT_HIP(ctx, hipMalloc((void**)&rowsq, R * 512 * 4));
+    RT_HIP(ctx, hipMalloc((void**)&rowsq_out, R * (N / 4 + 4) * 4));
     RT_HIP(ctx, hipMalloc((void**)&normw, (size_t)std::max(K, N) * 4));
     RT_HIP(ctx, hipMemsetAsync(wbuf, 0x3c, pb * n_mats, ctx->stream));
-    RT_HIP(ctx, hipMemsetAsync(a, 0x3c, (size_t)64 * K * 4, ctx->stream));
-    RT_HIP(ctx, hipMemsetAsync(out, 0, (size_t)64 * N * 4, ctx->stream));
-    RT_HIP(ctx, hipMemsetAsync(rowsq, 0x3c, (size_t)64 * 512 * 4, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(a, 0x3c, R * K * 4, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(out, 0, R * N * 4, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(rowsq, 0x3c, R * 512 * 4, ctx->stream));
     RT_HIP(ctx, hipMemsetAsync(normw, 0x3c, (size_t)std::max(K, N) * 4, ctx->stream));
     PackedW pw;
     pw.N = N; pw.K = K; pw.Np = (N + 31) / 32 * 32; pw.Kp = K; pw.Np16 = (N + 15) / 16 * 16;
@@ -774,11 +775,19 @@ int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_no
     RT_HIP(ctx, hipEventCreate(&e0));
     RT_HIP(ctx, hipEventCreate(&e1));
     int rc = RT_OK;
-    for (int i = 0; i < n_mats && !rc; ++i) { pw.data16 = wbuf + (pb / 2) * i; rc = launch_gemm_col(ctx, c, pw); }
+    // 65..128 rows: one 128-row launch, or (rt_debug_tune 3200) the two 64-row launches it replaces - the A/B of g_col_rows128
+    auto launch = [&](const ColArgs& c1) {
+        if (c1.M <= 64 || g_col_rows128) return launch_gemm_col(ctx, c1, pw);
+        ColArgs lo = c1, hi = c1;
+        lo.M = 64; hi.M = c1.M - 64; hi.row_off = 64;
+        const int r = launch_gemm_col(ctx, lo, pw);
+        return r ? r : launch_gemm_col(ctx, hi, pw);
+    };
+    for (int i = 0; i < n_mats && !rc; ++i) { pw.data16 = wbuf + (pb / 2) * i; rc = launch(c); }
     RT_HIP(ctx, hipEventRecord(e0, ctx->stream));
     for (int i = 0; i < iters && !rc; ++i) {
         pw.data16 = wbuf + (pb / 2) * (i % n_mats);
-        rc = launch_gemm_col(ctx, c, pw);
+        rc = launch(c);
     }
     RT_HIP(ctx, hipEventRecord(e1, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -887,7 +896,7 @@ int rt_bench_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_t V, co
 // (uniform softmax): the timing does not depend on the values.
 int rt_bench_attention_fused(rt_ctx* ctx, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t prefix_len, int32_t own_len,
                              int32_t shared, int32_t layers, int32_t iters, double* avg_us) {
-    if (!ctx || !avg_us || M < 1 || M > 64 || heads < 1 || kv_heads < 1 || heads % kv_heads || prefix_len < 0 || own_len < 1 || layers < 1 || iters < 1)
+    if (!ctx || !avg_us || M < 1 || M > 128 || heads < 1 || kv_heads < 1 || heads % kv_heads || prefix_len < 0 || own_len < 1 || layers < 1 || iters < 1)
         return rt_fail(ctx, RT_ERR_INVALID, "rt_bench_attention_fused: bad argument");
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
@@ -938,15 +947,25 @@ int rt_bench_attention_fused(rt_ctx* ctx, int32_t M, int32_t heads, int32_t kv_h
     for (int i = 0; i < layers && rc == RT_OK; ++i)          // warm-up: one pass over every layer
         rc = launch_attention_fused(ctx, qkv, M, heads, kv_heads, head_dim, nw, nw, 1e-6f, cosT, sinT, slot, pos, 0, 0, kv, i, out, nullptr, 1, -1);
     RT_HIP(ctx, hipEventRecord(e0, ctx->stream));
+    // more than 64 rows: frame-indexed, as a decode step on a wide batch launches it (one launch that keeps the 16-wave split);
+    // shared & 2: the same rows as blocks of 64 (the alternative that was weighed against it)
+    int32_t* frame = nullptr;
+    if (M > 64) {
+        RT_HIP(ctx, hipMalloc((void**)&frame, 4));
+        RT_HIP(ctx, hipMemsetAsync(frame, 0, 4, ctx->stream));
+    }
+    const int blk = (M > 64 && (shared & 2)) ? 64 : M;
     for (int i = 0; i < iters && rc == RT_OK; ++i)
-        rc = launch_attention_fused(ctx, qkv, M, heads, kv_heads, head_dim, nw, nw, 1e-6f, cosT, sinT, slot, pos, 0, 0, kv, i % layers, out, nullptr, 1, -1);
+        for (int r0 = 0; r0 < M && rc == RT_OK; r0 += blk)
+            rc = launch_attention_fused(ctx, qkv + (size_t)r0 * width, std::min(blk, M - r0), heads, kv_heads, head_dim, nw, nw, 1e-6f, cosT, sinT, slot + r0, pos + r0, 0,
+                                        0, kv, i % layers, out + (size_t)r0 * heads * head_dim, frame, 1, -1);
     RT_HIP(ctx, hipEventRecord(e1, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     float ms = 0;
     RT_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     *avg_us = (double)ms * 1e3 / iters;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    for (void* p : {(void*)kv.k, (void*)kv.v, (void*)qkv, (void*)cs, (void*)nw, (void*)pos, (void*)slot, (void*)out, (void*)tiles}) if (p) (void)hipFree(p);
+    for (void* p : {(void*)kv.k, (void*)kv.v, (void*)qkv, (void*)cs, (void*)nw, (void*)pos, (void*)slot, (void*)out, (void*)tiles, (void*)frame}) if (p) (void)hipFree(p);
     return rc;
 }
 

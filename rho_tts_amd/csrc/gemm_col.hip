@@ -1,4 +1,4 @@
-// Column-owner decode GEMM for gfx950 (M <= 32 rows per launch): one workgroup owns a 16-column tile of the output for the
+// Column-owner decode GEMM for gfx950 (M <= 128 rows per launch): one workgroup owns a 16-column tile of the output for the
 // WHOLE K, its 8 waves split K, every wave streams its own contiguous run of pre-tiled weights from HBM with
 // non-temporal 1-KiB loads (each weight byte is read exactly once, by exactly one wave), partial accumulators are
 // combined through LDS in a fixed order (deterministic, no float atomics, no partial slabs in HBM), and because a
@@ -47,6 +47,12 @@ __device__ __forceinline__ f4acc_t mfma16(s8_t a, s8_t b, f4acc_t c) {
 // 1.5x the CUs on the 1.7B talker, and one-per-CU would run them as a full round plus a half-empty one.
 // MT = 16-row sub-blocks per launch: 2 (M <= 32, every single-position decode pass) or 4 (M <= 64: the predictor's first
 // pass carries two positions per sequence; one 64-row launch streams the weights once instead of twice).
+// MT = 8 (M <= 128: decode on 65..128 rows, g_col_rows128) streams a weight matrix once for all 128 rows.  Same 8-wave K split,
+// same k order inside a wave and the same ww = 0..7 order in the combine, so a row gets the bits an MT = 2 / 4 launch gives it.
+// Its partials are combined in TWO rounds of four sub-blocks through the same 32 KiB of LDS (red[8][8][4][64] would be 64 KiB
+// plus sh_inv - more than a static array may take): one barrier pair more per accumulator set, no dynamic-LDS attribute to set
+// on twelve instantiations, and the kernel is bound by its A operand (every workgroup reads all 128 rows), not by LDS.
+// Shorter chunks (C = 2, gate/up 1) keep two chunks in flight inside 256 VGPRs.
 // NPRE = super-chunks requested up front WITHOUT a branch around them (1 or 2, chosen by the launcher from K; indices are
 // clamped so every request is a valid address).  Branch-free matters: the row-scale partials are requested just before the
 // chunks, and only when the number of younger loads is a compile-time constant can the compiler wait for them with a
@@ -60,6 +66,7 @@ __device__ __forceinline__ f4acc_t mfma16(s8_t a, s8_t b, f4acc_t c) {
 // workgroups, 15.8 for 512, 9.6 for 256 - tools/bench_gemm_col_sweep.py), and the extra columns reuse the A fragments already
 // in registers.  Every column is still summed by the same wave split in the same order: the bits do not change.
 constexpr int col_chunk(int epi, int mt, bool x) {                         // k-tiles (32 deep) per super-chunk
+    if (mt == 8) return epi == COL_SILU ? 1 : 2;
     return epi == COL_SILU ? (x ? (mt == 4 ? 2 : 4) : 2) : ((mt == 4 || mt == 1) ? 4 : 8);
 }
 // NORM = the launch applies an RMSNorm row scale (g.post_scale), as a compile-time property: its partials are then requested
@@ -67,7 +74,9 @@ constexpr int col_chunk(int epi, int mt, bool x) {                         // k-
 template <int EPI, int MT, int NPRE, bool X = false, bool NORM = false>
 __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && !X) ? 4 : 2) void k_gemm_col(ColArgs g) {
     static_assert(!X || (EPI == COL_SILU && MT >= 2), "the extra half pair exists for gate/up only");
-    __shared__ float red[WAVES][MT][4][64];  // 16 KiB per 32 rows: one 16x16 accumulator tile per sub-block and wave
+    constexpr int RMT = MT > 4 ? 4 : MT;     // sub-blocks per combine round (MT = 8: two rounds through the same 32 KiB)
+    constexpr int ROUNDS = MT / RMT;
+    __shared__ float red[WAVES][RMT][4][64]; // 16 KiB per 32 rows: one 16x16 accumulator tile per sub-block and wave
     __shared__ float sh_inv[16 * MT];        // RMSNorm row scales
     constexpr int NB = (EPI == COL_SILU) ? (X ? 3 : 2) : 1;
     constexpr int C = col_chunk(EPI, MT, X);
@@ -221,21 +230,24 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
     float val[NB][PASSES];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
-        if (b > 0) __syncthreads();
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
+        for (int rd = 0; rd < ROUNDS; ++rd) {
+            if (b > 0 || rd > 0) __syncthreads();
 #pragma unroll
-            for (int i = 0; i < 4; ++i) red[w][mt][i][lane] = acc[b][mt][i];
-        __syncthreads();
+            for (int mt = 0; mt < RMT; ++mt)
 #pragma unroll
-        for (int ps = 0; ps < PASSES; ++ps) {
-            float s = 0.f;
-            const int smt = 2 * ps + (tid >> 8);               // (MT = 1: the upper half of the workgroup has no sub-block)
-            if (smt < MT) {
+                for (int i = 0; i < 4; ++i) red[w][mt][i][lane] = acc[b][rd * RMT + mt][i];
+            __syncthreads();
 #pragma unroll
-                for (int ww = 0; ww < WAVES; ++ww) s += red[ww][smt < MT ? smt : 0][e_i][e_l];
+            for (int pp = 0; pp < (RMT + 1) / 2; ++pp) {
+                float s = 0.f;
+                const int smt = 2 * pp + (tid >> 8);           // (MT = 1: the upper half of the workgroup has no sub-block)
+                if (smt < RMT) {
+#pragma unroll
+                    for (int ww = 0; ww < WAVES; ++ww) s += red[ww][smt < RMT ? smt : 0][e_i][e_l];
+                }
+                val[b][rd * (RMT / 2) + pp] = s;
             }
-            val[b][ps] = s;
         }
     }
     if (g.stamps && blockIdx.x == 0 && tid == 0) g.stamps[4] = wall_clock64();
@@ -311,6 +323,19 @@ void launch_npre(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEve
 
 int dispatch_epi(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     const bool wide = g.M > 32, narrow = g.M <= 16 && g_col_rows16;
+    if (g.M > 64) {     // 65..128 rows: one launch streams the weights once for all of them
+        switch (g.epi) {
+            case COL_STORE: launch_npre<COL_STORE, 8>(ctx, g, grid, e0, e1); break;
+            case COL_RESID: launch_npre<COL_RESID, 8>(ctx, g, grid, e0, e1); break;
+            case COL_SILU:
+                if (g.x_tile0 > 0) launch_npre<COL_SILU, 8, true>(ctx, g, grid, e0, e1);
+                else launch_npre<COL_SILU, 8>(ctx, g, grid, e0, e1);
+                break;
+            default: return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: bad epilogue %d", g.epi);
+        }
+        RT_HIP(ctx, hipGetLastError());
+        return RT_OK;
+    }
     switch (g.epi) {
         case COL_STORE: wide ? launch_npre<COL_STORE, 4>(ctx, g, grid, e0, e1) : narrow ? launch_npre<COL_STORE, 1>(ctx, g, grid, e0, e1) : launch_npre<COL_STORE, 2>(ctx, g, grid, e0, e1); break;
         case COL_RESID: wide ? launch_npre<COL_RESID, 4>(ctx, g, grid, e0, e1) : narrow ? launch_npre<COL_RESID, 1>(ctx, g, grid, e0, e1) : launch_npre<COL_RESID, 2>(ctx, g, grid, e0, e1); break;
@@ -345,7 +370,7 @@ int col_split_for(int N, int n_cu) {
 }
 
 int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t ev_start, hipEvent_t ev_stop) {
-    if (a.M < 1 || a.M > 64) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: M=%d outside 1..64 (callers split larger row blocks)", a.M);
+    if (a.M < 1 || a.M > 128) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: M=%d outside 1..128 (callers split larger row blocks)", a.M);
     if (w.K != a.K || w.K % 32) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: K mismatch (%d vs %d) or not a multiple of 32", w.K, a.K);
     if (!w.data16) return rt_fail(ctx, RT_ERR_STATE, "gemm_col: weight has no 16-column decode copy");
     ColArgs g = a;

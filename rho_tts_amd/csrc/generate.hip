@@ -82,6 +82,7 @@ void gen_release(rt_model* m) {
     for (auto& ln : m->run->lanes) if (ln.stream && ln.stream != m->ctx->stream) (void)hipStreamSynchronize(ln.stream);
     delete m->run;
     m->run = nullptr;
+    m->rows128 = false;
     g_runs_in_flight.fetch_sub(1);
     for (auto& b : m->pool) if (b.tag == 1) { b.used = false; b.tag = 0; }
 }
@@ -198,7 +199,13 @@ int rt_gen_run::init(const rt_generate_args* a) {
     RT_HIP(ctx, hipMemcpyAsync(d_seed, &A.seed, 8, hipMemcpyHostToDevice, ctx->stream));
     codes_fs = (int64_t)B * G;
     // Column path (2B <= 64): xt = un-normalised talker residual stream + rowsq_t; legacy path: hn = final-norm output
-    col = g_decode_col && B <= g_col_max_rows && H % 32 == 0 && Hp % 32 == 0 && c.talker.inter % 32 == 0 && c.predictor.inter % 32 == 0;
+    // 65..128 rows: the column path only, and only while g_col_max_rows stands at its full 64 (a lowered limit asks for the legacy
+    // path, which does not exist above 64 rows)
+    col = g_decode_col && (B <= g_col_max_rows || (B > 64 && g_col_max_rows == 64)) && H % 32 == 0 && Hp % 32 == 0 && c.talker.inter % 32 == 0 &&
+          c.predictor.inter % 32 == 0;
+    if (B > 64 && !col)
+        return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_generate: %d rows (> 64) need the column decode path (rt_debug_tune 101 and 2064, widths %% 32)", B);
+    m->rows128 = B > 64 && g_col_rows128;
     NTt = H / 16 * col_split_for(H, ctx->n_cu); NTp = Hp / 16 * col_split_for(Hp, ctx->n_cu);   // rowsq partials per row
     head = &PW(m, "talker.codec_head");
     float* x_all = x;
@@ -231,7 +238,7 @@ int rt_gen_run::init(const rt_generate_args* a) {
         RT_TRY(pool_arr(m, (size_t)n * H, &ln.hn));
         RT_TRY(pool_arr(m, (size_t)n2 * Hp, &ln.xp));
         RT_TRY(pool_arr(m, (size_t)n2 * Hp, &ln.hn_p));
-        RT_TRY(pool_arr(m, (size_t)64 * 32768, &ln.logits));
+        RT_TRY(pool_arr(m, (size_t)std::max(64, n) * 32768, &ln.logits));     // [rows][<= 32768] logits (legacy path: the GEMM's slabs)
         RT_TRY(pool_arr(m, n2, &ln.d_slot_b));
         RT_TRY(pool_arr(m, n, &ln.d_pos_b));
         RT_TRY(pool_arr(m, n2, &ln.d_pos_p2));

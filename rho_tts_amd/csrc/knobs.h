@@ -33,7 +33,7 @@
         "rows: 2 -> 487 / 445, 3 -> 489 / 445, 4 -> 491 / 447, 6 -> 485 / 445, 8 -> 477 / 428, 12 -> 475 / 434 audio-s/s (a hand-over costs ~1.4 ms, a waiting row 0.13 ms per frame)") \
     X(1800, g_conv_tall, 1, 0, 2, "k>1 convs of the 96- / 192-channel stages: 0 128-row tiles, 1 256-row tiles for long inputs, 2 always") \
     X(1900, g_prefill_mid, 1, 0, 3, "prompt prefills of 65..1024 rows: 0 split-K tiled kernel, 1 k_gemm_mid (no split-K slabs), 2 / 3 force its 64 / 128 tiles") \
-    X(2000, g_col_max_rows, 64, 1, 64, "batches up to this many rows decode on the column-owner path.  Above 32 the talker's GEMMs take 64 rows per launch and the predictor's " \
+    X(2000, g_col_max_rows, 64, 1, 64, "batches of up to 64 rows decode on the column-owner path while they have at most this many rows (65..128 rows always do, and only while this stands at 64).  Above 32 the talker's GEMMs take 64 rows per launch and the predictor's " \
         "two-position first pass runs as two 64-row launches: 715 audio-s/s at batch 64 against 510 at batch 32 (1.7B, bench.py --batch 64) - every weight byte serves twice the rows for " \
         "~1.4x the launch time") \
     X(2100, g_fuse_conv, 1, 0, 1, "1: a 96-channel k>1 conv and the 1x1 conv behind its activation run as one launch (launch_conv_pair); 0 switches the 192-channel pairs off as well") \
@@ -46,7 +46,10 @@
     X(2900, g_c2w_lean, 1, 0, 1, "1: rt_code2wav drops the third unit's unread residual-stream store and the waveform copy (the last conv writes the caller's buffer)") \
     X(3000, g_fuse_conv192, 1, 0, 1, "1: the 192-channel conv pairs fuse as well, weight fragments staged through LDS") \
     X(3100, g_pred_qkv_table, 1, 0, 1, "predictor passes 2..G-1: 1 layer 0's q/k/v row of the drawn code is copied from the table rt_model_finalize builds (by the launch " \
-        "that embeds the code), 0 the layer-0 qkv GEMM launch runs (same bits either way)")
+        "that embeds the code), 0 the layer-0 qkv GEMM launch runs (same bits either way)") \
+    X(3200, g_col_rows128, 1, 0, 1, "generations on 65..128 rows: 1 one 128-row decode GEMM launch per weight matrix (k_gemm_col MT = 8: the weights are streamed once), " \
+        "0 two 64-row launches (same bits either way).  Measured (1.7B, profiles/r18_rows128.txt): bench.py --corpus 512 --batch 128 1014 audio-s/s with 1 against 887 with 0 (five alternating pairs; 824 on 64 rows); " \
+        "per launch at 128 rows qkv 13.7 / 16.3 us, o 12.0 / 14.2, gate/up 20.9 / 27.4, down 27.3 / 29.7 (one launch / two)")
 
 // The one switch set by rt_debug_tune's SECOND argument: applied when the code is 0..2 and the argument lies in lo..hi.
 #define RT_KNOB_ARG(X) \

@@ -47,6 +47,7 @@ void rt_gen_drop(struct rt_model* m);    // ends a generation in flight (defined
 
 struct rt_model {
     rt_gen_run* run = nullptr;         // generation in flight (rt_generate_begin .. rt_generate_end), else null
+    bool rows128 = false;              // the generation in flight decodes on 65..128 rows, one 128-row GEMM launch per matrix (col_gemm)
     int pool_tag = 0;                  // tag of the pool blocks handed out right now (1 while the generation in flight allocates)
     bool prefix_tiles_valid = false;   // kt_prefix / vt_prefix hold the current voice prefix (attention_mfma.hip)
     int64_t last_frames_run = 0, last_rows = 0, last_kept = 0, last_swaps = 0;   // rt_generate_stats

@@ -283,10 +283,10 @@ int rt_model_create(rt_ctx* ctx, const rt_model_config* cfg, rt_model** out_mode
     };
     if (bad_stack(c.talker) || bad_stack(c.predictor) || bad_stack(c.codec_tf))
         return rt_fail(ctx, RT_ERR_INVALID, "rt_model_create: unsupported stack dimensions (hidden/inter %% 16, head_dim in {32,64,128})");
-    if (c.n_groups < 2 || c.n_groups > 32 || c.num_quantizers < 1 || c.num_quantizers > c.n_groups || c.max_batch < 1 || c.max_batch > 64 ||
+    if (c.n_groups < 2 || c.n_groups > 32 || c.num_quantizers < 1 || c.num_quantizers > c.n_groups || c.max_batch < 1 || c.max_batch > 128 ||
         c.n_upsampling < 0 || c.n_upsampling > 4 || c.n_upsample_rates < 1 || c.n_upsample_rates > 8 || c.text_hidden % 16 ||
         c.max_positions < 8 || c.max_codec_frames < 1 || (c.decoder_dim >> c.n_upsample_rates) < 8 || (c.decoder_dim >> c.n_upsample_rates) % 8)
-        return rt_fail(ctx, RT_ERR_INVALID, "rt_model_create: unsupported configuration (n_groups 2..32, max_batch 1..64, channels %% 8)");
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_model_create: unsupported configuration (n_groups 2..32, max_batch 1..128, channels %% 8)");
     if (c.enc.filters > 0) {
         const rt_encoder_config& e = c.enc;
         bool bad = e.n_ratios < 1 || e.n_ratios > 8 || e.filters % 16 || 256 % e.filters || e.kernel < 1 || e.kernel > 15 || e.res_kernel < 1 ||

@@ -174,9 +174,11 @@ int alloc_dec_ws(rt_model* m, const rt_stack_dims& d, int M, DecWs* w) {
     RT_TRY(pool_arr(m, Mp * d.inter, &w->act));
     return RT_OK;
 }
-// Row blocks of up to 64 (one launch for the predictor's two-position first pass at batch 32).
+// Row blocks of up to 64 (one launch for the predictor's two-position first pass at batch 32).  A generation on 65..128 rows
+// takes blocks of 128 (rt_model::rows128: g_col_rows128) - batches of <= 64 rows keep the launches they always had, their
+// 66..128-row first predictor pass included.
 int col_gemm(rt_model* m, const ColArgs& a0, const PackedW& W, bool is_predictor) {
-    const int blk = g_col_rows64 ? 64 : 32;
+    const int blk = (m->rows128 && a0.M > 64) ? 128 : (g_col_rows64 ? 64 : 32);
     for (int r0 = 0; r0 < a0.M; r0 += blk) {
         ColArgs a = a0;
         a.nt = is_predictor ? g_pred_nt.load() : 1;

@@ -47,12 +47,27 @@ class GenerationParams:
         return RtSampling(int(ds), self.predictor_temperature, self.predictor_top_k, self.predictor_top_p, 1.0)
 
 
+# Decode-frame time on R rows relative to a frame on 32 rows.  32 -> 64 is the slope pick_rows always used;
+# 96 and 128 are the frame times measured in profiles/r18_rows128.txt (1.7B shapes, one MI355X), linear in between.
+FRAME_COST = ((32, 1.0), (64, 1.4), (96, 1.835), (128, 2.059))
+
+
+def frame_cost(rows: int) -> float:
+    if rows <= 64:
+        return 1.0 + 0.4 * max(0, rows - 32) / 32.0
+    for (r0, c0), (r1, c1) in zip(FRAME_COST, FRAME_COST[1:]):
+        if rows <= r1:
+            return c0 + (c1 - c0) * (rows - r0) / float(r1 - r0)
+    return FRAME_COST[-1][1]
+
+
 def pick_rows(plan: Sequence[int], max_batch: int) -> int:
     """Decode rows for a work list with estimated lengths ``plan`` on an engine of ``max_batch`` rows.  A frame on 33..64 rows
     costs up to ~1.4x a frame on 32 (measured), and a list-scheduled queue on R rows takes about
     max(longest, sum / R) frames: 32 busy rows with a queue beat 64 half-idle ones only when the lengths are ragged enough - so
     the narrower schedule is taken only when this model puts it clearly (10 %) ahead; n <= max_batch texts of similar length
-    stay one static batch."""
+    stay one static batch.  Above 64 rows the choice is among 32, 64 and the full width, with the measured frame costs
+    (FRAME_COST); a width whose row-frame costs more than a 64-row frame's is never taken."""
     n = len(plan)
     full = min(n, max_batch)
     if full <= 32 or not plan:
@@ -60,8 +75,15 @@ def pick_rows(plan: Sequence[int], max_batch: int) -> int:
 
     def cost(rows: int) -> float:
         frames = max(float(max(plan)), float(sum(plan)) / rows)
-        return frames * (1.0 + 0.4 * max(0, rows - 32) / 32.0)
-    return 32 if cost(32) < 0.9 * cost(full) else full
+        return frames * frame_cost(rows)
+    if full <= 64:
+        return 32 if cost(32) < 0.9 * cost(full) else full
+    widths = [r for r in (full, 64, 32) if frame_cost(r) / r <= frame_cost(64) / 64]
+    best = widths[0]
+    for r in widths[1:]:
+        if cost(r) < 0.9 * cost(best):
+            best = r
+    return best
 
 
 SYNTHETIC_ENV = "RHO_TTS_AMD_SYNTHETIC"
@@ -294,9 +316,9 @@ class Engine:
         wavs: List[Optional[torch.Tensor]] = [None] * n
         rows = self.pick_rows(plan)
         if continuous is None:
-            continuous = self.max_batch <= 64 and (n > self.max_batch or rows < min(n, self.max_batch))
-        if continuous and self.max_batch > 64:
-            raise ValueError(f"continuous batching decodes on at most 64 rows (engine built with max_batch={self.max_batch})")
+            continuous = self.max_batch <= 128 and (n > self.max_batch or rows < min(n, self.max_batch))
+        if continuous and self.max_batch > 128:
+            raise ValueError(f"continuous batching decodes on at most 128 rows (engine built with max_batch={self.max_batch})")
         if continuous and (n > self.max_batch or rows < n):
             order = sorted(range(n), key=lambda i: (-plan[i], i))          # longest first: short items fill the tail of the schedule
             codes = self.generate_codes([texts[i] for i in order], seed, [ids[i] for i in order], cancel_flag, [frames[i] for i in order],

@@ -687,7 +687,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
                     self._close_drift()
                     self._ctx.close()
                     self._ctx = None
-                self._engine = Engine(self.model_path, self._device_ordinal(), max_batch=max(1, min(64, int(self.batch_size))))
+                self._engine = Engine(self.model_path, self._device_ordinal(), max_batch=max(1, min(128, int(self.batch_size))))
                 # the reference refines the limit from the checkpoint's max_position_embeddings (qwen.py:131-139); a checkpoint
                 # without one keeps MAX_MODEL_CHARS.  (The KV allocation - cfg.max_positions - is a separate number.)
                 hf_pos = int(getattr(self._engine.cfg, "hf_max_position_embeddings", 0) or 0)
@@ -789,7 +789,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
     def _cut_batches(self, todo: List[int], work, bs: int) -> List[List[int]]:
         """The engine decodes any number of segments on its ``batch_size`` rows with continuous batching (finished rows are handed
         to the next queued segment, Engine.synthesize): the whole work list goes down in one call instead of being cut here."""
-        if len(todo) > bs and bs <= 64:
+        if len(todo) > bs and bs <= 128:
             return [list(todo)]
         return super()._cut_batches(todo, work, bs)
 

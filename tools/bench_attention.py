@@ -33,3 +33,9 @@ for prefix in (0, 64, 128, 256, 460):
         print(f"{prefix:7d} {own:4d} {a:10.2f} {b:12.2f}", flush=True)
 print("one row (a batch of 1), 460 + 35:", f"{run(1, 16, 8, 128, 460, 35, 1):.2f} us", flush=True)
 print("predictor form, 32 rows x 8 kv heads, 5 layers cycled:", " ".join(f"own {o}: {run(32, 16, 8, 128, 0, o, 0, layers=5):.2f} us" for o in (2, 8, 16)), flush=True)
+# a decode step on a wide batch (frame-indexed rows, 16-wave split kept above 64 rows): one launch against row blocks of 64 (shared | 2)
+for M in (96, 128):
+    one = [run(M, 16, 8, 128, 460, 35, 1) for _ in range(3)]
+    blocks = [run(M, 16, 8, 128, 460, 35, 3) for _ in range(3)]
+    print(f"{M} rows, 460 + 35: one launch {sorted(one)[1]:.2f} us (min {min(one):.2f} max {max(one):.2f})   blocks of 64 {sorted(blocks)[1]:.2f} us "
+          f"(min {min(blocks):.2f} max {max(blocks):.2f})   [64 rows: {run(64, 16, 8, 128, 460, 35, 1):.2f} us]", flush=True)

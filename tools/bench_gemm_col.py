@@ -20,6 +20,26 @@ if len(sys.argv) > 1 and sys.argv[1] == "hot":      # same matrix every launch, 
         ph = " ".join(f"{(st[i + 1] - st[i]) * 0.01:.2f}" for i in range(5))
         print(f"{name:26s} {mb:6.1f} MB  HOT {us.value:7.2f} us [{ph}]", flush=True)
     sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "rows128":  # 128 rows: one MT = 8 launch (3201) against the two 64-row launches it replaces (3200)
+    import statistics
+    for M, N, K, norm, epi, name in [s for s in shapes[:4]]:
+        mb = N * K * 2 / 1e6
+        n_mats = max(2, int(600 / mb) + 1)
+        t = {3201: [], 3200: []}
+        for _ in range(5):                          # alternating pairs
+            for code in (3201, 3200):
+                lib.rt_debug_tune(code, 0)
+                us = C.c_double()
+                rc = lib.rt_bench_gemm_col(ctx.handle, 128, N, K, norm, epi, n_mats, 400, C.byref(us), None)
+                assert rc == 0, rc
+                t[code].append(us.value)
+        lib.rt_debug_tune(3201, 0)
+        us = C.c_double()
+        assert lib.rt_bench_gemm_col(ctx.handle, 64, N, K, norm, epi, n_mats, 400, C.byref(us), None) == 0
+        line = "   ".join(f"{label} {statistics.median(v):7.2f} us (min {min(v):.2f} max {max(v):.2f}) {mb / statistics.median(v):5.2f} TB/s"
+                          for label, v in (("one 128-row launch", t[3201]), ("two 64-row launches", t[3200])))
+        print(f"{name:26s} {mb:6.1f} MB  M=128  {line}   [one 64-row launch {us.value:7.2f} us]", flush=True)
+    sys.exit(0)
 for M, N, K, norm, epi, name in shapes:
     mb = N * K * 2 / 1e6
     n_mats = max(2, int(600 / mb) + 1)
