@@ -435,7 +435,7 @@ RT_API int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int6
  * walk them: every window is decoded WITH timestamp tokens under the step rule (transformers' WhisperTimeStampLogitsProcessor), and
  * the seek rule (_retrieve_segment) closes segments at timestamp pairs, discards an unfinished tail and starts the clip's next
  * window at the last closed pair's timestamp, so a word that straddles a boundary is decoded again whole.  No conditioning on
- * previous text, no temperature fallback.  A round holds one window per unfinished clip; rounds run in groups of
+ * previous text.  Temperature fallback: rt_stt_set_fallback below.  A round holds one window per unfinished clip; rounds run in groups of
  * floor(32 / beam_size) windows as rt_stt_transcribe_beam.  A clip's result is what it gets as the only clip of a call.
  * rt_stt_set_timestamps: timestamp ids [timestamp_begin, timestamp_begin + n_timestamps), n_timestamps = chunk_seconds / 0.02 + 1;
  *   timestamp_begin - 1 is <|notimestamps|>.  Before rt_stt_finalize.  RT_ERR_INVALID: the vocabulary does not hold the ids, the
@@ -488,6 +488,44 @@ typedef struct rt_stt_seek_out {
 RT_API int rt_stt_set_timestamps(rt_stt* s, int32_t timestamp_begin, int32_t n_timestamps);
 RT_API int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate_in,
                                   const rt_stt_seek_opts* opts, rt_stt_seek_out* out);
+/* Temperature fallback ("temperature fallback"; faster-whisper's generate_with_fallback, which the reference's
+ * model.transcribe runs with temperatures 0, 0.2 .. 1.0, best_of 5, thresholds 2.4 and -1.0).  A policy applies to
+ * rt_stt_transcribe_ex and rt_stt_transcribe_seek only.  Per window, over the temperatures in order: temperature 0 is the beam decode
+ * at the call's beam_size; a temperature T > 0 decodes best_of independent sampled rows (Gumbel-max over the ids the step rule leaves,
+ * scores on the untempered log-probabilities) and keeps the one with the largest score / (ids + 1).  An attempt needs another one when
+ * ratio(text ids) > compression_ratio_threshold or score / (ids + 1) < logprob_threshold - unless no_speech_threshold and
+ * logprob_threshold are both set, no_speech > no_speech_threshold and the average is below logprob_threshold: that window is silence
+ * and the caller's silence rule deals with it.  The first attempt that needs no other is the window's result; when every temperature
+ * failed it is the attempt with the largest average among those within the compression threshold (among all when none is), the
+ * earliest on ties.  Later attempts decode over the encoder states the group still holds: no front-end or encoder launch is
+ * repeated.  A group holds floor(32 / max(beam_size, best_of)) windows while a policy is set.  A window's draws are keyed by (seed,
+ * window key, temperature index, sample index, step, id) - window key: the window's start in ticks (rt_stt_transcribe_seek) or its
+ * index in its clip (rt_stt_transcribe_ex) - so a clip's result does not depend on the other clips of the call.
+ * ratio: the compression ratio of one attempt's text ids (timestamps stripped), computed by the caller - the library links no zlib.
+ *   It runs on the thread that called rt_stt_transcribe_ex / rt_stt_transcribe_seek, with the context's mutex held: it must NOT call
+ *   back into the handle or its context.  A result that is NaN or <= 0 fails the call with RT_ERR_INVALID.  NULL: no compression test.
+ * rt_stt_set_fallback: after rt_stt_finalize, between calls; NULL clears the policy.  With no policy set every entry point issues
+ *   exactly the launches it issues without this feature and returns the same bits.  RT_ERR_INVALID (the policy is unchanged):
+ *   n_temperatures outside 1 .. 8, best_of outside 1 .. 8, temperatures negative, not finite or not strictly ascending, a
+ *   compression threshold without a callback, a no_speech_threshold on a handle without rt_stt_set_languages.
+ * rt_stt_fallback_report: per window of the last rt_stt_transcribe_ex / rt_stt_transcribe_seek call under a policy, in the order of
+ *   that call's per-window arrays: the attempts made, the temperature of the chosen attempt and its ratio (NaN without a callback).
+ *   Each array optional; n_windows receives the count; RT_ERR_LENGTH (nothing past cap is written) when cap is below it. */
+typedef float (*rt_stt_ratio_fn)(const int32_t* ids, int32_t n_ids, void* user);
+typedef struct rt_stt_fallback {
+    int32_t n_temperatures;            /* 1 .. 8 */
+    float temperatures[8];             /* strictly ascending, >= 0; only the first may be 0 */
+    int32_t best_of;                   /* 1 .. 8 */
+    float compression_ratio_threshold; /* NaN: off */
+    float logprob_threshold;           /* NaN: off */
+    float no_speech_threshold;         /* NaN: off; needs rt_stt_set_languages */
+    uint64_t seed;
+    rt_stt_ratio_fn ratio;             /* NULL: the compression test is off */
+    void* ratio_user;
+    int32_t reserved[4];
+} rt_stt_fallback;
+RT_API int rt_stt_set_fallback(rt_stt* s, const rt_stt_fallback* f);
+RT_API int rt_stt_fallback_report(rt_stt* s, int32_t cap, int32_t* h_attempts, float* h_temperature, float* h_ratio, int32_t* n_windows);
 /* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM:
  * row 0 of the same front end and encoder with the clip as its only window.  Of a clip longer than chunk_seconds the first
  * chunk is kept, and the resampler's taps at its end see the samples behind it. */

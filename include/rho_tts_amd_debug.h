@@ -142,6 +142,26 @@ RT_API int rt_debug_stt_beam_step_ts(rt_stt* s, const float* d_logits, int32_t r
                                      float* h_fin_score, int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows,
                                      int32_t* h_ts_flags_out, int32_t* h_ts_last_out);
 
+/* One sampled step of the temperature fallback (k_stt_sample_select; tests/test_stt_sample_kernel_gpu.py) on logits the caller
+ * supplies, shaped like rt_debug_stt_beam_step: n_rows rows (1 .. 8192, a multiple of `samples`, 1 .. 8), row r = sample r % samples
+ * of window r / samples; logits in HBM, float32: [n_rows][cfg.vocab] for row_stride == samples, one row per WINDOW
+ * ([n_rows / samples][cfg.vocab], the step behind the prefix) for row_stride == 1.  In: the temperature (> 0), the seed, the
+ * temperature's index in its policy, per row the window key and the sample index (a row's pick depends on these, the step and its
+ * logits alone), the rows' cumulative scores and done flags.  Out, per row: the pick (-1 for a row that came in done: such a row
+ * comes back as it went in), the new score, the winning perturbed value x / T + g, the done flag; and the rows still decoding.
+ * The book is allocated for the call, so the handle's decoder side does not grow with n_rows.
+ * _ts (a handle with rt_stt_set_timestamps): the timestamp instantiation, with the rows' history state in and out as
+ * rt_debug_stt_beam_step_ts. */
+RT_API int rt_debug_stt_sample_step(rt_stt* s, const float* d_logits, int32_t row_stride, int32_t n_rows, int32_t samples, float temperature, uint64_t seed,
+                                    int32_t temperature_index, const int32_t* h_key, const int32_t* h_sample, const float* h_scores_in, const int32_t* h_done,
+                                    int32_t first_step, int32_t step, int32_t* h_next_tok, float* h_scores_out, float* h_win_val, int32_t* h_done_out,
+                                    int32_t* h_live_rows);
+RT_API int rt_debug_stt_sample_step_ts(rt_stt* s, const float* d_logits, int32_t row_stride, int32_t n_rows, int32_t samples, float temperature, uint64_t seed,
+                                       int32_t temperature_index, const int32_t* h_key, const int32_t* h_sample, const float* h_scores_in, const int32_t* h_done,
+                                       int32_t first_step, int32_t step, int32_t max_initial_timestamp_index, const int32_t* h_ts_flags_in,
+                                       const int32_t* h_ts_last_in, int32_t* h_next_tok, float* h_scores_out, float* h_win_val, int32_t* h_done_out,
+                                       int32_t* h_live_rows, int32_t* h_ts_flags_out, int32_t* h_ts_last_out);
+
 /* k_stt_probe on logits the caller supplies (tests/test_stt_lang_kernel_gpu.py): n_rows (1 .. 32) rows of cfg.vocab float32 in HBM,
  * row r at d_logits + r * row_stride (row_stride >= cfg.vocab), with the handle's languages and no-speech id (rt_stt_set_languages)
  * -> per row the language id, its probability among the configured ids, and the no-speech probability. */

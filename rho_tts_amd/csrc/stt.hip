@@ -36,6 +36,12 @@
 // (stt_seek_rule): a round holds one window per unfinished clip at the clip's current offset, and the number of rounds is bounded
 // before the first launch.  Off unless rt_stt_set_timestamps was called; no other entry point changes.
 //
+// rt_stt_set_fallback gives rt_stt_transcribe_ex and rt_stt_transcribe_seek the temperature fallback of the reference's transcriber
+// ("temperature fallback"): after a group is decoded the host evaluates the rule per window (stt_fallback_group;
+// the compression ratio is the caller's callback), and the windows that need another attempt are decoded again by sampling -
+// best_of rows per window, k_stt_sample_select: Gumbel-max over the ids the step rules leave - over the encoder states the group
+// still holds.  Off unless a policy is set; no other entry point changes.
+//
 // The three beam entry points run their groups through one driver (stt_run_group) under one plan (SttPlan: the clips' language
 // requests, whether the probe runs, the timestamp rule); what each keeps for itself is how it forms its groups and what it makes of
 // the hypotheses - fixed cuts and joined ids (stt_transcribe_beam), rounds, offsets and the seek rule (stt_transcribe_seek).
@@ -341,6 +347,10 @@ struct SttTsRule { int t0, nt, max_initial; };
 // while it has room, the others become the next beams until B are taken.  logits row of beam j: w row_stride + j (the step behind
 // the prefix has one row per window: row_stride 1, one live beam).
 //
+// (k_stt_sample_select below repeats the range set-up, `kind`, the maximum pass, the sum pass and the logsumexp decision of this kernel
+// statement by statement - shared device functions would have had to leave this kernel's ISA as it is: a change to the masking or to
+// the timestamp rule is made in BOTH kernels.)
+//
 // TS (rt_stt_transcribe_seek): the same passes apply the timestamp rule.  From the row's history state every id is text, timestamp or
 // barred for this step: text ids are [text_lo, t0 - 1) under the mask, timestamp ids [ts_lo, ts_hi) whatever the mask says.  The
 // maximum pass and the sum pass each form the two parts' figures side by side (same order of reduction per part); timestamps win -
@@ -564,6 +574,193 @@ __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restric
     }
 }
 
+// ---------------------------------------------------------------------------------------------- sampled decoding (temperature fallback)
+// The generator of a sampled step ("temperature fallback"): the mix32 chain of rt_uniform (sampling.hip) over
+// (seed, window key, temperature index, sample index, step) per row and the id per element.  The top 23 bits of the hash are k;
+// u = (k + 0.5) 2^-23 is exact in float32 and lies in [2^-24, 1 - 2^-24], so g = -log(-log(u)) is finite.
+__device__ __forceinline__ unsigned stt_mix32(unsigned h) {
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+__device__ __forceinline__ unsigned stt_gumbel_row(unsigned seed_lo, unsigned seed_hi, unsigned key, unsigned t_index, unsigned sample, unsigned step) {
+    const unsigned a = stt_mix32(seed_lo ^ 0x85EBCA6Bu);
+    const unsigned b = stt_mix32(a + key * 0x9E3779B1u);
+    const unsigned c = stt_mix32(b + t_index * 0x85EBCA77u);
+    const unsigned d = stt_mix32(c + sample * 0xC2B2AE3Du + seed_hi);
+    return stt_mix32(d + step * 0x9E3779B1u);
+}
+__device__ __forceinline__ float stt_gumbel(unsigned row_hash, int id) {
+    const unsigned k = stt_mix32(row_hash + (unsigned)id * 0x85EBCA77u) >> 9;
+    const float u = __fmul_rn(__fadd_rn((float)k, 0.5f), 1.0f / 8388608.0f);
+    return -logf(-logf(u));
+}
+
+// What a sampled step takes beside the step rule: the temperature (> 0), the seed, the temperature's index in the policy, and per
+// row the window key and the sample index (a row's pick depends on these and its logits alone, not on where it sits in a launch)
+struct SttSampleRule { float T; unsigned seed_lo, seed_hi, t_index; const int32_t* key; const int32_t* sample; };
+
+// One sampled step, one workgroup per ROW (window x sample; row w S + j is sample j of window w, its logits at row
+// w row_stride + (row_stride > 1 ? j : 0): the step behind the prefix has one row of logits per window).  The passes of
+// k_stt_beam_select - masked maximum and sum exp on the UNTEMPERED logits, the two parts side by side under TS, the same order of
+// reduction - give the row's log-probabilities and the decision "timestamps win"; one more pass takes the arg-max of x / T + g(id)
+// over the surviving ids (Gumbel-max: the pick is distributed as softmax(x / T) over them), the lower id on ties.  A NaN or -inf
+// logit takes no part.  The row's score adds the untempered log-probability of the pick; end-of-sequence (or a row without any
+// survivor, which counts as ending) sets the row's done flag and takes it out of `live`; a row that is done rides along untouched.
+// The range set-up, `kind`, the two passes and the logsumexp decision are k_stt_beam_select's, repeated here: a change to the masking
+// or to the timestamp rule is made in BOTH kernels.
+// src: the row itself, and behind the prefix the window's first row, whose cache slot the prefix pass wrote.  win_val (tests, else
+// null): the winning perturbed value per row.
+template <bool TS>
+__global__ __launch_bounds__(1024) void k_stt_sample_select(const float* __restrict__ logits, int V, int row_stride, const uint8_t* __restrict__ mask,
+                                                            int first_step, int eos, int S, int step, SttBeamBook bk, SttTsRule ts, SttSampleRule sr,
+                                                            float* __restrict__ win_val) {
+    __shared__ float red_v[16];
+    __shared__ float red_w[16];
+    __shared__ int red_i[16];
+    const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    if (bk.done[r]) return;                                // (uniform)
+    const int w = r / S, j = r - w * S;
+    const uint8_t bad = first_step ? 3 : 1;
+    const float* x = logits + ((int64_t)w * row_stride + (row_stride > 1 ? j : 0)) * V;
+    int text_lo = 0, text_hi = 0, ts_lo = 0, ts_hi = 0, flags = 0, lts = 0;
+    if constexpr (TS) {
+        flags = bk.ts_flags[r]; lts = bk.ts_last[r];       // (thread 0 writes them behind the last barrier)
+        const bool last = flags & 1, pen = flags & 2;
+        text_hi = ts.t0 - 1;
+        ts_lo = ts.t0; ts_hi = min(ts.t0 + ts.nt, V);
+        if (lts > 0) ts_lo = max(ts_lo, (last && !pen) ? lts : lts + 1);
+        if (last && pen) ts_lo = ts_hi;
+        if (last && !pen) text_lo = eos;
+        if (first_step) {
+            text_lo = text_hi;
+            if (ts.max_initial >= 0) ts_hi = min(ts_hi, ts.t0 + ts.max_initial + 1);
+        }
+    }
+    // 0: barred, 1: text, 2: timestamp (TS == false: 1 is every id the mask leaves)
+    auto kind = [&](int i, int mk) -> int {
+        if constexpr (TS) {
+            if (i >= ts_lo && i < ts_hi) return 2;
+            return (i >= text_lo && i < text_hi && !(mk & bad)) ? 1 : 0;
+        } else {
+            return (mk & bad) ? 0 : 1;
+        }
+    };
+    float m = -INFINITY, m2 = -INFINITY;
+    for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+        float xv[STT_SEL_U];
+        int mk[STT_SEL_U];
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) {
+            const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
+            if (kd == 1 && xv[u] > m) m = xv[u];
+            if constexpr (TS) { if (kd == 2 && xv[u] > m2) m2 = xv[u]; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((tid & 63) == 0) red_v[wave] = m;
+    if constexpr (TS) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
+        if ((tid & 63) == 0) red_w[wave] = m2;
+    }
+    __syncthreads();
+    m = red_v[0];
+    for (int k = 1; k < 16; ++k) m = fmaxf(m, red_v[k]);
+    if constexpr (TS) {
+        m2 = red_w[0];
+        for (int k = 1; k < 16; ++k) m2 = fmaxf(m2, red_w[k]);
+    }
+    __syncthreads();
+    float sum = 0.f, sum2 = 0.f;
+    for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+        float xv[STT_SEL_U];
+        int mk[STT_SEL_U];
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) {
+            const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
+            if (kd == 1 && xv[u] == xv[u]) sum += expf(xv[u] - m);
+            if constexpr (TS) { if (kd == 2 && xv[u] == xv[u]) sum2 += expf(xv[u] - m2); }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if ((tid & 63) == 0) red_v[wave] = sum;
+    if constexpr (TS) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o, 64);
+        if ((tid & 63) == 0) red_w[wave] = sum2;
+    }
+    __syncthreads();
+    sum = red_v[0];
+    for (int k = 1; k < 16; ++k) sum += red_v[k];
+    if constexpr (TS) {
+        sum2 = red_w[0];
+        for (int k = 1; k < 16; ++k) sum2 += red_w[k];
+    }
+    __syncthreads();
+    float lse = m + logf(sum);
+    bool text_ok = true;
+    if constexpr (TS) {
+        const bool has_ts = m2 > -INFINITY, has_text = m > -INFINITY;
+        const float lse_ts = has_ts ? m2 + logf(sum2) : -INFINITY;
+        text_ok = has_text && !(lse_ts > m);
+        if (!text_ok) lse = lse_ts;
+        else if (has_ts) { const float mm = fmaxf(m, m2); lse = mm + logf(sum * expf(m - mm) + sum2 * expf(m2 - mm)); }
+    }
+    // the arg-max of x / T + g over the survivors
+    const unsigned row_hash = stt_gumbel_row(sr.seed_lo, sr.seed_hi, (unsigned)sr.key[r], sr.t_index, (unsigned)sr.sample[r], (unsigned)step);
+    float bv = -INFINITY;
+    int bi = STT_NO_ID;
+    for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+        float xv[STT_SEL_U];
+        int mk[STT_SEL_U];
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) {
+            const int i = base + 1024 * u;
+            const int kd = i < V ? kind(i, mk[u]) : 0;
+            if (kd == 0 || (kd == 1 && !text_ok)) continue;
+            const float v = __fadd_rn(__fdiv_rn(xv[u], sr.T), stt_gumbel(row_hash, i));
+            if (v > -INFINITY && cand_before(v, i, bv, bi)) { bv = v; bi = i; }      // (a NaN compares false)
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (cand_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if ((tid & 63) == 0) { red_v[wave] = bv; red_i[wave] = bi; }
+    __syncthreads();
+    if (tid != 0) return;
+    bv = red_v[0]; bi = red_i[0];
+    for (int k = 1; k < 16; ++k)
+        if (cand_before(red_v[k], red_i[k], bv, bi)) { bv = red_v[k]; bi = red_i[k]; }
+    const bool some = bi != STT_NO_ID;
+    const int tok = some ? bi : eos;
+    bk.next_tok[r] = tok;
+    bk.src[r] = row_stride > 1 ? r : w * S;
+    if (some) bk.score[r] = bk.score[r] + (x[bi] - lse);
+    bk.bp_tok[(int64_t)step * bk.R + r] = tok;
+    bk.bp_par[(int64_t)step * bk.R + r] = j;
+    if (win_val) win_val[r] = bv;
+    if constexpr (TS) {
+        const bool is_ts = tok >= ts.t0;
+        bk.ts_flags[r] = (is_ts ? 1 : 0) | ((first_step || (flags & 1)) ? 2 : 0);
+        bk.ts_last[r] = is_ts ? tok : lts;
+    }
+    if (tok == eos) {
+        bk.done[r] = 1;
+        atomicSub(bk.live, 1);
+    }
+}
+
 // The four planes of a decoder self-attention cache
 struct SttKvPlanes { const bf16_t* src[4]; bf16_t* dst[4]; };
 // Row r of the next step continues row src[r] of this one: positions [0, len) of every (layer, head) of cache slot src[r] are
@@ -648,8 +845,15 @@ struct SttBeam {
     int32_t* book_mem = nullptr;
     size_t book_n = 0;
     SttBeamBook book{};
+    // sampled decoding (stt_decode_sample_group): the row tables of a subset of the group's windows, their prefixes, and the rows'
+    // keys and sample indices, uploaded per attempt in one copy: [rows n_prefix] x 4 (pre_slot | pre_pos | pre_win | prefix), [rows] x 4
+    // (row_slot | row_win | key | sample)
+    int32_t* smp = nullptr;
     std::vector<void*> owned;
 };
+
+// One window's line of rt_stt_fallback_report
+struct SttFbWin { int32_t attempts = 1; float temperature = 0.f, ratio = NAN; };
 
 struct rt_stt {
     rt_ctx* ctx = nullptr;
@@ -684,6 +888,11 @@ struct rt_stt {
     // [STT_GROUP][n_prefix] a prefix per window (SttPlan; in timestamp mode n_prefix - 1 entries each, without <|notimestamps|>):
     // allocated by rt_stt_finalize for a handle with languages or timestamps
     int32_t* d_win_prefix = nullptr;
+    // rt_stt_set_fallback: the policy (fb_set: one is set) and, per window of the last call under it, what rt_stt_fallback_report returns
+    bool fb_set = false;
+    rt_stt_fallback fb{};
+    std::vector<SttFbWin> fb_report;
+    std::vector<int32_t> h_smp;
     std::vector<void*> owned;
 };
 
@@ -846,7 +1055,9 @@ int stt_frames_with_audio(const rt_stt_config& c, int64_t n16) {
 }
 
 // One window of the input of a call
-struct SttSpan { int clip; const float* pcm; int64_t n; };
+// (key: what the sampled decode of a fallback policy keys the window's draws by - its index in its clip on the fixed-cut path, its
+// start in ticks on the seek path)
+struct SttSpan { int clip; const float* pcm; int64_t n; uint32_t key = 0; };
 
 // Cuts every clip into consecutive chunk_seconds windows of the INPUT (an empty clip is one window of silence); first_only keeps a
 // clip's first window alone
@@ -854,7 +1065,7 @@ void stt_cut(const rt_stt_config& c, int sr, const float* const* d_pcm, const in
     const int64_t win = (int64_t)c.chunk_seconds * sr;              // one window, in input samples
     for (int i = 0; i < n_clips; ++i)
         for (int64_t off = 0; off == 0 || (off < n_samples[i] && !first_only); off += win)
-            all.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off : nullptr, std::min<int64_t>(win, n_samples[i] - off)});
+            all.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off : nullptr, std::min<int64_t>(win, n_samples[i] - off), (uint32_t)(off / win)});
 }
 
 // The front end of a group: B windows (device pointers at rate sr) -> log-mel [B][frames][n_mels] in s->grp.enc.mel, one launch per
@@ -1078,6 +1289,7 @@ int stt_beam_reserve(rt_stt* s, int rows) {
         nb.book_n = stt_beam_book_words(rows, c.max_new_tokens);
         RT_TRY(stt_alloc(s, nb.owned, nb.book_n, &nb.book_mem));
         nb.book = stt_beam_book(nb.book_mem, rows, c.max_new_tokens);
+        RT_TRY(stt_alloc(s, nb.owned, 4 * rp + 4 * r, &nb.smp));
         hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, s->ctx->stream, nb.row_pos, rows, 0, 0);
         RT_HIP(s->ctx, hipGetLastError());
         nb.rows = rows;
@@ -1108,6 +1320,9 @@ struct SttPlan {
     bool probe = false;                 // the probe pass runs: a clip detects, or the windows' no-speech probabilities are wanted
     const SttTsRule* ts = nullptr;      // timestamp mode: the prefix without its last entry (<|notimestamps|>), the rule at every step
     int32_t win_first[STT_GROUP] = {};  // the window table's second column, set per group (the first, a window's clip, is in its span)
+    // a fallback policy is set (rt_stt_set_fallback): the group's windows go through stt_fallback_group, which leaves here, per window
+    // of the group, what rt_stt_fallback_report returns
+    std::vector<SttFbWin>* fallback = nullptr;
     bool per_window() const { return h_req || probe || ts; }
     int n_prefix(const rt_stt_config& c) const { return ts ? c.n_prefix - 1 : c.n_prefix; }
 };
@@ -1136,6 +1351,14 @@ int stt_lang_prefix(rt_stt* s, int nW, int P) {
                        s->d_clip_lang, s->d_probe, s->d_win_prefix, s->d_probe + 3 * STT_GROUP);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
+}
+// The probe of a group on the beam path's decoder side, what stt_decode_beam_group and - under a fallback policy without a beam decode -
+// stt_run_group share: the probe pass on cache slot w of window w (s->beam.row_slot holds the identity), then the windows' prefixes
+// and the ids they took on the device
+int stt_probe_group(rt_stt* s, int nW, int P) {
+    SttBeam& bm = s->beam;
+    RT_TRY(stt_probe_pass(s, bm.dec, bm.row_slot, bm.row_pos, nW));
+    return stt_lang_prefix(s, nW, P);
 }
 // One step of beam search over nW windows: k_stt_beam_select, the timestamp instantiation when a rule is given
 int stt_beam_select(rt_stt* s, const float* d_logits, int row_stride, int nW, int first_step, int B, int step, const SttBeamBook& bk, const SttTsRule* ts) {
@@ -1172,10 +1395,7 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
         // the probe pass on cache slot w of window w (the prefix pass and the reorder behind it overwrite what it leaves in the
         // cache), then the windows' prefixes on the device.  Every language given and no no-speech probability wanted: no launch is
         // added to those of rt_stt_transcribe_beam
-        if (plan.probe) {
-            RT_TRY(stt_probe_pass(s, bm.dec, bm.row_slot, bm.row_pos, nW));
-            RT_TRY(stt_lang_prefix(s, nW, P));
-        }
+        if (plan.probe) RT_TRY(stt_probe_group(s, nW, P));
         bm.dec.tok = s->d_win_prefix;        // (without a probe every language is given: stt_run_group has copied the prefixes in)
     }
     RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
@@ -1227,6 +1447,101 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
     return RT_OK;
 }
 
+// What a group reports per window beside its hypothesis: the language its prefix took, that language's probability - the probe's
+// for the window where the clip asked for detection (the clip's own on its first window), 1 where it was given: a forced language
+// (or the handle's own) counts as certain, as in the reference's transcribers - and the no-speech probability (NaN without a probe)
+struct SttWinInfo { int32_t lang; float lang_prob, no_speech; };
+
+// One sampled step over `rows` rows: k_stt_sample_select, the timestamp instantiation when a rule is given
+int stt_sample_select(rt_stt* s, const float* d_logits, int row_stride, int rows, int first_step, int S, int step, const SttBeamBook& bk, const SttTsRule* ts,
+                      const SttSampleRule& sr, float* d_val) {
+    const rt_stt_config& c = s->cfg;
+    auto* select = ts ? k_stt_sample_select<true> : k_stt_sample_select<false>;
+    hipLaunchKernelGGL(select, dim3(rows), dim3(1024), 0, s->ctx->stream, d_logits, c.vocab, row_stride, s->d_mask, first_step, c.eos_id, S, step, bk,
+                       ts ? *ts : SttTsRule{}, sr, d_val);
+    RT_HIP(s->ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// Sampled decoding at temperature T (> 0; index t_index of the policy) of the windows `need` of the encoded group, S independent rows
+// each ("temperature fallback"): rows = need x S over the encoder states the group holds - nothing of the front
+// end or the encoder runs.  The prefix pass runs one row per window into the cache slot of the window's first row and the reorder
+// kernel fans it out once; after that every row continues itself and nothing is reordered.  One device-to-host read and one
+// synchronisation per step.  out[k]: the row of window need[k] with the largest score / (ids + 1), the lower sample index on a tie.
+int stt_decode_sample_group(rt_stt* s, const SttSpan* spans, const std::vector<int>& need, const std::vector<SttWinInfo>& info, int S, float T, int t_index,
+                            const SttPlan& plan, std::vector<SttHyp>& out) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    SttBeam& bm = s->beam;
+    const int nN = (int)need.size(), P = plan.n_prefix(c), rows = nN * S, R = bm.rows;
+    const size_t rp = (size_t)R * c.n_prefix;
+    const SttBeamBook& bk = bm.book;
+    const KvCache& cross = s->grp.enc.cross_kv;
+    // the tables of this attempt, laid out as SttBeam::smp says
+    std::vector<int32_t>& h = s->h_smp;
+    h.assign(4 * rp + 4 * (size_t)R, 0);
+    auto part = [&](int32_t* base, int k) { return k < 4 ? base + k * rp : base + 4 * rp + (size_t)(k - 4) * R; };
+    for (int k = 0; k < nN; ++k)
+        for (int i = 0; i < P; ++i) {
+            const size_t at = (size_t)k * P + i;
+            part(h.data(), 0)[at] = k * S; part(h.data(), 1)[at] = i; part(h.data(), 2)[at] = need[k];
+            part(h.data(), 3)[at] = (i == 1 && P > 1) ? info[need[k]].lang : c.prefix[i];
+        }
+    for (int r = 0; r < rows; ++r) {
+        part(h.data(), 4)[r] = r; part(h.data(), 5)[r] = need[r / S];
+        part(h.data(), 6)[r] = (int32_t)spans[need[r / S]].key; part(h.data(), 7)[r] = r % S;
+    }
+    RT_HIP(ctx, hipMemcpyAsync(bm.smp, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.next_tok, R, c.eos_id, 0);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.src, R, 0, 1);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.live, 1, rows, 0);
+    RT_HIP(ctx, hipGetLastError());
+    bm.dec.tok = part(bm.smp, 3);
+    RT_TRY(stt_decode_rows(s, bm.dec, cross, nN, P, 0, part(bm.smp, 0), part(bm.smp, 1), part(bm.smp, 2)));
+    const SttSampleRule sr{T, (unsigned)(s->fb.seed & 0xffffffffu), (unsigned)(s->fb.seed >> 32), (unsigned)t_index, part(bm.smp, 6), part(bm.smp, 7)};
+    const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
+    int steps = 0;
+    for (int step = 0; step < budget; ++step) {
+        RT_TRY(stt_sample_select(s, bm.dec.logits, step == 0 ? 1 : S, rows, step == 0 ? 1 : 0, S, step, bk, plan.ts, sr, nullptr));
+        steps = step + 1;
+        int32_t live = 0;
+        RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (live <= 0 || step + 1 >= budget) break;
+        if (step == 0 && S > 1) {                   // the window's first row holds the prefix: every row of the window takes it
+            RT_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, P));
+            std::swap(bm.dec.kv, bm.kv_next);
+        }
+        bm.dec.tok = bk.next_tok;
+        RT_TRY(stt_decode_rows(s, bm.dec, cross, rows, 1, P + step, part(bm.smp, 4), bm.row_pos, part(bm.smp, 5)));
+    }
+    s->h_book.resize(bm.book_n);
+    RT_HIP(ctx, hipMemcpyAsync(s->h_book.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const SttBeamBook hb = stt_beam_book(s->h_book.data(), R, c.max_new_tokens);
+    out.assign(nN, SttHyp{});
+    std::vector<int32_t> ids;
+    for (int k = 0; k < nN; ++k) {
+        double best = 0.0;
+        for (int j = 0; j < S; ++j) {
+            const int r = k * S + j;
+            ids.clear();
+            for (int u = 0; u < steps; ++u) {
+                const int32_t t = hb.bp_tok[(size_t)u * R + r];
+                if (t == c.eos_id) break;
+                ids.push_back(t);
+            }
+            const int count = (int)ids.size() + 1;
+            const double norm = (double)hb.score[r] / (double)count;
+            if (j > 0 && !(norm > best)) continue;
+            best = norm;
+            out[k].ids = ids; out[k].score = hb.score[r]; out[k].count = count;
+        }
+    }
+    return RT_OK;
+}
+
 // The per-call side of a plan with a probe: s->d_clip_lang holds every clip's request, and the probe's results have a host copy
 int stt_plan_begin(rt_stt* s, const SttPlan& plan, int n_clips) {
     rt_ctx* ctx = s->ctx;
@@ -1245,10 +1560,66 @@ int stt_plan_begin(rt_stt* s, const SttPlan& plan, int n_clips) {
     return RT_OK;
 }
 
-// What a group reports per window beside its hypothesis: the language its prefix took, that language's probability - the probe's
-// for the window where the clip asked for detection (the clip's own on its first window), 1 where it was given: a forced language
-// (or the handle's own) counts as certain, as in the reference's transcribers - and the no-speech probability (NaN without a probe)
-struct SttWinInfo { int32_t lang; float lang_prob, no_speech; };
+// The fallback loop over one decoded group ("temperature fallback"; faster-whisper's generate_with_fallback).
+// hyps: the beam decode of every window when the first temperature is 0.  Per temperature the windows that still need an attempt are
+// decoded (temperature 0: already there), and the rule is evaluated on the host: the compression ratio of the attempt's text ids (the
+// caller's callback; an attempt without text ids has ratio 0 and the callback is not asked) against its threshold, the average
+// log-probability against its own, and the silence exemption.  The number of attempts is bounded by n_temperatures.  On return
+// hyps[w] is the chosen attempt of window w.
+int stt_fallback_group(rt_stt* s, const SttSpan* spans, int nW, const SttPlan& plan, std::vector<SttHyp>& hyps, const std::vector<SttWinInfo>& info,
+                       std::vector<SttFbWin>& report) {
+    const rt_stt_fallback& f = s->fb;
+    struct Attempt { SttHyp hyp; float T, ratio, avg; bool ratio_ok; };
+    const bool cr_set = f.compression_ratio_threshold == f.compression_ratio_threshold, lp_set = f.logprob_threshold == f.logprob_threshold;
+    const bool ns_set = f.no_speech_threshold == f.no_speech_threshold;
+    std::vector<std::vector<Attempt>> tried(nW);
+    std::vector<int> chosen(nW, -1), need(nW), next;
+    for (int w = 0; w < nW; ++w) need[w] = w;
+    std::vector<SttHyp> got;
+    std::vector<int32_t> text;
+    for (int t = 0; t < f.n_temperatures && !need.empty(); ++t) {
+        const float T = f.temperatures[t];
+        if (T > 0.f) RT_TRY(stt_decode_sample_group(s, spans, need, info, f.best_of, T, t, plan, got));
+        else got = hyps;                                    // (t == 0, every window: the beam decode the caller ran)
+        next.clear();
+        for (size_t k = 0; k < need.size(); ++k) {
+            const int w = need[k];
+            Attempt a{std::move(got[k]), T, NAN, 0.f, true};
+            a.avg = a.hyp.score / (float)a.hyp.count;
+            if (f.ratio) {
+                text.clear();
+                for (int32_t id : a.hyp.ids)
+                    if (!plan.ts || id < plan.ts->t0) text.push_back(id);
+                a.ratio = text.empty() ? 0.f : f.ratio(text.data(), (int32_t)text.size(), f.ratio_user);
+                if (!text.empty() && !(a.ratio > 0.f))
+                    return rt_fail(s->ctx, RT_ERR_INVALID, "fallback: the ratio callback returned %g for %zu ids (a compression ratio is above 0)", (double)a.ratio, text.size());
+                a.ratio_ok = !(cr_set && a.ratio > f.compression_ratio_threshold);
+            }
+            bool needs = !a.ratio_ok || (lp_set && a.avg < f.logprob_threshold);
+            if (ns_set && lp_set && info[w].no_speech > f.no_speech_threshold && a.avg < f.logprob_threshold) needs = false;      // silence: the caller's rule
+            tried[w].push_back(std::move(a));
+            if (needs) next.push_back(w); else chosen[w] = (int)tried[w].size() - 1;
+        }
+        need.swap(next);
+    }
+    // every temperature failed: the largest average among the attempts within the compression threshold, among all when none is
+    for (int w : need) {
+        bool any_ok = false;
+        for (const Attempt& a : tried[w]) any_ok = any_ok || a.ratio_ok;
+        for (int k = 0; k < (int)tried[w].size(); ++k) {
+            if (any_ok && !tried[w][k].ratio_ok) continue;
+            if (chosen[w] < 0 || tried[w][k].avg > tried[w][chosen[w]].avg) chosen[w] = k;
+        }
+    }
+    report.assign(nW, SttFbWin{});
+    hyps.resize(nW);
+    for (int w = 0; w < nW; ++w) {
+        Attempt& a = tried[w][chosen[w]];
+        report[w].attempts = (int32_t)tried[w].size(); report[w].temperature = a.T; report[w].ratio = a.ratio;
+        hyps[w] = std::move(a.hyp);
+    }
+    return RT_OK;
+}
 
 // One group through the whole path, what rt_stt_transcribe_beam, rt_stt_transcribe_ex and rt_stt_transcribe_seek share: nW windows
 // at rate sr -> front end, encoder, beam search of width B under the plan.  The group's uploads come first, while the stream is
@@ -1270,7 +1641,16 @@ int stt_run_group(rt_stt* s, const SttSpan* spans, int nW, int sr, int B, const 
     }
     RT_TRY(stt_features_group(s, spans, nW, sr));
     RT_TRY(stt_encode(s, s->grp.enc, nW));
-    RT_TRY(stt_decode_beam_group(s, nW, B, hyps, plan));
+    // a policy whose first temperature is above 0 has no beam decode: the probe alone (stt_probe_group), behind the row tables it reads
+    const bool sampled_first = plan.fallback && s->fb.temperatures[0] > 0.f;
+    if (!sampled_first) RT_TRY(stt_decode_beam_group(s, nW, B, hyps, plan));
+    else if (plan.probe) {
+        SttBeam& bm = s->beam;
+        hipLaunchKernelGGL(k_stt_fill_beam_rows, dim3(1), dim3(256), 0, ctx->stream, bm.pre_slot, bm.pre_pos, bm.pre_win, nW * P, P, 1, bm.row_slot, bm.row_win, nW);
+        RT_HIP(ctx, hipGetLastError());
+        RT_TRY(stt_probe_group(s, nW, P));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
     if (plan.probe) RT_HIP(ctx, hipMemcpy(s->h_probe.data(), s->d_probe, 4 * STT_GROUP * 4, hipMemcpyDeviceToHost));     // (behind the group's last synchronisation)
     const float* pf = (const float*)s->h_probe.data();
     info.resize(nW);
@@ -1281,6 +1661,7 @@ int stt_run_group(rt_stt* s, const SttSpan* spans, int nW, int sr, int B, const 
         info[b].lang_prob = detected ? pf[STT_GROUP + b] : 1.0f;
         info[b].no_speech = plan.probe ? pf[2 * STT_GROUP + b] : NAN;
     }
+    if (plan.fallback) RT_TRY(stt_fallback_group(s, spans, nW, plan, hyps, info, *plan.fallback));
     return RT_OK;
 }
 
@@ -1300,12 +1681,17 @@ struct SttReport {
 int stt_transcribe_beam(rt_stt* s, const std::vector<SttSpan>& all, int n_clips, int sr, int beam_size, int32_t* h_tokens, int max_tokens, int32_t* h_n_tokens,
                         float* h_scores, const SttReport* rep) {
     std::fill(h_n_tokens, h_n_tokens + n_clips, 0);
-    const size_t per_group = (size_t)(STT_GROUP / beam_size);
+    // under a fallback policy (rt_stt_transcribe_ex only) a window takes max(beam_size, best_of) decoder rows
+    const bool fallback = rep && s->fb_set;
+    const int per_window = fallback ? std::max(beam_size, s->fb.best_of) : beam_size;
+    const size_t per_group = (size_t)(STT_GROUP / per_window);
     const int most = (int)std::min(all.size(), per_group);
     RT_TRY(stt_group_reserve(s, most));
-    RT_TRY(stt_beam_reserve(s, most * beam_size));
+    RT_TRY(stt_beam_reserve(s, most * per_window));
     SttPlan plan;
+    std::vector<SttFbWin> fb_group;
     if (rep) { plan.h_req = rep->h_req; plan.probe = rep->probe; }
+    if (fallback) { plan.fallback = &fb_group; s->fb_report.clear(); }
     RT_TRY(stt_plan_begin(s, plan, n_clips));
     std::vector<int32_t> first_at(n_clips, -1);      // a clip's first window, among `all`
     std::vector<double> sum(n_clips, 0.0);
@@ -1320,6 +1706,7 @@ int stt_transcribe_beam(rt_stt* s, const std::vector<SttSpan>& all, int n_clips,
             plan.win_first[b] = first_at[i] >= (int32_t)next ? first_at[i] - (int32_t)next : -1;
         }
         RT_TRY(stt_run_group(s, all.data() + next, nW, sr, beam_size, plan, hyps, info));
+        if (fallback) s->fb_report.insert(s->fb_report.end(), fb_group.begin(), fb_group.end());
         for (int b = 0; b < nW; ++b) {
             const int i = all[next + b].clip;
             for (int32_t t : hyps[b].ids)
@@ -1390,6 +1777,7 @@ struct SttSeekResult {
     std::vector<std::vector<int32_t>> ids;               // per clip: the text ids of its segments, joined
     std::vector<std::vector<SttSeekSeg>> segs;           // per clip, in order
     std::vector<std::vector<SttSeekWin>> wins;           // per clip, in order
+    std::vector<std::vector<SttFbWin>> fb;               // per clip, a line per window under a fallback policy
     std::vector<float> score, lang_prob;
     std::vector<int32_t> lang;
 };
@@ -1409,11 +1797,15 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
     plan.h_req = o.h_language; plan.probe = probe; plan.ts = &rule;
     int64_t max_rounds = 1;
     for (int i = 0; i < n_clips; ++i) max_rounds = std::max<int64_t>(max_rounds, (n_samples[i] + tick - 1) / tick + 1);
-    const size_t per_group = (size_t)(STT_GROUP / beam_size);
+    const int per_window = s->fb_set ? std::max(beam_size, s->fb.best_of) : beam_size;
+    const size_t per_group = (size_t)(STT_GROUP / per_window);
     const int most = (int)std::min<size_t>((size_t)n_clips, per_group);
     RT_TRY(stt_group_reserve(s, most));
-    RT_TRY(stt_beam_reserve(s, most * beam_size));
+    RT_TRY(stt_beam_reserve(s, most * per_window));
     RT_TRY(stt_plan_begin(s, plan, n_clips));
+    std::vector<SttFbWin> fb_group;
+    if (s->fb_set) plan.fallback = &fb_group;
+    res.fb.assign(n_clips, {});
     res.ids.assign(n_clips, {}); res.segs.assign(n_clips, {}); res.wins.assign(n_clips, {});
     res.score.assign(n_clips, 0.f); res.lang_prob.assign(n_clips, 1.f); res.lang.assign(n_clips, 0);     // (round 0 fills both for every clip)
     std::vector<int64_t> off(n_clips, 0);
@@ -1428,7 +1820,7 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
     for (int64_t round = 0; round < max_rounds; ++round) {
         spans.clear();
         for (int i = 0; i < n_clips; ++i)
-            if (!done[i]) spans.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off[i] : nullptr, std::min<int64_t>(win, n_samples[i] - off[i])});
+            if (!done[i]) spans.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off[i] : nullptr, std::min<int64_t>(win, n_samples[i] - off[i]), (uint32_t)(off[i] / tick)});
         if (spans.empty()) break;
         for (size_t next = 0; next < spans.size(); next += per_group) {
             const int nW = (int)std::min(per_group, spans.size() - next);
@@ -1457,6 +1849,7 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
                 }
                 if (advance <= 0) advance = whole;                  // (a window that would not move its clip moves it by a whole window)
                 res.wins[i].push_back({i, off[i], (int)h.ids.size(), h.score, ns, advance});
+                if (plan.fallback) res.fb[i].push_back(fb_group[b]);
                 off[i] += (int64_t)advance * tick;
                 if (off[i] >= n_samples[i]) done[i] = 1;
             }
@@ -1774,14 +2167,16 @@ int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int64_t* n_
     rep.h_req = opts->h_language;
     rep.h_lang = out->h_language; rep.h_lang_prob = out->h_language_prob;
     rep.win_clip = out->h_win_clip; rep.win_n_ids = out->h_win_n_ids; rep.win_logprob = out->h_win_logprob; rep.win_no_speech = out->h_win_no_speech;
-    rep.probe = rep.win_no_speech != nullptr;
+    rep.probe = rep.win_no_speech != nullptr || (s->fb_set && s->fb.no_speech_threshold == s->fb.no_speech_threshold);
     RT_TRY(stt_check_languages(s, "rt_stt_transcribe_ex", "languages or no-speech probabilities", rep.h_req, n_clips, rep.probe));
     std::vector<SttSpan> all;
     stt_cut(s->cfg, sample_rate, d_pcm, n_samples, n_clips, all);
+    s->fb_report.clear();                                            // (rt_stt_fallback_report speaks of the last call under a policy)
     const bool per_window = rep.win_clip || rep.win_n_ids || rep.win_logprob || rep.win_no_speech;
     if (per_window && (size_t)out->window_cap < all.size())
         return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_transcribe_ex: %zu windows, room for %d", all.size(), out->window_cap);
-    RT_TRY(stt_transcribe_beam(s, all, n_clips, sample_rate, opts->beam_size, out->h_tokens, opts->max_tokens, out->h_n_tokens, out->h_scores, &rep));
+    const int rc = stt_transcribe_beam(s, all, n_clips, sample_rate, opts->beam_size, out->h_tokens, opts->max_tokens, out->h_n_tokens, out->h_scores, &rep);
+    if (rc != RT_OK) { s->fb_report.clear(); return rc; }           // (a failed call - the ratio callback's, say - leaves no partial report)
     out->n_windows = (int32_t)all.size();
     return RT_OK;
 }
@@ -1819,9 +2214,10 @@ int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* 
     out->n_segments = out->n_windows = out->max_clip_tokens = 0;
     if (n_clips == 0) return RT_OK;
     const bool silence = opts->no_speech_threshold == opts->no_speech_threshold;
-    bool probe = out->h_win_no_speech != nullptr || silence;
+    bool probe = out->h_win_no_speech != nullptr || silence || (s->fb_set && s->fb.no_speech_threshold == s->fb.no_speech_threshold);
     RT_TRY(stt_check_languages(s, "rt_stt_transcribe_seek", "languages, no-speech probabilities or the silence rule", opts->h_language, n_clips, probe));
     SttSeekResult res;
+    s->fb_report.clear();
     RT_TRY(stt_transcribe_seek(s, d_pcm, n_samples, n_clips, sample_rate, *opts, probe, res));
     const double tick_s = (double)(int64_t)(0.02 * (double)sample_rate) / (double)sample_rate;
     int64_t n_seg = 0, n_win = 0;
@@ -1843,6 +2239,7 @@ int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* 
             if (out->h_seg_end) out->h_seg_end[at] = (float)((double)g.end_tick * tick_s);
             if (out->h_seg_n_ids) out->h_seg_n_ids[at] = g.n_ids;
         }
+        if (s->fb_set) s->fb_report.insert(s->fb_report.end(), res.fb[i].begin(), res.fb[i].end());
         for (const SttSeekWin& w : res.wins[i]) {
             const int64_t at = n_win++;
             if (at >= out->window_cap) continue;
@@ -1859,6 +2256,43 @@ int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* 
     if (n_seg > out->segment_cap || n_win > out->window_cap)
         return rt_fail(ctx, RT_ERR_LENGTH, "rt_stt_transcribe_seek: %lld segments and %lld windows, room for %d and %d", (long long)n_seg, (long long)n_win,
                        out->segment_cap, out->window_cap);
+    return RT_OK;
+}
+
+int rt_stt_set_fallback(rt_stt* s, const rt_stt_fallback* f) {
+    if (!s) return RT_ERR_INVALID;
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_set_fallback: call after rt_stt_finalize");
+    if (!f) { s->fb_set = false; s->fb = rt_stt_fallback{}; return RT_OK; }
+    if (f->n_temperatures < 1 || f->n_temperatures > 8 || f->best_of < 1 || f->best_of > STT_BEAM_MAX)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_fallback: n_temperatures %d and best_of %d must lie in 1 .. 8", f->n_temperatures, f->best_of);
+    for (int t = 0; t < f->n_temperatures; ++t) {
+        const float T = f->temperatures[t];
+        if (!(T >= 0.f) || std::isinf(T) || (t > 0 && !(T > f->temperatures[t - 1])))
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_fallback: temperature %d (%g) is negative, not finite or not above the one before it", t, (double)T);
+    }
+    if (f->compression_ratio_threshold == f->compression_ratio_threshold && !f->ratio)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_fallback: a compression_ratio_threshold needs the ratio callback");
+    if (f->no_speech_threshold == f->no_speech_threshold && s->lang_ids.empty())
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_fallback: a no_speech_threshold needs a handle with rt_stt_set_languages");
+    s->fb = *f;
+    s->fb_set = true;
+    return RT_OK;
+}
+
+int rt_stt_fallback_report(rt_stt* s, int32_t cap, int32_t* h_attempts, float* h_temperature, float* h_ratio, int32_t* n_windows) {
+    if (!s || cap < 0 || !n_windows) return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_fallback_report: bad argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    const int32_t n = (int32_t)s->fb_report.size();
+    *n_windows = n;
+    for (int32_t w = 0; w < std::min(n, cap); ++w) {
+        if (h_attempts) h_attempts[w] = s->fb_report[w].attempts;
+        if (h_temperature) h_temperature[w] = s->fb_report[w].temperature;
+        if (h_ratio) h_ratio[w] = s->fb_report[w].ratio;
+    }
+    if (n > cap) return rt_fail(ctx, RT_ERR_LENGTH, "rt_stt_fallback_report: %d windows, room for %d", n, cap);
     return RT_OK;
 }
 
@@ -1952,6 +2386,80 @@ int rt_debug_stt_beam_step_ts(rt_stt* s, const float* d_logits, int32_t row_stri
     return stt_debug_beam_step("rt_debug_stt_beam_step_ts", s, d_logits, row_stride, h_scores_in, n_windows, beam, h_n_live, h_n_finished, h_done, first_step, step,
                                h_next_tok, h_parent, h_scores_out, h_n_live_out, h_fin_beam, h_fin_score, h_n_finished_out, h_done_out, h_live_windows, &rule,
                                h_ts_flags_in, h_ts_last_in, h_ts_flags_out, h_ts_last_out);
+}
+
+}  // extern "C"
+
+namespace {
+// rt_debug_stt_sample_step, and - ts given - rt_debug_stt_sample_step_ts: k_stt_sample_select over a book of its own (n_rows rows,
+// allocated for the call: the handle's decoder side is not grown for a test's row count)
+int stt_debug_sample_step(const char* who, rt_stt* s, const float* d_logits, int32_t row_stride, int32_t n_rows, int32_t samples, float temperature, uint64_t seed,
+                          int32_t temperature_index, const int32_t* h_key, const int32_t* h_sample, const float* h_scores_in, const int32_t* h_done,
+                          int32_t first_step, int32_t step, int32_t* h_next_tok, float* h_scores_out, float* h_win_val, int32_t* h_done_out, int32_t* h_live_rows,
+                          const SttTsRule* ts = nullptr, const int32_t* h_flags_in = nullptr, const int32_t* h_last_in = nullptr, int32_t* h_flags_out = nullptr,
+                          int32_t* h_last_out = nullptr) {
+    if (!s || !d_logits || !h_key || !h_sample || !h_scores_in || !h_done || !h_next_tok || !h_scores_out || !h_win_val || !h_done_out || !h_live_rows ||
+        n_rows < 1 || n_rows > 8192 || samples < 1 || samples > STT_BEAM_MAX || n_rows % samples || (row_stride != 1 && row_stride != samples) ||
+        !(temperature > 0.f) || std::isinf(temperature) || temperature_index < 0 || step < 0 || step >= s->cfg.max_new_tokens)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "%s: bad argument (1 .. 8192 rows in windows of `samples` 1 .. %d, row_stride 1 or samples, temperature > 0)",
+                       who, STT_BEAM_MAX);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "%s: not finalized", who);
+    const int R = n_rows, steps = step + 1;
+    const size_t book_n = stt_beam_book_words(R, steps), n = book_n + 3 * (size_t)R;       // book | key | sample | winning value
+    std::vector<int32_t> hb(n, 0);
+    SttBeamBook h = stt_beam_book(hb.data(), R, steps);
+    int live = 0;
+    for (int r = 0; r < R; ++r) {
+        h.score[r] = h_scores_in[r]; h.next_tok[r] = -1; h.src[r] = -1; h.done[r] = h_done[r] ? 1 : 0;
+        hb[book_n + r] = h_key[r]; hb[book_n + R + r] = h_sample[r];
+        live += h_done[r] ? 0 : 1;
+        if (ts) { h.ts_flags[r] = h_flags_in[r]; h.ts_last[r] = h_last_in[r]; }
+    }
+    *h.live = live;
+    int32_t* d_mem = nullptr;
+    RT_HIP(ctx, hipMalloc((void**)&d_mem, n * 4));
+    const SttBeamBook bk = stt_beam_book(d_mem, R, steps);
+    const SttSampleRule sr{temperature, (unsigned)(seed & 0xffffffffu), (unsigned)(seed >> 32), (unsigned)temperature_index, d_mem + book_n, d_mem + book_n + R};
+    int rc = hipMemcpyAsync(d_mem, hb.data(), n * 4, hipMemcpyHostToDevice, ctx->stream) == hipSuccess ? RT_OK : RT_ERR_HIP;
+    if (rc == RT_OK) rc = stt_sample_select(s, d_logits, row_stride, R, first_step ? 1 : 0, samples, step, bk, ts, sr, (float*)(d_mem + book_n + 2 * (size_t)R));
+    if (rc == RT_OK && hipMemcpyAsync(hb.data(), d_mem, n * 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = RT_ERR_HIP;
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d_mem);
+    if (rc != RT_OK) return rc == RT_ERR_HIP ? rt_fail(ctx, RT_ERR_HIP, "%s: a copy failed", who) : rc;
+    RT_HIP(ctx, e);
+    const float* val = (const float*)(hb.data() + book_n + 2 * (size_t)R);
+    for (int r = 0; r < R; ++r) {
+        h_next_tok[r] = h.next_tok[r]; h_scores_out[r] = h.score[r]; h_win_val[r] = val[r]; h_done_out[r] = h.done[r];
+        if (ts) { h_flags_out[r] = h.ts_flags[r]; h_last_out[r] = h.ts_last[r]; }
+    }
+    *h_live_rows = *h.live;
+    return RT_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rt_debug_stt_sample_step(rt_stt* s, const float* d_logits, int32_t row_stride, int32_t n_rows, int32_t samples, float temperature, uint64_t seed,
+                             int32_t temperature_index, const int32_t* h_key, const int32_t* h_sample, const float* h_scores_in, const int32_t* h_done,
+                             int32_t first_step, int32_t step, int32_t* h_next_tok, float* h_scores_out, float* h_win_val, int32_t* h_done_out, int32_t* h_live_rows) {
+    return stt_debug_sample_step("rt_debug_stt_sample_step", s, d_logits, row_stride, n_rows, samples, temperature, seed, temperature_index, h_key, h_sample,
+                                 h_scores_in, h_done, first_step, step, h_next_tok, h_scores_out, h_win_val, h_done_out, h_live_rows);
+}
+
+int rt_debug_stt_sample_step_ts(rt_stt* s, const float* d_logits, int32_t row_stride, int32_t n_rows, int32_t samples, float temperature, uint64_t seed,
+                                int32_t temperature_index, const int32_t* h_key, const int32_t* h_sample, const float* h_scores_in, const int32_t* h_done,
+                                int32_t first_step, int32_t step, int32_t max_initial_timestamp_index, const int32_t* h_ts_flags_in, const int32_t* h_ts_last_in,
+                                int32_t* h_next_tok, float* h_scores_out, float* h_win_val, int32_t* h_done_out, int32_t* h_live_rows, int32_t* h_ts_flags_out,
+                                int32_t* h_ts_last_out) {
+    if (!s || s->ts_begin <= 0 || !h_ts_flags_in || !h_ts_last_in || !h_ts_flags_out || !h_ts_last_out || max_initial_timestamp_index < -1)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_sample_step_ts: bad argument (a handle with rt_stt_set_timestamps, the rows' history state)");
+    const SttTsRule rule{s->ts_begin, s->ts_count, max_initial_timestamp_index};
+    return stt_debug_sample_step("rt_debug_stt_sample_step_ts", s, d_logits, row_stride, n_rows, samples, temperature, seed, temperature_index, h_key, h_sample,
+                                 h_scores_in, h_done, first_step, step, h_next_tok, h_scores_out, h_win_val, h_done_out,
+                                 h_live_rows, &rule, h_ts_flags_in, h_ts_last_in, h_ts_flags_out, h_ts_last_out);
 }
 
 int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src, int32_t len,

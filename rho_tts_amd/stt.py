@@ -234,6 +234,33 @@ class RtSttSeekOut(C.Structure):
                 ("max_clip_tokens", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+RATIO_FN = C.CFUNCTYPE(C.c_float, C.POINTER(C.c_int32), C.c_int32, C.c_void_p)     # rt_stt_ratio_fn
+MAX_TEMPERATURES = 8
+
+
+class RtSttFallback(C.Structure):
+    _fields_ = [("n_temperatures", C.c_int32), ("temperatures", C.c_float * 8), ("best_of", C.c_int32), ("compression_ratio_threshold", C.c_float),
+                ("logprob_threshold", C.c_float), ("no_speech_threshold", C.c_float), ("seed", C.c_uint64), ("ratio", RATIO_FN), ("ratio_user", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+def check_temperatures(temperatures) -> Tuple[float, ...]:
+    """The temperatures of a fallback policy: 1 .. 8 finite values >= 0, strictly ascending (so only the first may be 0)."""
+    ts = tuple(float(t) for t in ((temperatures,) if isinstance(temperatures, (int, float)) else temperatures))
+    if not 1 <= len(ts) <= MAX_TEMPERATURES or any(not (t >= 0.0 and math.isfinite(t)) for t in ts) or any(b <= a for a, b in zip(ts, ts[1:])):
+        raise ValueError(f"temperatures must be 1 .. {MAX_TEMPERATURES} finite values >= 0 in strictly ascending order, got {temperatures!r}")
+    return ts
+
+
+@dataclass
+class SttFallbackWindow:
+    """One window's line of ``NativeSTT.fallback_report``: the attempts made, the temperature of the chosen one and its compression
+    ratio (NaN when the policy has no ratio callback)."""
+    attempts: int
+    temperature: float
+    compression_ratio: float
+
+
 @dataclass
 class SttSegment:
     """One closed segment of a clip (transcribe_ids_seek): start and end in seconds of the clip (and in ticks of 0.02 s, which is what
@@ -244,6 +271,10 @@ class SttSegment:
     start_tick: int = 0
     end_tick: int = 0
     text: Optional[str] = None           # WhisperTranscriber.batch_segments fills it
+    # under a fallback policy (WhisperTranscriber(temperatures=...)), of the window that closed the segment
+    temperature: float = 0.0
+    attempts: int = 1
+    compression_ratio: float = float("nan")
 
 
 @dataclass
@@ -332,6 +363,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_stt_transcribe_ex.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(RtSttDecodeOpts), C.POINTER(RtSttDecodeOut)]
     lib.rt_stt_set_timestamps.argtypes = [vp, i32, i32]
     lib.rt_stt_transcribe_seek.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(RtSttSeekOpts), C.POINTER(RtSttSeekOut)]
+    lib.rt_stt_set_fallback.argtypes = [vp, C.POINTER(RtSttFallback)]
+    lib.rt_stt_fallback_report.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)]
     lib.rt_stt_log_mel.argtypes = [vp, vp, i64, i32, vp]
     lib.rt_stt_encode.argtypes = [vp, vp, i64, i32, vp]
     _DECLARED = True
@@ -728,6 +761,67 @@ class NativeSTT:
             clips[w_clip[w]].windows.append(SttSeekWindow(int(w_off[w]), int(w_n[w]), float(w_lp[w]), float(w_ns[w]) if out.h_win_no_speech else nan, int(w_adv[w])))
         return clips
 
+    def set_fallback(self, temperatures, best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                     no_speech_threshold: Optional[float] = None, seed: int = 789, ratio=None) -> None:
+        """The temperature fallback of ``transcribe_ids_ex`` and ``transcribe_ids_seek`` (rt_stt_set_fallback; the rule: DESIGN.md section
+        5, "temperature fallback", restated in validation.needs_fallback / pick_attempt): a window whose attempt compresses above
+        ``compression_ratio_threshold`` or averages below ``logprob_threshold`` is decoded again at the next of ``temperatures`` - 0:
+        the beam decode of the call's width; above 0: ``best_of`` sampled rows - over the encoder states the call still holds.
+        ``temperatures`` None clears the policy.  ``ratio``: a callable on the list of an attempt's text ids (default, with a
+        compression threshold: validation.compression_ratio_ids at the model's vocabulary; given without a threshold it decides
+        nothing and only fills the report).  It runs inside the
+        native call, on the calling thread, with the context locked: it must not call into this model or its context.  A threshold
+        of None is off; ``no_speech_threshold`` exempts silent windows (it needs a model with languages)."""
+        if not getattr(self, "handle", None):
+            raise ValueError("set_fallback: the model is closed")
+        if temperatures is None:
+            self.ctx.check(self.lib.rt_stt_set_fallback(self.handle, None), "rt_stt_set_fallback")
+            self._ratio_cb = None
+            return
+        ts = check_temperatures(temperatures)
+        if isinstance(best_of, bool) or not isinstance(best_of, (int, np.integer)) or not 1 <= int(best_of) <= MAX_BEAM:
+            raise ValueError(f"best_of must be an integer in 1 .. {MAX_BEAM}, got {best_of!r}")
+        nan = float("nan")
+        f = RtSttFallback()
+        f.n_temperatures, f.best_of, f.seed = len(ts), int(best_of), int(seed) & 0xFFFFFFFFFFFFFFFF
+        for i, t in enumerate(ts):
+            f.temperatures[i] = t
+        f.compression_ratio_threshold = nan if compression_ratio_threshold is None else float(compression_ratio_threshold)
+        f.logprob_threshold = nan if logprob_threshold is None else float(logprob_threshold)
+        f.no_speech_threshold = nan if no_speech_threshold is None else float(no_speech_threshold)
+        cb = None
+        if compression_ratio_threshold is not None or ratio is not None:     # (a callback without a threshold only fills the report)
+            if ratio is None:
+                from .validation import compression_ratio_ids
+                vocab = int(self.cfg.vocab)
+                ratio = lambda ids: compression_ratio_ids(ids, vocab)          # noqa: E731
+            if isinstance(ratio, RATIO_FN):
+                cb = ratio
+            else:
+                fn = ratio
+
+                def _ratio(p_ids, n, _user):
+                    try:
+                        return float(fn([int(p_ids[i]) for i in range(n)]))
+                    except Exception:  # noqa: BLE001  (nothing may unwind through the native frames: NaN fails the call there)
+                        return float("nan")
+                cb = RATIO_FN(_ratio)
+            f.ratio = cb
+        self.ctx.check(self.lib.rt_stt_set_fallback(self.handle, C.byref(f)), "rt_stt_set_fallback")
+        self._ratio_cb = cb                                          # (the library calls it for as long as the policy stands)
+
+    def fallback_report(self) -> List[SttFallbackWindow]:
+        """Per window of the last ``transcribe_ids_ex`` / ``transcribe_ids_seek`` call under a policy, in the order of that call's windows
+        (clip by clip): attempts, the chosen attempt's temperature and compression ratio."""
+        n = C.c_int32()
+        rc = self.lib.rt_stt_fallback_report(self.handle, 0, None, None, None, C.byref(n))
+        if rc not in (_native.RT_OK, _native.RT_ERR_LENGTH):
+            self.ctx.check(rc, "rt_stt_fallback_report")
+        k = n.value
+        att, tmp, rat = _i32(k), _f32(k), _f32(k)
+        self.ctx.check(self.lib.rt_stt_fallback_report(self.handle, k, att, tmp, rat, C.byref(n)), "rt_stt_fallback_report")
+        return [SttFallbackWindow(int(att[i]), float(tmp[i]), float(rat[i])) for i in range(n.value)]
+
     def log_mel(self, audio, sample_rate: int) -> torch.Tensor:
         """[n_mels][frames] float32 (the layout of WhisperFeatureExtractor's ``input_features``)."""
         x = self._pcm(audio)
@@ -773,6 +867,10 @@ class SttDetail:
     language_prob: float = float("nan")  # its probability where it was detected, 1 where it was given
     no_speech_prob: float = float("nan")  # the largest of the clip's windows
     windows_dropped: int = 0             # windows the silence rule left out
+    # under a fallback policy (WhisperTranscriber(temperatures=...)), per window of the clip; empty without one
+    temperature: List[float] = field(default_factory=list)
+    attempts: List[int] = field(default_factory=list)
+    compression_ratio: List[float] = field(default_factory=list)
 
 
 class WhisperTranscriber:
@@ -786,14 +884,19 @@ class WhisperTranscriber:
     provider's names) - it takes position 1 of the forced prefix - or "auto": every clip's language is detected on its first window
     (``transcribe_ids_ex``).  ``no_speech_threshold`` (None: off; Whisper's transcribers use 0.6) and ``logprob_threshold`` switch the
     silence rule on (validation.window_is_silent): ``__call__`` and ``batch`` then go through ``transcribe_ids_ex`` and leave out the
-    ids of silent windows, so that a silent clip is "" and not what the decoder makes up."""
+    ids of silent windows, so that a silent clip is "" and not what the decoder makes up.  ``temperatures``: the temperature fallback
+    (``NativeSTT.set_fallback``) - the default ``(0.0,)`` sets no policy; ``(0.0, 0.2, 0.4, 0.6, 0.8, 1.0)`` with ``best_of`` 5 and
+    ``compression_ratio_threshold`` 2.4 is what the reference's ``model.transcribe`` runs with; the ratio is
+    validation.compression_ratio_text of the attempt's text.  Calls then go through ``transcribe_ids_ex`` (or the seek call), and
+    ``batch_detailed`` / ``batch_segments`` report ``temperature``, ``attempts`` and ``compression_ratio`` per window."""
     auto, no_speech_threshold, logprob_threshold = False, None, -1.0
     _ex = False                          # calls go through transcribe_ids_ex (a detected language, or the silence rule)
     timestamps = False                   # calls go through transcribe_ids_seek (the reference's long-form rule; see below)
+    fallback = False                     # a fallback policy is set on the model (temperatures other than (0.0,))
 
     def __init__(self, ctx: "_native.Context", model_dir: Optional[str] = None, synthetic: bool = False, cfg: Optional[SttConfig] = None, seed: int = 789,
                  beam_size: int = 1, language: str = "en", no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = -1.0,
-                 timestamps: bool = False):
+                 timestamps: bool = False, temperatures=(0.0,), best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4):
         """``timestamps``: every call decodes with timestamp tokens and walks a clip longer than one window by seek positions
         (``transcribe_ids_seek``), as the reference's ``model.transcribe`` does; a clip's text is its segments' texts joined with a
         space (stt_validator.py:136), and ``batch_segments`` returns them with their times."""
@@ -824,13 +927,33 @@ class WhisperTranscriber:
         self.timestamps = bool(timestamps)
         check_timestamp_config(cfg, self.timestamps)
         self.cfg = cfg
+        temps = check_temperatures(temperatures)
         self.model = NativeSTT(ctx, cfg, state)
-        self._ex = self.auto or no_speech_threshold is not None        # calls that must go through transcribe_ids_ex
+        self.fallback = temps != (0.0,)
+        if self.fallback:
+            from .validation import compression_ratio_text
+            self.model.set_fallback(temps, best_of, compression_ratio_threshold, logprob_threshold, no_speech_threshold, seed,
+                                    ratio=lambda ids: compression_ratio_text(self._text(ids) or ""))
+        self._ex = self.auto or no_speech_threshold is not None or self.fallback       # calls that must go through transcribe_ids_ex
 
     def _seek(self, audios, sample_rate: int) -> List[SttSeekClip]:
         return self.model.transcribe_ids_seek(audios, sample_rate, self.beam_size, "auto" if self.auto else None,
                                               no_speech_threshold=self.no_speech_threshold, logprob_threshold=self.logprob_threshold,
                                               no_speech=bool(self.cfg.languages))
+
+    def _fallback_lines(self, clips) -> List[List[SttFallbackWindow]]:
+        """``fallback_report`` of the call that returned ``clips``, cut per clip (no policy: empty lists)."""
+        if not self.fallback:
+            return [[] for _ in clips]
+        lines, out, at = self.model.fallback_report(), [], 0
+        for c in clips:
+            out.append(lines[at:at + len(c.windows)])
+            at += len(c.windows)
+        return out
+
+    @staticmethod
+    def _fallback_fields(lines: List[SttFallbackWindow]) -> dict:
+        return dict(temperature=[w.temperature for w in lines], attempts=[w.attempts for w in lines], compression_ratio=[w.compression_ratio for w in lines])
 
     def _segment_text(self, ids: List[int]) -> str:
         """One segment's text as the reference's transcriber hands it over (unstripped: the join and the final strip are the caller's)."""
@@ -846,7 +969,18 @@ class WhisperTranscriber:
         if not self.timestamps:
             raise ValueError("batch_segments needs WhisperTranscriber(timestamps=True)")
         clips = self._seek(audios, sample_rate)
-        return [[dataclasses.replace(g, text=self._segment_text(g.ids).strip()) for g in c.segments] for c in clips]
+        tick = int(0.02 * sample_rate)
+        out = []
+        for c, lines in zip(clips, self._fallback_lines(clips)):
+            segs = []
+            for g in c.segments:
+                extra = {}
+                if lines:                                             # the window the segment lies in: the last one that starts at or before it
+                    k = max(i for i, w in enumerate(c.windows) if w.offset // tick <= g.start_tick)
+                    extra = dict(temperature=lines[k].temperature, attempts=lines[k].attempts, compression_ratio=lines[k].compression_ratio)
+                segs.append(dataclasses.replace(g, text=self._segment_text(g.ids).strip(), **extra))
+            out.append(segs)
+        return out
 
     def _run(self, audios, sample_rate: int, scored: bool = False, detailed: bool = False, single: bool = False) -> List[SttDetail]:
         """The one place where the configuration picks the native call; the public methods are projections of what it returns.
@@ -856,11 +990,12 @@ class WhisperTranscriber:
         from .validation import window_is_silent
         if self.timestamps:
             out = []
-            for c in self._seek(audios, sample_rate):
+            clips = self._seek(audios, sample_rate)
+            for c, lines in zip(clips, self._fallback_lines(clips)):
                 dropped = sum(1 for w in c.windows if window_is_silent(w.no_speech_prob, w.avg_logprob, self.no_speech_threshold, self.logprob_threshold))
                 ns = [w.no_speech_prob for w in c.windows if w.no_speech_prob == w.no_speech_prob]
                 out.append(SttDetail(self._joined(c), c.ids, c.score, self.cfg.language_code(c.language) or str(c.language), c.language_prob,
-                                     max(ns) if ns else float("nan"), dropped))
+                                     max(ns) if ns else float("nan"), dropped, **self._fallback_fields(lines)))
             return out
         if not (self._ex or detailed):
             if self.beam_size > 1 or scored:
@@ -868,9 +1003,11 @@ class WhisperTranscriber:
                 return [SttDetail(self._text(i), i, s) for i, s in zip(ids, scores)]
             ids = [self.model.transcribe_ids(audios[0], sample_rate)] if single else self.model.transcribe_ids_batch(audios, sample_rate)
             return [SttDetail(self._text(i), i) for i in ids]
-        clips = self.model.transcribe_ids_ex(audios, sample_rate, self.beam_size, "auto" if self.auto else None)
+        # (under a fallback policy a model without languages comes here too: it has no probe pass, and reports no no-speech probability)
+        kw = {"no_speech": False} if self.fallback and not self.cfg.languages else {}
+        clips = self.model.transcribe_ids_ex(audios, sample_rate, self.beam_size, "auto" if self.auto else None, **kw)
         out = []
-        for c in clips:
+        for c, lines in zip(clips, self._fallback_lines(clips)):
             ids, at, kept, dropped = [], 0, [], 0
             for w in c.windows:
                 own = c.ids[at:at + w.n_ids]                          # (a max_tokens cut leaves the last windows short)
@@ -883,7 +1020,7 @@ class WhisperTranscriber:
             over = kept or c.windows
             avg = sum(w.logprob for w in over) / sum(w.n_ids + 1 for w in over)
             out.append(SttDetail(self._text(ids), ids, avg, self.cfg.language_code(c.language) or str(c.language),
-                                 c.language_prob, max(w.no_speech_prob for w in c.windows), dropped))
+                                 c.language_prob, max(w.no_speech_prob for w in c.windows), dropped, **self._fallback_fields(lines)))
         return out
 
     def _text(self, ids: List[int]) -> Optional[str]:

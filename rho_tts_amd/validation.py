@@ -87,3 +87,55 @@ def window_is_silent(no_speech_prob: float, avg_logprob: float, no_speech_thresh
     if no_speech_threshold is None or not no_speech_prob > no_speech_threshold:
         return False
     return logprob_threshold is None or avg_logprob < logprob_threshold
+
+
+# ---------------------------------------------------------------------------------------------- temperature fallback
+# The rule of Whisper's transcribers that decides whether a decoded window is decoded again at the next temperature (DESIGN.md
+# section 5, "temperature fallback"; faster-whisper's generate_with_fallback, transformers' _need_fallback, openai-whisper's
+# decode_with_fallback), restated: the native loop (csrc/stt.hip stt_fallback_group) applies the same statements, and the compression
+# ratio reaches it as a callback, since it is zlib's.
+def compression_ratio_ids(ids, vocab: int) -> float:
+    """transformers' ``_retrieve_compression_ratio``: every id as ``int(log2(vocab) / 8) + 1`` little-endian bytes, the length of
+    those bytes over the length of their zlib compression."""
+    import math
+    import zlib
+    length = int(math.log2(int(vocab)) / 8) + 1
+    raw = b"".join(int(t).to_bytes(length, "little") for t in ids)
+    return len(raw) / len(zlib.compress(raw))
+
+
+def compression_ratio_text(text: str) -> float:
+    """faster-whisper's ``get_compression_ratio`` on a window's text: the UTF-8 bytes of the stripped text over their zlib compression."""
+    import zlib
+    raw = text.strip().encode("utf-8")
+    return len(raw) / len(zlib.compress(raw))
+
+
+def needs_fallback(compression_ratio: Optional[float], avg_logprob: float, no_speech_prob: float = float("nan"),
+                   compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                   no_speech_threshold: Optional[float] = None) -> bool:
+    """Whether one attempt at a window must be followed by another: its text compresses too well (``compression_ratio`` ABOVE its
+    threshold) or its average log-probability is BELOW its threshold - unless the window is silence (``window_is_silent`` with both
+    thresholds set), which the caller's silence rule deals with.  A threshold of None, or no ratio, switches that test off."""
+    needs = False
+    if compression_ratio_threshold is not None and compression_ratio is not None and compression_ratio > compression_ratio_threshold:
+        needs = True
+    if logprob_threshold is not None and avg_logprob < logprob_threshold:
+        needs = True
+    if no_speech_threshold is not None and logprob_threshold is not None and no_speech_prob > no_speech_threshold and avg_logprob < logprob_threshold:
+        needs = False
+    return needs
+
+
+def pick_attempt(attempts, compression_ratio_threshold: Optional[float] = 2.4) -> int:
+    """The attempt that stands when every temperature failed: ``attempts`` is a list of (compression_ratio or None, avg_logprob) in the
+    order they were made; the largest average among those within the compression threshold wins, among all when none is within it,
+    and the earliest on a tie."""
+    def within(r):
+        return compression_ratio_threshold is None or r is None or not r > compression_ratio_threshold
+    pool = [k for k, (r, _) in enumerate(attempts) if within(r)] or list(range(len(attempts)))
+    best = pool[0]
+    for k in pool[1:]:
+        if attempts[k][1] > attempts[best][1]:
+            best = k
+    return best
