@@ -434,8 +434,8 @@ RT_API int rt_stt_transcribe_ex(rt_stt* s, const float* const* d_pcm, const int6
 /* Clips longer than one window by timestamps and seek ("timestamps and seek"), as the reference's transcribers
  * walk them: every window is decoded WITH timestamp tokens under the step rule (transformers' WhisperTimeStampLogitsProcessor), and
  * the seek rule (_retrieve_segment) closes segments at timestamp pairs, discards an unfinished tail and starts the clip's next
- * window at the last closed pair's timestamp, so a word that straddles a boundary is decoded again whole.  No conditioning on
- * previous text.  Temperature fallback: rt_stt_set_fallback below.  A round holds one window per unfinished clip; rounds run in groups of
+ * window at the last closed pair's timestamp, so a word that straddles a boundary is decoded again whole.  Conditioning on
+ * previous text and an initial prompt: rt_stt_set_prompt below (off by default).  Temperature fallback: rt_stt_set_fallback below.  A round holds one window per unfinished clip; rounds run in groups of
  * floor(32 / beam_size) windows as rt_stt_transcribe_beam.  A clip's result is what it gets as the only clip of a call.
  * rt_stt_set_timestamps: timestamp ids [timestamp_begin, timestamp_begin + n_timestamps), n_timestamps = chunk_seconds / 0.02 + 1;
  *   timestamp_begin - 1 is <|notimestamps|>.  Before rt_stt_finalize.  RT_ERR_INVALID: the vocabulary does not hold the ids, the
@@ -526,6 +526,35 @@ typedef struct rt_stt_fallback {
 } rt_stt_fallback;
 RT_API int rt_stt_set_fallback(rt_stt* s, const rt_stt_fallback* f);
 RT_API int rt_stt_fallback_report(rt_stt* s, int32_t cap, int32_t* h_attempts, float* h_temperature, float* h_ratio, int32_t* n_windows);
+/* Conditioning on previous text and an initial prompt ("conditioning on previous text"; faster-whisper's
+ * condition_on_previous_text, prompt_reset_on_temperature and initial_prompt, which the reference's model.transcribe runs with at True,
+ * 0.5 and none).  A policy applies to rt_stt_transcribe_seek only: the fixed-cut calls decode a clip's windows side by side and have
+ * no "previous".  A clip's history starts as the initial prompt; every window that is not silent adds the ids of its closed segments,
+ * timestamps included (not a discarded tail, not a segment of no duration or without a text id).  A window's prompt is the history
+ * behind the clip's reset mark, cut to its last n_text_ctx / 2 - 1 ids; a window with a prompt decodes behind
+ * [sot_prev_id] + prompt + the timestamp-mode prefix, a window without one behind that prefix alone, in every attempt of a fallback
+ * policy.  Prompt ids are not scored and are no part of the generated history the step rule reads.  The window's budget is
+ * min(max_new_tokens, n_text_ctx - its prefix length).  After a window the mark moves to the end of the history when
+ * condition_on_previous is 0 or the window's chosen attempt ran at a temperature above reset_on_temperature (0 without a fallback
+ * policy).  A clip's result stays what it gets as the only clip of a call.
+ * rt_stt_set_prompt: after rt_stt_finalize, between calls; NULL clears the policy; h_initial is copied.  With no policy set every
+ *   entry point issues exactly the launches it issues without this feature and returns the same bits.  RT_ERR_INVALID (the policy is
+ *   unchanged): a handle without rt_stt_set_timestamps; sot_prev_id outside the vocabulary or not above end-of-sequence; an initial id
+ *   outside [0, vocab); a reset temperature that is negative or infinite; a policy that neither conditions nor carries an initial
+ *   prompt; a text context without room for a prompt behind the forced prefix.
+ * rt_stt_prompt_report: per window of the last rt_stt_transcribe_seek call under a policy, in the order of that call's per-window
+ *   arrays: the length of the prompt the window used and whether the reset mark moved behind it.  Each array optional; n_windows
+ *   receives the count; RT_ERR_LENGTH (nothing past cap is written) when cap is below it. */
+typedef struct rt_stt_prompt {
+    int32_t sot_prev_id;               /* <|startofprev|> */
+    int32_t condition_on_previous;     /* 0 / 1 */
+    float reset_on_temperature;        /* NaN: never reset */
+    const int32_t* h_initial;          /* copied by the call; NULL / 0: none */
+    int32_t n_initial;
+    int32_t reserved[4];
+} rt_stt_prompt;
+RT_API int rt_stt_set_prompt(rt_stt* s, const rt_stt_prompt* p);
+RT_API int rt_stt_prompt_report(rt_stt* s, int32_t cap, int32_t* h_prompt_len, int32_t* h_reset, int32_t* n_windows);
 /* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM:
  * row 0 of the same front end and encoder with the clip as its only window.  Of a clip longer than chunk_seconds the first
  * chunk is kept, and the resampler's taps at its end see the samples behind it. */

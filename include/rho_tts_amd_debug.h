@@ -130,6 +130,18 @@ RT_API int rt_debug_stt_beam_step(rt_stt* s, const float* d_logits, int32_t row_
                                   float* h_fin_score, int32_t* h_n_finished_out, int32_t* h_done_out, int32_t* h_live_windows);
 RT_API int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src,
                                      int32_t len, uint16_t* h_planes);
+/* The kernels of a prompt policy on their own (rt_stt_set_prompt; tests/test_stt_prompt_kernel_gpu.py).
+ * rt_debug_stt_beam_reorder_range: rt_debug_stt_beam_reorder with a range per row - row h_src[r]'s positions [h_lo[r], h_hi[r]),
+ *   0 <= lo <= hi <= max_pos, go into row r of the second cache; everything else of it keeps the sentinel.
+ * rt_debug_stt_prompt_prefix: the ragged prefix pass.  The first window of n_windows clips (1 .. 32) goes through the front end and
+ *   the encoder; window w then decodes the h_len[w] tokens it is given (h_tokens: the windows' tokens one after the other, each an id
+ *   of the vocabulary; 1 .. min(n_text_ctx / 2 + n_prefix - 1, n_text_ctx - 1) per window) at positions 0 .. h_len[w] - 1 of a cache
+ *   slot of its own, all windows' rows in ONE pass, and d_logits [n_windows][vocab] (HBM, float32) receives the logits of every
+ *   window's last row.  A window's logits do not depend on what it shares the pass with. */
+RT_API int rt_debug_stt_beam_reorder_range(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src,
+                                           const int32_t* h_lo, const int32_t* h_hi, uint16_t* h_planes);
+RT_API int rt_debug_stt_prompt_prefix(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_windows, int32_t sample_rate_in,
+                                      const int32_t* h_tokens, const int32_t* h_len, float* d_logits);
 /* rt_debug_stt_beam_step under the timestamp rule (tests/test_stt_seek_kernel_gpu.py; a handle with rt_stt_set_timestamps): the step
  * as rt_stt_transcribe_seek launches it.  Further in, per row: the history state - h_ts_flags_in bit 0: the row's last generated
  * token is a timestamp, bit 1: the one before it is (or the history holds fewer than two tokens); h_ts_last_in: the last timestamp
@@ -329,11 +341,17 @@ RT_API int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t
  *   3000/3001 the codec decoder's 192-channel residual units as two launches / one fused launch (k = 7 with tap unrolling; 2100 switches both widths off)
  *   3100/3101 predictor passes 2..G-1: layer 0's qkv GEMM launch / its q/k/v row copied from the per-code table built by rt_model_finalize
  *   3200/3201 generations on 65..128 rows: two 64-row decode GEMM launches per weight matrix / one 128-row launch (same bits)
+ *   3300/3301 speech-to-text under a prompt policy, the cache gather between beam steps: positions [0, longest prefix + step) of every row / each row's generated positions only (same bits)
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
 RT_API int rt_debug_tune(int32_t code, int32_t arg);
 RT_API int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_norm, int32_t epi, int32_t n_mats, int32_t iters,
                              double* avg_us, int64_t* stamps8);
+/* The cache gather between two beam steps of the speech-to-text decoder on its own (tools/bench_stt_prompt.py): two caches of
+ * [layers][rows][heads][max_pos][head_dim] x 4 planes, neighbouring rows swap; microseconds per launch (device events over `iters`
+ * launches back to back) of the ranged form over positions [prefix, prefix + step) and of the uniform form over [0, prefix + step). */
+RT_API int rt_bench_stt_gather(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, int32_t prefix, int32_t step,
+                               int32_t iters, double* us_ranged, double* us_uniform);
 RT_API int rt_bench_launch(rt_ctx* ctx, int32_t grid_wgs, int32_t n, int32_t use_graph, int32_t reps, double* us_per_launch);
 RT_API int rt_bench_grid_barrier(rt_ctx* ctx, int32_t wgs, int32_t threads, int32_t n, int32_t mode, double* us_per_barrier, int32_t* aborted);
 RT_API int rt_bench_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_t V, const rt_sampling* sp, int32_t iters, double* avg_us,

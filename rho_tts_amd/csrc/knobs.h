@@ -49,7 +49,9 @@
         "that embeds the code), 0 the layer-0 qkv GEMM launch runs (same bits either way)") \
     X(3200, g_col_rows128, 1, 0, 1, "generations on 65..128 rows: 1 one 128-row decode GEMM launch per weight matrix (k_gemm_col MT = 8: the weights are streamed once), " \
         "0 two 64-row launches (same bits either way).  Measured (1.7B, profiles/r18_rows128.txt): bench.py --corpus 512 --batch 128 1014 audio-s/s with 1 against 887 with 0 (five alternating pairs; 824 on 64 rows); " \
-        "per launch at 128 rows qkv 13.7 / 16.3 us, o 12.0 / 14.2, gate/up 20.9 / 27.4, down 27.3 / 29.7 (one launch / two)")
+        "per launch at 128 rows qkv 13.7 / 16.3 us, o 12.0 / 14.2, gate/up 20.9 / 27.4, down 27.3 / 29.7 (one launch / two)") \
+    X(3300, g_stt_gather_ranged, 1, 0, 1, "speech-to-text under a prompt policy, the gather between beam steps: 1 the ranged form (generated positions only; the prefix " \
+        "sits in both caches), 0 the uniform form over [0, longest prefix of the group + step) (same bits either way; profiles/r20_stt_prompt.txt)")
 
 // The one switch set by rt_debug_tune's SECOND argument: applied when the code is 0..2 and the argument lies in lo..hi.
 #define RT_KNOB_ARG(X) \

@@ -42,6 +42,13 @@
 // best_of rows per window, k_stt_sample_select: Gumbel-max over the ids the step rules leave - over the encoder states the group
 // still holds.  Off unless a policy is set; no other entry point changes.
 //
+// rt_stt_set_prompt gives rt_stt_transcribe_seek the reference's conditioning on previous text and an initial prompt (DESIGN.md section
+// 5, "conditioning on previous text"): the host keeps a history and a reset mark per clip, and a window with a prompt decodes behind
+// <|startofprev|> + prompt + prefix.  The windows of a group then have prefixes of different lengths: one ragged prefix pass over
+// sum(P_w) rows under row tables (stt_prompt_tables, stt_decode_tab), per-window positions and budgets at every step (k_stt_retire),
+// and a gather between beam steps that moves generated positions only (k_stt_beam_reorder_range).  Off unless a policy is set; no
+// other entry point changes.
+//
 // The three beam entry points run their groups through one driver (stt_run_group) under one plan (SttPlan: the clips' language
 // requests, whether the probe runs, the timestamp rule); what each keeps for itself is how it forms its groups and what it makes of
 // the hypotheses - fixed cuts and joined ids (stt_transcribe_beam), rounds, offsets and the seek rule (stt_transcribe_seek).
@@ -50,6 +57,7 @@
 #include <map>
 
 #include "kernels.h"
+#include "knobs.h"
 #include "resample.h"
 
 namespace {
@@ -791,6 +799,58 @@ __global__ void k_stt_fill_beam_rows(int32_t* __restrict__ pre_slot, int32_t* __
     }
 }
 
+// ---------------------------------------------------------------------------------------------- conditioning on previous text (rt_stt_set_prompt)
+// The kernels of a prompt policy ("conditioning on previous text"): windows of one group decode behind prefixes
+// of different lengths, so every row of a pass takes its position from a table the host laid out and proved in range.
+//
+// x[r][:] = token_embedding[tok[r]] + position_embedding[pos[r]]: k_stt_embed with the row's position read from a table
+__global__ void k_stt_embed_rows(const bf16_t* __restrict__ tok_emb, const float* __restrict__ pos_emb, const int32_t* __restrict__ tok,
+                                 const int32_t* __restrict__ pos, int D, float* __restrict__ x) {
+    const int r = blockIdx.x;
+    const int64_t t = tok[r], at = pos[r];
+    for (int i = threadIdx.x; i < D; i += blockDim.x) x[(int64_t)r * D + i] = bf16_to_f32(tok_emb[t * D + i]) + pos_emb[at * D + i];
+}
+// The tokens of a ragged prefix pass: the host lays a window's prompt ids out as they are and writes -(1 + k) where entry k of the
+// window's forced prefix goes - the device may have decided its language (k_stt_lang_prefix) - which this kernel fills in
+__global__ void k_stt_prompt_tokens(int32_t* __restrict__ tok, const int32_t* __restrict__ win, int n, const int32_t* __restrict__ win_prefix, int P) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int t = tok[i];
+        const int forced = win_prefix[win[i] * P + min(max(-t - 1, 0), P - 1)];      // (asked for whatever t is: no load behind a per-lane branch)
+        tok[i] = t < 0 ? forced : t;
+    }
+}
+// out[w][:] = x[rows[w]][:]: the last prefix row of every window, dense, for the final LayerNorm (D is a multiple of 8)
+__global__ void k_stt_take_rows(const float* __restrict__ x, const int32_t* __restrict__ rows, int D, float* __restrict__ out) {
+    const float4* s4 = (const float4*)(x + (int64_t)rows[blockIdx.x] * D);
+    float4* d4 = (float4*)(out + (int64_t)blockIdx.x * D);
+    for (int i = threadIdx.x; i < D / 4; i += blockDim.x) d4[i] = s4[i];
+}
+// k_stt_beam_reorder with a range per row: positions [lo[r], hi[r]) of slot src[r] go to slot r of the other cache (skip_self: the
+// two caches are one, and a row that continues itself has nothing to move).  The prefix of a window never diverges between its rows,
+// so it is written into both caches once and the gather between steps moves the generated positions alone.
+__global__ __launch_bounds__(256) void k_stt_beam_reorder_range(SttKvPlanes p, const int32_t* __restrict__ src, const int32_t* __restrict__ lo,
+                                                                const int32_t* __restrict__ hi, int slots, int heads, int max_pos, int head_dim, int skip_self) {
+    const int h = blockIdx.x, r = blockIdx.y, l = blockIdx.z;
+    const int from = src[r], a0 = max(lo[r], 0), a1 = min(hi[r], max_pos);
+    if (from < 0 || from >= slots || a1 <= a0 || (skip_self && from == r)) return;
+    const int64_t per = (int64_t)max_pos * head_dim;
+    const int64_t a = (((int64_t)l * slots + from) * heads + h) * per + (int64_t)a0 * head_dim;
+    const int64_t b = (((int64_t)l * slots + r) * heads + h) * per + (int64_t)a0 * head_dim;
+    const int n16 = (a1 - a0) * head_dim / 8;              // (head_dim is a multiple of 32)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint4* s4 = (const uint4*)(p.src[q] + a);
+        uint4* d4 = (uint4*)(p.dst[q] + b);
+        for (int i = threadIdx.x; i < n16; i += 256) d4[i] = s4[i];
+    }
+}
+// A unit (a window of the beam path, a row of the sampled path) whose budget is `step` stops: its done flag is set and it leaves
+// `live`, as if it had ended - the select kernels then pass it by, and the host offers what it holds to the ranker
+__global__ void k_stt_retire(int32_t* __restrict__ done, int32_t* __restrict__ live, const int32_t* __restrict__ budget, int n, int step) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n && budget[k] == step && !done[k]) { done[k] = 1; atomicSub(live, 1); }
+}
+
 }  // namespace
 
 // Windows of one group: the rows of every launch.  Compile-time: the group's buffers - about 79 MB per window at Whisper-tiny
@@ -852,6 +912,30 @@ struct SttBeam {
     std::vector<void*> owned;
 };
 
+// The device side of a prompt policy (rt_stt_set_prompt), for groups of `wins` windows and `rows` decoder rows: the workspaces of the
+// ragged prefix pass - one row per prefix token of every window, at most max_prefix each - and the tables of one decode.  Nothing of
+// it exists until a policy is first used; it grows with the group as the beam path's set does.  The existing sets are not enlarged.
+struct SttPrompt {
+    int wins = 0, rows = 0;
+    SttWork work;                       // [wins max_prefix] rows
+    float* xlast = nullptr;             // [wins][D] every window's last prefix row, dense
+    int32_t* enc_last = nullptr;        // [wins max_prefix] n_ctx - 1 throughout
+    int32_t* tab = nullptr;             // the tables of one decode (SttPrTab), uploaded in one copy
+    size_t tab_n = 0;
+    std::vector<void*> owned;
+};
+// The tables of one decode under a prompt policy, as offsets into SttPrompt::tab (and into the host copy they are laid out in).  M
+// rows of the prefix pass: cache slot of the window's first decoder row, position, window of the group, token (-(1 + k): entry k of
+// the window's forced prefix, k_stt_prompt_tokens).  Per window: its last prefix row and its budget.  Per decoder row: its budget,
+// its prefix length, zero, its window's first row; per step and row: the position the step's pass writes and the end of the range
+// the gather before it moves, both clamped to what the row's budget allows - a window whose budget is spent rides along in place.
+struct SttPrTab {
+    int M = 0, nW = 0, rows = 0, steps = 0, longest = 0;      // steps: the largest budget of the group; longest: its longest prefix
+    size_t pre_slot = 0, pre_pos = 0, pre_win = 0, pre_tok = 0, last_row = 0, win_budget = 0, row_budget = 0, base = 0, zero = 0, fan_src = 0, step_pos = 0,
+           step_hi = 0, total = 0;
+    std::vector<char> retire_win, retire_row;    // [steps + 1] a window / a row has this budget, below the largest
+};
+
 // One window's line of rt_stt_fallback_report
 struct SttFbWin { int32_t attempts = 1; float temperature = 0.f, ratio = NAN; };
 
@@ -893,6 +977,15 @@ struct rt_stt {
     rt_stt_fallback fb{};
     std::vector<SttFbWin> fb_report;
     std::vector<int32_t> h_smp;
+    // rt_stt_set_prompt: the policy (pr_set: one is set; pr_initial: the copy of its initial prompt), its device side, the tables of the
+    // decode in flight with their host copy, and per window of the last seek call what rt_stt_prompt_report returns
+    bool pr_set = false;
+    rt_stt_prompt pr{};
+    std::vector<int32_t> pr_initial;
+    SttPrompt prm;
+    SttPrTab pr_tab;
+    std::vector<int32_t> h_prm;
+    std::vector<std::pair<int32_t, int32_t>> pr_report;      // (prompt length, the reset mark moved behind the window)
     std::vector<void*> owned;
 };
 
@@ -1306,6 +1399,146 @@ int stt_beam_reorder(rt_ctx* ctx, const KvCache& from, const KvCache& to, const 
     return RT_OK;
 }
 
+// The ranged form: row r takes positions [lo[r], hi[r]) of row src[r]; `from` and `to` may be one cache (rows that continue themselves
+// are passed by).  The caller has proved 0 <= lo <= hi <= max_pos on the host; the kernel clamps all the same.
+int stt_beam_reorder_range(rt_ctx* ctx, const KvCache& from, const KvCache& to, const int32_t* d_src, const int32_t* d_lo, const int32_t* d_hi, int rows) {
+    if (rows <= 0) return RT_OK;
+    SttKvPlanes p{{from.k, from.v, from.k_lo, from.v_lo}, {to.k, to.v, to.k_lo, to.v_lo}};
+    hipLaunchKernelGGL(k_stt_beam_reorder_range, dim3(from.kv_heads, rows, from.layers), dim3(256), 0, ctx->stream, p, d_src, d_lo, d_hi, from.slots, from.kv_heads,
+                       from.max_pos, from.head_dim, from.k == to.k ? 1 : 0);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- conditioning on previous text (host side)
+// The longest prompt a window takes, and the longest prefix that makes: <|startofprev|>, the prompt, the timestamp-mode prefix
+int stt_prompt_cap(const rt_stt_config& c) { return c.n_text_ctx / 2 - 1; }
+int stt_max_prefix(const rt_stt_config& c) { return 1 + stt_prompt_cap(c) + c.n_prefix - 1; }
+
+// The prompt side holds at least `wins` windows and `rows` decoder rows (stt_reserve, as the beam path's)
+int stt_prompt_reserve(rt_stt* s, int wins, int rows) {
+    if (s->prm.wins >= wins && s->prm.rows >= rows) return RT_OK;
+    wins = std::max(wins, s->prm.wins); rows = std::max(rows, s->prm.rows);
+    return stt_reserve(s, s->prm, [&](SttPrompt& np) -> int {
+        const rt_stt_config& c = s->cfg;
+        const size_t cr = (size_t)wins * stt_max_prefix(c);
+        RT_TRY(stt_alloc_work(s, np.owned, cr, np.work));
+        RT_TRY(stt_alloc(s, np.owned, (size_t)wins * c.d_model, &np.xlast));
+        RT_TRY(stt_alloc(s, np.owned, cr, &np.enc_last));
+        np.tab_n = 4 * cr + 2 * (size_t)wins + 4 * (size_t)rows + 2 * (size_t)c.max_new_tokens * rows;
+        RT_TRY(stt_alloc(s, np.owned, np.tab_n, &np.tab));
+        hipLaunchKernelGGL(k_stt_fill_i32, dim3(64), dim3(256), 0, s->ctx->stream, np.enc_last, (int)cr, c.n_ctx - 1, 0);
+        RT_HIP(s->ctx, hipGetLastError());
+        np.wins = wins; np.rows = rows;
+        return RT_OK;
+    });
+}
+
+// Lays the tables of one decode out in s->h_prm (SttPrTab) and uploads them: nN windows of `per` decoder rows each, window k of the
+// decode being window need[k] of the group (null: k itself) with the prefix tokens toks[k] (forced entries as markers).  Memory
+// safety is decided here, before the decode's first launch: every prefix length, every position a pass will write and every table
+// entry is checked against what was allocated; a failure launches nothing.
+int stt_prompt_tables(rt_stt* s, const std::vector<std::vector<int32_t>>& toks, const int* need, int nN, int per) {
+    const rt_stt_config& c = s->cfg;
+    const SttPrompt& pm = s->prm;
+    SttPrTab& t = s->pr_tab;
+    t = SttPrTab{};
+    t.nW = nN; t.rows = nN * per;
+    for (int k = 0; k < nN; ++k) {
+        const int P = (int)toks[k].size();
+        if (P < 1 || P > stt_max_prefix(c) || P > c.n_text_ctx - 1) return rt_fail(s->ctx, RT_ERR_INVALID, "prompt: a prefix of %d tokens (1 .. %d)", P, std::min(stt_max_prefix(c), c.n_text_ctx - 1));
+        t.M += P;
+        t.longest = std::max(t.longest, P);
+        t.steps = std::max(t.steps, std::min(c.max_new_tokens, c.n_text_ctx - P));
+    }
+    if (nN < 1 || nN > pm.wins || t.rows > pm.rows || t.rows > s->beam.rows || (size_t)t.M > (size_t)pm.wins * stt_max_prefix(c))
+        return rt_fail(s->ctx, RT_ERR_INVALID, "prompt: %d windows of %d rows do not fit the buffers reserved for them", nN, per);
+    size_t at = 0;
+    auto take = [&](size_t n) { const size_t q = at; at += n; return q; };
+    t.pre_slot = take(t.M); t.pre_pos = take(t.M); t.pre_win = take(t.M); t.pre_tok = take(t.M);
+    t.last_row = take(nN); t.win_budget = take(nN);
+    t.row_budget = take(t.rows); t.base = take(t.rows); t.zero = take(t.rows); t.fan_src = take(t.rows);
+    t.step_pos = take((size_t)t.steps * t.rows); t.step_hi = take((size_t)t.steps * t.rows);
+    t.total = at;
+    if (t.total > pm.tab_n) return rt_fail(s->ctx, RT_ERR_INVALID, "prompt: tables of %zu entries, room for %zu", t.total, pm.tab_n);
+    t.retire_win.assign(t.steps + 1, 0); t.retire_row.assign(t.steps + 1, 0);
+    std::vector<int32_t>& h = s->h_prm;
+    h.assign(t.total, 0);
+    int row = 0;
+    for (int k = 0; k < nN; ++k) {
+        const int P = (int)toks[k].size(), budget = std::min(c.max_new_tokens, c.n_text_ctx - P);     // (P + budget - 1 <= n_text_ctx - 1)
+        for (int i = 0; i < P; ++i, ++row) {
+            h[t.pre_slot + row] = k * per; h[t.pre_pos + row] = i; h[t.pre_win + row] = need ? need[k] : k; h[t.pre_tok + row] = toks[k][i];
+        }
+        h[t.last_row + k] = row - 1;
+        h[t.win_budget + k] = budget;
+        if (budget < t.steps) t.retire_win[budget] = t.retire_row[budget] = 1;
+        for (int r = k * per; r < (k + 1) * per; ++r) {
+            h[t.row_budget + r] = budget; h[t.base + r] = P; h[t.fan_src + r] = k * per;
+            for (int st = 0; st < t.steps; ++st) {
+                h[t.step_pos + (size_t)st * t.rows + r] = std::min(P + st, P + budget - 1);
+                h[t.step_hi + (size_t)st * t.rows + r] = std::min(P + st, P + budget);
+            }
+        }
+    }
+    RT_HIP(s->ctx, hipMemcpyAsync(pm.tab, h.data(), t.total * 4, hipMemcpyHostToDevice, s->ctx->stream));
+    return RT_OK;
+}
+
+// M decoder rows under row tables - row r: token tok[r] at position pos[r] of slot slot[r] of `kv`, over slot cross_slot[r] of the
+// cross-attention cache - through the launches stt_decode_rows issues, with the embedding reading the row's position from the
+// table.  take (null: every row, n_out = M): the rows whose logits are wanted, n_out of them -> d_logits [n_out][vocab].
+int stt_decode_tab(rt_stt* s, const SttWork& k, const KvCache& kv, const KvCache& cross, int M, const int32_t* tok, const int32_t* slot, const int32_t* pos,
+                   const int32_t* cross_slot, const int32_t* enc_last, const int32_t* take, int n_out, float* d_logits) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    const int D = c.d_model;
+    SttSlot* emb = stt_find(s, "dec.tok");
+    hipLaunchKernelGGL(k_stt_embed_rows, dim3(M), dim3(128), 0, ctx->stream, emb->tbl, SVEC(s, "dec.pos"), tok, pos, D, k.x);
+    RT_HIP(ctx, hipGetLastError());
+    for (int i = 0; i < c.dec_layers; ++i) RT_TRY(stt_layer(s, "dec.l" + std::to_string(i), k, M, kv, i, slot, pos, pos, 0, &cross, cross_slot, enc_last));
+    const float* last = k.x;
+    if (take) {
+        hipLaunchKernelGGL(k_stt_take_rows, dim3(n_out), dim3(64), 0, ctx->stream, k.x, take, D, s->prm.xlast);
+        RT_HIP(ctx, hipGetLastError());
+        last = s->prm.xlast;
+    }
+    RT_TRY(stt_ln(s, last, D, n_out, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), k.xn));
+    RT_TRY(stt_gemm(s, k.xn, n_out, emb->pw, nullptr, ACT_NONE, nullptr, d_logits));
+    return RT_OK;
+}
+
+// The ragged prefix pass of the decode whose tables are up (s->pr_tab): every window's prefix rows in one pass into the cache slot of
+// the window's first row of `kv`, the logits of every window's last prefix row -> d_logits [nW][vocab].  resolve: the forced entries
+// are markers, filled in from s->d_win_prefix first (P entries per window of the group).
+int stt_prompt_prefix_pass(rt_stt* s, const KvCache& kv, float* d_logits, bool resolve, int P) {
+    const SttPrTab& t = s->pr_tab;
+    int32_t* tab = s->prm.tab;
+    if (resolve) {
+        hipLaunchKernelGGL(k_stt_prompt_tokens, dim3((t.M + 255) / 256), dim3(256), 0, s->ctx->stream, tab + t.pre_tok, tab + t.pre_win, t.M, s->d_win_prefix, P);
+        RT_HIP(s->ctx, hipGetLastError());
+    }
+    return stt_decode_tab(s, s->prm.work, kv, s->grp.enc.cross_kv, t.M, tab + t.pre_tok, tab + t.pre_slot, tab + t.pre_pos, tab + t.pre_win, s->prm.enc_last,
+                          tab + t.last_row, t.nW, d_logits);
+}
+// The prefix tokens of a window under a prompt policy: <|startofprev|>, the prompt and the P forced entries (as markers), or - without
+// a prompt - the forced entries alone
+void stt_prompt_prefix_tokens(rt_stt* s, const std::vector<int32_t>& prompt, int P, std::vector<int32_t>& out) {
+    out.clear();
+    if (!prompt.empty()) { out.push_back(s->pr.sot_prev_id); out.insert(out.end(), prompt.begin(), prompt.end()); }
+    for (int k = 0; k < P; ++k) out.push_back(-(1 + k));
+}
+// Units (windows of the beam path, rows of the sampled one) whose budget is `step` stop before that step
+int stt_retire(rt_stt* s, const SttBeamBook& bk, bool by_row, int step) {
+    const SttPrTab& t = s->pr_tab;
+    const std::vector<char>& at = by_row ? t.retire_row : t.retire_win;
+    if (step >= (int)at.size() || !at[step]) return RT_OK;
+    const int n = by_row ? t.rows : t.nW;
+    hipLaunchKernelGGL(k_stt_retire, dim3((n + 63) / 64), dim3(64), 0, s->ctx->stream, bk.done, bk.live, s->prm.tab + (by_row ? t.row_budget : t.win_budget), n, step);
+    RT_HIP(s->ctx, hipGetLastError());
+    return RT_OK;
+}
+
 // What beam search gives for one window: the ids of the chosen hypothesis, its cumulative log-probability and the tokens it counts
 // (the ids and end-of-sequence)
 struct SttHyp { std::vector<int32_t> ids; float score = 0.f; int count = 1; };
@@ -1323,6 +1556,9 @@ struct SttPlan {
     // a fallback policy is set (rt_stt_set_fallback): the group's windows go through stt_fallback_group, which leaves here, per window
     // of the group, what rt_stt_fallback_report returns
     std::vector<SttFbWin>* fallback = nullptr;
+    // a prompt policy is set (rt_stt_set_prompt; timestamp mode only): per window of the group the prompt ids it decodes behind (empty:
+    // none).  The group then runs the ragged prefix pass and per-window budgets (stt_prompt_tables), whatever the prompts' lengths
+    const std::vector<int32_t>* prompt = nullptr;
     bool per_window() const { return h_req || probe || ts; }
     int n_prefix(const rt_stt_config& c) const { return ts ? c.n_prefix - 1 : c.n_prefix; }
 };
@@ -1398,16 +1634,40 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
         if (plan.probe) RT_TRY(stt_probe_group(s, nW, P));
         bm.dec.tok = s->d_win_prefix;        // (without a probe every language is given: stt_run_group has copied the prefixes in)
     }
-    RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
-    const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
+    // under a prompt policy (stt_run_group has laid the tables out): the ragged prefix pass, then the prefix - which never diverges
+    // between a window's beams - into every row's slot of BOTH caches, so that the gather between steps moves generated positions only
+    const SttPrTab* pt = plan.prompt ? &s->pr_tab : nullptr;
+    const int32_t* tab = s->prm.tab;
+    if (pt) {
+        RT_TRY(stt_prompt_prefix_pass(s, bm.dec.kv, bm.dec.logits, true, P));
+        RT_TRY(stt_beam_reorder_range(ctx, bm.dec.kv, bm.dec.kv, tab + pt->fan_src, tab + pt->zero, tab + pt->base, rows));
+        RT_TRY(stt_beam_reorder_range(ctx, bm.dec.kv, bm.kv_next, tab + pt->fan_src, tab + pt->zero, tab + pt->base, rows));
+    } else {
+        RT_TRY(stt_decode_rows(s, bm.dec, cross, nW, P, 0, bm.pre_slot, bm.pre_pos, bm.pre_win));
+    }
+    const int budget = pt ? pt->steps : std::min(c.max_new_tokens, c.n_text_ctx - P);
     int steps = 0;
     for (int step = 0; step < budget; ++step) {
         RT_TRY(stt_beam_select(s, bm.dec.logits, step == 0 ? 1 : B, nW, step == 0 ? 1 : 0, B, step, bk, plan.ts));
         steps = step + 1;
+        if (pt) RT_TRY(stt_retire(s, bk, false, step + 1));      // (a window whose budget is spent: before the read, which then counts it out)
         int32_t live = 0;
         RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (live <= 0 || step + 1 >= budget) break;
+        if (pt) {
+            if (!g_stt_gather_ranged) {         // (the A/B of the ranged form: what the gather costs when it moves the prefix at every step)
+                // (a short-prefix window sets the step count and a long-prefix one the length: cut at the cache's end)
+                RT_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, std::min(pt->longest + step, c.n_text_ctx)));
+                std::swap(bm.dec.kv, bm.kv_next);
+            } else if (step > 0) {              // (behind the first step nothing is generated yet, and both caches hold the prefix)
+                RT_TRY(stt_beam_reorder_range(ctx, bm.dec.kv, bm.kv_next, bk.src, tab + pt->base, tab + pt->step_hi + (size_t)step * rows, rows));
+                std::swap(bm.dec.kv, bm.kv_next);
+            }
+            RT_TRY(stt_decode_tab(s, bm.dec.work, bm.dec.kv, cross, rows, bk.next_tok, bm.row_slot, tab + pt->step_pos + (size_t)step * rows, bm.row_win,
+                                  bm.dec.enc_last, nullptr, rows, bm.dec.logits));
+            continue;
+        }
         RT_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, P + step));
         std::swap(bm.dec.kv, bm.kv_next);
         bm.dec.tok = bk.next_tok;
@@ -1442,7 +1702,9 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
             if (t_last >= 0) history(w, t_last, b, out[w].ids); else out[w].ids.clear();
         };
         for (int k = 0; k < n_f; ++k) offer(h.fin_step[w * B + k] - 1, h.fin_beam[w * B + k], h.fin_score[w * B + k]);
-        for (int i = 0; i < std::min(h.n_live[w], B) && n_f < B; ++i, ++n_f) offer(steps - 1, i, h.score[w * B + i]);
+        // (a window that stopped at a budget of its own offers its beams as they stood at its last step)
+        const int last = (pt ? std::min(steps, s->h_prm[pt->win_budget + w]) : steps) - 1;
+        for (int i = 0; i < std::min(h.n_live[w], B) && n_f < B; ++i, ++n_f) offer(last, i, h.score[w * B + i]);
     }
     return RT_OK;
 }
@@ -1497,21 +1759,40 @@ int stt_decode_sample_group(rt_stt* s, const SttSpan* spans, const std::vector<i
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.src, R, 0, 1);
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.live, 1, rows, 0);
     RT_HIP(ctx, hipGetLastError());
-    bm.dec.tok = part(bm.smp, 3);
-    RT_TRY(stt_decode_rows(s, bm.dec, cross, nN, P, 0, part(bm.smp, 0), part(bm.smp, 1), part(bm.smp, 2)));
+    // under a prompt policy every attempt of a window decodes behind the prefix its beam attempt had: the same prompt, the same tables
+    // but for the rows per window
+    const SttPrTab* pt = nullptr;
+    const int32_t* tab = s->prm.tab;
+    if (plan.prompt) {
+        std::vector<std::vector<int32_t>> toks(nN);
+        for (int k = 0; k < nN; ++k) stt_prompt_prefix_tokens(s, plan.prompt[need[k]], P, toks[k]);
+        RT_TRY(stt_prompt_tables(s, toks, need.data(), nN, S));
+        pt = &s->pr_tab;
+        RT_TRY(stt_prompt_prefix_pass(s, bm.dec.kv, bm.dec.logits, true, P));
+    } else {
+        bm.dec.tok = part(bm.smp, 3);
+        RT_TRY(stt_decode_rows(s, bm.dec, cross, nN, P, 0, part(bm.smp, 0), part(bm.smp, 1), part(bm.smp, 2)));
+    }
     const SttSampleRule sr{T, (unsigned)(s->fb.seed & 0xffffffffu), (unsigned)(s->fb.seed >> 32), (unsigned)t_index, part(bm.smp, 6), part(bm.smp, 7)};
-    const int budget = std::min(c.max_new_tokens, c.n_text_ctx - P);
+    const int budget = pt ? pt->steps : std::min(c.max_new_tokens, c.n_text_ctx - P);
     int steps = 0;
     for (int step = 0; step < budget; ++step) {
         RT_TRY(stt_sample_select(s, bm.dec.logits, step == 0 ? 1 : S, rows, step == 0 ? 1 : 0, S, step, bk, plan.ts, sr, nullptr));
         steps = step + 1;
+        if (pt) RT_TRY(stt_retire(s, bk, true, step + 1));
         int32_t live = 0;
         RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (live <= 0 || step + 1 >= budget) break;
         if (step == 0 && S > 1) {                   // the window's first row holds the prefix: every row of the window takes it
-            RT_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, P));
+            if (pt) RT_TRY(stt_beam_reorder_range(ctx, bm.dec.kv, bm.kv_next, tab + pt->fan_src, tab + pt->zero, tab + pt->base, rows));
+            else RT_TRY(stt_beam_reorder(ctx, bm.dec.kv, bm.kv_next, bk.src, rows, P));
             std::swap(bm.dec.kv, bm.kv_next);
+        }
+        if (pt) {
+            RT_TRY(stt_decode_tab(s, bm.dec.work, bm.dec.kv, cross, rows, bk.next_tok, part(bm.smp, 4), tab + pt->step_pos + (size_t)step * rows, part(bm.smp, 5),
+                                  bm.dec.enc_last, nullptr, rows, bm.dec.logits));
+            continue;
         }
         bm.dec.tok = bk.next_tok;
         RT_TRY(stt_decode_rows(s, bm.dec, cross, rows, 1, P + step, part(bm.smp, 4), bm.row_pos, part(bm.smp, 5)));
@@ -1527,7 +1808,8 @@ int stt_decode_sample_group(rt_stt* s, const SttSpan* spans, const std::vector<i
         for (int j = 0; j < S; ++j) {
             const int r = k * S + j;
             ids.clear();
-            for (int u = 0; u < steps; ++u) {
+            const int n_steps = pt ? std::min(steps, s->h_prm[pt->row_budget + r]) : steps;      // (a row that stopped at a budget of its own)
+            for (int u = 0; u < n_steps; ++u) {
                 const int32_t t = hb.bp_tok[(size_t)u * R + r];
                 if (t == c.eos_id) break;
                 ids.push_back(t);
@@ -1639,10 +1921,15 @@ int stt_run_group(rt_stt* s, const SttSpan* spans, int nW, int sr, int B, const 
             RT_HIP(ctx, hipMemcpyAsync(s->d_win_prefix, s->h_meta.data(), (size_t)nW * P * 4, hipMemcpyHostToDevice, ctx->stream));
         }
     }
-    RT_TRY(stt_features_group(s, spans, nW, sr));
-    RT_TRY(stt_encode(s, s->grp.enc, nW));
     // a policy whose first temperature is above 0 has no beam decode: the probe alone (stt_probe_group), behind the row tables it reads
     const bool sampled_first = plan.fallback && s->fb.temperatures[0] > 0.f;
+    if (plan.prompt && !sampled_first) {       // the tables of the beam decode under a prompt policy, with the other uploads
+        std::vector<std::vector<int32_t>> toks(nW);
+        for (int b = 0; b < nW; ++b) stt_prompt_prefix_tokens(s, plan.prompt[b], P, toks[b]);
+        RT_TRY(stt_prompt_tables(s, toks, nullptr, nW, B));
+    }
+    RT_TRY(stt_features_group(s, spans, nW, sr));
+    RT_TRY(stt_encode(s, s->grp.enc, nW));
     if (!sampled_first) RT_TRY(stt_decode_beam_group(s, nW, B, hyps, plan));
     else if (plan.probe) {
         SttBeam& bm = s->beam;
@@ -1731,7 +2018,8 @@ int stt_transcribe_beam(rt_stt* s, const std::vector<SttSpan>& all, int n_clips,
 
 // ---------------------------------------------------------------------------------------------- timestamps and seek (rt_stt_transcribe_seek)
 // A closed segment of one window: start and end in ticks of the window, and its text ids (timestamps stripped)
-struct SttSeg { int start = 0, end = 0; std::vector<int32_t> ids; };
+// (raw: every id of the slice, its timestamps included - what the clip's history gains under a prompt policy)
+struct SttSeg { int start = 0, end = 0; std::vector<int32_t> ids, raw; };
 
 // The seek rule ("timestamps and seek") on one window's hypothesis `seq` (end-of-sequence stripped, timestamp
 // ids are those >= t0): consecutive timestamp pairs close segments; with a single trailing timestamp the window is consumed whole;
@@ -1744,6 +2032,7 @@ int stt_seek_rule(const std::vector<int32_t>& seq, int t0, int own, int whole, s
     auto close = [&](int a, int b, int start, int end) {
         SttSeg g;
         g.start = start; g.end = end;
+        g.raw.assign(seq.begin() + a, seq.begin() + b);
         for (int k = a; k < b; ++k)
             if (!is_ts(k)) g.ids.push_back(seq[k]);
         segs.push_back(std::move(g));
@@ -1771,7 +2060,7 @@ int stt_seek_rule(const std::vector<int32_t>& seq, int t0, int own, int whole, s
 }
 
 // What one decoded window of a seek call leaves behind
-struct SttSeekWin { int clip; int64_t off; int n_ids; float logprob, no_speech; int advance; };
+struct SttSeekWin { int clip; int64_t off; int n_ids; float logprob, no_speech; int advance; int prompt_len = 0, reset = 0; };
 struct SttSeekSeg { int clip; int64_t start_tick, end_tick; int n_ids; };
 struct SttSeekResult {
     std::vector<std::vector<int32_t>> ids;               // per clip: the text ids of its segments, joined
@@ -1805,6 +2094,12 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
     RT_TRY(stt_plan_begin(s, plan, n_clips));
     std::vector<SttFbWin> fb_group;
     if (s->fb_set) plan.fallback = &fb_group;
+    // a prompt policy ("conditioning on previous text"): per clip the history - it starts as the initial prompt -
+    // and the reset mark; a window's prompt is the history behind the mark, cut to its last stt_prompt_cap ids
+    const bool prompted = s->pr_set;
+    if (prompted) RT_TRY(stt_prompt_reserve(s, most, most * per_window));
+    std::vector<std::vector<int32_t>> hist(prompted ? n_clips : 0, s->pr_initial), prompts;
+    std::vector<size_t> mark(prompted ? n_clips : 0, 0);
     res.fb.assign(n_clips, {});
     res.ids.assign(n_clips, {}); res.segs.assign(n_clips, {}); res.wins.assign(n_clips, {});
     res.score.assign(n_clips, 0.f); res.lang_prob.assign(n_clips, 1.f); res.lang.assign(n_clips, 0);     // (round 0 fills both for every clip)
@@ -1822,8 +2117,17 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
         for (int i = 0; i < n_clips; ++i)
             if (!done[i]) spans.push_back({i, n_samples[i] > 0 ? d_pcm[i] + off[i] : nullptr, std::min<int64_t>(win, n_samples[i] - off[i]), (uint32_t)(off[i] / tick)});
         if (spans.empty()) break;
+        if (prompted) {
+            prompts.assign(spans.size(), {});
+            for (size_t k = 0; k < spans.size(); ++k) {
+                const std::vector<int32_t>& hs = hist[spans[k].clip];
+                const size_t from = std::max(mark[spans[k].clip], hs.size() - std::min(hs.size(), (size_t)stt_prompt_cap(c)));
+                prompts[k].assign(hs.begin() + from, hs.end());
+            }
+        }
         for (size_t next = 0; next < spans.size(); next += per_group) {
             const int nW = (int)std::min(per_group, spans.size() - next);
+            if (prompted) plan.prompt = prompts.data() + next;
             // a clip's language is fixed by its first window: round 0 detects, later rounds find it in d_clip_lang
             for (int b = 0; b < nW; ++b) plan.win_first[b] = round == 0 ? b : -1;
             RT_TRY(stt_run_group(s, spans.data() + next, nW, sr, beam_size, plan, hyps, info));
@@ -1847,8 +2151,18 @@ int stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* n_s
                         res.ids[i].insert(res.ids[i].end(), g.ids.begin(), g.ids.end());
                     }
                 }
+                // the history gains the window's closed segments, timestamps included - not a discarded tail, not a segment of no
+                // duration or without a text id - and the mark moves behind them when conditioning is off or the chosen attempt ran
+                // above the reset temperature.  A silent window leaves both as they are.
+                int reset = 0;
+                if (prompted && !silent) {
+                    for (const SttSeg& g : segs)
+                        if (g.start != g.end && !g.ids.empty()) hist[i].insert(hist[i].end(), g.raw.begin(), g.raw.end());
+                    const float T = plan.fallback ? fb_group[b].temperature : 0.f;
+                    if (!s->pr.condition_on_previous || T > s->pr.reset_on_temperature) { mark[i] = hist[i].size(); reset = 1; }
+                }
                 if (advance <= 0) advance = whole;                  // (a window that would not move its clip moves it by a whole window)
-                res.wins[i].push_back({i, off[i], (int)h.ids.size(), h.score, ns, advance});
+                res.wins[i].push_back({i, off[i], (int)h.ids.size(), h.score, ns, advance, prompted ? (int)prompts[next + b].size() : 0, reset});
                 if (plan.fallback) res.fb[i].push_back(fb_group[b]);
                 off[i] += (int64_t)advance * tick;
                 if (off[i] >= n_samples[i]) done[i] = 1;
@@ -1914,7 +2228,7 @@ int rt_stt_destroy(rt_stt* s) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& sl : s->slots) { if (sl.raw) (void)hipFree(sl.raw); if (sl.raw2) (void)hipFree(sl.raw2); }
-    for (auto* owned : {&s->owned, &s->grp.owned, &s->beam.owned})
+    for (auto* owned : {&s->owned, &s->grp.owned, &s->beam.owned, &s->prm.owned})
         for (void* p : *owned) (void)hipFree(p);
     if (s->rs.d_h) (void)hipFree(s->rs.d_h);
     delete s;
@@ -2218,6 +2532,7 @@ int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* 
     RT_TRY(stt_check_languages(s, "rt_stt_transcribe_seek", "languages, no-speech probabilities or the silence rule", opts->h_language, n_clips, probe));
     SttSeekResult res;
     s->fb_report.clear();
+    s->pr_report.clear();
     RT_TRY(stt_transcribe_seek(s, d_pcm, n_samples, n_clips, sample_rate, *opts, probe, res));
     const double tick_s = (double)(int64_t)(0.02 * (double)sample_rate) / (double)sample_rate;
     int64_t n_seg = 0, n_win = 0;
@@ -2241,6 +2556,7 @@ int rt_stt_transcribe_seek(rt_stt* s, const float* const* d_pcm, const int64_t* 
         }
         if (s->fb_set) s->fb_report.insert(s->fb_report.end(), res.fb[i].begin(), res.fb[i].end());
         for (const SttSeekWin& w : res.wins[i]) {
+            if (s->pr_set) s->pr_report.push_back({w.prompt_len, w.reset});
             const int64_t at = n_win++;
             if (at >= out->window_cap) continue;
             if (out->h_win_clip) out->h_win_clip[at] = i;
@@ -2278,6 +2594,43 @@ int rt_stt_set_fallback(rt_stt* s, const rt_stt_fallback* f) {
         return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_fallback: a no_speech_threshold needs a handle with rt_stt_set_languages");
     s->fb = *f;
     s->fb_set = true;
+    return RT_OK;
+}
+
+int rt_stt_set_prompt(rt_stt* s, const rt_stt_prompt* p) {
+    if (!s) return RT_ERR_INVALID;
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_stt_set_prompt: call after rt_stt_finalize");
+    if (!p) { s->pr_set = false; s->pr = rt_stt_prompt{}; s->pr_initial.clear(); return RT_OK; }
+    const rt_stt_config& c = s->cfg;
+    if (s->ts_begin <= 0) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_prompt: the handle has no timestamp ids (rt_stt_set_timestamps)");
+    if (p->sot_prev_id <= c.eos_id || p->sot_prev_id >= c.vocab)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_prompt: <|startofprev|> = %d is not a special id of the vocabulary of %d (above end-of-sequence %d)", p->sot_prev_id, c.vocab, c.eos_id);
+    if (p->n_initial < 0 || (p->n_initial > 0 && !p->h_initial)) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_prompt: %d initial ids without an array", p->n_initial);
+    for (int i = 0; i < p->n_initial; ++i)
+        if (p->h_initial[i] < 0 || p->h_initial[i] >= c.vocab) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_prompt: initial id %d outside the vocabulary of %d", p->h_initial[i], c.vocab);
+    if (p->reset_on_temperature < 0.f || std::isinf(p->reset_on_temperature)) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_prompt: a reset temperature of %g (>= 0, finite, or NaN for none)", (double)p->reset_on_temperature);
+    if (!p->condition_on_previous && p->n_initial == 0) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_prompt: a policy neither conditions on previous text nor carries an initial prompt");
+    if (stt_prompt_cap(c) < 1 || stt_max_prefix(c) > c.n_text_ctx - 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_prompt: a text context of %d has no room for a prompt behind %d forced ids", c.n_text_ctx, c.n_prefix);
+    s->pr = *p;
+    s->pr_initial.assign(p->h_initial, p->h_initial + p->n_initial);
+    s->pr.h_initial = nullptr;
+    s->pr_set = true;
+    return RT_OK;
+}
+
+int rt_stt_prompt_report(rt_stt* s, int32_t cap, int32_t* h_prompt_len, int32_t* h_reset, int32_t* n_windows) {
+    if (!s || cap < 0 || !n_windows) return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_prompt_report: bad argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    const int32_t n = (int32_t)s->pr_report.size();
+    *n_windows = n;
+    for (int32_t w = 0; w < std::min(n, cap); ++w) {
+        if (h_prompt_len) h_prompt_len[w] = s->pr_report[w].first;
+        if (h_reset) h_reset[w] = s->pr_report[w].second;
+    }
+    if (n > cap) return rt_fail(ctx, RT_ERR_LENGTH, "rt_stt_prompt_report: %d windows, room for %d", n, cap);
     return RT_OK;
 }
 
@@ -2462,13 +2815,19 @@ int rt_debug_stt_sample_step_ts(rt_stt* s, const float* d_logits, int32_t row_st
                                  h_live_rows, &rule, h_ts_flags_in, h_ts_last_in, h_ts_flags_out, h_ts_last_out);
 }
 
-int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src, int32_t len,
-                              uint16_t* h_planes) {
+}  // extern "C"
+
+namespace {
+// rt_debug_stt_beam_reorder (h_lo null: positions [0, len) of every row) and rt_debug_stt_beam_reorder_range ([h_lo[r], h_hi[r]))
+int stt_debug_reorder(const char* who, rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src, int32_t len,
+                      const int32_t* h_lo, const int32_t* h_hi, uint16_t* h_planes) {
     if (!ctx || !h_src || !h_planes || layers < 1 || rows < 1 || rows > STT_GROUP || heads < 1 || max_pos < 1 || head_dim < 32 || head_dim % 32 || len < 0 ||
-        len > max_pos)
-        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_beam_reorder: bad argument");
-    for (int r = 0; r < rows; ++r)
-        if (h_src[r] < 0 || h_src[r] >= rows) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_beam_reorder: src[%d] outside the rows", r);
+        len > max_pos || (h_lo && !h_hi))
+        return rt_fail(ctx, RT_ERR_INVALID, "%s: bad argument", who);
+    for (int r = 0; r < rows; ++r) {
+        if (h_src[r] < 0 || h_src[r] >= rows) return rt_fail(ctx, RT_ERR_INVALID, "%s: src[%d] outside the rows", who, r);
+        if (h_lo && (h_lo[r] < 0 || h_hi[r] < h_lo[r] || h_hi[r] > max_pos)) return rt_fail(ctx, RT_ERR_INVALID, "%s: row %d: range [%d, %d) outside [0, %d]", who, r, h_lo[r], h_hi[r], max_pos);
+    }
     CtxLock g(ctx);
     RT_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)layers * rows * heads * max_pos * head_dim;           // one plane
@@ -2479,17 +2838,22 @@ int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t
             host[(4 + q) * n + i] = 0xbeef;                                                 // the destination: a sentinel
         }
     bf16_t* d = nullptr;
-    int32_t* d_src = nullptr;
+    int32_t* d_src = nullptr;                              // src | lo | hi
     RT_HIP(ctx, hipMalloc((void**)&d, 8 * n * 2));
     auto run = [&]() -> int {
-        RT_HIP(ctx, hipMalloc((void**)&d_src, (size_t)rows * 4));
+        RT_HIP(ctx, hipMalloc((void**)&d_src, (size_t)rows * 3 * 4));
         RT_HIP(ctx, hipMemcpyAsync(d, host.data(), 8 * n * 2, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(ctx, hipMemcpyAsync(d_src, h_src, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (h_lo) {
+            RT_HIP(ctx, hipMemcpyAsync(d_src + rows, h_lo, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+            RT_HIP(ctx, hipMemcpyAsync(d_src + 2 * rows, h_hi, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
         KvCache a, b;
         a.layers = b.layers = layers; a.slots = b.slots = rows; a.kv_heads = b.kv_heads = heads; a.max_pos = b.max_pos = max_pos; a.head_dim = b.head_dim = head_dim;
         a.k = d; a.v = d + n; a.k_lo = d + 2 * n; a.v_lo = d + 3 * n;
         b.k = d + 4 * n; b.v = d + 5 * n; b.k_lo = d + 6 * n; b.v_lo = d + 7 * n;
-        RT_TRY(stt_beam_reorder(ctx, a, b, d_src, rows, len));
+        if (h_lo) RT_TRY(stt_beam_reorder_range(ctx, a, b, d_src, d_src + rows, d_src + 2 * rows, rows));
+        else RT_TRY(stt_beam_reorder(ctx, a, b, d_src, rows, len));
         RT_HIP(ctx, hipMemcpyAsync(h_planes, d, 8 * n * 2, hipMemcpyDeviceToHost, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return RT_OK;
@@ -2499,6 +2863,98 @@ int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t
     (void)hipFree(d);
     if (d_src) (void)hipFree(d_src);
     return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int rt_debug_stt_beam_reorder(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src, int32_t len,
+                              uint16_t* h_planes) {
+    return stt_debug_reorder("rt_debug_stt_beam_reorder", ctx, layers, rows, heads, max_pos, head_dim, h_src, len, nullptr, nullptr, h_planes);
+}
+
+int rt_debug_stt_beam_reorder_range(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, const int32_t* h_src,
+                                    const int32_t* h_lo, const int32_t* h_hi, uint16_t* h_planes) {
+    if (!h_lo || !h_hi) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_beam_reorder_range: null range");
+    return stt_debug_reorder("rt_debug_stt_beam_reorder_range", ctx, layers, rows, heads, max_pos, head_dim, h_src, 0, h_lo, h_hi, h_planes);
+}
+
+int rt_bench_stt_gather(rt_ctx* ctx, int32_t layers, int32_t rows, int32_t heads, int32_t max_pos, int32_t head_dim, int32_t prefix, int32_t step, int32_t iters,
+                        double* us_ranged, double* us_uniform) {
+    if (!ctx || !us_ranged || !us_uniform || layers < 1 || rows < 1 || rows > STT_GROUP || heads < 1 || max_pos < 1 || head_dim < 32 || head_dim % 32 || prefix < 0 ||
+        step < 0 || prefix + step > max_pos || iters < 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_bench_stt_gather: bad argument (rows <= %d, prefix + step <= max_pos)", STT_GROUP);
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)layers * rows * heads * max_pos * head_dim;           // one plane
+    std::vector<int32_t> tab(3 * (size_t)rows);                                    // src (neighbours swap) | lo | hi
+    for (int r = 0; r < rows; ++r) { tab[r] = (r ^ 1) < rows ? (r ^ 1) : r; tab[rows + r] = prefix; tab[2 * rows + r] = prefix + step; }
+    bf16_t* d = nullptr;
+    int32_t* d_tab = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto run = [&]() -> int {
+        RT_HIP(ctx, hipMalloc((void**)&d, 8 * n * 2));
+        RT_HIP(ctx, hipMalloc((void**)&d_tab, tab.size() * 4));
+        RT_HIP(ctx, hipMemsetAsync(d, 0, 8 * n * 2, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipEventCreate(&e0)); RT_HIP(ctx, hipEventCreate(&e1));
+        KvCache a, b;
+        a.layers = b.layers = layers; a.slots = b.slots = rows; a.kv_heads = b.kv_heads = heads; a.max_pos = b.max_pos = max_pos; a.head_dim = b.head_dim = head_dim;
+        a.k = d; a.v = d + n; a.k_lo = d + 2 * n; a.v_lo = d + 3 * n;
+        b.k = d + 4 * n; b.v = d + 5 * n; b.k_lo = d + 6 * n; b.v_lo = d + 7 * n;
+        for (int form = 0; form < 2; ++form) {
+            float ms = 0.f;
+            for (int i = -1; i < iters; ++i) {                 // (one launch before the clock starts)
+                if (i == 0) RT_HIP(ctx, hipEventRecord(e0, ctx->stream));
+                if (form == 0) RT_TRY(stt_beam_reorder_range(ctx, i & 1 ? b : a, i & 1 ? a : b, d_tab, d_tab + rows, d_tab + 2 * rows, rows));
+                else RT_TRY(stt_beam_reorder(ctx, i & 1 ? b : a, i & 1 ? a : b, d_tab, rows, prefix + step));
+            }
+            RT_HIP(ctx, hipEventRecord(e1, ctx->stream));
+            RT_HIP(ctx, hipEventSynchronize(e1));
+            RT_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
+            *(form == 0 ? us_ranged : us_uniform) = (double)ms * 1e3 / iters;
+        }
+        return RT_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(ctx->stream);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (d) (void)hipFree(d);
+    if (d_tab) (void)hipFree(d_tab);
+    return rc;
+}
+
+int rt_debug_stt_prompt_prefix(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_windows, int32_t sample_rate, const int32_t* h_tokens,
+                               const int32_t* h_len, float* d_logits) {
+    if (!s || !h_tokens || !h_len || !d_logits || n_windows < 1 || n_windows > STT_GROUP || sample_rate < 1000 || stt_check_clips(d_pcm, n_samples, n_windows))
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_prompt_prefix: bad argument (1 .. %d windows)", STT_GROUP);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_debug_stt_prompt_prefix: not finalized");
+    const rt_stt_config& c = s->cfg;
+    std::vector<std::vector<int32_t>> toks(n_windows);
+    for (int w = 0, at = 0; w < n_windows; ++w) {
+        if (h_len[w] < 1 || h_len[w] > std::min(stt_max_prefix(c), c.n_text_ctx - 1))
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_prompt_prefix: window %d: %d tokens (1 .. %d)", w, h_len[w], std::min(stt_max_prefix(c), c.n_text_ctx - 1));
+        for (int i = 0; i < h_len[w]; ++i, ++at) {
+            if (h_tokens[at] < 0 || h_tokens[at] >= c.vocab) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_prompt_prefix: token %d outside the vocabulary of %d", h_tokens[at], c.vocab);
+            toks[w].push_back(h_tokens[at]);
+        }
+    }
+    std::vector<SttSpan> group;
+    stt_cut(c, sample_rate, d_pcm, n_samples, n_windows, group, true);
+    RT_TRY(stt_group_reserve(s, n_windows));
+    RT_TRY(stt_beam_reserve(s, n_windows));
+    RT_TRY(stt_prompt_reserve(s, n_windows, n_windows));
+    RT_TRY(stt_prompt_tables(s, toks, nullptr, n_windows, 1));
+    RT_TRY(stt_features_group(s, group.data(), n_windows, sample_rate));
+    RT_TRY(stt_encode(s, s->grp.enc, n_windows));
+    RT_TRY(stt_prompt_prefix_pass(s, s->beam.dec.kv, s->beam.dec.logits, false, 0));
+    RT_HIP(ctx, hipMemcpyAsync(d_logits, s->beam.dec.logits, (size_t)n_windows * c.vocab * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RT_OK;
 }
 
 int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_clips, int32_t sample_rate, float* d_states) {

@@ -35,6 +35,7 @@ WHISPER_LANGUAGE_CODES = (
     "et mk br eu is hy ne mn bs kk sq sw gl mr pa si km sn yo so af oc ka be tg sd gu am yi lo uz fo ht ps tk nn mt sa lb my bo tl mg as tt haw ln ha "
     "ba jw su").split()
 CLASSIC_FIRST_LANGUAGE_ID, CLASSIC_NO_SPEECH_ID = 50259, 50362
+CLASSIC_SOT_PREV_ID = 50361              # <|startofprev|> of the same vocabulary
 # the languages the provider advertises (provider_info) -> Whisper's codes
 _PROVIDER_LANGUAGES = {"english": "en", "chinese": "zh", "japanese": "ja", "korean": "ko"}
 
@@ -94,6 +95,9 @@ class SttConfig:
     # (1 s, as in openai's and faster-whisper's transcribers; -1: no limit)
     timestamp_begin: Optional[int] = None
     max_initial_timestamp_index: int = 50
+    # <|startofprev|>, which opens a window's prompt (NativeSTT.set_prompt; a generation config's `prev_sot_token_id`); None: a
+    # vocabulary this build does not know - such a model takes no prompt
+    sot_prev_id: Optional[int] = CLASSIC_SOT_PREV_ID
 
     @property
     def n_timestamps(self) -> int:
@@ -163,6 +167,11 @@ class SttConfig:
         # timestamp ids follow <|notimestamps|>; the seek path needs the prefix to end in it and the vocabulary to hold them
         if nts is not None and len(c.prefix) > 1 and c.prefix[-1] == int(nts) and int(nts) + 1 + c.n_timestamps <= c.vocab and c.eos_id < int(nts):
             c.timestamp_begin = int(nts) + 1
+        prev = gen.get("prev_sot_token_id")
+        if prev is not None and c.eos_id < int(prev) < c.vocab:
+            c.sot_prev_id = int(prev)
+        elif not (start == SttConfig.prefix[0] and c.vocab > CLASSIC_SOT_PREV_ID):
+            c.sot_prev_id = None
         if language != "en":
             c = c.with_language(language)
         elif len(c.prefix) > 1:
@@ -196,7 +205,7 @@ def tiny_test_config() -> SttConfig:
     """A few-thousand-parameter model of the same topology for quick tests (2-s chunks)."""
     return SttConfig(d_model=64, heads=2, ffn=128, enc_layers=2, dec_layers=2, n_mels=16, n_ctx=100, n_text_ctx=32, vocab=300,
                      chunk_seconds=2, eos_id=290, prefix=(291, 292, 293), suppress_from=290, begin_suppress=(7, 290), max_new_tokens=12,
-                     languages={}, no_speech_id=-1)
+                     languages={}, no_speech_id=-1, sot_prev_id=None)
 
 
 class RtSttConfig(C.Structure):
@@ -244,6 +253,37 @@ class RtSttFallback(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class RtSttPrompt(C.Structure):
+    _fields_ = [("sot_prev_id", C.c_int32), ("condition_on_previous", C.c_int32), ("reset_on_temperature", C.c_float), ("h_initial", C.POINTER(C.c_int32)),
+                ("n_initial", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+@dataclass
+class SttPromptWindow:
+    """One window's line of ``NativeSTT.prompt_report``: the length of the prompt it decoded behind, and whether the clip's reset mark
+    moved behind it (the next window then starts from an empty prompt)."""
+    prompt_len: int
+    reset: bool
+
+
+def check_prompt_args(cfg: "SttConfig", initial_ids, condition_on_previous, reset_on_temperature) -> Tuple[List[int], Optional[float]]:
+    """The argument rules of ``NativeSTT.set_prompt``, before anything touches a device: (initial ids, reset temperature)."""
+    if cfg.timestamp_begin is None:
+        raise ValueError("set_prompt: the configuration has no timestamp ids (SttConfig.timestamp_begin): a prompt applies to the seek path only")
+    if cfg.sot_prev_id is None or not cfg.eos_id < int(cfg.sot_prev_id) < cfg.vocab:
+        raise ValueError(f"set_prompt: the configuration has no <|startofprev|> id (SttConfig.sot_prev_id = {cfg.sot_prev_id!r})")
+    if isinstance(initial_ids, (str, bytes)):
+        raise ValueError("set_prompt: initial_ids are token ids (WhisperTranscriber(initial_prompt=...) takes a string)")
+    ids = [] if initial_ids is None else list(initial_ids)
+    if any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < cfg.vocab for t in ids):
+        raise ValueError(f"set_prompt: initial ids must be integers in [0, {cfg.vocab})")
+    if not condition_on_previous and not ids:
+        raise ValueError("set_prompt: a policy either conditions on previous text or carries an initial prompt")
+    if reset_on_temperature is not None and not (float(reset_on_temperature) >= 0.0 and math.isfinite(float(reset_on_temperature))):
+        raise ValueError(f"set_prompt: reset_on_temperature must be None or a finite value >= 0, got {reset_on_temperature!r}")
+    return [int(t) for t in ids], None if reset_on_temperature is None else float(reset_on_temperature)
+
+
 def check_temperatures(temperatures) -> Tuple[float, ...]:
     """The temperatures of a fallback policy: 1 .. 8 finite values >= 0, strictly ascending (so only the first may be 0)."""
     ts = tuple(float(t) for t in ((temperatures,) if isinstance(temperatures, (int, float)) else temperatures))
@@ -275,6 +315,7 @@ class SttSegment:
     temperature: float = 0.0
     attempts: int = 1
     compression_ratio: float = float("nan")
+    prompt_len: int = 0                  # under a prompt policy, of the window that closed the segment
 
 
 @dataclass
@@ -286,6 +327,7 @@ class SttSeekWindow:
     logprob: float
     no_speech_prob: float                # NaN where the probe pass did not run
     advance: int
+    prompt_len: int = 0                  # under a prompt policy (NativeSTT.set_prompt): the ids of previous text it decoded behind
 
     @property
     def avg_logprob(self) -> float:
@@ -365,6 +407,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_stt_transcribe_seek.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(RtSttSeekOpts), C.POINTER(RtSttSeekOut)]
     lib.rt_stt_set_fallback.argtypes = [vp, C.POINTER(RtSttFallback)]
     lib.rt_stt_fallback_report.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)]
+    lib.rt_stt_set_prompt.argtypes = [vp, C.POINTER(RtSttPrompt)]
+    lib.rt_stt_prompt_report.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.rt_stt_log_mel.argtypes = [vp, vp, i64, i32, vp]
     lib.rt_stt_encode.argtypes = [vp, vp, i64, i32, vp]
     _DECLARED = True
@@ -759,7 +803,46 @@ class NativeSTT:
             clips[i].segments.append(SttSegment(float(g_s[g]), float(g_e[g]), ids, int(g_st[g]), int(g_et[g])))
         for w in range(out.n_windows):
             clips[w_clip[w]].windows.append(SttSeekWindow(int(w_off[w]), int(w_n[w]), float(w_lp[w]), float(w_ns[w]) if out.h_win_no_speech else nan, int(w_adv[w])))
+        if self._prompt_set:                                      # the report's lines follow the per-window arrays: clip by clip
+            lines = iter(self.prompt_report())
+            for c in clips:
+                c.windows = [dataclasses.replace(w, prompt_len=next(lines).prompt_len) for w in c.windows]
         return clips
+
+    _prompt_set = False
+
+    def set_prompt(self, initial_ids=None, condition_on_previous: bool = False, reset_on_temperature: Optional[float] = 0.5) -> None:
+        """Conditioning on previous text and an initial prompt for ``transcribe_ids_seek`` (rt_stt_set_prompt; the rule: DESIGN.md
+        section 5, "conditioning on previous text", restated in validation.prompt_for_window / history_after_window).
+        ``initial_ids``: token ids in front of every clip's first window; ``condition_on_previous``: every later window decodes behind
+        the tail of what its clip produced so far; ``reset_on_temperature``: that history is dropped behind a window whose chosen
+        attempt ran above this temperature (None: never).  Neither ``initial_ids`` nor ``condition_on_previous``: the policy is
+        cleared, and every call is what it is without one."""
+        if not getattr(self, "handle", None):
+            raise ValueError("set_prompt: the model is closed")
+        if not initial_ids and not condition_on_previous:
+            self.ctx.check(self.lib.rt_stt_set_prompt(self.handle, None), "rt_stt_set_prompt")
+            self._prompt_set = False
+            return
+        ids, reset = check_prompt_args(self.cfg, initial_ids, condition_on_previous, reset_on_temperature)
+        p = RtSttPrompt()
+        p.sot_prev_id, p.condition_on_previous, p.reset_on_temperature = int(self.cfg.sot_prev_id), 1 if condition_on_previous else 0, float("nan") if reset is None else reset
+        arr = (C.c_int32 * max(len(ids), 1))(*ids)
+        if ids:
+            p.h_initial, p.n_initial = arr, len(ids)
+        self.ctx.check(self.lib.rt_stt_set_prompt(self.handle, C.byref(p)), "rt_stt_set_prompt")
+        self._prompt_set = True
+
+    def prompt_report(self) -> List[SttPromptWindow]:
+        """Per window of the last ``transcribe_ids_seek`` call under a prompt policy, in the order of that call's windows (clip by clip)."""
+        n = C.c_int32()
+        rc = self.lib.rt_stt_prompt_report(self.handle, 0, None, None, C.byref(n))
+        if rc not in (_native.RT_OK, _native.RT_ERR_LENGTH):
+            self.ctx.check(rc, "rt_stt_prompt_report")
+        k = n.value
+        ln, rs = _i32(k), _i32(k)
+        self.ctx.check(self.lib.rt_stt_prompt_report(self.handle, k, ln, rs, C.byref(n)), "rt_stt_prompt_report")
+        return [SttPromptWindow(int(ln[i]), bool(rs[i])) for i in range(n.value)]
 
     def set_fallback(self, temperatures, best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
                      no_speech_threshold: Optional[float] = None, seed: int = 789, ratio=None) -> None:
@@ -871,6 +954,7 @@ class SttDetail:
     temperature: List[float] = field(default_factory=list)
     attempts: List[int] = field(default_factory=list)
     compression_ratio: List[float] = field(default_factory=list)
+    prompt_len: List[int] = field(default_factory=list)      # under a prompt policy, per window of the clip; empty without one
 
 
 class WhisperTranscriber:
@@ -893,13 +977,21 @@ class WhisperTranscriber:
     _ex = False                          # calls go through transcribe_ids_ex (a detected language, or the silence rule)
     timestamps = False                   # calls go through transcribe_ids_seek (the reference's long-form rule; see below)
     fallback = False                     # a fallback policy is set on the model (temperatures other than (0.0,))
+    prompted = False                     # a prompt policy is set on the model (condition_on_previous_text / initial_prompt)
 
     def __init__(self, ctx: "_native.Context", model_dir: Optional[str] = None, synthetic: bool = False, cfg: Optional[SttConfig] = None, seed: int = 789,
                  beam_size: int = 1, language: str = "en", no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = -1.0,
-                 timestamps: bool = False, temperatures=(0.0,), best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4):
+                 timestamps: bool = False, temperatures=(0.0,), best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4,
+                 condition_on_previous_text: bool = False, initial_prompt=None, prompt_reset_on_temperature: Optional[float] = 0.5):
         """``timestamps``: every call decodes with timestamp tokens and walks a clip longer than one window by seek positions
         (``transcribe_ids_seek``), as the reference's ``model.transcribe`` does; a clip's text is its segments' texts joined with a
-        space (stt_validator.py:136), and ``batch_segments`` returns them with their times."""
+        space (stt_validator.py:136), and ``batch_segments`` returns them with their times.  ``condition_on_previous_text``,
+        ``initial_prompt`` and ``prompt_reset_on_temperature`` (``NativeSTT.set_prompt``; faster-whisper's options of the same names,
+        which default to True, None and 0.5 there): both need ``timestamps=True``.  ``initial_prompt`` is a string - encoded as
+        faster-whisper encodes it, ``" " + text.strip()`` through the tokenizer - or a sequence of token ids, the only form a model
+        without a tokenizer takes.  ``batch_detailed`` / ``batch_segments`` then report ``prompt_len`` per window."""
+        if (condition_on_previous_text or initial_prompt is not None) and not timestamps:
+            raise ValueError("condition_on_previous_text and initial_prompt need timestamps=True: only the seek path has a previous window")
         self.beam_size = check_beam_size(beam_size)
         self.auto = language == "auto"
         self.no_speech_threshold, self.logprob_threshold = no_speech_threshold, logprob_threshold
@@ -935,6 +1027,23 @@ class WhisperTranscriber:
             self.model.set_fallback(temps, best_of, compression_ratio_threshold, logprob_threshold, no_speech_threshold, seed,
                                     ratio=lambda ids: compression_ratio_text(self._text(ids) or ""))
         self._ex = self.auto or no_speech_threshold is not None or self.fallback       # calls that must go through transcribe_ids_ex
+        self.prompted = False
+        if condition_on_previous_text or initial_prompt is not None:
+            try:
+                self.model.set_prompt(self._prompt_ids(initial_prompt), bool(condition_on_previous_text), prompt_reset_on_temperature)
+            except Exception:
+                self.model.close()
+                raise
+            self.prompted = self.model._prompt_set               # (an empty prompt without conditioning sets no policy)
+
+    def _prompt_ids(self, initial_prompt) -> Optional[List[int]]:
+        if initial_prompt is None:
+            return None
+        if isinstance(initial_prompt, str):
+            if self.tokenizer is None:
+                raise ValueError("initial_prompt as a string needs a checkpoint with a tokenizer; pass token ids")
+            return list(self.tokenizer.encode(" " + initial_prompt.strip(), add_special_tokens=False).ids)
+        return list(initial_prompt)
 
     def _seek(self, audios, sample_rate: int) -> List[SttSeekClip]:
         return self.model.transcribe_ids_seek(audios, sample_rate, self.beam_size, "auto" if self.auto else None,
@@ -975,9 +1084,11 @@ class WhisperTranscriber:
             segs = []
             for g in c.segments:
                 extra = {}
-                if lines:                                             # the window the segment lies in: the last one that starts at or before it
+                if lines or self.prompted:                            # the window the segment lies in: the last one that starts at or before it
                     k = max(i for i, w in enumerate(c.windows) if w.offset // tick <= g.start_tick)
-                    extra = dict(temperature=lines[k].temperature, attempts=lines[k].attempts, compression_ratio=lines[k].compression_ratio)
+                    extra = dict(prompt_len=c.windows[k].prompt_len)
+                    if lines:
+                        extra.update(temperature=lines[k].temperature, attempts=lines[k].attempts, compression_ratio=lines[k].compression_ratio)
                 segs.append(dataclasses.replace(g, text=self._segment_text(g.ids).strip(), **extra))
             out.append(segs)
         return out
@@ -995,7 +1106,8 @@ class WhisperTranscriber:
                 dropped = sum(1 for w in c.windows if window_is_silent(w.no_speech_prob, w.avg_logprob, self.no_speech_threshold, self.logprob_threshold))
                 ns = [w.no_speech_prob for w in c.windows if w.no_speech_prob == w.no_speech_prob]
                 out.append(SttDetail(self._joined(c), c.ids, c.score, self.cfg.language_code(c.language) or str(c.language), c.language_prob,
-                                     max(ns) if ns else float("nan"), dropped, **self._fallback_fields(lines)))
+                                     max(ns) if ns else float("nan"), dropped, **self._fallback_fields(lines),
+                                     prompt_len=[w.prompt_len for w in c.windows] if self.prompted else []))
             return out
         if not (self._ex or detailed):
             if self.beam_size > 1 or scored:

@@ -127,6 +127,32 @@ def needs_fallback(compression_ratio: Optional[float], avg_logprob: float, no_sp
     return needs
 
 
+def prompt_for_window(history, reset_mark: int, cap: int):
+    """The prompt a window decodes behind ("conditioning on previous text"; faster-whisper's ``get_prompt`` on
+    ``all_tokens[prompt_reset_since:]``): the clip's history behind the reset mark, cut to its last ``cap`` ids
+    (``cap = n_text_ctx // 2 - 1``).  Empty: the window decodes behind the timestamp-mode prefix alone."""
+    tail = [int(t) for t in history[int(reset_mark):]]
+    return tail[len(tail) - min(len(tail), int(cap)):]
+
+
+def history_after_window(history, reset_mark: int, segments, silent: bool = False, condition_on_previous: bool = True, temperature: float = 0.0,
+                         reset_on_temperature: Optional[float] = 0.5):
+    """(history, reset mark) of a clip after one window.  ``segments``: the window's closed segments in order as (start tick, end
+    tick, text ids, every id of the slice with its timestamps) - a discarded tail is no segment.  A silent window changes nothing.
+    Otherwise every segment with a duration and at least one text id adds all of its ids, and the mark moves to the end of the
+    history when conditioning is off or the window's chosen attempt ran at a ``temperature`` above ``reset_on_temperature`` (None:
+    never).  The native loop (csrc/stt.hip stt_transcribe_seek) applies the same statements."""
+    history = [int(t) for t in history]
+    if silent:
+        return history, int(reset_mark)
+    for start, end, text, raw in segments:
+        if start != end and len(text):
+            history += [int(t) for t in raw]
+    if not condition_on_previous or (reset_on_temperature is not None and temperature > reset_on_temperature):
+        reset_mark = len(history)
+    return history, int(reset_mark)
+
+
 def pick_attempt(attempts, compression_ratio_threshold: Optional[float] = 2.4) -> int:
     """The attempt that stands when every temperature failed: ``attempts`` is a list of (compression_ratio or None, avg_logprob) in the
     order they were made; the largest average among those within the compression threshold wins, among all when none is within it,
