@@ -342,6 +342,8 @@ RT_API int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t
  *   3100/3101 predictor passes 2..G-1: layer 0's qkv GEMM launch / its q/k/v row copied from the per-code table built by rt_model_finalize
  *   3200/3201 generations on 65..128 rows: two 64-row decode GEMM launches per weight matrix / one 128-row launch (same bits)
  *   3300/3301 speech-to-text under a prompt policy, the cache gather between beam steps: positions [0, longest prefix + step) of every row / each row's generated positions only (same bits)
+ *   3400/3401 the decode GEMMs' RMSNorm sum-of-squares partials (rows of n partials, n % 64 == 0, n <= 256): stored plainly and fetched one dword per request / stored permuted and fetched 16 bytes per request (same bits)
+ *   3500/3501 STORE / RESID decode GEMM launches of up to 32 rows: weight / activation chunks of 8 k-tiles / of the length of the wave's run (4 for K <= 1024, 6 for K = 3072; same bits)
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
 RT_API int rt_debug_tune(int32_t code, int32_t arg);

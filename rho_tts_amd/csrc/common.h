@@ -171,6 +171,16 @@ __host__ __device__ __forceinline__ int64_t tile_off(int m, int k, int K) {
     return ((((int64_t)(m >> 4) * (K >> 5) + (k >> 5)) * 64 + ((((k >> 3) & 3) << 4) | (m & 15))) << 3) + (k & 7);
 }
 
+// Where partial j of a row of n RMSNorm sum-of-squares partials (a `rowsq` row) is stored when the row has the PERMUTED layout
+// (ColArgs::rowsq_perm; every reader and writer of such a row goes through this one function).  Inside each block of 64 partials
+// the 16 x 4 index matrix (j & 15, (j >> 4) & 3) is transposed, so that the four partials r + 16 (4 q + c), c = 0..3, which one
+// lane of the column-owner GEMM's row-scale prologue sums, are the four floats of ONE 16-byte load at p + 64 q + 4 r.
+// A bijection on [0, n) when n % 64 == 0 (slot 0 stays 0: the kernels that write one total and zeros need no change); the
+// identity for every other n.
+__host__ __device__ __forceinline__ int rowsq_slot(int j, int n) {
+    return (n & 63) ? j : (64 * (j >> 6) + 4 * (j & 15) + ((j >> 4) & 3));
+}
+
 // bf16 <-> f32 (round-to-nearest-even, NaN preserved by the hardware cast on gfx950)
 typedef unsigned short bf16_t;
 __device__ __forceinline__ float bf16_to_f32(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }

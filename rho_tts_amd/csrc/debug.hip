@@ -767,7 +767,8 @@ int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_no
     ColArgs c;
     c.nt = (a_norm & 2) ? 0 : 1;             // bit 1: cacheable weight loads (hot-cache experiment with n_mats = 1)
     a_norm &= 1;
-    c.A = a; c.post_scale = a_norm; c.rowsq = rowsq; c.rowsq_n = K / 16; c.eps = 1e-6f; c.M = M; c.K = K; c.epi = epi;
+    // (as many partials per row as the RESID launch of width K in front of such a launch emits: 256 at K = 2048, 128 at K = 1024)
+    c.A = a; c.post_scale = a_norm; c.rowsq = rowsq; c.rowsq_n = K / 16 * col_split_for(K, ctx->n_cu); c.eps = 1e-6f; c.M = M; c.K = K; c.epi = epi;
     c.next_bf16 = epi == COL_RESID ? act : nullptr; c.next_norm_w = normw;
     c.out = out; c.ldc = epi == COL_SILU ? N / 2 : N; c.split = epi == COL_SILU ? col_split_silu(N, ctx->n_cu) : col_split_for(N, ctx->n_cu);
     c.rowsq_out = rowsq_out; c.rowsq_out_n = N / 16 * c.split; c.out_bf16 = act;
@@ -801,6 +802,7 @@ int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_no
         c.stamps = st;
         pw.data16 = wbuf + (pb / 2) * (iters % n_mats);
         rc = launch_gemm_col(ctx, c, pw);
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the context's stream does not wait for, nor hold up, the copy below)
         RT_HIP(ctx, hipMemcpy(stamps8, st, 64, hipMemcpyDeviceToHost));
         (void)hipFree(st);
     }

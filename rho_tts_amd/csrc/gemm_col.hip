@@ -71,7 +71,10 @@ constexpr int col_chunk(int epi, int mt, bool x) {                         // k-
 }
 // NORM = the launch applies an RMSNorm row scale (g.post_scale), as a compile-time property: its partials are then requested
 // without any branch (see the row-scale block), and launches without a scale carry no requests for them at all.
-template <int EPI, int MT, int NPRE, bool X = false, bool NORM = false>
+// WQ (NORM only) = how the row-scale partials are requested: 0 one dword per partial from plain rows, 2 / 4 that many 16-byte
+// requests per lane and 32 rows from PERMUTED rows (common.h rowsq_slot; rows of 64..128 / 192..256 partials).
+// CF = chunk length fitted to the wave's run of k-tiles by the launcher (launch_chunk: 4 or 6; 0: col_chunk).
+template <int EPI, int MT, int NPRE, bool X = false, bool NORM = false, int WQ = 0, int CF = 0>
 __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && !X) ? 4 : 2) void k_gemm_col(ColArgs g) {
     static_assert(!X || (EPI == COL_SILU && MT >= 2), "the extra half pair exists for gate/up only");
     constexpr int RMT = MT > 4 ? 4 : MT;     // sub-blocks per combine round (MT = 8: two rounds through the same 32 KiB)
@@ -79,7 +82,9 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
     __shared__ float red[WAVES][RMT][4][64]; // 16 KiB per 32 rows: one 16x16 accumulator tile per sub-block and wave
     __shared__ float sh_inv[16 * MT];        // RMSNorm row scales
     constexpr int NB = (EPI == COL_SILU) ? (X ? 3 : 2) : 1;
-    constexpr int C = col_chunk(EPI, MT, X);
+    static_assert(WQ == 0 || NORM, "wide requests exist for the row-scale partials only");
+    static_assert(CF == 0 || (EPI != COL_SILU && MT == 2), "fitted chunks exist for STORE / RESID launches of up to 32 rows only");
+    constexpr int C = CF ? CF : col_chunk(EPI, MT, X);
     constexpr int PASSES = (MT + 1) / 2;     // epilogue / row-scale passes of 32 rows (MT = 1: half of one)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r = lane & 15, qd = lane >> 4;
@@ -139,9 +144,23 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
     const int n = nt * 16 + (e_l & 15);
     const bool e_mine = ((e_l & 15) >> cw_shift) == sub;
     const bool n_ok = n < g.N && e_mine;
-    float rq[PASSES][16];                      // rowsq partials of rows 32 ps + 4 w + qd, 16 per lane (<= 256 partials per row)
+    float rq[PASSES][WQ ? 1 : 16];             // rowsq partials of rows 32 ps + 4 w + qd, 16 per lane (<= 256 partials per row)
+    f4_t rq4[PASSES][WQ ? WQ : 1];             // ... or the same partials as WQ 16-byte pieces (permuted rows)
     constexpr int RQ_MAX = 256;
-    if constexpr (NORM) {   // row scales: the 16-lane group (w, qd) owns rows 4w + qd (+ 32 per pass), its lanes split the partials.
+    if constexpr (NORM && WQ > 0) {
+        // Permuted rows (rowsq_n % 64 == 0, rowsq_n <= 64 WQ): piece q at p + 64 q + 4 r holds exactly partials r + 16 (4 q + c),
+        // c = 0..3 - the 16 dword requests per lane below arrive as WQ requests.  Branch-free like them: q is clamped to the last
+        // block of 64 that exists (a valid, 16-byte aligned address: launch_gemm_col) and masked when summed.
+        const int q_last = (g.rowsq_n >> 6) - 1;
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+            const int row_i = 32 * ps + 4 * w + qd;
+            const int row = g.row_off + (row_i < g.M ? row_i : g.M - 1);
+            const f4_t* p = reinterpret_cast<const f4_t*>(g.rowsq + (int64_t)row * g.rowsq_n) + r;
+#pragma unroll
+            for (int q = 0; q < WQ; ++q) rq4[ps][q] = p[16 * (q < q_last ? q : q_last)];
+        }
+    } else if constexpr (NORM) {   // row scales: the 16-lane group (w, qd) owns rows 4w + qd (+ 32 per pass), its lanes split the partials.
         // NO runtime branch around these requests: behind `if (g.post_scale)` the compiler merged this block with the summation
         // below and placed the first add (0 + rq[0][0]) at the join - a `s_waitcnt` for the first partial IN FRONT of the weight
         // chunks' requests, so every NORM launch (qkv, gate/up, the heads: 222 per frame) began to stream its weights one L2
@@ -182,9 +201,14 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
         for (int ps = 0; ps < PASSES; ++ps) {
             const int row_i = 32 * ps + 4 * w + qd;
             float s = 0.f;
+            if constexpr (WQ > 0) {               // the same values in the same `it` = 4 q + c order as below: the same bits
 #pragma unroll
-            for (int it = 0; it < 16; ++it) s += (r + 16 * it < g.rowsq_n) ? rq[ps][it] : 0.f;
-            if (g.rowsq_n > RQ_MAX) {             // (more partials than the unrolled window: not a shape the model produces)
+                for (int it = 0; it < 4 * WQ; ++it) s += (r + 16 * it < g.rowsq_n) ? rq4[ps][it >> 2][it & 3] : 0.f;
+            } else {
+#pragma unroll
+                for (int it = 0; it < 16; ++it) s += (r + 16 * it < g.rowsq_n) ? rq[ps][it] : 0.f;
+            }
+            if (WQ == 0 && g.rowsq_n > RQ_MAX) {             // (more partials than the unrolled window: not a shape the model produces)
                 const int row = g.row_off + (row_i < g.M ? row_i : g.M - 1);
                 const float* p = g.rowsq + (int64_t)row * g.rowsq_n;
                 for (int j = RQ_MAX + r; j < g.rowsq_n; j += 16) s += p[j];
@@ -276,7 +300,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
             // (DPP adds: the four dependent ds_bpermute round trips of a __shfl_xor butterfly sat in the tail of every RESID launch -
             //  two per layer - between the last store of x and the store of its sums of squares)
             sq = group_sum_f32<16>(sq);
-            if ((e_l & 15) == 0 && e_row < g.M) g.rowsq_out[(int64_t)(g.row_off + e_row) * g.rowsq_out_n + blockIdx.x] = sq;
+            if ((e_l & 15) == 0 && e_row < g.M) g.rowsq_out[(int64_t)(g.row_off + e_row) * g.rowsq_out_n + (g.rowsq_perm ? rowsq_slot((int)blockIdx.x, g.rowsq_out_n) : (int)blockIdx.x)] = sq;
         } else {                                  // COL_SILU: gate = tile nt, up = tile nt + offset
             if (ok) {
                 const float u = val[1][ps] * inv;
@@ -293,31 +317,49 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
     if (g.stamps && blockIdx.x == 0 && tid == 0) g.stamps[5] = wall_clock64();
 }
 
-template <int EPI, int MT, int NPRE, bool X, bool NORM>
+template <int EPI, int MT, int NPRE, bool X, bool NORM, int WQ, int CF>
 void launch_one(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
-    if (!e0 && !e1) hipLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM>), grid, dim3(512), 0, ctx->stream, g);   // plain launches are what a stream capture records
-    else hipExtLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM>), grid, dim3(512), 0, ctx->stream, e0, e1, 0, g);   // device-side begin/end stamps
+    if (!e0 && !e1) hipLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF>), grid, dim3(512), 0, ctx->stream, g);   // plain launches are what a stream capture records
+    else hipExtLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF>), grid, dim3(512), 0, ctx->stream, e0, e1, 0, g);   // device-side begin/end stamps
 }
 
-template <int EPI, int MT, bool X, bool NORM>
+template <int EPI, int MT, bool X, bool NORM, int WQ, int CF>
 void launch_npre2(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     // every wave needs at least one k-tile for the clamped (branch-free) requests to be valid addresses
-    constexpr int C = col_chunk(EPI, MT, X);
+    constexpr int C = CF ? CF : col_chunk(EPI, MT, X);
     const int kchunk = (g.KT + WAVES - 1) / WAVES;
     const bool all_waves_busy = g.KT >= WAVES && (WAVES - 1) * kchunk < g.KT;
     const int n_sc = (kchunk + C - 1) / C;
-    if (!all_waves_busy) launch_one<EPI, MT, 0, X, NORM>(ctx, g, grid, e0, e1);
-    else if (n_sc >= 2) launch_one<EPI, MT, 2, X, NORM>(ctx, g, grid, e0, e1);
-    else launch_one<EPI, MT, 1, X, NORM>(ctx, g, grid, e0, e1);
+    if (!all_waves_busy) launch_one<EPI, MT, 0, X, NORM, WQ, CF>(ctx, g, grid, e0, e1);
+    else if (n_sc >= 2) launch_one<EPI, MT, 2, X, NORM, WQ, CF>(ctx, g, grid, e0, e1);
+    else launch_one<EPI, MT, 1, X, NORM, WQ, CF>(ctx, g, grid, e0, e1);
+}
+
+// The chunk length follows the wave's run of k-tiles where it is known to be short (STORE / RESID launches of up to 32 rows, whose
+// chunk is 8 k-tiles): a run of <= 4 (K <= 1024) takes ONE chunk of 4 and a run of 9..12 (K = 3072) TWO chunks of 6, both still
+// requested up front without a branch.  With chunks of 8 the clamped requests of the tail re-load the run's last tile - as many
+// requests as the real ones at K = 1024, half of the second chunk at K = 3072.  Same k order inside a wave: the same bits.
+template <int EPI, int MT, bool X, bool NORM, int WQ>
+void launch_chunk(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
+    if constexpr (EPI != COL_SILU && MT == 2) {
+        const int kchunk = (g.KT + WAVES - 1) / WAVES;
+        if (g_col_chunk_fit && kchunk <= 4) return launch_npre2<EPI, MT, X, NORM, WQ, 4>(ctx, g, grid, e0, e1);
+        if (g_col_chunk_fit && kchunk > 8 && kchunk <= 12) return launch_npre2<EPI, MT, X, NORM, WQ, 6>(ctx, g, grid, e0, e1);
+    }
+    launch_npre2<EPI, MT, X, NORM, WQ, 0>(ctx, g, grid, e0, e1);
 }
 
 // (the residual epilogue never follows an RMSNorm in this model: one instantiation less per shape)
 template <int EPI, int MT, bool X = false>
 void launch_npre(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     if (g.post_scale) {
-        if constexpr (EPI != COL_RESID) launch_npre2<EPI, MT, X, true>(ctx, g, grid, e0, e1);
+        if constexpr (EPI != COL_RESID) {
+            if (g.rowsq_wide == 2) launch_chunk<EPI, MT, X, true, 2>(ctx, g, grid, e0, e1);
+            else if (g.rowsq_wide == 4) launch_chunk<EPI, MT, X, true, 4>(ctx, g, grid, e0, e1);
+            else launch_chunk<EPI, MT, X, true, 0>(ctx, g, grid, e0, e1);
+        }
     } else {
-        launch_npre2<EPI, MT, X, false>(ctx, g, grid, e0, e1);
+        launch_chunk<EPI, MT, X, false, 0>(ctx, g, grid, e0, e1);
     }
 }
 
@@ -369,6 +411,8 @@ int col_split_for(int N, int n_cu) {
     return 1;
 }
 
+bool rowsq_permuted(int n) { return g_rowsq_wide && n % 64 == 0 && n >= 64 && n <= 256; }
+
 int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t ev_start, hipEvent_t ev_stop) {
     if (a.M < 1 || a.M > 128) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: M=%d outside 1..128 (callers split larger row blocks)", a.M);
     if (w.K != a.K || w.K % 32) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: K mismatch (%d vs %d) or not a multiple of 32", w.K, a.K);
@@ -399,5 +443,10 @@ int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t 
     if (g.post_scale && (!g.rowsq || g.rowsq_n < 1)) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: row scaling without partials");
     if (g.post_scale && g.epi == COL_RESID) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "gemm_col: the residual epilogue has no row-scaled instantiation");
     if (g.next_bf16 && !g.next_norm_w) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: next operand without its norm weight");
+    // the layout of the rowsq rows under the current plan, resolved HERE for producer and consumer alike (the kernel reads no global)
+    g.rowsq_perm = (g.epi == COL_RESID && rowsq_permuted(g.rowsq_out_n)) ? 1 : 0;
+    g.rowsq_wide = (g.post_scale && rowsq_permuted(g.rowsq_n)) ? (g.rowsq_n <= 128 ? 2 : 4) : 0;
+    if (g.rowsq_wide && (reinterpret_cast<uintptr_t>(g.rowsq) & 15))     // (rowsq_n % 64 == 0: a row stride of a multiple of 256 bytes)
+        return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: rowsq rows read in 16-byte pieces must be 16-byte aligned");
     return dispatch_epi(ctx, g, dim3(tiles * g.split), ev_start, ev_stop);
 }

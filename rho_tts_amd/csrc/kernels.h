@@ -114,7 +114,13 @@ struct ColArgs {
     const bf16_t* Wp = nullptr;
     int NT = 0, KT = 0, N = 0, up_tile_offset = 0;
     int x_tile0 = 0;                // gate/up: > 0 = workgroups own 1.5 pairs, the halves come from pairs x_tile0 ...
+    int rowsq_perm = 0;             // RESID: 1 = partial j is stored at rowsq_slot(j, rowsq_out_n) (rowsq_permuted(rowsq_out_n))
+    int rowsq_wide = 0;             // NORM: 0 = plain rows, one dword request per partial; 2 / 4 = permuted rows, that many
+                                    //       16-byte requests per lane and 32 rows (rowsq_permuted(rowsq_n))
 };
+// Whether rowsq rows of n partials have the permuted layout (common.h rowsq_slot) under the current launch plan (g_rowsq_wide):
+// the ONE predicate behind every producer and consumer of such a row, so that they cannot disagree.
+bool rowsq_permuted(int n);
 int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // rowsq[M][0] = sum_k x[m][k]^2  (seed of the first NORM prologue of a stack)
 // src_rows / dst_rows (device, [M], optional): block i reads x row src_rows[i] and writes (tiled / rowsq) row dst_rows[i]

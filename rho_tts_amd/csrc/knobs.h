@@ -51,7 +51,12 @@
         "0 two 64-row launches (same bits either way).  Measured (1.7B, profiles/r18_rows128.txt): bench.py --corpus 512 --batch 128 1014 audio-s/s with 1 against 887 with 0 (five alternating pairs; 824 on 64 rows); " \
         "per launch at 128 rows qkv 13.7 / 16.3 us, o 12.0 / 14.2, gate/up 20.9 / 27.4, down 27.3 / 29.7 (one launch / two)") \
     X(3300, g_stt_gather_ranged, 1, 0, 1, "speech-to-text under a prompt policy, the gather between beam steps: 1 the ranged form (generated positions only; the prefix " \
-        "sits in both caches), 0 the uniform form over [0, longest prefix of the group + step) (same bits either way; profiles/r20_stt_prompt.txt)")
+        "sits in both caches), 0 the uniform form over [0, longest prefix of the group + step) (same bits either way; profiles/r20_stt_prompt.txt)") \
+    X(3400, g_rowsq_wide, 1, 0, 1, "RMSNorm sum-of-squares partials of the decode GEMMs, rows of n partials with n % 64 == 0 and n <= 256: 1 stored permuted (rowsq_slot) " \
+        "and fetched by the row-scale prologue in 2 / 4 16-byte requests per lane, 0 stored plainly and fetched in 16 dword requests (same bits either way; " \
+        "profiles/r21_gemm_col_prologue.txt)") \
+    X(3500, g_col_chunk_fit, 1, 0, 1, "STORE / RESID decode GEMM launches of up to 32 rows: 1 the chunk length follows the wave's run of k-tiles (one chunk of 4 for K <= 1024, " \
+        "two of 6 for K = 3072: no clamped re-loads of the run's last tile), 0 chunks of 8 (same bits either way; profiles/r21_gemm_col_prologue.txt)")
 
 // The one switch set by rt_debug_tune's SECOND argument: applied when the code is 0..2 and the argument lies in lo..hi.
 #define RT_KNOB_ARG(X) \

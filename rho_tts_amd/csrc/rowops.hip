@@ -286,11 +286,12 @@ __global__ __launch_bounds__(256) void k_embed_rowsq(const GatherSrc* __restrict
 // rmsnorm of the column path's tiled residual stream back to plain rows: out[row][c] = w[c] * x[row][c] * rsqrt(sum(rowsq[row]) / H
 // + eps).  Only an equal-width predictor needs it (its first input row is the talker's normalised hidden state itself).
 __global__ __launch_bounds__(256) void k_norm_tiled_rows(const float* __restrict__ x_tiled, const float* __restrict__ rowsq, int rowsq_n,
-                                                         const float* __restrict__ w, float eps, int H, float* __restrict__ out) {
+                                                         const float* __restrict__ w, float eps, int H, float* __restrict__ out, int perm) {
     __shared__ float sh[4];
     const int row = blockIdx.x;
     float s = 0.f;
-    for (int j = threadIdx.x; j < rowsq_n; j += 256) s += rowsq[(int64_t)row * rowsq_n + j];
+    // (perm: the row has the permuted layout - thread j still takes partial j, so the block sum adds the same values in the same order)
+    for (int j = threadIdx.x; j < rowsq_n; j += 256) s += rowsq[(int64_t)row * rowsq_n + (perm ? rowsq_slot(j, rowsq_n) : j)];
     const float inv = rsqrtf(block_sum_f32(s, sh) / (float)H + eps);
     for (int c = threadIdx.x * 4; c < H; c += 1024) {
         const f4_t v = *reinterpret_cast<const f4_t*>(x_tiled + tile_off(row, c, H));
@@ -592,7 +593,8 @@ int launch_norm_tiled_rows(rt_ctx* ctx, const float* x_tiled, const float* rowsq
                            float* out) {
     if (M <= 0) return RT_OK;
     if (H % 8) return rt_fail(ctx, RT_ERR_INVALID, "norm_tiled_rows: H %d not a multiple of 8", H);
-    hipLaunchKernelGGL(k_norm_tiled_rows, dim3(M), dim3(256), 0, ctx->stream, x_tiled, rowsq, rowsq_n, w, eps, H, out);
+    hipLaunchKernelGGL(k_norm_tiled_rows, dim3(M), dim3(256), 0, ctx->stream, x_tiled, rowsq, rowsq_n, w, eps, H, out,
+                       rowsq_permuted(rowsq_n) ? 1 : 0);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }

@@ -40,6 +40,30 @@ if len(sys.argv) > 1 and sys.argv[1] == "rows128":  # 128 rows: one MT = 8 launc
                           for label, v in (("one 128-row launch", t[3201]), ("two 64-row launches", t[3200])))
         print(f"{name:26s} {mb:6.1f} MB  M=128  {line}   [one 64-row launch {us.value:7.2f} us]", flush=True)
     sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "prologue":
+    # what a launch does before its weight stream starts: the row-scale partials' layout (3400/3401) and the chunk length (3500/3501),
+    # at 32 and 64 rows; in-kernel stamps 0 -> 1 (requests issued, row scales summed) and 0 -> 5 (whole workgroup 0).
+    # `prologue plain`: no switch is touched (a build without them), one column
+    import statistics
+    plain = len(sys.argv) > 2 and sys.argv[2] == "plain"
+    for M in (32, 64):
+        for _, N, K, norm, epi, name in shapes[:10]:
+            mb = N * K * 2 / 1e6
+            n_mats = max(2, int(600 / mb) + 1)
+            cols = []
+            for wide in ((0,) if plain else (0, 1)):
+                for fit in ((0,) if plain else (0, 1)):
+                    if not plain:
+                        assert lib.rt_debug_tune(3400 + wide, 0) == 0 and lib.rt_debug_tune(3500 + fit, 0) == 0
+                    t, s01, s05 = [], [], []
+                    for _ in range(3):
+                        us = C.c_double()
+                        st = (C.c_int64 * 8)()
+                        assert lib.rt_bench_gemm_col(ctx.handle, M, N, K, norm, epi, n_mats, 300, C.byref(us), st) == 0
+                        t.append(us.value); s01.append((st[1] - st[0]) * 0.01); s05.append((st[5] - st[0]) * 0.01)
+                    cols.append(f"{'plain' if plain else f'wide {wide} fit {fit}'}: {statistics.median(t):6.2f} us (min {min(t):.2f}) 0>1 {statistics.median(s01):.2f} 0>5 {statistics.median(s05):.2f}")
+            print(f"M={M:2d} {name:24s} " + " | ".join(cols), flush=True)
+    sys.exit(0)
 for M, N, K, norm, epi, name in shapes:
     mb = N * K * 2 / 1e6
     n_mats = max(2, int(600 / mb) + 1)
