@@ -555,6 +555,36 @@ typedef struct rt_stt_prompt {
 } rt_stt_prompt;
 RT_API int rt_stt_set_prompt(rt_stt* s, const rt_stt_prompt* p);
 RT_API int rt_stt_prompt_report(rt_stt* s, int32_t cap, int32_t* h_prompt_len, int32_t* h_reset, int32_t* n_windows);
+/* Token times of KNOWN text by dynamic time warping over cross-attention (Whisper's word-timestamp method; the definition and its
+ * deviations: DESIGN.md section 5, "word times").  All h_ pointers are host memory.
+ * rt_stt_set_alignment: n_heads (1 .. 32) pairs (decoder layer, head) in h_layer_head [n_heads][2] and the width of the median filter
+ *   along time (odd, 1 .. 31; Whisper uses 7).  Before or after rt_stt_finalize; the buffers are allocated by the first rt_stt_align.
+ *   RT_ERR_INVALID: a pair out of range, a pair given twice, an even width.
+ * rt_stt_align: every entry of d_pcm / n_samples is ONE window of at most chunk_seconds (a later window of a long clip: d_pcm + offset);
+ *   window w carries the text ids h_text_ids[h_text_offsets[w] .. h_text_offsets[w + 1]) - no timestamp ids, no end-of-sequence, at
+ *   most n_text_ctx - n_prefix - 1 of them - and decodes them teacher-forced behind the handle's prefix (which ends in
+ *   <|notimestamps|>), position 1 replaced by h_language[w] where h_language is given (a configured id; detection is not offered
+ *   here).  Windows run in groups of up to 32; a window's results are bit for bit those it has as the only window of a call.
+ *   A window with n ids has n + 1 alignment rows; row k predicts token k of ids + [end-of-sequence].  Outputs, each optional:
+ *   h_token_frame [sum (n + 1)]: per row the frame (0.02 s each) at which the path enters it - a token's start is its own entry, its end
+ *   the next one, the last entry of a window (the end-of-sequence row) the end of its last token; h_token_logprob [sum n]:
+ *   log_softmax over the text ids [0, eos_id) of the row's logits at the token; h_n_frames [n_windows]: the frames F of the window,
+ *   clamp(resampled length / hop / 2, 1, n_ctx).  A window WITHOUT ids has no entries in the first two (sums run over the others).
+ *   RT_ERR_LENGTH: a window longer than chunk_seconds, too many ids.  RT_ERR_INVALID: an id outside [0, vocab) or not a text id
+ *   (>= eos_id: a special or timestamp id has no log-probability over the text ids), a handle without rt_stt_set_alignment, a
+ *   language that is not configured.  On any error nothing is launched and the handle stays usable.
+ *   Memory: beside the group's buffers the first call allocates, and later calls grow, workspaces for the rows of the pass and the
+ *   probabilities W as windows x heads x r_max x f_max floats, r_max and f_max the group's largest n + 1 and F: 380 MiB measured for 32
+ *   windows of 30 s with 60 ids and 12 heads; the worst case - 32 windows of 30 s, 32 heads, 449 rows each - is 2.7 GB for W alone. */
+typedef struct rt_stt_align_out {
+    int32_t* h_token_frame;
+    float* h_token_logprob;
+    int32_t* h_n_frames;
+    int32_t reserved[4];
+} rt_stt_align_out;
+RT_API int rt_stt_set_alignment(rt_stt* s, const int32_t* h_layer_head, int32_t n_heads, int32_t median_width);
+RT_API int rt_stt_align(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_windows, int32_t sample_rate_in, const int32_t* h_text_ids,
+                        const int32_t* h_text_offsets, const int32_t* h_language, rt_stt_align_out* out);
 /* Stages on their own (tests): the log-mel features [2 n_ctx][n_mels] and the encoder states [n_ctx][d_model], float32 in HBM:
  * row 0 of the same front end and encoder with the clip as its only window.  Of a clip longer than chunk_seconds the first
  * chunk is kept, and the resampler's taps at its end see the samples behind it. */

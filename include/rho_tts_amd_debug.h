@@ -180,6 +180,30 @@ RT_API int rt_debug_stt_sample_step_ts(rt_stt* s, const float* d_logits, int32_t
 RT_API int rt_debug_stt_probe(rt_stt* s, const float* d_logits, int64_t row_stride, int32_t n_rows, int32_t* h_lang, float* h_lang_prob,
                               float* h_no_speech);
 
+/* The kernels of rt_stt_align one at a time (tests/test_stt_align_gpu.py; csrc/stt_align.hip).  d_ pointers are HBM, h_ host memory.
+ * rt_debug_stt_align_probs: k_stt_align_probs on q [q_rows][heads * head_dim] (float32) and one layer of a cross-attention cache the
+ *   caller supplies as planes d_k_hi / d_k_lo (bf16 bits, [slots][heads][n_ctx][head_dim]; d_k_lo may be null): alignment row a reads row
+ *   h_src[a] of q over slot h_slot[a] and writes t < h_frames[a]; the n_heads heads h_heads[] are written in that order to
+ *   d_W [n_heads][n_rows][ldw] (ldw >= every h_frames[a]; cells that are not written keep the caller's bytes).
+ * rt_debug_stt_align_matrix: k_stt_align_stats + k_stt_align_matrix on d_W [n_heads][n][F] -> d_M [n][F].
+ * rt_debug_stt_dtw: k_stt_dtw on d_M [n][F] -> h_frames [n]; trace_mode -1: the trace in LDS when it fits, 0: in global memory,
+ *   1: in LDS (RT_ERR_INVALID when it does not fit).
+ * rt_debug_stt_align_stages: one group (1 .. 32 windows, every one with ids) of a real rt_stt_align call, arguments as there, and
+ *   beside its outputs the call's W as [n_windows][n_heads][h_shape[0]][h_shape[1]] (zero where nothing is written: rows >= n + 1,
+ *   t >= F of the window) in h_W and its M, window by window [n + 1][F], in h_M (capacities in floats; RT_ERR_LENGTH with h_shape set
+ *   when one is short). */
+RT_API int rt_debug_stt_align_probs(rt_ctx* ctx, const float* d_q, int32_t q_rows, int32_t heads, int32_t head_dim, const uint16_t* d_k_hi, const uint16_t* d_k_lo,
+                                    int32_t slots, int32_t n_ctx, const int32_t* h_src, const int32_t* h_slot, const int32_t* h_frames, int32_t n_rows,
+                                    const int32_t* h_heads, int32_t n_heads, int32_t ldw, float* d_W);
+RT_API int rt_debug_stt_align_matrix(rt_ctx* ctx, const float* d_W, int32_t n_heads, int32_t n, int32_t F, int32_t median_width, float* d_M);
+RT_API int rt_debug_stt_dtw(rt_ctx* ctx, const float* d_M, int32_t n, int32_t F, int32_t trace_mode, int32_t* h_frames);
+/* Events around the launches rt_stt_align adds to a decoder pass (tools/bench_stt_align.py): returns the milliseconds summed since the
+ * last call - the capture launches, statistics + matrix, the paths - clears the sums and switches the recording on or off. */
+RT_API int rt_debug_stt_align_timing(rt_stt* s, int32_t on, double* ms_capture, double* ms_matrix, double* ms_dtw);
+RT_API int rt_debug_stt_align_stages(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_windows, int32_t sample_rate_in,
+                                     const int32_t* h_text_ids, const int32_t* h_text_offsets, const int32_t* h_language, float* h_W, int64_t w_cap, float* h_M,
+                                     int64_t m_cap, int32_t* h_shape, int32_t* h_token_frame, float* h_token_logprob);
+
 /* ------------------------------------------------------------------ row kernels on their own (tests/test_rowops_gpu.py)
  * Each hook checks its arguments, calls the production launch_* function of rowops.hip (so the launcher's dispatch and its refusals
  * are under test too), synchronises the stream and returns the status.  All pointers are HBM unless named h_*; matrices are

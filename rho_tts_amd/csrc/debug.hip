@@ -1014,4 +1014,94 @@ int rt_bench_grid_barrier(rt_ctx* ctx, int32_t wgs, int32_t threads, int32_t n, 
     return RT_OK;
 }
 
+// The kernels of rt_stt_align one at a time (csrc/stt_align.hip): the production launchers over tables made for the call
+int rt_debug_stt_align_probs(rt_ctx* ctx, const float* d_q, int32_t q_rows, int32_t heads, int32_t head_dim, const uint16_t* d_k_hi, const uint16_t* d_k_lo,
+                             int32_t slots, int32_t n_ctx, const int32_t* h_src, const int32_t* h_slot, const int32_t* h_frames, int32_t n_rows,
+                             const int32_t* h_heads, int32_t n_heads, int32_t ldw, float* d_W) {
+    if (!ctx || !d_q || !d_k_hi || !h_src || !h_slot || !h_frames || !h_heads || !d_W || q_rows < 1 || heads < 1 || slots < 1 || n_ctx < 1 || n_rows < 1 ||
+        n_heads < 1 || n_heads > ALIGN_HEADS_MAX || ldw < 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_align_probs: bad argument");
+    AlignHeads hs{};
+    for (int i = 0; i < n_heads; ++i) {
+        if (h_heads[i] < 0 || h_heads[i] >= heads) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_align_probs: head %d outside %d heads", h_heads[i], heads);
+        hs.head[i] = h_heads[i]; hs.out[i] = i;
+    }
+    hs.n = n_heads;
+    std::vector<int32_t> tab(3 * (size_t)n_rows);
+    std::vector<int64_t> off(n_rows);
+    for (int a = 0; a < n_rows; ++a) {
+        if (h_src[a] < 0 || h_src[a] >= q_rows || h_slot[a] < 0 || h_slot[a] >= slots || h_frames[a] < 0 || h_frames[a] > std::min(ldw, n_ctx))
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_align_probs: row %d: source row, slot or frames out of range", a);
+        tab[a] = h_src[a]; tab[n_rows + a] = h_slot[a]; tab[2 * (size_t)n_rows + a] = h_frames[a];
+        off[a] = (int64_t)a * ldw;
+    }
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    int32_t* d_tab = nullptr;
+    int64_t* d_off = nullptr;
+    auto run = [&]() -> int {
+        RT_HIP(ctx, hipMalloc((void**)&d_tab, tab.size() * 4));
+        RT_HIP(ctx, hipMalloc((void**)&d_off, off.size() * 8));
+        RT_HIP(ctx, hipMemcpyAsync(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        KvCache kv;
+        kv.layers = 1; kv.slots = slots; kv.kv_heads = heads; kv.max_pos = n_ctx; kv.head_dim = head_dim;
+        kv.k = (bf16_t*)d_k_hi; kv.k_lo = (bf16_t*)d_k_lo;
+        RT_TRY(launch_align_probs(ctx, d_q, heads, head_dim, kv, 0, AlignRows{d_tab, d_tab + n_rows, d_tab + 2 * (size_t)n_rows, d_off}, n_rows, hs, (int64_t)n_rows * ldw, d_W));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(ctx->stream);
+    if (d_tab) (void)hipFree(d_tab);
+    if (d_off) (void)hipFree(d_off);
+    return rc;
+}
+
+int rt_debug_stt_align_matrix(rt_ctx* ctx, const float* d_W, int32_t n_heads, int32_t n, int32_t F, int32_t median_width, float* d_M) {
+    if (!ctx || !d_W || !d_M || n < 1 || F < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_align_matrix: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const AlignWin win{n, F, 0, 0, 0, 0};
+    AlignWin* d_win = nullptr;
+    double* stats = nullptr;
+    auto run = [&]() -> int {
+        RT_HIP(ctx, hipMalloc((void**)&d_win, sizeof(AlignWin)));
+        RT_HIP(ctx, hipMalloc((void**)&stats, (size_t)std::max(n_heads, 1) * F * 2 * sizeof(double)));
+        RT_HIP(ctx, hipMemcpyAsync(d_win, &win, sizeof(AlignWin), hipMemcpyHostToDevice, ctx->stream));
+        RT_TRY(launch_align_matrix(ctx, d_W, d_win, 1, n_heads, (int64_t)n * F, F, n, F, median_width, stats, d_M));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(ctx->stream);
+    if (d_win) (void)hipFree(d_win);
+    if (stats) (void)hipFree(stats);
+    return rc;
+}
+
+int rt_debug_stt_dtw(rt_ctx* ctx, const float* d_M, int32_t n, int32_t F, int32_t trace_mode, int32_t* h_frames) {
+    if (!ctx || !d_M || !h_frames || n < 1 || F < 1 || trace_mode < -1 || trace_mode > 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_dtw: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const AlignWin win{n, F, 0, 0, 0, 0};
+    AlignWin* d_win = nullptr;
+    uint32_t* trace = nullptr;
+    int32_t* frames = nullptr;
+    auto run = [&]() -> int {
+        RT_HIP(ctx, hipMalloc((void**)&d_win, sizeof(AlignWin)));
+        RT_HIP(ctx, hipMalloc((void**)&trace, align_trace_words(n, F) * 4));
+        RT_HIP(ctx, hipMalloc((void**)&frames, (size_t)n * 4));
+        RT_HIP(ctx, hipMemcpyAsync(d_win, &win, sizeof(AlignWin), hipMemcpyHostToDevice, ctx->stream));
+        RT_TRY(launch_align_dtw(ctx, d_M, d_win, 1, n, F, trace, trace_mode, frames));
+        RT_HIP(ctx, hipMemcpyAsync(h_frames, frames, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return RT_OK;
+    };
+    const int rc = run();
+    (void)hipStreamSynchronize(ctx->stream);
+    for (void* p : {(void*)d_win, (void*)trace, (void*)frames}) if (p) (void)hipFree(p);
+    return rc;
+}
+
 }  // extern "C"

@@ -306,3 +306,30 @@ int launch_rvq(rt_ctx* ctx, const float* sem, float* aco, int T, int D, int K, i
 int launch_stats_pool(rt_ctx* ctx, const float* x, int T, int C, float* out);
 // y [N] = act(W [N][K] x [K] + b): f32 weights, one wave per output
 int launch_gemv_f32(rt_ctx* ctx, const float* W, const float* b, const float* x, int N, int K, int relu, float* y);
+
+// ------------------------------------------------------------------------------ token alignment (stt_align.hip)
+// Cross-attention probabilities of chosen (row, head) pairs, their normalised and filtered mean, and the monotone token-to-frame
+// path by dynamic time warping: what rt_stt_align adds behind a teacher-forced decoder pass ("word times").
+constexpr int ALIGN_HEADS_MAX = 32;     // alignment heads of a model
+constexpr int ALIGN_MEDIAN_MAX = 31;    // widest median filter
+// The alignment rows of one capture launch (device tables, one entry per row): the row of q, the slot of the cross-attention cache it
+// attends over, the positions written (t < frames) and where the row's line of head slot 0 starts in W
+struct AlignRows { const int32_t* src; const int32_t* slot; const int32_t* frames; const int64_t* out; };
+// The alignment heads of one layer: the model's head and its place in the order given to rt_stt_set_alignment
+struct AlignHeads { int n; int32_t head[ALIGN_HEADS_MAX]; int32_t out[ALIGN_HEADS_MAX]; };
+// One window of the matrix and path kernels: n rows (tokens + 1) and F frames; W[head][row][t] at w_off + head * head_stride + row * ldw + t,
+// M [n][F] dense at m_off, the n frame indices at f_off, the path kernel's trace (global form) at t_off (32-bit words)
+struct AlignWin { int32_t n, F; int64_t w_off, m_off, f_off, t_off; };
+// W[...] = softmax_t(q . k_t / sqrt(d)) over ALL max_pos positions of the slot, t < frames written; q [rows][heads * head_dim]
+int launch_align_probs(rt_ctx* ctx, const float* q, int heads, int head_dim, const KvCache& cross, int layer, const AlignRows& rows, int n_rows,
+                       const AlignHeads& hs, int64_t head_stride, float* W);
+// out[r] = log_softmax(logits[r][0 .. hi))[tok[r]]
+int launch_align_logprob(rt_ctx* ctx, const float* logits, int V, int n_rows, const int32_t* tok, int hi, float* out);
+// stats [n_win][n_heads][ldw] (mean, std) pairs of float64 (scratch); M as AlignWin says
+int launch_align_matrix(rt_ctx* ctx, const float* W, const AlignWin* d_wins, int n_win, int n_heads, int64_t head_stride, int ldw, int max_n, int max_F, int width,
+                        double* stats, float* M);
+// words of the path kernel's trace for a window of n rows and F frames (2 bits per cell of the (n + 1) x (F + 1) table, a row's cells
+// in words of its own)
+inline size_t align_trace_words(int n, int F) { return (size_t)(n + 1) * (size_t)((F + 16) / 16); }
+// trace_mode: -1 the trace lives in LDS when the largest window's fits, 0 in d_trace (global), 1 in LDS (refused when it does not fit)
+int launch_align_dtw(rt_ctx* ctx, const float* M, const AlignWin* d_wins, int n_win, int max_n, int max_F, uint32_t* d_trace, int trace_mode, int32_t* frames);

@@ -49,11 +49,18 @@
 // and a gather between beam steps that moves generated positions only (k_stt_beam_reorder_range).  Off unless a policy is set; no
 // other entry point changes.
 //
+// rt_stt_align gives the times of KNOWN text ("word times"): one teacher-forced pass over a group's windows with
+// their text ids behind the prefix, during which stt_layer's capture argument has the kernels of stt_align.hip write the cross-attention
+// probabilities of the alignment heads (rt_stt_set_alignment) out beside the unchanged attention launch; normalisation, median filter and
+// head mean, and the monotone token-to-frame path by dynamic time warping follow on the device.  Nothing of it exists until the first
+// call; the capture argument is null everywhere else, and no other entry point changes.
+//
 // The three beam entry points run their groups through one driver (stt_run_group) under one plan (SttPlan: the clips' language
 // requests, whether the probe runs, the timestamp rule); what each keeps for itself is how it forms its groups and what it makes of
 // the hypotheses - fixed cuts and joined ids (stt_transcribe_beam), rounds, offsets and the seek rule (stt_transcribe_seek).
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <map>
 
 #include "kernels.h"
@@ -939,6 +946,27 @@ struct SttPrTab {
 // One window's line of rt_stt_fallback_report
 struct SttFbWin { int32_t attempts = 1; float temperature = 0.f, ratio = NAN; };
 
+// What stt_layer takes to write cross-attention probabilities out (rt_stt_align): the alignment rows of the pass, per decoder layer its
+// alignment heads, and W[window][head][row][F_max] with the stride between two heads of a window
+struct SttCapture { AlignRows rows; int n_rows; const AlignHeads* per_layer; int64_t head_stride; float* W; };
+
+// The device side of rt_stt_align (nothing of it exists until the first call; replaced by a larger set when a group needs more, as the
+// beam path's set): workspaces for the rows of the teacher-forced pass, a chunk of logits, W, M, the path kernel's outputs and scratch,
+// and the tables of one group, uploaded in one copy
+constexpr int STT_ALIGN_CHUNK = 256;    // rows of logits formed at a time
+struct SttAlignNeed { size_t rows = 0, w = 0, m = 0, stats = 0, trace = 0, tab = 0, arows = 0; };
+struct SttAlignBuf {
+    SttAlignNeed has;
+    SttWork work;                       // [rows]
+    int32_t* enc_last = nullptr;        // [rows] n_ctx - 1 throughout
+    float *xl = nullptr, *xn = nullptr, *logits = nullptr;     // [STT_ALIGN_CHUNK] rows: taken, normed, their logits
+    float *W = nullptr, *M = nullptr, *lp = nullptr;           // lp [arows]
+    double* stats = nullptr;
+    uint32_t* trace = nullptr;
+    int32_t *frames = nullptr, *tab = nullptr;                 // frames [arows]
+    std::vector<void*> owned;
+};
+
 struct rt_stt {
     rt_ctx* ctx = nullptr;
     rt_stt_config cfg{};
@@ -986,6 +1014,19 @@ struct rt_stt {
     SttPrTab pr_tab;
     std::vector<int32_t> h_prm;
     std::vector<std::pair<int32_t, int32_t>> pr_report;      // (prompt length, the reset mark moved behind the window)
+    // rt_stt_set_alignment: the alignment heads as (decoder layer, head) in the caller's order (empty: rt_stt_align refuses), the same
+    // per layer, the median width; the device side and the host copies of what a group uploads and reads back
+    std::vector<std::pair<int32_t, int32_t>> al_heads;
+    std::vector<AlignHeads> al_layers;
+    int32_t al_width = 0;
+    SttAlignBuf aln;
+    std::vector<int32_t> h_aln, h_aln_frames;
+    std::vector<float> h_aln_lp;
+    // rt_debug_stt_align_timing: events around the launches rt_stt_align adds (0: the capture launches, 1: statistics + matrix, 2: the
+    // paths), summed per class when a group has synchronised
+    bool al_clock = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> al_events[3];
+    double al_ms[3] = {0.0, 0.0, 0.0};
     std::vector<void*> owned;
 };
 
@@ -1205,11 +1246,40 @@ int stt_features_group(rt_stt* s, const SttSpan* spans, int B, int sr) {
     return RT_OK;
 }
 
+// Events around the launches of one class while rt_debug_stt_align_timing is on (off: nothing is created or recorded)
+struct SttAlignSpan {
+    rt_stt* s; int cls; hipEvent_t a = nullptr, b = nullptr;
+    SttAlignSpan(rt_stt* s_, int cls_) : s(s_), cls(cls_) {
+        if (!s->al_clock) return;
+        if (hipEventCreate(&a) != hipSuccess) { a = nullptr; return; }
+        if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); a = b = nullptr; return; }
+        (void)hipEventRecord(a, s->ctx->stream);
+    }
+    ~SttAlignSpan() {
+        if (!a || !b) return;
+        (void)hipEventRecord(b, s->ctx->stream);
+        s->al_events[cls].push_back({a, b});
+    }
+};
+// (behind the group's synchronisation)
+void stt_align_clock_collect(rt_stt* s) {
+    for (int c = 0; c < 3; ++c) {
+        for (auto& e : s->al_events[c]) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) s->al_ms[c] += (double)ms;
+            (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second);
+        }
+        s->al_events[c].clear();
+    }
+}
+
 // one pre-LN layer over M rows of k.x (in place).  self-attention over cache `kv` (row r is written at slot[r], wpos[r] + pos_add and
 // attends up to apos[r]); cross != null: the decoder's encoder-attention block between the two, over slot cross_slot[r] of *cross up
-// to cross_last[r]
+// to cross_last[r].  cap (rt_stt_align; null everywhere else, and then every launch is what it was): the layer's alignment heads get
+// their cross-attention probabilities written out by a launch of their own beside the attention launch, which is left as it is
 int stt_layer(rt_stt* s, const std::string& p, const SttWork& k, int M, const KvCache& kv, int layer, const int32_t* slot, const int32_t* wpos,
-              const int32_t* apos, int pos_add, const KvCache* cross = nullptr, const int32_t* cross_slot = nullptr, const int32_t* cross_last = nullptr) {
+              const int32_t* apos, int pos_add, const KvCache* cross = nullptr, const int32_t* cross_slot = nullptr, const int32_t* cross_last = nullptr,
+              const SttCapture* cap = nullptr) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int H = c.heads, d = c.d_model / c.heads, D = c.d_model;
@@ -1223,6 +1293,10 @@ int stt_layer(rt_stt* s, const std::string& p, const SttWork& k, int M, const Kv
         RT_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".lnc_w"), SVEC(s, p + ".lnc_b"), xn));
         RT_TRY(stt_gemm(s, xn, M, SPW(s, p + ".cwq"), SVEC(s, p + ".cbq"), ACT_NONE, nullptr, q));
         RT_TRY(launch_attention(ctx, q, M, H, H, d, cross_slot, cross_last, 0, 0, *cross, layer, nullptr, nullptr, 0, ao));
+        if (cap && cap->per_layer[layer].n > 0) {
+            SttAlignSpan span(s, 0);
+            RT_TRY(launch_align_probs(ctx, q, H, d, *cross, layer, cap->rows, cap->n_rows, cap->per_layer[layer], cap->head_stride, cap->W));
+        }
         RT_TRY(stt_gemm(s, ao, M, SPW(s, p + ".cwo"), SVEC(s, p + ".cbo"), ACT_NONE, x, x));
     }
     RT_TRY(stt_ln(s, x, D, M, SVEC(s, p + ".ln2_w"), SVEC(s, p + ".ln2_b"), xn));
@@ -1488,15 +1562,24 @@ int stt_prompt_tables(rt_stt* s, const std::vector<std::vector<int32_t>>& toks, 
 // M decoder rows under row tables - row r: token tok[r] at position pos[r] of slot slot[r] of `kv`, over slot cross_slot[r] of the
 // cross-attention cache - through the launches stt_decode_rows issues, with the embedding reading the row's position from the
 // table.  take (null: every row, n_out = M): the rows whose logits are wanted, n_out of them -> d_logits [n_out][vocab].
+// (stt_decode_tab_rows: the embedding and the decoder layers of such a pass, k.x holding every row's state behind the last layer - what
+//  stt_decode_tab runs in front of its tail, and what rt_stt_align runs, with the capture argument set, in front of a tail of its own)
+int stt_decode_tab_rows(rt_stt* s, const SttWork& k, const KvCache& kv, const KvCache& cross, int M, const int32_t* tok, const int32_t* slot, const int32_t* pos,
+                        const int32_t* cross_slot, const int32_t* enc_last, const SttCapture* cap = nullptr) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    hipLaunchKernelGGL(k_stt_embed_rows, dim3(M), dim3(128), 0, ctx->stream, stt_find(s, "dec.tok")->tbl, SVEC(s, "dec.pos"), tok, pos, c.d_model, k.x);
+    RT_HIP(ctx, hipGetLastError());
+    for (int i = 0; i < c.dec_layers; ++i) RT_TRY(stt_layer(s, "dec.l" + std::to_string(i), k, M, kv, i, slot, pos, pos, 0, &cross, cross_slot, enc_last, cap));
+    return RT_OK;
+}
 int stt_decode_tab(rt_stt* s, const SttWork& k, const KvCache& kv, const KvCache& cross, int M, const int32_t* tok, const int32_t* slot, const int32_t* pos,
                    const int32_t* cross_slot, const int32_t* enc_last, const int32_t* take, int n_out, float* d_logits) {
     rt_ctx* ctx = s->ctx;
     const rt_stt_config& c = s->cfg;
     const int D = c.d_model;
     SttSlot* emb = stt_find(s, "dec.tok");
-    hipLaunchKernelGGL(k_stt_embed_rows, dim3(M), dim3(128), 0, ctx->stream, emb->tbl, SVEC(s, "dec.pos"), tok, pos, D, k.x);
-    RT_HIP(ctx, hipGetLastError());
-    for (int i = 0; i < c.dec_layers; ++i) RT_TRY(stt_layer(s, "dec.l" + std::to_string(i), k, M, kv, i, slot, pos, pos, 0, &cross, cross_slot, enc_last));
+    RT_TRY(stt_decode_tab_rows(s, k, kv, cross, M, tok, slot, pos, cross_slot, enc_last));
     const float* last = k.x;
     if (take) {
         hipLaunchKernelGGL(k_stt_take_rows, dim3(n_out), dim3(64), 0, ctx->stream, k.x, take, D, s->prm.xlast);
@@ -2194,6 +2277,192 @@ int stt_check_languages(rt_stt* s, const char* who, const char* wants, const int
     return RT_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------- token times (rt_stt_align)
+// Frames of a window of n_in samples at rate sr ("word times"): half the log-mel frames of its resampled length
+// (Resampler::n_out, restated so that nothing has to be designed first), at least 1, at most n_ctx.  One frame is 0.02 s.
+int stt_align_frames(const rt_stt_config& c, int sr, int64_t n_in) {
+    int64_t n16 = n_in;
+    if (sr != c.sample_rate) {
+        int a = sr, b = c.sample_rate;
+        while (b) { const int t = a % b; a = b; b = t; }
+        const int64_t L = c.sample_rate / a, M = sr / a;
+        n16 = (n_in * L + M - 1) / M;
+    }
+    return (int)std::min<int64_t>(std::max<int64_t>(n16 / c.hop / 2, 1), c.n_ctx);
+}
+
+// The alignment side holds what `need` asks for (stt_reserve, as the beam path's)
+int stt_align_reserve(rt_stt* s, const SttAlignNeed& need) {
+    const SttAlignNeed& h = s->aln.has;
+    if (h.rows >= need.rows && h.w >= need.w && h.m >= need.m && h.stats >= need.stats && h.trace >= need.trace && h.tab >= need.tab && h.arows >= need.arows) return RT_OK;
+    SttAlignNeed n;
+    n.rows = std::max(h.rows, need.rows); n.w = std::max(h.w, need.w); n.m = std::max(h.m, need.m); n.stats = std::max(h.stats, need.stats);
+    n.trace = std::max(h.trace, need.trace); n.tab = std::max(h.tab, need.tab); n.arows = std::max(h.arows, need.arows);
+    return stt_reserve(s, s->aln, [&](SttAlignBuf& nb) -> int {
+        const rt_stt_config& c = s->cfg;
+        RT_TRY(stt_alloc_work(s, nb.owned, n.rows, nb.work));
+        RT_TRY(stt_alloc(s, nb.owned, n.rows, &nb.enc_last));
+        RT_TRY(stt_alloc(s, nb.owned, (size_t)STT_ALIGN_CHUNK * c.d_model, &nb.xl)); RT_TRY(stt_alloc(s, nb.owned, (size_t)STT_ALIGN_CHUNK * c.d_model, &nb.xn));
+        RT_TRY(stt_alloc(s, nb.owned, (size_t)STT_ALIGN_CHUNK * c.vocab, &nb.logits));
+        RT_TRY(stt_alloc(s, nb.owned, n.w, &nb.W)); RT_TRY(stt_alloc(s, nb.owned, n.m, &nb.M)); RT_TRY(stt_alloc(s, nb.owned, n.arows, &nb.lp));
+        RT_TRY(stt_alloc(s, nb.owned, n.stats, &nb.stats)); RT_TRY(stt_alloc(s, nb.owned, n.trace, &nb.trace));
+        RT_TRY(stt_alloc(s, nb.owned, n.arows, &nb.frames)); RT_TRY(stt_alloc(s, nb.owned, n.tab, &nb.tab));
+        hipLaunchKernelGGL(k_stt_fill_i32, dim3(64), dim3(256), 0, s->ctx->stream, nb.enc_last, (int)n.rows, c.n_ctx - 1, 0);
+        RT_HIP(s->ctx, hipGetLastError());
+        nb.has = n;
+        return RT_OK;
+    });
+}
+
+// One window of an rt_stt_align call: its samples, its text ids and the id position 1 of its prefix takes
+struct SttAlignItem { SttSpan span; const int32_t* ids; int n; int32_t lang; };
+// What rt_debug_stt_align_stages reads of a group (host memory; caps in floats): W [window][head][r_max][f_max] and M, window by window
+struct SttAlignStages { float* h_W; size_t w_cap; float* h_M; size_t m_cap; int32_t r_max, f_max; };
+
+// One group (1 .. STT_GROUP windows, every one with ids) through the four steps: front end and encoder; ONE teacher-forced pass over
+// the rows [prefix + ids] of every window - stt_decode_tab's embedding and layers (stt_decode_tab_rows) with the capture argument set,
+// and its tail (final LayerNorm, LM head) run here over the rows that predict a text id only, STT_ALIGN_CHUNK at a time: the logits of
+// every row at once would be rows x vocab floats; the probabilities' normalisation, filter and head mean; the paths.  Row k of a window's alignment rows sits at
+// position P - 1 + k and predicts token k of ids + [end-of-sequence]; the row whose input would be end-of-sequence is not fed.
+// h_frames [sum (n + 1)], h_lp [sum n] (null: not wanted).  The group's uploads come first, while the stream is idle.
+int stt_align_group(rt_stt* s, const SttAlignItem* it, int nW, int sr, int32_t* h_frames, float* h_lp, SttAlignStages* stages) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    const int P = c.n_prefix, NH = (int)s->al_heads.size(), D = c.d_model;
+    size_t M = 0, A = 0, L = 0, m_n = 0, trace_n = 0;
+    int r_max = 0, f_max = 0;
+    std::vector<int> F(nW);
+    for (int b = 0; b < nW; ++b) {
+        F[b] = stt_align_frames(c, sr, it[b].span.n);
+        M += (size_t)P + it[b].n; A += (size_t)it[b].n + 1; L += it[b].n;
+        r_max = std::max(r_max, it[b].n + 1); f_max = std::max(f_max, F[b]);
+        m_n += (size_t)(it[b].n + 1) * F[b];
+        trace_n += align_trace_words(it[b].n + 1, F[b]);
+    }
+    const int64_t head_stride = (int64_t)r_max * f_max;
+    constexpr size_t WIN_WORDS = sizeof(AlignWin) / 4;
+    static_assert(sizeof(AlignWin) % 8 == 0, "AlignWin is laid out in 64-bit units");
+    // the tables of the group (32-bit words; the two 64-bit parts first)
+    const size_t o_wins = 0, o_aout = o_wins + WIN_WORDS * nW, o_tok = o_aout + 2 * A, o_slot = o_tok + M, o_pos = o_slot + M, o_asrc = o_pos + M, o_aslot = o_asrc + A,
+                 o_afr = o_aslot + A, o_lrow = o_afr + A, o_ltok = o_lrow + L, tab_n = o_ltok + L;
+    SttAlignNeed need;
+    need.rows = M; need.w = (size_t)nW * NH * head_stride; need.m = m_n; need.stats = (size_t)nW * NH * f_max * 2; need.trace = trace_n; need.tab = tab_n; need.arows = A;
+    RT_TRY(stt_group_reserve(s, nW));
+    RT_TRY(stt_align_reserve(s, need));
+    SttAlignBuf& ab = s->aln;
+    std::vector<int32_t>& h = s->h_aln;
+    h.assign(tab_n, 0);
+    std::vector<SttSpan> spans(nW);
+    {
+        std::vector<AlignWin> wins(nW);
+        std::vector<int64_t> aout(A);
+        size_t row = 0, a = 0, l = 0, m_off = 0, t_off = 0;
+        for (int b = 0; b < nW; ++b) {
+            spans[b] = it[b].span;
+            const int n = it[b].n;
+            wins[b] = AlignWin{n + 1, F[b], (int64_t)b * NH * head_stride, (int64_t)m_off, (int64_t)a, (int64_t)t_off};
+            m_off += (size_t)(n + 1) * F[b];
+            t_off += align_trace_words(n + 1, F[b]);
+            for (int i = 0; i < P + n; ++i, ++row) {
+                h[o_tok + row] = i < P ? ((i == 1 && P > 1) ? it[b].lang : c.prefix[i]) : it[b].ids[i - P];
+                h[o_slot + row] = b; h[o_pos + row] = i;
+                if (i < P - 1) continue;
+                const int k = i - (P - 1);                 // alignment row k: predicts ids[k], the last one end-of-sequence
+                h[o_asrc + a] = (int32_t)row; h[o_aslot + a] = b; h[o_afr + a] = F[b];
+                aout[a] = wins[b].w_off + (int64_t)k * f_max;
+                ++a;
+                if (k < n) { h[o_lrow + l] = (int32_t)row; h[o_ltok + l] = it[b].ids[k]; ++l; }
+            }
+        }
+        memcpy(h.data() + o_wins, wins.data(), sizeof(AlignWin) * nW);
+        memcpy(h.data() + o_aout, aout.data(), 8 * A);
+    }
+    RT_HIP(ctx, hipMemcpyAsync(ab.tab, h.data(), tab_n * 4, hipMemcpyHostToDevice, ctx->stream));
+    const int32_t* tab = ab.tab;
+    const AlignWin* d_wins = reinterpret_cast<const AlignWin*>(tab + o_wins);
+    RT_TRY(stt_features_group(s, spans.data(), nW, sr));
+    for (int b = 0; b < nW; ++b)      // (stt_align_frames restates the resampled length: held against what the front end made of the window)
+        if (F[b] != (int)std::min<int64_t>(std::max<int64_t>(s->h_wins[b].n16 / c.hop / 2, 1), c.n_ctx))
+            return rt_fail(ctx, RT_ERR_STATE, "align: window %d: %d frames planned, the front end holds %lld samples", b, F[b], (long long)s->h_wins[b].n16);
+    RT_TRY(stt_encode(s, s->grp.enc, nW));
+    // the teacher-forced pass
+    const KvCache& cross = s->grp.enc.cross_kv;
+    SttSlot* emb = stt_find(s, "dec.tok");
+    const SttWork& k = ab.work;
+    SttCapture cap{AlignRows{tab + o_asrc, tab + o_aslot, tab + o_afr, reinterpret_cast<const int64_t*>(tab + o_aout)}, (int)A, s->al_layers.data(), head_stride, ab.W};
+    RT_TRY(stt_decode_tab_rows(s, k, s->grp.dec.kv, cross, (int)M, tab + o_tok, tab + o_slot, tab + o_pos, tab + o_slot, ab.enc_last, &cap));
+    // token log-probabilities: log_softmax over the text ids [0, end-of-sequence) at the token a row predicts
+    for (size_t at = 0; at < L; at += STT_ALIGN_CHUNK) {
+        const int n = (int)std::min<size_t>(STT_ALIGN_CHUNK, L - at);
+        hipLaunchKernelGGL(k_stt_take_rows, dim3(n), dim3(64), 0, ctx->stream, k.x, tab + o_lrow + at, D, ab.xl);
+        RT_HIP(ctx, hipGetLastError());
+        RT_TRY(stt_ln(s, ab.xl, D, n, SVEC(s, "dec.ln_w"), SVEC(s, "dec.ln_b"), ab.xn));
+        RT_TRY(stt_gemm(s, ab.xn, n, emb->pw, nullptr, ACT_NONE, nullptr, ab.logits));
+        RT_TRY(launch_align_logprob(ctx, ab.logits, c.vocab, n, tab + o_ltok + at, c.eos_id, ab.lp + at));
+    }
+    {
+        SttAlignSpan span(s, 1);
+        RT_TRY(launch_align_matrix(ctx, ab.W, d_wins, nW, NH, head_stride, f_max, r_max, f_max, s->al_width, ab.stats, ab.M));
+    }
+    {
+        SttAlignSpan span(s, 2);
+        RT_TRY(launch_align_dtw(ctx, ab.M, d_wins, nW, r_max, f_max, ab.trace, -1, ab.frames));
+    }
+    s->h_aln_frames.resize(A); s->h_aln_lp.resize(std::max<size_t>(L, 1));
+    RT_HIP(ctx, hipMemcpyAsync(s->h_aln_frames.data(), ab.frames, A * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (L) RT_HIP(ctx, hipMemcpyAsync(s->h_aln_lp.data(), ab.lp, L * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    stt_align_clock_collect(s);
+    if (h_frames) std::copy(s->h_aln_frames.begin(), s->h_aln_frames.end(), h_frames);
+    if (h_lp) std::copy(s->h_aln_lp.begin(), s->h_aln_lp.begin() + L, h_lp);
+    if (stages) {
+        stages->r_max = r_max; stages->f_max = f_max;
+        if (need.w > stages->w_cap || m_n > stages->m_cap) return rt_fail(ctx, RT_ERR_LENGTH, "align stages: %zu and %zu floats, room for %zu and %zu", need.w, m_n, stages->w_cap, stages->m_cap);
+        // (the capture writes rows <= n, t < F of every window and nothing reads the other cells: the copy shows them as zeros)
+        RT_HIP(ctx, hipMemcpy(stages->h_W, ab.W, need.w * 4, hipMemcpyDeviceToHost));
+        RT_HIP(ctx, hipMemcpy(stages->h_M, ab.M, m_n * 4, hipMemcpyDeviceToHost));
+        for (int b = 0; b < nW; ++b)
+            for (int hh = 0; hh < NH; ++hh)
+                for (int r = 0; r < r_max; ++r)
+                    for (int t = 0; t < f_max; ++t)
+                        if (r > it[b].n || t >= F[b]) stages->h_W[((size_t)b * NH + hh) * head_stride + (size_t)r * f_max + t] = 0.f;
+    }
+    return RT_OK;
+}
+
+// The argument rules of rt_stt_align, all of them before the first launch, and the call's windows as items
+int stt_align_check(rt_stt* s, const char* who, const float* const* d_pcm, const int64_t* n_samples, int32_t n_windows, int32_t sr, const int32_t* h_text_ids,
+                    const int32_t* h_text_offsets, const int32_t* h_language, std::vector<SttAlignItem>& items) {
+    rt_ctx* ctx = s->ctx;
+    const rt_stt_config& c = s->cfg;
+    if (n_windows < 0 || sr < 1000 || stt_check_clips(d_pcm, n_samples, n_windows) || (n_windows > 0 && !h_text_offsets) || (n_windows > 0 && h_text_offsets[0] != 0))
+        return rt_fail(ctx, RT_ERR_INVALID, "%s: bad argument", who);
+    if (!s->finalized) return rt_fail(ctx, RT_ERR_STATE, "%s: not finalized", who);
+    if (s->al_heads.empty()) return rt_fail(ctx, RT_ERR_INVALID, "%s: the handle has no alignment heads (rt_stt_set_alignment)", who);
+    bool probe = false;
+    RT_TRY(stt_check_languages(s, who, "languages", h_language, n_windows, probe));
+    if (probe) return rt_fail(ctx, RT_ERR_INVALID, "%s: a window's language must be given (-1, detection, is not offered here: detect with rt_stt_detect_language)", who);
+    const int room = c.n_text_ctx - c.n_prefix - 1;
+    items.clear();
+    for (int w = 0; w < n_windows; ++w) {
+        const int64_t n = (int64_t)h_text_offsets[w + 1] - h_text_offsets[w];
+        if (n < 0 || (n > 0 && !h_text_ids)) return rt_fail(ctx, RT_ERR_INVALID, "%s: window %d: text offsets must not decrease", who, w);
+        if (n > room) return rt_fail(ctx, RT_ERR_LENGTH, "%s: length: window %d has %lld text ids, a text context of %d behind %d forced ids takes %d", who, w, (long long)n, c.n_text_ctx, c.n_prefix, room);
+        if (n_samples[w] > (int64_t)c.chunk_seconds * sr)
+            return rt_fail(ctx, RT_ERR_LENGTH, "%s: length: window %d has %lld samples, one window is at most %d s", who, w, (long long)n_samples[w], c.chunk_seconds);
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t id = h_text_ids[h_text_offsets[w] + i];
+            if (id < 0 || id >= c.vocab) return rt_fail(ctx, RT_ERR_INVALID, "%s: window %d: id %d outside the vocabulary of %d", who, w, id, c.vocab);
+            // (a token's log-probability is taken over the text ids [0, end-of-sequence): a special or timestamp id has none)
+            if (id >= c.eos_id) return rt_fail(ctx, RT_ERR_INVALID, "%s: window %d: id %d is not a text id (end-of-sequence is %d)", who, w, id, c.eos_id);
+        }
+        items.push_back({SttSpan{w, n_samples[w] > 0 ? d_pcm[w] : nullptr, n_samples[w]}, h_text_ids ? h_text_ids + h_text_offsets[w] : nullptr, (int)n,
+                         h_language ? h_language[w] : (c.n_prefix > 1 ? c.prefix[1] : 0)});
+    }
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2228,7 +2497,7 @@ int rt_stt_destroy(rt_stt* s) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& sl : s->slots) { if (sl.raw) (void)hipFree(sl.raw); if (sl.raw2) (void)hipFree(sl.raw2); }
-    for (auto* owned : {&s->owned, &s->grp.owned, &s->beam.owned, &s->prm.owned})
+    for (auto* owned : {&s->owned, &s->grp.owned, &s->beam.owned, &s->prm.owned, &s->aln.owned})
         for (void* p : *owned) (void)hipFree(p);
     if (s->rs.d_h) (void)hipFree(s->rs.d_h);
     delete s;
@@ -2972,6 +3241,92 @@ int rt_debug_stt_encode_batch(rt_stt* s, const float* const* d_pcm, const int64_
     RT_HIP(ctx, hipMemcpyAsync(d_states, s->grp.enc.out, (size_t)n_clips * s->cfg.n_ctx * s->cfg.d_model * 4, hipMemcpyDeviceToDevice, ctx->stream));
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return RT_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+int rt_stt_set_alignment(rt_stt* s, const int32_t* h_layer_head, int32_t n_heads, int32_t median_width) {
+    if (!s || !h_layer_head) return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_set_alignment: null argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    const rt_stt_config& c = s->cfg;
+    if (n_heads < 1 || n_heads > ALIGN_HEADS_MAX) return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_alignment: %d heads (1 .. %d)", n_heads, ALIGN_HEADS_MAX);
+    if (median_width < 1 || median_width > ALIGN_MEDIAN_MAX || !(median_width & 1))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_alignment: a median width of %d (odd, 1 .. %d)", median_width, ALIGN_MEDIAN_MAX);
+    std::vector<std::pair<int32_t, int32_t>> heads;
+    std::vector<AlignHeads> layers(c.dec_layers, AlignHeads{});
+    for (int i = 0; i < n_heads; ++i) {
+        const int32_t l = h_layer_head[2 * i], h = h_layer_head[2 * i + 1];
+        if (l < 0 || l >= c.dec_layers || h < 0 || h >= c.heads)
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_alignment: pair %d = (%d, %d) outside %d decoder layers of %d heads", i, l, h, c.dec_layers, c.heads);
+        if (std::find(heads.begin(), heads.end(), std::make_pair(l, h)) != heads.end())
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_stt_set_alignment: pair (%d, %d) is given twice", l, h);
+        heads.push_back({l, h});
+        AlignHeads& a = layers[l];
+        a.head[a.n] = h; a.out[a.n] = i; ++a.n;
+    }
+    s->al_heads = std::move(heads);
+    s->al_layers = std::move(layers);
+    s->al_width = median_width;
+    return RT_OK;
+}
+
+int rt_stt_align(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_windows, int32_t sample_rate, const int32_t* h_text_ids,
+                 const int32_t* h_text_offsets, const int32_t* h_language, rt_stt_align_out* out) {
+    if (!s || !out) return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_stt_align: null argument");
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<SttAlignItem> items;
+    RT_TRY(stt_align_check(s, "rt_stt_align", d_pcm, n_samples, n_windows, sample_rate, h_text_ids, h_text_offsets, h_language, items));
+    if (out->h_n_frames)
+        for (int w = 0; w < n_windows; ++w) out->h_n_frames[w] = stt_align_frames(s->cfg, sample_rate, n_samples[w]);
+    // groups of up to STT_GROUP windows with ids, in the call's order; a window without ids has no entries and takes part in nothing
+    std::vector<SttAlignItem> group;
+    size_t f_at = 0, l_at = 0;
+    for (size_t next = 0; next <= items.size(); ++next) {
+        if (next < items.size() && items[next].n > 0) group.push_back(items[next]);
+        if (group.empty() || (next < items.size() && (int)group.size() < STT_GROUP)) continue;
+        size_t A = 0, L = 0;
+        for (const SttAlignItem& it : group) { A += (size_t)it.n + 1; L += it.n; }
+        RT_TRY(stt_align_group(s, group.data(), (int)group.size(), sample_rate, out->h_token_frame ? out->h_token_frame + f_at : nullptr,
+                               out->h_token_logprob ? out->h_token_logprob + l_at : nullptr, nullptr));
+        f_at += A; l_at += L;
+        group.clear();
+    }
+    return RT_OK;
+}
+
+int rt_debug_stt_align_timing(rt_stt* s, int32_t on, double* ms_capture, double* ms_matrix, double* ms_dtw) {
+    if (!s) return RT_ERR_INVALID;
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    if (ms_capture) *ms_capture = s->al_ms[0];
+    if (ms_matrix) *ms_matrix = s->al_ms[1];
+    if (ms_dtw) *ms_dtw = s->al_ms[2];
+    for (double& v : s->al_ms) v = 0.0;
+    s->al_clock = on != 0;
+    return RT_OK;
+}
+
+int rt_debug_stt_align_stages(rt_stt* s, const float* const* d_pcm, const int64_t* n_samples, int32_t n_windows, int32_t sample_rate, const int32_t* h_text_ids,
+                              const int32_t* h_text_offsets, const int32_t* h_language, float* h_W, int64_t w_cap, float* h_M, int64_t m_cap, int32_t* h_shape,
+                              int32_t* h_token_frame, float* h_token_logprob) {
+    if (!s || !h_W || !h_M || !h_shape || w_cap < 0 || m_cap < 0 || n_windows < 1 || n_windows > STT_GROUP)
+        return rt_fail(s ? s->ctx : nullptr, RT_ERR_INVALID, "rt_debug_stt_align_stages: bad argument (1 .. %d windows)", STT_GROUP);
+    rt_ctx* ctx = s->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<SttAlignItem> items;
+    RT_TRY(stt_align_check(s, "rt_debug_stt_align_stages", d_pcm, n_samples, n_windows, sample_rate, h_text_ids, h_text_offsets, h_language, items));
+    for (const SttAlignItem& it : items)
+        if (it.n < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_stt_align_stages: every window needs text ids");
+    SttAlignStages st{h_W, (size_t)w_cap, h_M, (size_t)m_cap, 0, 0};
+    const int rc = stt_align_group(s, items.data(), n_windows, sample_rate, h_token_frame, h_token_logprob, &st);
+    h_shape[0] = st.r_max; h_shape[1] = st.f_max;
+    return rc;
 }
 
 }  // extern "C"

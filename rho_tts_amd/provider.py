@@ -1034,6 +1034,16 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
     def sample_rate(self) -> int:
         return 24000 if self._engine is None else self._engine.cfg.sample_rate
 
+    def word_times(self, audio: torch.Tensor, text):
+        """When each word of ``text`` (a string, or token ids) is spoken in ``audio`` (one window of generated audio at ``sample_rate``):
+        the transcriber's forced alignment (stt.WhisperTranscriber.align), a list of stt.SttWord with times in seconds - for captions,
+        highlighting and lip-sync.  The text is the known target, so the result does not depend on what a transcription would hear."""
+        align = getattr(getattr(self, "transcriber", None), "align", None)
+        if align is None:
+            raise ValueError("word_times needs a transcriber with forced alignment: set `transcriber` to a stt.WhisperTranscriber "
+                             "(the option that is missing: transcriber=WhisperTranscriber(...))")
+        return align([audio], self.sample_rate, [text])[0]
+
     def close(self) -> None:
         with self._lock:
             self._close_speed_pitch()                          # (before the context they live on)

@@ -98,6 +98,18 @@ class SttConfig:
     # <|startofprev|>, which opens a window's prompt (NativeSTT.set_prompt; a generation config's `prev_sot_token_id`); None: a
     # vocabulary this build does not know - such a model takes no prompt
     sot_prev_id: Optional[int] = CLASSIC_SOT_PREV_ID
+    # word times (NativeSTT.align_ids): the (decoder layer, head) pairs whose cross-attention follows the audio and the width of the
+    # median filter along time - a generation config's `alignment_heads` and `median_filter_width`; None: OpenAI's default, every head
+    # of the upper half of the decoder layers (``aligned_heads``)
+    alignment_heads: Optional[Tuple[Tuple[int, int], ...]] = None
+    median_filter_width: int = 7
+
+    @property
+    def aligned_heads(self) -> Tuple[Tuple[int, int], ...]:
+        """The alignment heads in the order they are averaged in: the configured ones, or every head of the upper half of the decoder."""
+        if self.alignment_heads is not None:
+            return tuple((int(l), int(h)) for l, h in self.alignment_heads)
+        return tuple((l, h) for l in range(self.dec_layers // 2, self.dec_layers) for h in range(self.heads))
 
     @property
     def n_timestamps(self) -> int:
@@ -176,6 +188,10 @@ class SttConfig:
             c = c.with_language(language)
         elif len(c.prefix) > 1:
             c.language = c.language_code(c.prefix[1]) or "en"
+        if gen.get("alignment_heads"):
+            c.alignment_heads = tuple((int(l), int(h)) for l, h in gen["alignment_heads"])
+        if gen.get("median_filter_width"):
+            c.median_filter_width = int(gen["median_filter_width"])
         if gen.get("begin_suppress_tokens"):
             c.begin_suppress = tuple(int(t) for t in gen["begin_suppress_tokens"] if 0 <= int(t) < c.vocab)[:4]
         # Whisper's vocabularies put every special id (language, task, timestamps) behind end-of-sequence
@@ -258,6 +274,11 @@ class RtSttPrompt(C.Structure):
                 ("n_initial", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class RtSttAlignOut(C.Structure):
+    _fields_ = [("h_token_frame", C.POINTER(C.c_int32)), ("h_token_logprob", C.POINTER(C.c_float)), ("h_n_frames", C.POINTER(C.c_int32)),
+                ("reserved", C.c_int32 * 4)]
+
+
 @dataclass
 class SttPromptWindow:
     """One window's line of ``NativeSTT.prompt_report``: the length of the prompt it decoded behind, and whether the clip's reset mark
@@ -301,6 +322,30 @@ class SttFallbackWindow:
     compression_ratio: float
 
 
+FRAME_SECONDS = 0.02           # one frame of the alignment: two log-mel hops, the tick of the timestamp ids
+
+
+@dataclass
+class SttTokenTimes:
+    """One window of ``NativeSTT.align_ids``: per text id its start and end in seconds of the window and its log-probability (log_softmax
+    over the text ids of the logits that predict it), and the window's frames."""
+    start: List[float]
+    end: List[float]
+    logprob: List[float]
+    n_frames: int
+
+
+@dataclass
+class SttWord:
+    """One word of a segment or of an aligned text: start and end in seconds, ``probability`` = exp(mean log-probability of its ids),
+    and ``ids``, the token ids it was grouped from (a segment's words hold the segment's ids in order; beyond faster-whisper's ``Word``)."""
+    word: str
+    start: float
+    end: float
+    probability: float
+    ids: List[int] = field(default_factory=list)
+
+
 @dataclass
 class SttSegment:
     """One closed segment of a clip (transcribe_ids_seek): start and end in seconds of the clip (and in ticks of 0.02 s, which is what
@@ -316,6 +361,7 @@ class SttSegment:
     attempts: int = 1
     compression_ratio: float = float("nan")
     prompt_len: int = 0                  # under a prompt policy, of the window that closed the segment
+    words: Optional[List[SttWord]] = None    # WhisperTranscriber(word_timestamps=True).batch_segments fills it
 
 
 @dataclass
@@ -409,6 +455,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_stt_fallback_report.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)]
     lib.rt_stt_set_prompt.argtypes = [vp, C.POINTER(RtSttPrompt)]
     lib.rt_stt_prompt_report.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    lib.rt_stt_set_alignment.argtypes = [vp, C.POINTER(i32), i32, i32]
+    lib.rt_stt_align.argtypes = [vp, C.POINTER(vp), C.POINTER(i64), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(RtSttAlignOut)]
     lib.rt_stt_log_mel.argtypes = [vp, vp, i64, i32, vp]
     lib.rt_stt_encode.argtypes = [vp, vp, i64, i32, vp]
     _DECLARED = True
@@ -574,6 +622,108 @@ def _clip_ids(toks, counts, n: int, cap: int) -> List[List[int]]:
     return [[int(toks[i * cap + k]) for k in range(counts[i])] for i in range(n)]
 
 
+# ---------------------------------------------------------------------------------------------- word grouping (host, no GPU)
+# OpenAI's rules (whisper/tokenizer.py split_tokens_on_unicode / split_tokens_on_spaces, whisper/timing.py merge_punctuations) restated
+# over a ``decode(ids) -> str`` callable that renders ids as they are (no special id skipped).  A group is (text, positions): the
+# positions index the ids that were passed in, so a caller looks the group's times up by position.  OpenAI's word-duration clamps and
+# its hallucination_silence_threshold are not restated ("word times").
+PREPEND_PUNCTUATIONS = "\"'“¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+_PUNCTUATION = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"          # string.punctuation
+UNSPACED_LANGUAGES = ("zh", "ja", "th", "lo", "my", "yue")     # written without spaces: every decodable piece is a word
+
+
+def split_tokens_on_unicode(ids: Sequence[int], decode) -> List[Tuple[str, List[int]]]:
+    """Pieces that decode to whole characters: an id whose bytes end inside a UTF-8 sequence decodes to U+FFFD and is carried over to
+    the next id - unless the full text has a genuine U+FFFD at that place."""
+    full = decode(list(ids))
+    out: List[Tuple[str, List[int]]] = []
+    cur: List[int] = []
+    offset = 0
+    for k, _ in enumerate(ids):
+        cur.append(k)
+        text = decode([ids[i] for i in cur])
+        at = text.find("�")
+        if at < 0 or (offset + at < len(full) and full[offset + at] == "�"):
+            out.append((text, cur))
+            cur = []
+            offset += len(text)
+    return out
+
+
+def split_tokens_on_spaces(ids: Sequence[int], decode, eot: Optional[int] = None) -> List[Tuple[str, List[int]]]:
+    """Words of a language written with spaces: a piece opens a word when it starts with a space, is punctuation, is a special id
+    (>= ``eot``) or is the first; every other piece continues the word before it."""
+    out: List[Tuple[str, List[int]]] = []
+    for text, pos in split_tokens_on_unicode(ids, decode):
+        special = eot is not None and ids[pos[0]] >= eot
+        if special or text.startswith(" ") or text.strip() in _PUNCTUATION or not out:
+            out.append((text, list(pos)))
+        else:
+            out[-1] = (out[-1][0] + text, out[-1][1] + list(pos))
+    return out
+
+
+def merge_punctuations(groups: List[Tuple[str, List[int]]], prepended: str = PREPEND_PUNCTUATIONS, appended: str = APPEND_PUNCTUATIONS) -> List[Tuple[str, List[int]]]:
+    """Opening punctuation joins the word behind it, closing punctuation the word before it; the emptied groups are dropped."""
+    g = [[t, list(p)] for t, p in groups]
+    i, j = len(g) - 2, len(g) - 1
+    while i >= 0:
+        if g[i][0].startswith(" ") and g[i][0].strip() in prepended:
+            g[j][0], g[j][1] = g[i][0] + g[j][0], g[i][1] + g[j][1]
+            g[i][0], g[i][1] = "", []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(g):
+        if not g[i][0].endswith(" ") and g[j][0] in appended:
+            g[i][0], g[i][1] = g[i][0] + g[j][0], g[i][1] + g[j][1]
+            g[j][0], g[j][1] = "", []
+        else:
+            i = j
+        j += 1
+    return [(t, p) for t, p in g if p]
+
+
+def group_words(ids: Sequence[int], decode=None, eot: Optional[int] = None, spaces: bool = True) -> List[Tuple[str, List[int]]]:
+    """The words of ``ids`` as (text, positions).  Without ``decode`` (a model without a tokenizer) every id is the word ``"<id>"``, as
+    ``WhisperTranscriber._text`` renders them."""
+    if decode is None:
+        return [(f"<{int(t)}>", [k]) for k, t in enumerate(ids)]
+    pieces = split_tokens_on_spaces(ids, decode, eot) if spaces else split_tokens_on_unicode(ids, decode)
+    return merge_punctuations(pieces)
+
+
+def words_from_times(ids: Sequence[int], times: "SttTokenTimes", first: int, groups: List[Tuple[str, List[int]]], shift: float = 0.0) -> List["SttWord"]:
+    """``groups`` over ``ids`` - which are the ids ``first ..`` of the window ``times`` speaks of - as words: a word starts with its first
+    id and ends with its last, and its probability is exp(mean log-probability)."""
+    out = []
+    for text, pos in groups:
+        lp = [times.logprob[first + k] for k in pos]
+        out.append(SttWord(text, shift + times.start[first + pos[0]], shift + times.end[first + pos[-1]], math.exp(sum(lp) / len(lp)), [int(ids[k]) for k in pos]))
+    return out
+
+
+MAX_ALIGNMENT_HEADS, MAX_MEDIAN_WIDTH = 32, 31       # rt_stt_set_alignment's limits
+
+
+def alignment_error(cfg: "SttConfig") -> Optional[str]:
+    """Why ``cfg``'s alignment heads and median width cannot be set on a model (rt_stt_set_alignment's rules, checked before anything
+    touches a device), or None.  Word times are optional: a model they cannot be set on loads and transcribes as before, and
+    ``NativeSTT.align_ids`` raises with this text."""
+    heads, width = cfg.aligned_heads, cfg.median_filter_width
+    where = "the configuration's alignment_heads" if cfg.alignment_heads is not None else \
+        "the default (every head of the upper half of the decoder; give SttConfig.alignment_heads or a generation config's `alignment_heads`)"
+    if not 1 <= len(heads) <= MAX_ALIGNMENT_HEADS:
+        return f"{where} names {len(heads)} heads; word times take 1 .. {MAX_ALIGNMENT_HEADS}"
+    if len(set(heads)) != len(heads) or any(not (0 <= l < cfg.dec_layers and 0 <= h < cfg.heads) for l, h in heads):
+        return f"{where} holds a pair twice or outside {cfg.dec_layers} decoder layers of {cfg.heads} heads"
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not 1 <= int(width) <= MAX_MEDIAN_WIDTH or int(width) % 2 == 0:
+        return f"median_filter_width must be an odd integer in 1 .. {MAX_MEDIAN_WIDTH}, got {width!r}"
+    return None
+
+
 class NativeSTT:
     """One ``rt_stt``: the speech-to-text model in HBM, on the context (GPU, stream) of the TTS engine it validates."""
 
@@ -608,6 +758,18 @@ class NativeSTT:
         if cfg.timestamp_begin is not None:
             ctx.check(self.lib.rt_stt_set_timestamps(self.handle, int(cfg.timestamp_begin), int(cfg.n_timestamps)), "rt_stt_set_timestamps")
         ctx.check(self.lib.rt_stt_finalize(self.handle), "rt_stt_finalize")
+        self._set_alignment()
+
+    def _set_alignment(self) -> None:
+        """Word times are optional: heads that cannot be set (``alignment_error``) leave the model as it was before they existed - no
+        native call, nothing raised - and ``align_ids`` raises at use."""
+        cfg = self.cfg
+        self.alignment_error = alignment_error(cfg)
+        if self.alignment_error is None:
+            heads = cfg.aligned_heads
+            flat = (C.c_int32 * (2 * len(heads)))(*[int(v) for pair in heads for v in pair])
+            if self.lib.rt_stt_set_alignment(self.handle, flat, len(heads), int(cfg.median_filter_width)) != _native.RT_OK:
+                self.alignment_error = "rt_stt_set_alignment refused the alignment heads"
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -738,6 +900,52 @@ class NativeSTT:
         for w in range(out.n_windows):
             clips[w_clip[w]].windows.append(SttWindow(int(w_n[w]), float(w_lp[w]), float(w_ns[w]) if no_speech else float("nan")))
         return clips
+
+    @property
+    def align_room(self) -> int:
+        """The text ids one window of ``align_ids`` takes: the text context behind the forced prefix, less the end-of-sequence row."""
+        return int(self.cfg.n_text_ctx) - len(self.cfg.prefix) - 1
+
+    def align_ids(self, windows, sample_rate: int, ids, languages=None) -> List[SttTokenTimes]:
+        """Forced alignment of known text from ONE native call (rt_stt_align; the rule: DESIGN.md section 5, "word times"): every entry
+        of ``windows`` is one window of at most ``chunk_seconds`` and ``ids[w]`` its text ids (no timestamp ids, no end-of-sequence, at
+        most ``align_room``).  Per window the start and end of every id in seconds of the window and its log-probability.
+        ``languages``: None - the configured prefix; else a code or token id for all windows or one per window (no detection)."""
+        if not getattr(self, "handle", None):
+            raise ValueError("align_ids: the model is closed")
+        if getattr(self, "alignment_error", None):
+            raise ValueError(f"align_ids: this model has no alignment heads: {self.alignment_error}")
+        ids = [[int(t) for t in w] for w in ids]
+        xs, n, ptrs, lens = self._clips(windows)
+        if len(ids) != n:
+            raise ValueError(f"{len(ids)} id lists for {n} windows")
+        limit = int(self.cfg.chunk_seconds) * int(sample_rate)
+        for w, (x, t) in enumerate(zip(xs, ids)):
+            if x.numel() > limit:
+                raise ValueError(f"align_ids: window {w} has {x.numel()} samples; one window is at most {self.cfg.chunk_seconds} s ({limit} samples)")
+            if len(t) > self.align_room:
+                raise ValueError(f"align_ids: window {w} has {len(t)} text ids; one window takes at most {self.align_room}")
+            if any(not 0 <= v < self.cfg.eos_id for v in t):
+                raise ValueError(f"align_ids: window {w} holds an id outside the text ids [0, {self.cfg.eos_id}): no special or timestamp ids")
+        req = self._languages(languages, n)
+        if req is not None and any(v < 0 for v in req):
+            raise ValueError("align_ids: a window's language must be given (no detection here: use detect_language)")
+        offs = [0]
+        for t in ids:
+            offs.append(offs[-1] + len(t))
+        n_rows = sum(len(t) + 1 for t in ids if t)
+        flat = (C.c_int32 * max(offs[-1], 1))(*[t for w in ids for t in w])
+        frames, lps, nfr = _i32(n_rows), _f32(offs[-1]), _i32(n)
+        out = RtSttAlignOut()
+        out.h_token_frame, out.h_token_logprob, out.h_n_frames = frames, lps, nfr
+        self.ctx.check(self.lib.rt_stt_align(self.handle, ptrs, lens, n, int(sample_rate), flat, (C.c_int32 * (n + 1))(*offs), req, C.byref(out)), "rt_stt_align")
+        res, at = [], 0
+        for w, t in enumerate(ids):
+            k = len(t)
+            fr = [int(frames[at + i]) for i in range(k + 1)] if k else []
+            at += k + 1 if k else 0
+            res.append(SttTokenTimes([f * FRAME_SECONDS for f in fr[:-1]], [f * FRAME_SECONDS for f in fr[1:]], [float(lps[offs[w] + i]) for i in range(k)], int(nfr[w])))
+        return res
 
     def seek_caps(self, n_samples: Sequence[int], sample_rate: int) -> Tuple[int, int, int]:
         """(tokens per clip, segments, windows) the first attempt of ``transcribe_ids_seek`` leaves room for.  A repeat costs a whole
@@ -978,18 +1186,24 @@ class WhisperTranscriber:
     timestamps = False                   # calls go through transcribe_ids_seek (the reference's long-form rule; see below)
     fallback = False                     # a fallback policy is set on the model (temperatures other than (0.0,))
     prompted = False                     # a prompt policy is set on the model (condition_on_previous_text / initial_prompt)
+    word_timestamps = False              # batch_segments fills every segment's words (NativeSTT.align_ids)
 
     def __init__(self, ctx: "_native.Context", model_dir: Optional[str] = None, synthetic: bool = False, cfg: Optional[SttConfig] = None, seed: int = 789,
                  beam_size: int = 1, language: str = "en", no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = -1.0,
                  timestamps: bool = False, temperatures=(0.0,), best_of: int = 5, compression_ratio_threshold: Optional[float] = 2.4,
-                 condition_on_previous_text: bool = False, initial_prompt=None, prompt_reset_on_temperature: Optional[float] = 0.5):
+                 condition_on_previous_text: bool = False, initial_prompt=None, prompt_reset_on_temperature: Optional[float] = 0.5,
+                 word_timestamps: bool = False):
         """``timestamps``: every call decodes with timestamp tokens and walks a clip longer than one window by seek positions
         (``transcribe_ids_seek``), as the reference's ``model.transcribe`` does; a clip's text is its segments' texts joined with a
         space (stt_validator.py:136), and ``batch_segments`` returns them with their times.  ``condition_on_previous_text``,
         ``initial_prompt`` and ``prompt_reset_on_temperature`` (``NativeSTT.set_prompt``; faster-whisper's options of the same names,
         which default to True, None and 0.5 there): both need ``timestamps=True``.  ``initial_prompt`` is a string - encoded as
         faster-whisper encodes it, ``" " + text.strip()`` through the tokenizer - or a sequence of token ids, the only form a model
-        without a tokenizer takes.  ``batch_detailed`` / ``batch_segments`` then report ``prompt_len`` per window."""
+        without a tokenizer takes.  ``batch_detailed`` / ``batch_segments`` then report ``prompt_len`` per window.
+        ``word_timestamps`` (faster-whisper's option of the same name; needs ``timestamps=True``): ``batch_segments`` fills every
+        segment's ``words`` from one more native call (``NativeSTT.align_ids``) over the windows the segments lie in."""
+        if word_timestamps and not timestamps:
+            raise ValueError("word_timestamps needs timestamps=True: words are placed inside the segments of the seek path")
         if (condition_on_previous_text or initial_prompt is not None) and not timestamps:
             raise ValueError("condition_on_previous_text and initial_prompt need timestamps=True: only the seek path has a previous window")
         self.beam_size = check_beam_size(beam_size)
@@ -1021,6 +1235,11 @@ class WhisperTranscriber:
         self.cfg = cfg
         temps = check_temperatures(temperatures)
         self.model = NativeSTT(ctx, cfg, state)
+        self.word_timestamps = bool(word_timestamps)
+        if self.word_timestamps and self.model.alignment_error:
+            msg = self.model.alignment_error
+            self.model.close()
+            raise ValueError(f"word_timestamps=True: this model has no alignment heads: {msg}")
         self.fallback = temps != (0.0,)
         if self.fallback:
             from .validation import compression_ratio_text
@@ -1091,7 +1310,72 @@ class WhisperTranscriber:
                         extra.update(temperature=lines[k].temperature, attempts=lines[k].attempts, compression_ratio=lines[k].compression_ratio)
                 segs.append(dataclasses.replace(g, text=self._segment_text(g.ids).strip(), **extra))
             out.append(segs)
+        if self.word_timestamps:
+            self._fill_words(list(audios), sample_rate, clips, out)
         return out
+
+    def _decode_raw(self):
+        """``decode(ids) -> str`` for the word grouping (ids rendered as they are), or None for a model without a tokenizer."""
+        if self.tokenizer is None:
+            return None
+        return lambda ids: self.tokenizer.decode(list(ids), skip_special_tokens=False)
+
+    def _words(self, ids: List[int], times: SttTokenTimes, first: int, shift: float, language: Optional[str] = None) -> List[SttWord]:
+        spaces = (language or self.cfg.language) not in UNSPACED_LANGUAGES
+        return words_from_times(ids, times, first, group_words(ids, self._decode_raw(), self.cfg.eos_id, spaces), shift)
+
+    def _fill_words(self, audios, sample_rate: int, clips: List[SttSeekClip], out: List[List[SttSegment]]) -> None:
+        """``words`` of every segment of ``out`` (``batch_segments``): segments are grouped by the window they lie in - the last window that
+        starts at or before them - and every such window of every clip goes through ONE ``align_ids`` call with the segments' ids joined;
+        times are shifted by the window's offset.  Under ``language="auto"`` a clip's windows are aligned, and split into words, under
+        the language the seek call detected for the clip.  The text ids of one window fit ``align_room`` - a segment spends two of the
+        window's at most ``n_text_ctx - n_prefix`` generated ids on its timestamps - so a window that holds more is an error."""
+        tick, win, room = int(0.02 * sample_rate), int(self.cfg.chunk_seconds) * int(sample_rate), self.model.align_room
+        jobs = []                                                     # (audio, offset in samples, [segments], the clip's language id)
+        for audio, c, segs in zip(audios, clips, out):
+            x = audio if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio, dtype=np.float32))
+            x = x.detach().reshape(-1)
+            by_window: Dict[int, List[SttSegment]] = {}
+            for g in segs:
+                g.words = []
+                if g.ids:
+                    k = max(i for i, w in enumerate(c.windows) if w.offset // tick <= g.start_tick)
+                    by_window.setdefault(k, []).append(g)
+            for k in sorted(by_window):
+                n = sum(len(g.ids) for g in by_window[k])
+                if n > room:
+                    raise RuntimeError(f"word_timestamps: the segments of the window at sample {c.windows[k].offset} hold {n} text ids; one window takes {room}")
+                jobs.append((x, c.windows[k].offset, by_window[k], int(c.language)))
+        if not jobs:
+            return
+        times = self.model.align_ids([x[off:off + win] for x, off, _, _ in jobs], sample_rate, [[t for g in piece for t in g.ids] for _, _, piece, _ in jobs],
+                                     languages=[lang for _, _, _, lang in jobs] if self.auto else None)
+        for (x, off, piece, lang), tt in zip(jobs, times):
+            first = 0
+            for g in piece:
+                g.words = self._words(g.ids, tt, first, off / float(sample_rate), self.cfg.language_code(lang) if self.auto else None)
+                first += len(g.ids)
+
+    def align(self, audios, sample_rate: int, texts_or_ids) -> List[List[SttWord]]:
+        """Forced alignment of known text to audio, one window per clip: per clip the words of its text with their times in seconds of
+        the clip.  ``texts_or_ids``: per clip a string - encoded as ``initial_prompt`` is, ``" " + text.strip()`` through the tokenizer,
+        which a model without one cannot do - or a sequence of token ids.  A clip longer than one window raises."""
+        audios, texts_or_ids = list(audios), list(texts_or_ids)
+        if len(audios) != len(texts_or_ids):
+            raise ValueError(f"{len(texts_or_ids)} texts for {len(audios)} clips")
+        limit = int(self.cfg.chunk_seconds) * int(sample_rate)
+        ids = []
+        for i, (a, t) in enumerate(zip(audios, texts_or_ids)):
+            n = a.numel() if isinstance(a, torch.Tensor) else int(np.asarray(a).size)
+            if n > limit:
+                raise ValueError(f"align: clip {i} has {n} samples; forced alignment takes one window of at most {self.cfg.chunk_seconds} s ({limit} samples) per clip")
+            if isinstance(t, str):
+                if self.tokenizer is None:
+                    raise ValueError("align: text as a string needs a checkpoint with a tokenizer; pass token ids")
+                t = self.tokenizer.encode(" " + t.strip(), add_special_tokens=False).ids
+            ids.append([int(v) for v in t])
+        times = self.model.align_ids(audios, sample_rate, ids)
+        return [self._words(t, tt, 0, 0.0) for t, tt in zip(ids, times)]
 
     def _run(self, audios, sample_rate: int, scored: bool = False, detailed: bool = False, single: bool = False) -> List[SttDetail]:
         """The one place where the configuration picks the native call; the public methods are projections of what it returns.
