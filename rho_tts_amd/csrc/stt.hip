@@ -41,6 +41,9 @@
 // the compression ratio is the caller's callback), and the windows that need another attempt are decoded again by sampling -
 // best_of rows per window, k_stt_sample_select: Gumbel-max over the ids the step rules leave - over the encoder states the group
 // still holds.  Off unless a policy is set; no other entry point changes.
+// The decoding step rule - the ids a row may take, its normaliser, "timestamps win", the next history state - is stated once
+// (stt_step_ids, stt_step_kind, stt_row_norm, stt_ts_next) and called by both select kernels; the two group decoders share the book's
+// reset, the tail of a step and the book's fetch (stt_book_reset, stt_step_live, stt_book_fetch).
 //
 // rt_stt_set_prompt gives rt_stt_transcribe_seek the reference's conditioning on previous text and an initial prompt (DESIGN.md section
 // 5, "conditioning on previous text"): the host keeps a history and a reset mark per clip, and a window with a prompt decodes behind
@@ -355,22 +358,135 @@ struct SttBeamBook {
 // <|notimestamps|>; max_initial: the largest timestamp index the first generated token may take, -1: no limit
 struct SttTsRule { int t0, nt, max_initial; };
 
-// One step of the rule, one workgroup per window.  Per live row: the masked maximum, sum exp(x - max) (per thread in index order,
-// butterfly per wave, the 16 wave sums in wave order: a row's log-probabilities do not depend on what else is in the launch), then
-// every thread's 9 best (lp, id) in registers, merged through LDS into the row's B + 1 best.  Then wave 0 ranks the window's
-// <= 72 candidates by (score descending, beam, id) and thread 0 walks them: end-of-sequence candidates enter the finished list
-// while it has room, the others become the next beams until B are taken.  logits row of beam j: w row_stride + j (the step behind
-// the prefix has one row per window: row_stride 1, one live beam).
-//
-// (k_stt_sample_select below repeats the range set-up, `kind`, the maximum pass, the sum pass and the logsumexp decision of this kernel
-// statement by statement - shared device functions would have had to leave this kernel's ISA as it is: a change to the masking or to
-// the timestamp rule is made in BOTH kernels.)
-//
-// TS (rt_stt_transcribe_seek): the same passes apply the timestamp rule.  From the row's history state every id is text, timestamp or
-// barred for this step: text ids are [text_lo, t0 - 1) under the mask, timestamp ids [ts_lo, ts_hi) whatever the mask says.  The
-// maximum pass and the sum pass each form the two parts' figures side by side (same order of reduction per part); timestamps win -
-// every text id is barred - when m_ts + log(s_ts) > m_text, and the row's normaliser follows from the parts that survive.  Thread 0
-// writes a next beam's state from its parent's.  TS == false compiles to the statements the kernel had before the rule existed.
+// The decoding step rule, stated once for beam search (k_stt_beam_select) and sampled decoding (k_stt_sample_select): which ids a row
+// may take at a step, and the normaliser of its log-probabilities over them.  Text ids are [text_lo, text_hi) under the mask (bit 0 of
+// a byte bars an id at every step, bit 1 at the first), timestamp ids [ts_lo, ts_hi) whatever the mask says; under TS
+// (rt_stt_transcribe_seek) the ranges follow from the row's history state, else there are none and every id the mask leaves is text
+struct SttStepIds { int text_lo, text_hi, ts_lo, ts_hi, bad; };
+template <bool TS>
+__device__ __forceinline__ SttStepIds stt_step_ids(int flags, int lts, int first_step, int eos, int V, const SttTsRule& ts) {
+    SttStepIds a{0, 0, 0, 0, first_step ? 3 : 1};
+    if constexpr (TS) {
+        const bool last = flags & 1, pen = flags & 2;
+        a.text_hi = ts.t0 - 1;                                 // <|notimestamps|> never appears
+        a.ts_lo = ts.t0; a.ts_hi = min(ts.t0 + ts.nt, V);
+        if (lts > 0) a.ts_lo = max(a.ts_lo, (last && !pen) ? lts : lts + 1);      // timestamps do not decrease (nor repeat, outside a pair)
+        if (last && pen) a.ts_lo = a.ts_hi;                    // behind a pair (or a lone first timestamp): text
+        if (last && !pen) a.text_lo = eos;                     // closing a pair: a timestamp or the end
+        if (first_step) {                                      // the first generated token is a timestamp, at most max_initial
+            a.text_lo = a.text_hi;
+            if (ts.max_initial >= 0) a.ts_hi = min(a.ts_hi, ts.t0 + ts.max_initial + 1);
+        }
+    }
+    return a;
+}
+// id i with mask byte mk - 0: barred, 1: text, 2: timestamp
+template <bool TS>
+__device__ __forceinline__ int stt_step_kind(const SttStepIds& a, int i, int mk) {
+    if constexpr (TS) {
+        if (i >= a.ts_lo && i < a.ts_hi) return 2;
+        return (i >= a.text_lo && i < a.text_hi && !(mk & a.bad)) ? 1 : 0;
+    } else {
+        return (mk & a.bad) ? 0 : 1;
+    }
+}
+// The history state of the row that continues one with (flags, lts) by `tok`
+__device__ __forceinline__ void stt_ts_next(int tok, int first_step, int flags, int lts, const SttTsRule& ts, int32_t* flags_out, int32_t* last_out) {
+    const bool is_ts = tok >= ts.t0;
+    *flags_out = (is_ts ? 1 : 0) | ((first_step || (flags & 1)) ? 2 : 0);
+    *last_out = is_ts ? tok : lts;
+}
+
+// The normaliser of row x over the ids `a` leaves, by all 1024 threads of a workgroup: the masked maximum, then sum exp(x - max) - per
+// thread in index order, butterfly per wave, the 16 wave values (red_v; red_w: the timestamp part) in wave order, so a row's
+// log-probabilities do not depend on what else is in the launch, nor on which kernel asks.  A NaN logit takes no part.
+// TS: each pass forms the figures of the text part and of the timestamp part side by side (same order of reduction per part);
+// timestamps win - every text id is barred, text_ok false - when m_ts + log(s_ts) > m_text, and lse follows from the parts that
+// survive.  TS == false: the text part alone, and nothing to decide.
+// Every pass over a row (these two, the callers' third) asks for STT_SEL_U logits and mask bytes of the thread at once,
+// unconditionally (clamped indices): one round trip per 4 elements instead of one per element behind a per-lane branch (DESIGN.md
+// section 9 row 0; 8 would spill at 1024 threads).
+struct SttRowNorm { float lse; bool text_ok; };
+template <bool TS>
+__device__ __forceinline__ SttRowNorm stt_row_norm(const float* __restrict__ x, const uint8_t* __restrict__ mask, int V, const SttStepIds& a,
+                                                   float* red_v, float* red_w) {
+    const int tid = threadIdx.x, wave = tid >> 6;
+    float m = -INFINITY, m2 = -INFINITY;                       // (m2, sum2: the timestamp part, TS only)
+    for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+        float xv[STT_SEL_U];
+        int mk[STT_SEL_U];
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) {
+            const int kd = base + 1024 * u < V ? stt_step_kind<TS>(a, base + 1024 * u, mk[u]) : 0;
+            if (kd == 1 && xv[u] > m) m = xv[u];
+            if constexpr (TS) { if (kd == 2 && xv[u] > m2) m2 = xv[u]; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((tid & 63) == 0) red_v[wave] = m;
+    if constexpr (TS) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
+        if ((tid & 63) == 0) red_w[wave] = m2;
+    }
+    __syncthreads();
+    m = red_v[0];
+    for (int k = 1; k < 16; ++k) m = fmaxf(m, red_v[k]);
+    if constexpr (TS) {
+        m2 = red_w[0];
+        for (int k = 1; k < 16; ++k) m2 = fmaxf(m2, red_w[k]);
+    }
+    __syncthreads();
+    float sum = 0.f, sum2 = 0.f;
+    for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
+        float xv[STT_SEL_U];
+        int mk[STT_SEL_U];
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
+#pragma unroll
+        for (int u = 0; u < STT_SEL_U; ++u) {
+            const int kd = base + 1024 * u < V ? stt_step_kind<TS>(a, base + 1024 * u, mk[u]) : 0;
+            if (kd == 1 && xv[u] == xv[u]) sum += expf(xv[u] - m);
+            if constexpr (TS) { if (kd == 2 && xv[u] == xv[u]) sum2 += expf(xv[u] - m2); }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if ((tid & 63) == 0) red_v[wave] = sum;
+    if constexpr (TS) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o, 64);
+        if ((tid & 63) == 0) red_w[wave] = sum2;
+    }
+    __syncthreads();
+    sum = red_v[0];
+    for (int k = 1; k < 16; ++k) sum += red_v[k];
+    if constexpr (TS) {
+        sum2 = red_w[0];
+        for (int k = 1; k < 16; ++k) sum2 += red_w[k];
+    }
+    __syncthreads();
+    SttRowNorm n{m + logf(sum), true};
+    if constexpr (TS) {
+        // the comparison needs no normaliser: logsumexp(timestamps) > max(text) on the raw logits is the same on log-probabilities
+        const bool has_ts = m2 > -INFINITY, has_text = m > -INFINITY;
+        const float lse_ts = has_ts ? m2 + logf(sum2) : -INFINITY;
+        n.text_ok = has_text && !(lse_ts > m);
+        if (!n.text_ok) n.lse = lse_ts;
+        else if (has_ts) { const float mm = fmaxf(m, m2); n.lse = mm + logf(sum * expf(m - mm) + sum2 * expf(m2 - mm)); }
+    }
+    return n;
+}
+
+// One step of beam search, one workgroup per window.  Per live row: the step rule's ids and normaliser (above), then every thread's
+// 9 best (lp, id) in registers, merged through LDS into the row's B + 1 best.  Then wave 0 ranks the window's <= 72 candidates by
+// (score descending, beam, id) and thread 0 walks them: end-of-sequence candidates enter the finished list while it has room, the
+// others become the next beams until B are taken.  logits row of beam j: w row_stride + j (the step behind the prefix has one row
+// per window: row_stride 1, one live beam).  TS (rt_stt_transcribe_seek): the timestamp rule applies, and thread 0 writes a next
+// beam's history state from its parent's.
 template <bool TS>
 __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restrict__ logits, int V, int row_stride, const uint8_t* __restrict__ mask,
                                                           int first_step, int eos, int B, int step, SttBeamBook bk, SttTsRule ts) {
@@ -383,110 +499,14 @@ __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restric
     const int w = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
     if (bk.done[w]) return;                                // (uniform: a completed window rides along untouched)
     const int nl = min(bk.n_live[w], B), K = B + 1;
-    const uint8_t bad = first_step ? 3 : 1;
     if constexpr (TS) {
         if (tid < B) { sh_flags[tid] = bk.ts_flags[w * B + tid]; sh_last[tid] = bk.ts_last[w * B + tid]; }
         __syncthreads();
     }
     for (int j = 0; j < nl; ++j) {
         const float* x = logits + ((int64_t)w * row_stride + j) * V;
-        int text_lo = 0, text_hi = 0, ts_lo = 0, ts_hi = 0;
-        if constexpr (TS) {
-            const bool last = sh_flags[j] & 1, pen = sh_flags[j] & 2;
-            const int lts = sh_last[j];
-            text_hi = ts.t0 - 1;                               // <|notimestamps|> never appears
-            ts_lo = ts.t0; ts_hi = min(ts.t0 + ts.nt, V);
-            if (lts > 0) ts_lo = max(ts_lo, (last && !pen) ? lts : lts + 1);      // timestamps do not decrease (nor repeat, outside a pair)
-            if (last && pen) ts_lo = ts_hi;                    // behind a pair (or a lone first timestamp): text
-            if (last && !pen) text_lo = eos;                   // closing a pair: a timestamp or the end
-            if (first_step) {                                  // the first generated token is a timestamp, at most max_initial
-                text_lo = text_hi;
-                if (ts.max_initial >= 0) ts_hi = min(ts_hi, ts.t0 + ts.max_initial + 1);
-            }
-        }
-        // 0: barred, 1: text, 2: timestamp
-        auto kind = [&](int i, int mk) -> int {
-            if (i >= ts_lo && i < ts_hi) return 2;
-            return (i >= text_lo && i < text_hi && !(mk & bad)) ? 1 : 0;
-        };
-        // every pass asks for STT_SEL_U logits and mask bytes of the thread at once, unconditionally (clamped indices): one round trip
-        // per 4 elements instead of one per element behind a per-lane branch (8 would spill at 1024 threads)
-        float m = -INFINITY, m2 = -INFINITY;                   // (m2, sum2: the timestamp part, TS only)
-        for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
-            float xv[STT_SEL_U];
-            int mk[STT_SEL_U];
-#pragma unroll
-            for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
-#pragma unroll
-            for (int u = 0; u < STT_SEL_U; ++u) {
-                if constexpr (TS) {
-                    const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
-                    if (kd == 1 && xv[u] > m) m = xv[u];
-                    if (kd == 2 && xv[u] > m2) m2 = xv[u];
-                } else {
-                    if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] > m) m = xv[u];
-                }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-        if ((tid & 63) == 0) red_v[wave] = m;
-        if constexpr (TS) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
-            if ((tid & 63) == 0) red_w[wave] = m2;
-        }
-        __syncthreads();
-        m = red_v[0];
-        for (int k = 1; k < 16; ++k) m = fmaxf(m, red_v[k]);
-        if constexpr (TS) {
-            m2 = red_w[0];
-            for (int k = 1; k < 16; ++k) m2 = fmaxf(m2, red_w[k]);
-        }
-        __syncthreads();
-        float sum = 0.f, sum2 = 0.f;
-        for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
-            float xv[STT_SEL_U];
-            int mk[STT_SEL_U];
-#pragma unroll
-            for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
-#pragma unroll
-            for (int u = 0; u < STT_SEL_U; ++u) {
-                if constexpr (TS) {
-                    const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
-                    if (kd == 1 && xv[u] == xv[u]) sum += expf(xv[u] - m);
-                    if (kd == 2 && xv[u] == xv[u]) sum2 += expf(xv[u] - m2);
-                } else {
-                    if (base + 1024 * u < V && !(mk[u] & bad) && xv[u] == xv[u]) sum += expf(xv[u] - m);
-                }
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-        if ((tid & 63) == 0) red_v[wave] = sum;
-        if constexpr (TS) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o, 64);
-            if ((tid & 63) == 0) red_w[wave] = sum2;
-        }
-        __syncthreads();
-        sum = red_v[0];
-        for (int k = 1; k < 16; ++k) sum += red_v[k];
-        if constexpr (TS) {
-            sum2 = red_w[0];
-            for (int k = 1; k < 16; ++k) sum2 += red_w[k];
-        }
-        __syncthreads();
-        float lse = m + logf(sum);
-        bool text_ok = true;
-        if constexpr (TS) {
-            // the comparison needs no normaliser: logsumexp(timestamps) > max(text) on the raw logits is the same on log-probabilities
-            const bool has_ts = m2 > -INFINITY, has_text = m > -INFINITY;
-            const float lse_ts = has_ts ? m2 + logf(sum2) : -INFINITY;
-            text_ok = has_text && !(lse_ts > m);
-            if (!text_ok) lse = lse_ts;
-            else if (has_ts) { const float mm = fmaxf(m, m2); lse = mm + logf(sum * expf(m - mm) + sum2 * expf(m2 - mm)); }
-        }
+        const SttStepIds a = stt_step_ids<TS>(TS ? sh_flags[j] : 0, TS ? sh_last[j] : 0, first_step, eos, V, ts);
+        const auto [lse, text_ok] = stt_row_norm<TS>(x, mask, V, a, red_v, red_w);
         float cv[STT_CAND];
         int ci[STT_CAND];
 #pragma unroll
@@ -500,12 +520,8 @@ __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restric
             for (int u = 0; u < STT_SEL_U; ++u) {
                 const int i = base + 1024 * u;
                 const float lp = xv[u] - lse;
-                if constexpr (TS) {
-                    const int kd = i < V ? kind(i, mk[u]) : 0;
-                    if (kd == 0 || (kd == 1 && !text_ok)) continue;
-                } else {
-                    if (i >= V || (mk[u] & bad)) continue;
-                }
+                const int kd = i < V ? stt_step_kind<TS>(a, i, mk[u]) : 0;
+                if (kd == 0 || (kd == 1 && !text_ok)) continue;
                 if (!(lp == lp) || !cand_before(lp, i, cv[STT_CAND - 1], ci[STT_CAND - 1])) continue;
                 cv[STT_CAND - 1] = lp; ci[STT_CAND - 1] = i;
 #pragma unroll
@@ -572,11 +588,7 @@ __global__ __launch_bounds__(1024) void k_stt_beam_select(const float* __restric
             bk.score[row] = sc;
             bk.bp_tok[(int64_t)step * bk.R + row] = c_tok[id];
             bk.bp_par[(int64_t)step * bk.R + row] = c_beam[id];
-            if constexpr (TS) {
-                const bool is_ts = c_tok[id] >= ts.t0;
-                bk.ts_flags[row] = (is_ts ? 1 : 0) | ((first_step || (sh_flags[c_beam[id]] & 1)) ? 2 : 0);
-                bk.ts_last[row] = is_ts ? c_tok[id] : sh_last[c_beam[id]];
-            }
+            if constexpr (TS) stt_ts_next(c_tok[id], first_step, sh_flags[c_beam[id]], sh_last[c_beam[id]], ts, &bk.ts_flags[row], &bk.ts_last[row]);
             ++nb;
         }
     }
@@ -615,14 +627,12 @@ __device__ __forceinline__ float stt_gumbel(unsigned row_hash, int id) {
 struct SttSampleRule { float T; unsigned seed_lo, seed_hi, t_index; const int32_t* key; const int32_t* sample; };
 
 // One sampled step, one workgroup per ROW (window x sample; row w S + j is sample j of window w, its logits at row
-// w row_stride + (row_stride > 1 ? j : 0): the step behind the prefix has one row of logits per window).  The passes of
-// k_stt_beam_select - masked maximum and sum exp on the UNTEMPERED logits, the two parts side by side under TS, the same order of
-// reduction - give the row's log-probabilities and the decision "timestamps win"; one more pass takes the arg-max of x / T + g(id)
-// over the surviving ids (Gumbel-max: the pick is distributed as softmax(x / T) over them), the lower id on ties.  A NaN or -inf
-// logit takes no part.  The row's score adds the untempered log-probability of the pick; end-of-sequence (or a row without any
-// survivor, which counts as ending) sets the row's done flag and takes it out of `live`; a row that is done rides along untouched.
-// The range set-up, `kind`, the two passes and the logsumexp decision are k_stt_beam_select's, repeated here: a change to the masking
-// or to the timestamp rule is made in BOTH kernels.
+// w row_stride + (row_stride > 1 ? j : 0): the step behind the prefix has one row of logits per window).  The step rule (the
+// functions k_stt_beam_select calls) on the UNTEMPERED logits gives the row's log-probabilities and the decision "timestamps win";
+// one more pass takes the arg-max of x / T + g(id) over the surviving ids (Gumbel-max: the pick is distributed as softmax(x / T)
+// over them), the lower id on ties.  A NaN or -inf logit takes no part.  The row's score adds the untempered log-probability of the
+// pick; end-of-sequence (or a row without any survivor, which counts as ending) sets the row's done flag and takes it out of `live`;
+// a row that is done rides along untouched.
 // src: the row itself, and behind the prefix the window's first row, whose cache slot the prefix pass wrote.  win_val (tests, else
 // null): the winning perturbed value per row.
 template <bool TS>
@@ -635,98 +645,11 @@ __global__ __launch_bounds__(1024) void k_stt_sample_select(const float* __restr
     const int r = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
     if (bk.done[r]) return;                                // (uniform)
     const int w = r / S, j = r - w * S;
-    const uint8_t bad = first_step ? 3 : 1;
     const float* x = logits + ((int64_t)w * row_stride + (row_stride > 1 ? j : 0)) * V;
-    int text_lo = 0, text_hi = 0, ts_lo = 0, ts_hi = 0, flags = 0, lts = 0;
-    if constexpr (TS) {
-        flags = bk.ts_flags[r]; lts = bk.ts_last[r];       // (thread 0 writes them behind the last barrier)
-        const bool last = flags & 1, pen = flags & 2;
-        text_hi = ts.t0 - 1;
-        ts_lo = ts.t0; ts_hi = min(ts.t0 + ts.nt, V);
-        if (lts > 0) ts_lo = max(ts_lo, (last && !pen) ? lts : lts + 1);
-        if (last && pen) ts_lo = ts_hi;
-        if (last && !pen) text_lo = eos;
-        if (first_step) {
-            text_lo = text_hi;
-            if (ts.max_initial >= 0) ts_hi = min(ts_hi, ts.t0 + ts.max_initial + 1);
-        }
-    }
-    // 0: barred, 1: text, 2: timestamp (TS == false: 1 is every id the mask leaves)
-    auto kind = [&](int i, int mk) -> int {
-        if constexpr (TS) {
-            if (i >= ts_lo && i < ts_hi) return 2;
-            return (i >= text_lo && i < text_hi && !(mk & bad)) ? 1 : 0;
-        } else {
-            return (mk & bad) ? 0 : 1;
-        }
-    };
-    float m = -INFINITY, m2 = -INFINITY;
-    for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
-        float xv[STT_SEL_U];
-        int mk[STT_SEL_U];
-#pragma unroll
-        for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
-#pragma unroll
-        for (int u = 0; u < STT_SEL_U; ++u) {
-            const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
-            if (kd == 1 && xv[u] > m) m = xv[u];
-            if constexpr (TS) { if (kd == 2 && xv[u] > m2) m2 = xv[u]; }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((tid & 63) == 0) red_v[wave] = m;
-    if constexpr (TS) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
-        if ((tid & 63) == 0) red_w[wave] = m2;
-    }
-    __syncthreads();
-    m = red_v[0];
-    for (int k = 1; k < 16; ++k) m = fmaxf(m, red_v[k]);
-    if constexpr (TS) {
-        m2 = red_w[0];
-        for (int k = 1; k < 16; ++k) m2 = fmaxf(m2, red_w[k]);
-    }
-    __syncthreads();
-    float sum = 0.f, sum2 = 0.f;
-    for (int base = tid; base < V; base += 1024 * STT_SEL_U) {
-        float xv[STT_SEL_U];
-        int mk[STT_SEL_U];
-#pragma unroll
-        for (int u = 0; u < STT_SEL_U; ++u) { const int i = min(base + 1024 * u, V - 1); xv[u] = x[i]; mk[u] = mask[i]; }
-#pragma unroll
-        for (int u = 0; u < STT_SEL_U; ++u) {
-            const int kd = base + 1024 * u < V ? kind(base + 1024 * u, mk[u]) : 0;
-            if (kd == 1 && xv[u] == xv[u]) sum += expf(xv[u] - m);
-            if constexpr (TS) { if (kd == 2 && xv[u] == xv[u]) sum2 += expf(xv[u] - m2); }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if ((tid & 63) == 0) red_v[wave] = sum;
-    if constexpr (TS) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum2 += __shfl_xor(sum2, o, 64);
-        if ((tid & 63) == 0) red_w[wave] = sum2;
-    }
-    __syncthreads();
-    sum = red_v[0];
-    for (int k = 1; k < 16; ++k) sum += red_v[k];
-    if constexpr (TS) {
-        sum2 = red_w[0];
-        for (int k = 1; k < 16; ++k) sum2 += red_w[k];
-    }
-    __syncthreads();
-    float lse = m + logf(sum);
-    bool text_ok = true;
-    if constexpr (TS) {
-        const bool has_ts = m2 > -INFINITY, has_text = m > -INFINITY;
-        const float lse_ts = has_ts ? m2 + logf(sum2) : -INFINITY;
-        text_ok = has_text && !(lse_ts > m);
-        if (!text_ok) lse = lse_ts;
-        else if (has_ts) { const float mm = fmaxf(m, m2); lse = mm + logf(sum * expf(m - mm) + sum2 * expf(m2 - mm)); }
-    }
+    int flags = 0, lts = 0;
+    if constexpr (TS) { flags = bk.ts_flags[r]; lts = bk.ts_last[r]; }      // (thread 0 writes them behind the last barrier)
+    const SttStepIds a = stt_step_ids<TS>(flags, lts, first_step, eos, V, ts);
+    const auto [lse, text_ok] = stt_row_norm<TS>(x, mask, V, a, red_v, red_w);
     // the arg-max of x / T + g over the survivors
     const unsigned row_hash = stt_gumbel_row(sr.seed_lo, sr.seed_hi, (unsigned)sr.key[r], sr.t_index, (unsigned)sr.sample[r], (unsigned)step);
     float bv = -INFINITY;
@@ -739,7 +662,7 @@ __global__ __launch_bounds__(1024) void k_stt_sample_select(const float* __restr
 #pragma unroll
         for (int u = 0; u < STT_SEL_U; ++u) {
             const int i = base + 1024 * u;
-            const int kd = i < V ? kind(i, mk[u]) : 0;
+            const int kd = i < V ? stt_step_kind<TS>(a, i, mk[u]) : 0;
             if (kd == 0 || (kd == 1 && !text_ok)) continue;
             const float v = __fadd_rn(__fdiv_rn(xv[u], sr.T), stt_gumbel(row_hash, i));
             if (v > -INFINITY && cand_before(v, i, bv, bi)) { bv = v; bi = i; }      // (a NaN compares false)
@@ -765,11 +688,7 @@ __global__ __launch_bounds__(1024) void k_stt_sample_select(const float* __restr
     bk.bp_tok[(int64_t)step * bk.R + r] = tok;
     bk.bp_par[(int64_t)step * bk.R + r] = j;
     if (win_val) win_val[r] = bv;
-    if constexpr (TS) {
-        const bool is_ts = tok >= ts.t0;
-        bk.ts_flags[r] = (is_ts ? 1 : 0) | ((first_step || (flags & 1)) ? 2 : 0);
-        bk.ts_last[r] = is_ts ? tok : lts;
-    }
+    if constexpr (TS) stt_ts_next(tok, first_step, flags, lts, ts, &bk.ts_flags[r], &bk.ts_last[r]);
     if (tok == eos) {
         bk.done[r] = 1;
         atomicSub(bk.live, 1);
@@ -1621,6 +1540,36 @@ int stt_retire(rt_stt* s, const SttBeamBook& bk, bool by_row, int step) {
     RT_HIP(s->ctx, hipGetLastError());
     return RT_OK;
 }
+// What beam search and sampled decoding share around the group's book (s->beam.book).  Before the first step: zeros, every row's next
+// token end-of-sequence and its source itself, `live` units decoding (windows of the beam path, rows of the sampled one)
+int stt_book_reset(rt_stt* s, int live) {
+    rt_ctx* ctx = s->ctx;
+    SttBeam& bm = s->beam;
+    RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bm.book.next_tok, bm.rows, s->cfg.eos_id, 0);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bm.book.src, bm.rows, 0, 1);
+    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bm.book.live, 1, live, 0);
+    RT_HIP(ctx, hipGetLastError());
+    return RT_OK;
+}
+// Behind the select of `step`: under a prompt policy the units whose budget is spent retire (before the read, which then counts them
+// out), then the step's one device-to-host read and one synchronisation -> the units still decoding
+int stt_step_live(rt_stt* s, bool prompt, bool by_row, int step, int32_t* live) {
+    if (prompt) RT_TRY(stt_retire(s, s->beam.book, by_row, step + 1));
+    RT_HIP(s->ctx, hipMemcpyAsync(live, s->beam.book.live, 4, hipMemcpyDeviceToHost, s->ctx->stream));
+    RT_HIP(s->ctx, hipStreamSynchronize(s->ctx->stream));
+    return RT_OK;
+}
+// The book as the steps left it -> s->h_book, and the pointers into that copy
+int stt_book_fetch(rt_stt* s, SttBeamBook* h) {
+    rt_ctx* ctx = s->ctx;
+    SttBeam& bm = s->beam;
+    s->h_book.resize(bm.book_n);
+    RT_HIP(ctx, hipMemcpyAsync(s->h_book.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *h = stt_beam_book(s->h_book.data(), bm.rows, s->cfg.max_new_tokens);
+    return RT_OK;
+}
 
 // What beam search gives for one window: the ids of the chosen hypothesis, its cumulative log-probability and the tokens it counts
 // (the ids and end-of-sequence)
@@ -1702,11 +1651,8 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
     const int P = plan.n_prefix(c), rows = nW * B, R = bm.rows;
     const SttBeamBook& bk = bm.book;
     const KvCache& cross = s->grp.enc.cross_kv;
-    RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.next_tok, R, c.eos_id, 0);
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.src, R, 0, 1);
+    RT_TRY(stt_book_reset(s, nW));
     hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.n_live, nW, 1, 0);
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.live, 1, nW, 0);
     hipLaunchKernelGGL(k_stt_fill_beam_rows, dim3(1), dim3(256), 0, ctx->stream, bm.pre_slot, bm.pre_pos, bm.pre_win, nW * P, P, B, bm.row_slot, bm.row_win, rows);
     RT_HIP(ctx, hipGetLastError());
     bm.dec.tok = s->grp.d_prefix;                // (the forced prefix of every window: the group keeps it)
@@ -1733,10 +1679,8 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
     for (int step = 0; step < budget; ++step) {
         RT_TRY(stt_beam_select(s, bm.dec.logits, step == 0 ? 1 : B, nW, step == 0 ? 1 : 0, B, step, bk, plan.ts));
         steps = step + 1;
-        if (pt) RT_TRY(stt_retire(s, bk, false, step + 1));      // (a window whose budget is spent: before the read, which then counts it out)
         int32_t live = 0;
-        RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RT_TRY(stt_step_live(s, pt != nullptr, false, step, &live));
         if (live <= 0 || step + 1 >= budget) break;
         if (pt) {
             if (!g_stt_gather_ranged) {         // (the A/B of the ranged form: what the gather costs when it moves the prefix at every step)
@@ -1756,10 +1700,8 @@ int stt_decode_beam_group(rt_stt* s, int nW, int B, std::vector<SttHyp>& out, co
         bm.dec.tok = bk.next_tok;
         RT_TRY(stt_decode_rows(s, bm.dec, cross, rows, 1, P + step, bm.row_slot, bm.row_pos, bm.row_win));
     }
-    s->h_book.resize(bm.book_n);
-    RT_HIP(ctx, hipMemcpyAsync(s->h_book.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const SttBeamBook h = stt_beam_book(s->h_book.data(), R, c.max_new_tokens);
+    SttBeamBook h;
+    RT_TRY(stt_book_fetch(s, &h));
     out.assign(nW, SttHyp{});
     // the tokens of beam `b` as it stood after step t: follow the back-pointers to step 0
     auto history = [&](int w, int t, int b, std::vector<int32_t>& ids) {
@@ -1837,11 +1779,7 @@ int stt_decode_sample_group(rt_stt* s, const SttSpan* spans, const std::vector<i
         part(h.data(), 6)[r] = (int32_t)spans[need[r / S]].key; part(h.data(), 7)[r] = r % S;
     }
     RT_HIP(ctx, hipMemcpyAsync(bm.smp, h.data(), h.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemsetAsync(bm.book_mem, 0, bm.book_n * 4, ctx->stream));
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.next_tok, R, c.eos_id, 0);
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.src, R, 0, 1);
-    hipLaunchKernelGGL(k_stt_fill_i32, dim3(1), dim3(64), 0, ctx->stream, bk.live, 1, rows, 0);
-    RT_HIP(ctx, hipGetLastError());
+    RT_TRY(stt_book_reset(s, rows));
     // under a prompt policy every attempt of a window decodes behind the prefix its beam attempt had: the same prompt, the same tables
     // but for the rows per window
     const SttPrTab* pt = nullptr;
@@ -1862,10 +1800,8 @@ int stt_decode_sample_group(rt_stt* s, const SttSpan* spans, const std::vector<i
     for (int step = 0; step < budget; ++step) {
         RT_TRY(stt_sample_select(s, bm.dec.logits, step == 0 ? 1 : S, rows, step == 0 ? 1 : 0, S, step, bk, plan.ts, sr, nullptr));
         steps = step + 1;
-        if (pt) RT_TRY(stt_retire(s, bk, true, step + 1));
         int32_t live = 0;
-        RT_HIP(ctx, hipMemcpyAsync(&live, bk.live, 4, hipMemcpyDeviceToHost, ctx->stream));
-        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RT_TRY(stt_step_live(s, pt != nullptr, true, step, &live));
         if (live <= 0 || step + 1 >= budget) break;
         if (step == 0 && S > 1) {                   // the window's first row holds the prefix: every row of the window takes it
             if (pt) RT_TRY(stt_beam_reorder_range(ctx, bm.dec.kv, bm.kv_next, tab + pt->fan_src, tab + pt->zero, tab + pt->base, rows));
@@ -1880,10 +1816,8 @@ int stt_decode_sample_group(rt_stt* s, const SttSpan* spans, const std::vector<i
         bm.dec.tok = bk.next_tok;
         RT_TRY(stt_decode_rows(s, bm.dec, cross, rows, 1, P + step, part(bm.smp, 4), bm.row_pos, part(bm.smp, 5)));
     }
-    s->h_book.resize(bm.book_n);
-    RT_HIP(ctx, hipMemcpyAsync(s->h_book.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const SttBeamBook hb = stt_beam_book(s->h_book.data(), R, c.max_new_tokens);
+    SttBeamBook hb;
+    RT_TRY(stt_book_fetch(s, &hb));
     out.assign(nN, SttHyp{});
     std::vector<int32_t> ids;
     for (int k = 0; k < nN; ++k) {
@@ -2973,8 +2907,7 @@ int stt_debug_beam_step(const char* who, rt_stt* s, const float* d_logits, int32
     *h.live = live;
     RT_HIP(ctx, hipMemcpyAsync(bm.book_mem, hb.data(), bm.book_n * 4, hipMemcpyHostToDevice, ctx->stream));
     RT_TRY(stt_beam_select(s, d_logits, row_stride, n_windows, first_step ? 1 : 0, beam, step, bk, ts));
-    RT_HIP(ctx, hipMemcpyAsync(hb.data(), bm.book_mem, bm.book_n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RT_TRY(stt_book_fetch(s, &h));
     for (int r = 0; r < R; ++r) {
         h_next_tok[r] = h.next_tok[r]; h_parent[r] = h.src[r]; h_scores_out[r] = h.score[r];
         h_fin_beam[r] = h.fin_beam[r]; h_fin_score[r] = h.fin_score[r];
