@@ -368,9 +368,15 @@ RT_API int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t
  *   3300/3301 speech-to-text under a prompt policy, the cache gather between beam steps: positions [0, longest prefix + step) of every row / each row's generated positions only (same bits)
  *   3400/3401 the decode GEMMs' RMSNorm sum-of-squares partials (rows of n partials, n % 64 == 0, n <= 256): stored plainly and fetched one dword per request / stored permuted and fetched 16 bytes per request (same bits)
  *   3500/3501 STORE / RESID decode GEMM launches of up to 32 rows: weight / activation chunks of 8 k-tiles / of the length of the wave's run (4 for K <= 1024, 6 for K = 3072; same bits)
+ *   3600/3601/3602 decode GEMM launches whose workgroups fill at most half of the CUs: one workgroup per column tile for all rows / launches of 33..64 rows as two 32-row blocks / also launches of 17..32 rows as two 16-row blocks (same bits either way)
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
 RT_API int rt_debug_tune(int32_t code, int32_t arg);
+/* The row-block rule of the column-owner decode GEMM's launcher as host arithmetic (no GPU is touched): the rows per block that a
+ * launch of M rows, width N (gate + up for epi 2), epilogue epi and sub-tile split (<= 0: the automatic one) takes on a device of
+ * n_cu compute units under the current switches (3600..3602), or 0 when one workgroup per column tile has all the rows.
+ * A bad argument returns -1. */
+RT_API int rt_debug_col_row_blocks(int32_t n_cu, int32_t M, int32_t N, int32_t epi, int32_t split);
 RT_API int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_norm, int32_t epi, int32_t n_mats, int32_t iters,
                              double* avg_us, int64_t* stamps8);
 /* The cache gather between two beam steps of the speech-to-text decoder on its own (tools/bench_stt_prompt.py): two caches of

@@ -703,6 +703,15 @@ int rt_debug_tune(int32_t code, int32_t arg) {
     return RT_ERR_INVALID;          // a code no row of knobs.h accepts: nothing changes
 }
 
+// launch_gemm_col's row-block decision (gemm_col.hip col_workgroups + col_row_blocks) without a launch
+int rt_debug_col_row_blocks(int32_t n_cu, int32_t M, int32_t N, int32_t epi, int32_t split) {
+    if (n_cu < 1 || M < 1 || M > 128 || N < 1 || epi < COL_STORE || epi > COL_SILU || (epi == COL_SILU && N % 32) || split > 4 || split == 3) return -1;
+    std::shared_lock<std::shared_mutex> plan(g_tune_mu);      // (the switches do not move under the two reads)
+    bool x_form = false;
+    const int wg = col_workgroups(n_cu, M, N, epi, split, &x_form);
+    return col_row_blocks(n_cu, M, wg, x_form);
+}
+
 int rt_bench_gemm_skinny(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t split_k, int32_t n_mats, int32_t iters, double* avg_us,
                          int32_t* used_split) {
     if (!ctx || !avg_us || M < 1 || M > 64 || N < 32 || K < 16 || K % 16 || n_mats < 1 || iters < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_bench_gemm_skinny: bad argument");

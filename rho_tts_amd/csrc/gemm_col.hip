@@ -53,6 +53,9 @@ __device__ __forceinline__ f4acc_t mfma16(s8_t a, s8_t b, f4acc_t c) {
 // plus sh_inv - more than a static array may take): one barrier pair more per accumulator set, no dynamic-LDS attribute to set
 // on twelve instantiations, and the kernel is bound by its A operand (every workgroup reads all 128 rows), not by LDS.
 // Shorter chunks (C = 2, gate/up 1) keep two chunks in flight inside 256 VGPRs.
+// Row blocks (RB, g_col_row_blocks): a launch of 17..64 rows whose column tiles fill at most half of the CUs (N = 1024: 128
+// workgroups on 256) runs as gridDim.y = 2 blocks of 16 / 32 rows with the MT = 1 / 2 code - every workgroup pulls half of A
+// through its CU's L1, which is what bounds these launches; the weights are read by both blocks.  Same bits again.
 // NPRE = super-chunks requested up front WITHOUT a branch around them (1 or 2, chosen by the launcher from K; indices are
 // clamped so every request is a valid address).  Branch-free matters: the row-scale partials are requested just before the
 // chunks, and only when the number of younger loads is a compile-time constant can the compiler wait for them with a
@@ -74,20 +77,28 @@ constexpr int col_chunk(int epi, int mt, bool x) {                         // k-
 // WQ (NORM only) = how the row-scale partials are requested: 0 one dword per partial from plain rows, 2 / 4 that many 16-byte
 // requests per lane and 32 rows from PERMUTED rows (common.h rowsq_slot; rows of 64..128 / 192..256 partials).
 // CF = chunk length fitted to the wave's run of k-tiles by the launcher (launch_chunk: 4 or 6; 0: col_chunk).
-template <int EPI, int MT, int NPRE, bool X = false, bool NORM = false, int WQ = 0, int CF = 0>
-__global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && !X) ? 4 : 2) void k_gemm_col(ColArgs g) {
+// RB = the launch deals its rows over gridDim.y row blocks of 16 MT rows (launch_gemm_col, col_row_blocks): the workgroup derives
+// its own first row and row count from blockIdx.y and reads that part of A alone; the column tile, the sub-tile and the rowsq_out
+// slot stay keyed on blockIdx.x.  A compile-time flag, so that every launch without blocks keeps the code it had.  A 16-row block
+// (MT = 1) has a CU to itself: it is free of the decode lanes' 128-VGPR bound and takes the chunk lengths of a 32-row launch.
+template <int EPI, int MT, int NPRE, bool X = false, bool NORM = false, int WQ = 0, int CF = 0, bool RB = false>
+__global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || (MT == 1 && !RB)) && !X) ? 4 : 2) void k_gemm_col(ColArgs g) {
     static_assert(!X || (EPI == COL_SILU && MT >= 2), "the extra half pair exists for gate/up only");
+    static_assert(!RB || (!X && MT <= 2), "row blocks have 16 or 32 rows, and the 1.5-pair form is never blocked");
     constexpr int RMT = MT > 4 ? 4 : MT;     // sub-blocks per combine round (MT = 8: two rounds through the same 32 KiB)
     constexpr int ROUNDS = MT / RMT;
     __shared__ float red[WAVES][RMT][4][64]; // 16 KiB per 32 rows: one 16x16 accumulator tile per sub-block and wave
     __shared__ float sh_inv[16 * MT];        // RMSNorm row scales
     constexpr int NB = (EPI == COL_SILU) ? (X ? 3 : 2) : 1;
     static_assert(WQ == 0 || NORM, "wide requests exist for the row-scale partials only");
-    static_assert(CF == 0 || (EPI != COL_SILU && MT == 2), "fitted chunks exist for STORE / RESID launches of up to 32 rows only");
-    constexpr int C = CF ? CF : col_chunk(EPI, MT, X);
+    static_assert(CF == 0 || (EPI != COL_SILU && (MT == 2 || (MT == 1 && RB))), "fitted chunks exist for STORE / RESID launches of up to 32 rows only");
+    constexpr int C = CF ? CF : col_chunk(EPI, (RB && MT == 1) ? 2 : MT, X);
     constexpr int PASSES = (MT + 1) / 2;     // epilogue / row-scale passes of 32 rows (MT = 1: half of one)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r = lane & 15, qd = lane >> 4;
+    const int rb0 = RB ? (int)blockIdx.y * (16 * MT) : 0;   // first row of this workgroup's row block inside the launch
+    const int row_off = g.row_off + rb0;
+    const int M = RB ? (g.M - rb0 < 16 * MT ? g.M - rb0 : 16 * MT) : g.M;
     const int sp_shift = g.split == 4 ? 2 : (g.split == 2 ? 1 : 0);
     const int nt = blockIdx.x >> sp_shift, sub = blockIdx.x & (g.split - 1);
     const int cw_shift = 4 - sp_shift;                        // log2 of the columns this workgroup owns
@@ -98,7 +109,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
     if (kt_hi > g.KT) kt_hi = g.KT;
     const int n_k = kt_hi > kt_lo ? kt_hi - kt_lo : 0;
     const int n_sc = (n_k + C - 1) / C;
-    const int n_mt = (g.M + 15) >> 4;                         // sub-blocks that hold rows
+    const int n_mt = (M + 15) >> 4;                         // sub-blocks that hold rows
 
     const s8_t* wp[NB];
     wp[0] = reinterpret_cast<const s8_t*>(g.Wp) + ((int64_t)nt * g.KT + kt_lo) * 64 + lane;
@@ -111,8 +122,8 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         int row = mt * 16 + r;
-        if (row >= g.M) row = g.M - 1;                  // clamp: computed on valid memory, never stored
-        ap[mt] = reinterpret_cast<const s8_t*>(reinterpret_cast<const bf16_t*>(g.A) + tile_off(g.row_off + row, kt_lo * 32 + qd * 8, g.K));
+        if (row >= M) row = M - 1;                  // clamp: computed on valid memory, never stored
+        ap[mt] = reinterpret_cast<const s8_t*>(reinterpret_cast<const bf16_t*>(g.A) + tile_off(row_off + row, kt_lo * 32 + qd * 8, g.K));
     }
 
     struct Chunk {
@@ -134,7 +145,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
         }
     };
 
-    if (g.stamps && blockIdx.x == 0 && tid == 0) g.stamps[0] = wall_clock64();
+    if (g.stamps && blockIdx.x == 0 && (!RB || blockIdx.y == 0) && tid == 0) g.stamps[0] = wall_clock64();
     // The small operands of the prologue / epilogue are requested FIRST: vector-memory loads return in issue order, so anything
     // issued behind the 16 KiB weight / activation chunks would only arrive after them - the RMSNorm row scales used to cost
     // every NORM launch 1-1.5 us that way (in-kernel stamps, tools/bench_gemm_col.py), and the epilogue's per-column vectors a
@@ -155,7 +166,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
             const int row_i = 32 * ps + 4 * w + qd;
-            const int row = g.row_off + (row_i < g.M ? row_i : g.M - 1);
+            const int row = row_off + (row_i < M ? row_i : M - 1);
             const f4_t* p = reinterpret_cast<const f4_t*>(g.rowsq + (int64_t)row * g.rowsq_n) + r;
 #pragma unroll
             for (int q = 0; q < WQ; ++q) rq4[ps][q] = p[16 * (q < q_last ? q : q_last)];
@@ -169,7 +180,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
             const int row_i = 32 * ps + 4 * w + qd;
-            const int row = g.row_off + (row_i < g.M ? row_i : g.M - 1);
+            const int row = row_off + (row_i < M ? row_i : M - 1);
             const float* p = g.rowsq + (int64_t)row * g.rowsq_n;
 #pragma unroll
             for (int it = 0; it < 16; ++it) {
@@ -189,7 +200,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
     for (int ps = 0; ps < PASSES; ++ps) {
         const int e_row = (2 * ps + (tid >> 8)) * 16 + (e_l >> 4) * 4 + e_i;
         xres[ps] = 0.f;
-        if (EPI == COL_RESID && e_row < g.M && n_ok) xres[ps] = g.out[tile_off(g.row_off + e_row, n, (int)g.ldc)];
+        if (EPI == COL_RESID && e_row < M && n_ok) xres[ps] = g.out[tile_off(row_off + e_row, n, (int)g.ldc)];
     }
     __builtin_amdgcn_sched_barrier(0);          // keep the small requests ahead of the chunks ...
     Chunk c0, c1;
@@ -209,7 +220,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
                 for (int it = 0; it < 16; ++it) s += (r + 16 * it < g.rowsq_n) ? rq[ps][it] : 0.f;
             }
             if (WQ == 0 && g.rowsq_n > RQ_MAX) {             // (more partials than the unrolled window: not a shape the model produces)
-                const int row = g.row_off + (row_i < g.M ? row_i : g.M - 1);
+                const int row = row_off + (row_i < M ? row_i : M - 1);
                 const float* p = g.rowsq + (int64_t)row * g.rowsq_n;
                 for (int j = RQ_MAX + r; j < g.rowsq_n; j += 16) s += p[j];
             }
@@ -217,7 +228,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
             if (r == 0 && row_i < 16 * MT) sh_inv[row_i] = rsqrtf(s / (float)g.K + g.eps);
         }
     }
-    if (g.stamps && blockIdx.x == 0 && tid == 0) g.stamps[1] = wall_clock64();
+    if (g.stamps && blockIdx.x == 0 && (!RB || blockIdx.y == 0) && tid == 0) g.stamps[1] = wall_clock64();
 
     f4acc_t acc[NB][MT];
 #pragma unroll
@@ -241,7 +252,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
     };
     for (int sc = 0; sc < n_sc; sc += 2) {
         consume(sc, c0);
-        if (g.stamps && sc == 0 && blockIdx.x == 0 && tid == 0) g.stamps[2] = wall_clock64();
+        if (g.stamps && sc == 0 && blockIdx.x == 0 && (!RB || blockIdx.y == 0) && tid == 0) g.stamps[2] = wall_clock64();
         if (sc + 2 < n_sc) issue(sc + 2, c0);
         if (sc + 1 < n_sc) {
             consume(sc + 1, c1);
@@ -249,7 +260,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
         }
     }
 
-    if (g.stamps && blockIdx.x == 0 && tid == 0) g.stamps[3] = wall_clock64();
+    if (g.stamps && blockIdx.x == 0 && (!RB || blockIdx.y == 0) && tid == 0) g.stamps[3] = wall_clock64();
     // ---- combine the 8 K-partials through LDS in a fixed order and run the fused epilogue (one output per thread and pass)
     float val[NB][PASSES];
 #pragma unroll
@@ -274,17 +285,17 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
             }
         }
     }
-    if (g.stamps && blockIdx.x == 0 && tid == 0) g.stamps[4] = wall_clock64();
+    if (g.stamps && blockIdx.x == 0 && (!RB || blockIdx.y == 0) && tid == 0) g.stamps[4] = wall_clock64();
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
         const int e_row = (2 * ps + (tid >> 8)) * 16 + (e_l >> 4) * 4 + e_i;
-        const bool ok = e_row < g.M && n_ok;
+        const bool ok = e_row < M && n_ok;
         const float inv = (NORM && e_row < 16 * MT) ? sh_inv[e_row] : 1.f;       // (published before the reduce barriers)
         float v = val[0][ps] * inv;
         if (EPI == COL_STORE) {
             if (ok) {
                 v += e_bias;
-                g.out[(int64_t)(g.row_off + e_row) * g.ldc + n] = v;    // STORE outputs (qkv, logits, mtp rows) stay row-major
+                g.out[(int64_t)(row_off + e_row) * g.ldc + n] = v;    // STORE outputs (qkv, logits, mtp rows) stay row-major
             }
         } else if (EPI == COL_RESID) {
             float xn = 0.f;
@@ -292,7 +303,7 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
                 v += e_bias;
                 v *= e_scale;
                 xn = xres[ps] + v;
-                const int64_t o = tile_off(g.row_off + e_row, n, (int)g.ldc);
+                const int64_t o = tile_off(row_off + e_row, n, (int)g.ldc);
                 g.out[o] = xn;
                 if (g.next_bf16) g.next_bf16[o] = f32_to_bf16(e_nw * xn);   // operand of the GEMM behind the next RMSNorm
             }
@@ -300,70 +311,82 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || MT == 1) && 
             // (DPP adds: the four dependent ds_bpermute round trips of a __shfl_xor butterfly sat in the tail of every RESID launch -
             //  two per layer - between the last store of x and the store of its sums of squares)
             sq = group_sum_f32<16>(sq);
-            if ((e_l & 15) == 0 && e_row < g.M) g.rowsq_out[(int64_t)(g.row_off + e_row) * g.rowsq_out_n + (g.rowsq_perm ? rowsq_slot((int)blockIdx.x, g.rowsq_out_n) : (int)blockIdx.x)] = sq;
+            if ((e_l & 15) == 0 && e_row < M) g.rowsq_out[(int64_t)(row_off + e_row) * g.rowsq_out_n + (g.rowsq_perm ? rowsq_slot((int)blockIdx.x, g.rowsq_out_n) : (int)blockIdx.x)] = sq;
         } else {                                  // COL_SILU: gate = tile nt, up = tile nt + offset
             if (ok) {
                 const float u = val[1][ps] * inv;
-                g.out_bf16[tile_off(g.row_off + e_row, n, (int)g.ldc)] = f32_to_bf16(v / (1.f + __expf(-v)) * u);
+                g.out_bf16[tile_off(row_off + e_row, n, (int)g.ldc)] = f32_to_bf16(v / (1.f + __expf(-v)) * u);
             }
             if (X) {                              // the extra half pair: gate in columns 0..7 of its tile, up in 8..15 of the same row
                 const float gx = val[NB - 1][ps] * inv;
                 const float ux = __shfl_down(gx, 8, 16);
                 const int nx = x_tile * 16 + x_col0 + (e_l & 7);
-                if (e_row < g.M && (e_l & 15) < 8 && nx < g.N) g.out_bf16[tile_off(g.row_off + e_row, nx, (int)g.ldc)] = f32_to_bf16(gx / (1.f + __expf(-gx)) * ux);
+                if (e_row < M && (e_l & 15) < 8 && nx < g.N) g.out_bf16[tile_off(row_off + e_row, nx, (int)g.ldc)] = f32_to_bf16(gx / (1.f + __expf(-gx)) * ux);
             }
         }
     }
-    if (g.stamps && blockIdx.x == 0 && tid == 0) g.stamps[5] = wall_clock64();
+    if (g.stamps && blockIdx.x == 0 && (!RB || blockIdx.y == 0) && tid == 0) g.stamps[5] = wall_clock64();
 }
 
-template <int EPI, int MT, int NPRE, bool X, bool NORM, int WQ, int CF>
+template <int EPI, int MT, int NPRE, bool X, bool NORM, int WQ, int CF, bool RB>
 void launch_one(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
-    if (!e0 && !e1) hipLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF>), grid, dim3(512), 0, ctx->stream, g);   // plain launches are what a stream capture records
-    else hipExtLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF>), grid, dim3(512), 0, ctx->stream, e0, e1, 0, g);   // device-side begin/end stamps
+    if (!e0 && !e1) hipLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF, RB>), grid, dim3(512), 0, ctx->stream, g);   // plain launches are what a stream capture records
+    else hipExtLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF, RB>), grid, dim3(512), 0, ctx->stream, e0, e1, 0, g);   // device-side begin/end stamps
 }
 
-template <int EPI, int MT, bool X, bool NORM, int WQ, int CF>
+template <int EPI, int MT, bool X, bool NORM, int WQ, int CF, bool RB>
 void launch_npre2(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     // every wave needs at least one k-tile for the clamped (branch-free) requests to be valid addresses
-    constexpr int C = CF ? CF : col_chunk(EPI, MT, X);
+    constexpr int C = CF ? CF : col_chunk(EPI, (RB && MT == 1) ? 2 : MT, X);      // (as the kernel has it)
     const int kchunk = (g.KT + WAVES - 1) / WAVES;
     const bool all_waves_busy = g.KT >= WAVES && (WAVES - 1) * kchunk < g.KT;
     const int n_sc = (kchunk + C - 1) / C;
-    if (!all_waves_busy) launch_one<EPI, MT, 0, X, NORM, WQ, CF>(ctx, g, grid, e0, e1);
-    else if (n_sc >= 2) launch_one<EPI, MT, 2, X, NORM, WQ, CF>(ctx, g, grid, e0, e1);
-    else launch_one<EPI, MT, 1, X, NORM, WQ, CF>(ctx, g, grid, e0, e1);
+    if (!all_waves_busy) launch_one<EPI, MT, 0, X, NORM, WQ, CF, RB>(ctx, g, grid, e0, e1);
+    else if (n_sc >= 2) launch_one<EPI, MT, 2, X, NORM, WQ, CF, RB>(ctx, g, grid, e0, e1);
+    else launch_one<EPI, MT, 1, X, NORM, WQ, CF, RB>(ctx, g, grid, e0, e1);
 }
 
 // The chunk length follows the wave's run of k-tiles where it is known to be short (STORE / RESID launches of up to 32 rows, whose
 // chunk is 8 k-tiles): a run of <= 4 (K <= 1024) takes ONE chunk of 4 and a run of 9..12 (K = 3072) TWO chunks of 6, both still
 // requested up front without a branch.  With chunks of 8 the clamped requests of the tail re-load the run's last tile - as many
 // requests as the real ones at K = 1024, half of the second chunk at K = 3072.  Same k order inside a wave: the same bits.
-template <int EPI, int MT, bool X, bool NORM, int WQ>
+// A 16-row block of a row-blocked launch (RB, MT = 1) takes the same lengths: it has a CU, and so 256 VGPRs, to itself.
+template <int EPI, int MT, bool X, bool NORM, int WQ, bool RB>
 void launch_chunk(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
-    if constexpr (EPI != COL_SILU && MT == 2) {
+    if constexpr (EPI != COL_SILU && (MT == 2 || (MT == 1 && RB))) {
         const int kchunk = (g.KT + WAVES - 1) / WAVES;
-        if (g_col_chunk_fit && kchunk <= 4) return launch_npre2<EPI, MT, X, NORM, WQ, 4>(ctx, g, grid, e0, e1);
-        if (g_col_chunk_fit && kchunk > 8 && kchunk <= 12) return launch_npre2<EPI, MT, X, NORM, WQ, 6>(ctx, g, grid, e0, e1);
+        if (g_col_chunk_fit && kchunk <= 4) return launch_npre2<EPI, MT, X, NORM, WQ, 4, RB>(ctx, g, grid, e0, e1);
+        if (g_col_chunk_fit && kchunk > 8 && kchunk <= 12) return launch_npre2<EPI, MT, X, NORM, WQ, 6, RB>(ctx, g, grid, e0, e1);
     }
-    launch_npre2<EPI, MT, X, NORM, WQ, 0>(ctx, g, grid, e0, e1);
+    launch_npre2<EPI, MT, X, NORM, WQ, 0, RB>(ctx, g, grid, e0, e1);
 }
 
 // (the residual epilogue never follows an RMSNorm in this model: one instantiation less per shape)
-template <int EPI, int MT, bool X = false>
+template <int EPI, int MT, bool X = false, bool RB = false>
 void launch_npre(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     if (g.post_scale) {
         if constexpr (EPI != COL_RESID) {
-            if (g.rowsq_wide == 2) launch_chunk<EPI, MT, X, true, 2>(ctx, g, grid, e0, e1);
-            else if (g.rowsq_wide == 4) launch_chunk<EPI, MT, X, true, 4>(ctx, g, grid, e0, e1);
-            else launch_chunk<EPI, MT, X, true, 0>(ctx, g, grid, e0, e1);
+            if (g.rowsq_wide == 2) launch_chunk<EPI, MT, X, true, 2, RB>(ctx, g, grid, e0, e1);
+            else if (g.rowsq_wide == 4) launch_chunk<EPI, MT, X, true, 4, RB>(ctx, g, grid, e0, e1);
+            else launch_chunk<EPI, MT, X, true, 0, RB>(ctx, g, grid, e0, e1);
         }
     } else {
-        launch_chunk<EPI, MT, X, false, 0>(ctx, g, grid, e0, e1);
+        launch_chunk<EPI, MT, X, false, 0, RB>(ctx, g, grid, e0, e1);
     }
 }
 
 int dispatch_epi(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
+    if (g.row_block) {  // row blocks: MT follows the block's rows (32 -> 2, 16 -> 1), not the launch's
+        const bool b32 = g.row_block == 32;
+        switch (g.epi) {
+            case COL_STORE: b32 ? launch_npre<COL_STORE, 2, false, true>(ctx, g, grid, e0, e1) : launch_npre<COL_STORE, 1, false, true>(ctx, g, grid, e0, e1); break;
+            case COL_RESID: b32 ? launch_npre<COL_RESID, 2, false, true>(ctx, g, grid, e0, e1) : launch_npre<COL_RESID, 1, false, true>(ctx, g, grid, e0, e1); break;
+            case COL_SILU: b32 ? launch_npre<COL_SILU, 2, false, true>(ctx, g, grid, e0, e1) : launch_npre<COL_SILU, 1, false, true>(ctx, g, grid, e0, e1); break;
+            default: return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: bad epilogue %d", g.epi);
+        }
+        RT_HIP(ctx, hipGetLastError());
+        return RT_OK;
+    }
     const bool wide = g.M > 32, narrow = g.M <= 16 && g_col_rows16;
     if (g.M > 64) {     // 65..128 rows: one launch streams the weights once for all of them
         switch (g.epi) {
@@ -411,6 +434,37 @@ int col_split_for(int N, int n_cu) {
     return 1;
 }
 
+// Workgroups along x of a launch, and whether gate/up takes the 1.5-pairs-per-workgroup form (launch_gemm_col and the debug query)
+int col_workgroups(int n_cu, int M, int N, int epi, int split, bool* x_form) {
+    if (x_form) *x_form = false;
+    if (epi != COL_SILU) {
+        if (split <= 0) split = col_split_for(N, n_cu);
+        return (N + 15) / 16 * split;
+    }
+    if (split <= 0) split = col_split_silu(N, n_cu);
+    const int tiles = (N + 15) / 16 / 2;
+    // more pairs than CUs but no more than 1.5x: 2/3 of them as workgroups, each with half of one of the others
+    const int wg = tiles / 3 * 2;
+    const bool narrow = M <= 16 && g_col_rows16;
+    if (g_col_silu_x && split == 1 && !narrow && tiles % 3 == 0 && tiles > n_cu && wg <= n_cu && (N / 2) % 16 == 0) {
+        if (x_form) *x_form = true;
+        return wg;
+    }
+    return tiles * split;
+}
+
+// Row blocks (g_col_row_blocks): a launch whose workgroups fill at most half of the CUs deals its rows over the other half -
+// 33..64 rows as two 32-row blocks (value >= 1), 17..32 rows as two 16-row blocks (value 2).  Each workgroup then pulls half of
+// A through its CU's L1; the weights are read by both blocks (the predictor's are cache resident).  Launches of <= 16 or >= 65
+// rows, launches with a workgroup for more than half of the CUs and the 1.5-pair gate/up form are never blocked.
+int col_row_blocks(int n_cu, int M, int wg, bool x_form) {
+    const int v = g_col_row_blocks;
+    if (x_form || v < 1 || wg < 1 || 2 * wg > n_cu) return 0;
+    if (M >= 33 && M <= 64) return 32;
+    if (v >= 2 && M >= 17 && M <= 32) return 16;
+    return 0;
+}
+
 bool rowsq_permuted(int n) { return g_rowsq_wide && n % 64 == 0 && n >= 64 && n <= 256; }
 
 int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t ev_start, hipEvent_t ev_stop) {
@@ -423,22 +477,22 @@ int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t 
     g.KT = w.K / 32;
     if (g.split != 1 && g.split != 2 && g.split != 4) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: split %d (1, 2 or 4)", g.split);
     int tiles = g.NT;
+    bool x_form = false;
+    const int wg = col_workgroups(ctx->n_cu, g.M, w.N, g.epi, g.split, &x_form);     // tiles x split, after the X decision
     if (g.epi == COL_SILU) {
         if (w.N % 32) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: gate/up width %d not a multiple of 32", w.N);
         tiles = g.NT / 2;
         g.up_tile_offset = g.NT / 2;
         g.N = w.N / 2;
         g.x_tile0 = 0;
-        // more pairs than CUs but no more than 1.5x: 2/3 of them as workgroups, each with half of one of the others
-        const int wg = tiles / 3 * 2;
-        const bool narrow = g.M <= 16 && g_col_rows16;
-        if (g_col_silu_x && g.split == 1 && !narrow && tiles % 3 == 0 && tiles > ctx->n_cu && wg <= ctx->n_cu && (w.N / 2) % 16 == 0) {
+        if (x_form) {
             g.x_tile0 = wg;
             tiles = wg;
         }
     } else {
         g.N = w.N;
     }
+    if (wg != tiles * g.split) return rt_fail(ctx, RT_ERR_STATE, "gemm_col: %d workgroups planned, %d x %d tiles", wg, tiles, g.split);
     if (g.epi == COL_RESID && (!g.rowsq_out || g.rowsq_out_n < g.NT * g.split)) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: rowsq_out too small");
     if (g.post_scale && (!g.rowsq || g.rowsq_n < 1)) return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: row scaling without partials");
     if (g.post_scale && g.epi == COL_RESID) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "gemm_col: the residual epilogue has no row-scaled instantiation");
@@ -448,5 +502,8 @@ int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t 
     g.rowsq_wide = (g.post_scale && rowsq_permuted(g.rowsq_n)) ? (g.rowsq_n <= 128 ? 2 : 4) : 0;
     if (g.rowsq_wide && (reinterpret_cast<uintptr_t>(g.rowsq) & 15))     // (rowsq_n % 64 == 0: a row stride of a multiple of 256 bytes)
         return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: rowsq rows read in 16-byte pieces must be 16-byte aligned");
-    return dispatch_epi(ctx, g, dim3(tiles * g.split), ev_start, ev_stop);
+    // rows dealt over the CUs a narrow launch leaves idle: grid.y row blocks, each workgroup reads its block of A alone
+    g.row_block = col_row_blocks(ctx->n_cu, g.M, wg, x_form);
+    const int n_blocks = g.row_block ? (g.M + g.row_block - 1) / g.row_block : 1;
+    return dispatch_epi(ctx, g, dim3(wg, n_blocks), ev_start, ev_stop);
 }

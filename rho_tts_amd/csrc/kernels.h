@@ -117,7 +117,16 @@ struct ColArgs {
     int rowsq_perm = 0;             // RESID: 1 = partial j is stored at rowsq_slot(j, rowsq_out_n) (rowsq_permuted(rowsq_out_n))
     int rowsq_wide = 0;             // NORM: 0 = plain rows, one dword request per partial; 2 / 4 = permuted rows, that many
                                     //       16-byte requests per lane and 32 rows (rowsq_permuted(rowsq_n))
+    int row_block = 0;              // rows per row block (16 or 32: grid.y blocks of that many rows, the last one ragged); 0: no blocks,
+                                    //       one workgroup per column tile has all M rows (col_row_blocks)
 };
+// The launcher's row-block rule as host arithmetic (g_col_row_blocks): rows per block for a launch of M rows whose column tiles make
+// `wg` workgroups (tiles x split, after the gate/up X decision), or 0.  A narrow launch that leaves at least half of the CUs
+// without a workgroup deals its rows over them: every workgroup then reads half of the A operand.
+int col_row_blocks(int n_cu, int M, int wg, bool x_form);
+// `wg` and the X decision of a launch (what launch_gemm_col computes): N is the weight's width (gate + up for COL_SILU), split <= 0
+// takes the automatic sub-tile split.
+int col_workgroups(int n_cu, int M, int N, int epi, int split, bool* x_form);
 // Whether rowsq rows of n partials have the permuted layout (common.h rowsq_slot) under the current launch plan (g_rowsq_wide):
 // the ONE predicate behind every producer and consumer of such a row, so that they cannot disagree.
 bool rowsq_permuted(int n);

@@ -56,7 +56,10 @@
         "and fetched by the row-scale prologue in 2 / 4 16-byte requests per lane, 0 stored plainly and fetched in 16 dword requests (same bits either way; " \
         "profiles/r21_gemm_col_prologue.txt)") \
     X(3500, g_col_chunk_fit, 1, 0, 1, "STORE / RESID decode GEMM launches of up to 32 rows: 1 the chunk length follows the wave's run of k-tiles (one chunk of 4 for K <= 1024, " \
-        "two of 6 for K = 3072: no clamped re-loads of the run's last tile), 0 chunks of 8 (same bits either way; profiles/r21_gemm_col_prologue.txt)")
+        "two of 6 for K = 3072: no clamped re-loads of the run's last tile), 0 chunks of 8 (same bits either way; profiles/r21_gemm_col_prologue.txt)") \
+    X(3600, g_col_row_blocks, 2, 0, 2, "decode GEMM launches whose workgroups fill at most half of the CUs (the predictor's o / down / mtp: 128 on 256) deal their rows over " \
+        "gridDim.y: 0 never, 1 launches of 33..64 rows as two 32-row blocks, 2 also launches of 17..32 rows as two 16-row blocks (same bits either way; " \
+        "profiles/r24_row_blocks.txt)")
 
 // The one switch set by rt_debug_tune's SECOND argument: applied when the code is 0..2 and the argument lies in lo..hi.
 #define RT_KNOB_ARG(X) \

@@ -64,6 +64,26 @@ if len(sys.argv) > 1 and sys.argv[1] == "prologue":
                     cols.append(f"{'plain' if plain else f'wide {wide} fit {fit}'}: {statistics.median(t):6.2f} us (min {min(t):.2f}) 0>1 {statistics.median(s01):.2f} 0>5 {statistics.median(s05):.2f}")
             print(f"M={M:2d} {name:24s} " + " | ".join(cols), flush=True)
     sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "rows":
+    # the narrow predictor launches (N = 1024: 128 workgroups on 256 CUs) by row count, cacheable weights cycling through 32 matrices
+    # (what the predictor's Infinity-Cache resident weights are to its 15 passes); median of three runs of 300 launches.
+    # `rows`: no switch is touched (a build without 3600); `rows blocks`: one column per value of 3600 / 3601 / 3602
+    import statistics
+    codes = (3600, 3601, 3602) if len(sys.argv) > 2 and sys.argv[2] == "blocks" else (None,)
+    for N, K, norm, epi, name in ((1024, 2048, 0, 1, "pred o    RESID"), (1024, 3072, 0, 1, "pred down RESID"), (1024, 2048, 1, 0, "pred mtp  NORM STORE")):
+        for M in (16, 32, 64):
+            cols = []
+            for code in codes:
+                if code is not None:
+                    assert lib.rt_debug_tune(code, 0) == 0
+                t = []
+                for _ in range(3):
+                    us = C.c_double()
+                    assert lib.rt_bench_gemm_col(ctx.handle, M, N, K, norm | 2, epi, 32, 300, C.byref(us), None) == 0
+                    t.append(us.value)
+                cols.append(f"{'' if code is None else str(code) + ': '}{statistics.median(t):6.2f} us (min {min(t):.2f} max {max(t):.2f})")
+            print(f"{name:22s} M={M:2d}  " + " | ".join(cols), flush=True)
+    sys.exit(0)
 for M, N, K, norm, epi, name in shapes:
     mb = N * K * 2 / 1e6
     n_mats = max(2, int(600 / mb) + 1)
