@@ -53,7 +53,8 @@ RT_API int rt_debug_attention_planes(rt_ctx* ctx, const float* d_q, int32_t M, i
                                      const void* d_k_lo, const void* d_v_hi, const void* d_v_lo, int32_t slots, int32_t max_pos,
                                      float* d_out_f32);
 /* The dominant decode kernel on its own (gemm_col.hip k_gemm_col; launched as model_stack.hip launches it: row blocks of <= 64, or ONE launch of 65..128 rows unless rt_debug_tune(3200),
- * production sub-tile split when split = 0).  Row-major operands; the hook converts to / from the fragment-tiled layout.
+ * production sub-tile split when split = 0).  Row-major operands; the hook converts to / from the fragment-tiled layout (x, next and
+ * act in buffers as wide as N rounded up to whole 32-column k-tiles, so that any N is a valid width).
  *   A [M][K] bf16, W [N][K] bf16 (epi 2: gate rows [0, N/2) then up rows), M <= 128, K % 32 == 0, row_off % 16 == 0
  *   d_rowsq [M][rowsq_n] or NULL: partial sums of squares of the pre-norm row; acc rows are scaled by rsqrt(sum/K + eps)
  *   epi 0 STORE: d_x [M][N] f32 out = scale_row * (A W^T) + bias
@@ -369,6 +370,7 @@ RT_API int rt_debug_voice_encode_stages(rt_model* m, const float* h_pcm, int64_t
  *   3400/3401 the decode GEMMs' RMSNorm sum-of-squares partials (rows of n partials, n % 64 == 0, n <= 256): stored plainly and fetched one dword per request / stored permuted and fetched 16 bytes per request (same bits)
  *   3500/3501 STORE / RESID decode GEMM launches of up to 32 rows: weight / activation chunks of 8 k-tiles / of the length of the wave's run (4 for K <= 1024, 6 for K = 3072; same bits)
  *   3600/3601/3602 decode GEMM launches whose workgroups fill at most half of the CUs: one workgroup per column tile for all rows / launches of 33..64 rows as two 32-row blocks / also launches of 17..32 rows as two 16-row blocks (same bits either way)
+ *   3700/3701/3702 STORE / RESID decode GEMM launches at split 2 whose half-tile workgroups fill more than half of the CUs: half tiles for all rows / launches of 33..64 rows as whole tiles x two 32-row blocks / also launches of 17..32 rows as whole tiles x two 16-row blocks (same bits either way)
  * The rt_bench_* entry points are the microbenchmarks behind tools/bench_*.py (for rt_bench_gemm_col choose
  * n_mats * N * K * 2 bytes > 512 MB to stream from HBM, not from cache). */
 RT_API int rt_debug_tune(int32_t code, int32_t arg);
@@ -377,6 +379,10 @@ RT_API int rt_debug_tune(int32_t code, int32_t arg);
  * n_cu compute units under the current switches (3600..3602), or 0 when one workgroup per column tile has all the rows.
  * A bad argument returns -1. */
 RT_API int rt_debug_col_row_blocks(int32_t n_cu, int32_t M, int32_t N, int32_t epi, int32_t split);
+/* The tile-block rule of the same launcher (3700..3702), same arguments: 16 / 32 when the launch runs whole-tile workgroups with its
+ * rows dealt over two blocks of that many rows while its rowsq row keeps the split-2 layout, or 0 (rt_debug_col_row_blocks answers
+ * for the row-block rule alone, which comes first; the two never hold together).  A bad argument returns -1. */
+RT_API int rt_debug_col_tile_blocks(int32_t n_cu, int32_t M, int32_t N, int32_t epi, int32_t split);
 RT_API int rt_bench_gemm_col(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t a_norm, int32_t epi, int32_t n_mats, int32_t iters,
                              double* avg_us, int64_t* stamps8);
 /* The cache gather between two beam steps of the speech-to-text decoder on its own (tools/bench_stt_prompt.py): two caches of

@@ -54,21 +54,22 @@ __global__ void k_iota64(int64_t* p, int n) {
     if (i < n) p[i] = i;
 }
 
-// row-major <-> fragment-tiled (common.h tile_off) converters for the column-GEMM hook
+// row-major <-> fragment-tiled (common.h tile_off) converters for the column-GEMM hook; ld = the tiled buffer's width, K rounded
+// up to whole 32-column k-tiles (a width that is none would fold a row block's last half tile onto the next row block's first)
 template <typename T>
-__global__ void k_tile_rows(const T* __restrict__ src, int M, int K, int row_off, T* __restrict__ dst) {
+__global__ void k_tile_rows(const T* __restrict__ src, int M, int K, int row_off, T* __restrict__ dst, int ld) {
     const int64_t n = (int64_t)M * K;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int m = (int)(i / K), k = (int)(i % K);
-        dst[tile_off(row_off + m, k, K)] = src[i];
+        dst[tile_off(row_off + m, k, ld)] = src[i];
     }
 }
 template <typename T>
-__global__ void k_untile_rows(const T* __restrict__ src, int M, int K, int row_off, T* __restrict__ dst) {
+__global__ void k_untile_rows(const T* __restrict__ src, int M, int K, int row_off, T* __restrict__ dst, int ld) {
     const int64_t n = (int64_t)M * K;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int m = (int)(i / K), k = (int)(i % K);
-        dst[i] = src[tile_off(row_off + m, k, K)];
+        dst[i] = src[tile_off(row_off + m, k, ld)];
     }
 }
 }  // namespace
@@ -185,6 +186,7 @@ int rt_debug_gemm_col(rt_ctx* ctx, const void* d_a_bf16, int32_t M, int32_t K, c
     const int No = epi == COL_SILU ? N / 2 : N;                  // output width
     if (split <= 0) split = epi == COL_SILU ? col_split_silu(N, ctx->n_cu) : col_split_for(N, ctx->n_cu);
     const int rows = (row_off + M + 31) / 32 * 32;               // tiled buffers hold whole 32-row blocks (alloc_dec_ws)
+    const int ldt = (No + 31) / 32 * 32;                         // ... of whole 32-column k-tiles (No itself in the model: every width is a multiple of 32)
     bf16_t *w16 = nullptr, *a_t = nullptr, *next_t = nullptr, *act_t = nullptr;
     float *x_t = nullptr, *rowsq_all = nullptr, *rowsq_out_all = nullptr;
     int rc = RT_OK;
@@ -200,11 +202,11 @@ int rt_debug_gemm_col(rt_ctx* ctx, const void* d_a_bf16, int32_t M, int32_t K, c
     pw.N = N; pw.K = K;
     rc = launch_pack_weight16(ctx, (const bf16_t*)d_w_bf16, N, K, w16, &pw);
     const int nb = 256;
-    hipLaunchKernelGGL((k_tile_rows<bf16_t>), dim3(nb), dim3(256), 0, ctx->stream, (const bf16_t*)d_a_bf16, M, K, row_off, a_t);
+    hipLaunchKernelGGL((k_tile_rows<bf16_t>), dim3(nb), dim3(256), 0, ctx->stream, (const bf16_t*)d_a_bf16, M, K, row_off, a_t, K);
     const int n_part = (N + 15) / 16 * split;                    // RESID: rowsq partials per row
     ColArgs c;
     c.A = a_t; c.M = M; c.K = K; c.epi = epi; c.split = split; c.row_off = row_off; c.nt = nt ? 1 : 0; c.eps = eps;
-    c.bias = d_bias; c.scale = d_scale; c.ldc = No;
+    c.bias = d_bias; c.scale = d_scale; c.ldc = epi == COL_STORE ? No : ldt;
     if (d_rowsq) {                                               // rowsq rows are addressed by absolute row (row_off + m)
         DBG_HIP(hipMalloc((void**)&rowsq_all, (size_t)rows * rowsq_n * 4));
         DBG_HIP(hipMemsetAsync(rowsq_all, 0, (size_t)rows * rowsq_n * 4, ctx->stream));
@@ -214,20 +216,20 @@ int rt_debug_gemm_col(rt_ctx* ctx, const void* d_a_bf16, int32_t M, int32_t K, c
     if (epi == COL_STORE) {
         c.out = d_x - (size_t)row_off * No;                       // as col_head does: output rows are indexed from row_off
     } else if (epi == COL_RESID) {
-        DBG_HIP(hipMalloc((void**)&x_t, (size_t)rows * No * 4));
-        DBG_HIP(hipMemsetAsync(x_t, 0, (size_t)rows * No * 4, ctx->stream));
-        hipLaunchKernelGGL((k_tile_rows<float>), dim3(nb), dim3(256), 0, ctx->stream, (const float*)d_x, M, No, row_off, x_t);
+        DBG_HIP(hipMalloc((void**)&x_t, (size_t)rows * ldt * 4));
+        DBG_HIP(hipMemsetAsync(x_t, 0, (size_t)rows * ldt * 4, ctx->stream));
+        hipLaunchKernelGGL((k_tile_rows<float>), dim3(nb), dim3(256), 0, ctx->stream, (const float*)d_x, M, No, row_off, x_t, ldt);
         DBG_HIP(hipMalloc((void**)&rowsq_out_all, (size_t)rows * n_part * 4));
         DBG_HIP(hipMemsetAsync(rowsq_out_all, 0, (size_t)rows * n_part * 4, ctx->stream));
         c.out = x_t; c.rowsq_out = rowsq_out_all; c.rowsq_out_n = n_part;
         if (d_next_bf16) {
-            DBG_HIP(hipMalloc((void**)&next_t, (size_t)rows * No * 2));
-            DBG_HIP(hipMemsetAsync(next_t, 0, (size_t)rows * No * 2, ctx->stream));
+            DBG_HIP(hipMalloc((void**)&next_t, (size_t)rows * ldt * 2));
+            DBG_HIP(hipMemsetAsync(next_t, 0, (size_t)rows * ldt * 2, ctx->stream));
             c.next_bf16 = next_t; c.next_norm_w = d_next_norm_w;
         }
     } else {
-        DBG_HIP(hipMalloc((void**)&act_t, (size_t)rows * No * 2));
-        DBG_HIP(hipMemsetAsync(act_t, 0, (size_t)rows * No * 2, ctx->stream));
+        DBG_HIP(hipMalloc((void**)&act_t, (size_t)rows * ldt * 2));
+        DBG_HIP(hipMemsetAsync(act_t, 0, (size_t)rows * ldt * 2, ctx->stream));
         c.out_bf16 = act_t;
     }
     const int blk = (M > 64 && g_col_rows128) ? 128 : (g_col_rows64 ? 64 : 32);   // (65..128 rows: what a generation that wide launches)
@@ -238,12 +240,12 @@ int rt_debug_gemm_col(rt_ctx* ctx, const void* d_a_bf16, int32_t M, int32_t K, c
         rc = launch_gemm_col(ctx, a, pw);
     }
     if (!rc && epi == COL_RESID) {
-        hipLaunchKernelGGL((k_untile_rows<float>), dim3(nb), dim3(256), 0, ctx->stream, (const float*)x_t, M, No, row_off, d_x);
-        if (next_t) hipLaunchKernelGGL((k_untile_rows<bf16_t>), dim3(nb), dim3(256), 0, ctx->stream, (const bf16_t*)next_t, M, No, row_off, (bf16_t*)d_next_bf16);
+        hipLaunchKernelGGL((k_untile_rows<float>), dim3(nb), dim3(256), 0, ctx->stream, (const float*)x_t, M, No, row_off, d_x, ldt);
+        if (next_t) hipLaunchKernelGGL((k_untile_rows<bf16_t>), dim3(nb), dim3(256), 0, ctx->stream, (const bf16_t*)next_t, M, No, row_off, (bf16_t*)d_next_bf16, ldt);
         DBG_HIP(hipMemcpyAsync(d_rowsq_out, rowsq_out_all + (size_t)row_off * n_part, (size_t)M * n_part * 4, hipMemcpyDeviceToDevice, ctx->stream));
     }
     if (!rc && epi == COL_SILU)
-        hipLaunchKernelGGL((k_untile_rows<bf16_t>), dim3(nb), dim3(256), 0, ctx->stream, (const bf16_t*)act_t, M, No, row_off, (bf16_t*)d_act_bf16);
+        hipLaunchKernelGGL((k_untile_rows<bf16_t>), dim3(nb), dim3(256), 0, ctx->stream, (const bf16_t*)act_t, M, No, row_off, (bf16_t*)d_act_bf16, ldt);
     if (!rc) DBG_HIP(hipGetLastError());
 #undef DBG_HIP
     cleanup();
@@ -400,13 +402,13 @@ int dbg_tile_in(rt_ctx* ctx, DbgBufs& bufs, const T* rows_rm, int rows, int H, T
     const size_t pad = (size_t)(rows + 15) / 16 * 16;
     RT_HIP(ctx, bufs.alloc(tiled, pad * H * sizeof(T)));
     RT_HIP(ctx, hipMemsetAsync(*tiled, 0, pad * H * sizeof(T), ctx->stream));
-    hipLaunchKernelGGL((k_tile_rows<T>), dim3(256), dim3(256), 0, ctx->stream, rows_rm, rows, H, 0, *tiled);
+    hipLaunchKernelGGL((k_tile_rows<T>), dim3(256), dim3(256), 0, ctx->stream, rows_rm, rows, H, 0, *tiled, H);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
 template <typename T>
 int dbg_tile_out(rt_ctx* ctx, const T* tiled, int rows, int H, T* rows_rm) {
-    hipLaunchKernelGGL((k_untile_rows<T>), dim3(256), dim3(256), 0, ctx->stream, tiled, rows, H, 0, rows_rm);
+    hipLaunchKernelGGL((k_untile_rows<T>), dim3(256), dim3(256), 0, ctx->stream, tiled, rows, H, 0, rows_rm, H);
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
@@ -710,6 +712,17 @@ int rt_debug_col_row_blocks(int32_t n_cu, int32_t M, int32_t N, int32_t epi, int
     bool x_form = false;
     const int wg = col_workgroups(n_cu, M, N, epi, split, &x_form);
     return col_row_blocks(n_cu, M, wg, x_form);
+}
+
+// ... and its tile-block decision (col_tile_blocks, taken only where the row-block rule does not hold)
+int rt_debug_col_tile_blocks(int32_t n_cu, int32_t M, int32_t N, int32_t epi, int32_t split) {
+    if (n_cu < 1 || M < 1 || M > 128 || N < 1 || epi < COL_STORE || epi > COL_SILU || (epi == COL_SILU && N % 32) || split > 4 || split == 3) return -1;
+    std::shared_lock<std::shared_mutex> plan(g_tune_mu);
+    if (epi == COL_SILU) return 0;
+    if (split <= 0) split = col_split_for(N, n_cu);
+    bool x_form = false;
+    if (col_row_blocks(n_cu, M, col_workgroups(n_cu, M, N, epi, split, &x_form), x_form)) return 0;
+    return col_tile_blocks(n_cu, M, (N + 15) / 16, epi, split);
 }
 
 int rt_bench_gemm_skinny(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t split_k, int32_t n_mats, int32_t iters, double* avg_us,

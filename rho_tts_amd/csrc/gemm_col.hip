@@ -81,10 +81,20 @@ constexpr int col_chunk(int epi, int mt, bool x) {                         // k-
 // its own first row and row count from blockIdx.y and reads that part of A alone; the column tile, the sub-tile and the rowsq_out
 // slot stay keyed on blockIdx.x.  A compile-time flag, so that every launch without blocks keeps the code it had.  A 16-row block
 // (MT = 1) has a CU to itself: it is free of the decode lanes' 128-VGPR bound and takes the chunk lengths of a 32-row launch.
-template <int EPI, int MT, int NPRE, bool X = false, bool NORM = false, int WQ = 0, int CF = 0, bool RB = false>
+// Tile blocks (g_col_tile_blocks): a STORE / RESID launch of 17..64 rows whose HALF tiles (split 2) just fit the CUs (the 1.7B talker's
+// o / down and the predictor's head, N = 2048: 256 workgroups of 32 rows x 8 columns) runs as the same number of workgroups of 16 rows x
+// 16 columns - whole tiles (g.split 1 as launched, g.lay_split 2), rows over gridDim.y = 2, the RB code.  What bounds these launches
+// is bytes into the CUs' L1s, (rows + columns) x K x 2 per workgroup: 32 K instead of 40 K (64 rows: 48 K instead of 72 K), and no MFMA
+// multiplies zero columns; each weight byte is requested by the two workgroups of a tile (same XCD).  Measured: down 11.92 -> 10.18 us,
+// o 5.76 -> 5.17, head 4.17 -> 3.81 per launch, 184.2 -> 180.1 ms per step.
+// HP (RB RESID only) = such a workgroup stores BOTH half-tile sums of squares of its tile, slots 2 nt and 2 nt + 1 of the row the callers
+// laid out for split 2: the 8-lane sums group_sum_f32<16> forms before its last add, whose other operand is the +0 of the half that a
+// half-tile workgroup does not own - the same bits.
+template <int EPI, int MT, int NPRE, bool X = false, bool NORM = false, int WQ = 0, int CF = 0, bool RB = false, bool HP = false>
 __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || (MT == 1 && !RB)) && !X) ? 4 : 2) void k_gemm_col(ColArgs g) {
     static_assert(!X || (EPI == COL_SILU && MT >= 2), "the extra half pair exists for gate/up only");
     static_assert(!RB || (!X && MT <= 2), "row blocks have 16 or 32 rows, and the 1.5-pair form is never blocked");
+    static_assert(!HP || (RB && EPI == COL_RESID), "two half-tile partials per workgroup exist for row-blocked RESID launches only");
     constexpr int RMT = MT > 4 ? 4 : MT;     // sub-blocks per combine round (MT = 8: two rounds through the same 32 KiB)
     constexpr int ROUNDS = MT / RMT;
     __shared__ float red[WAVES][RMT][4][64]; // 16 KiB per 32 rows: one 16x16 accumulator tile per sub-block and wave
@@ -310,8 +320,14 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || (MT == 1 && 
             float sq = xn * xn;                   // a 16-lane group = one row's 16 columns
             // (DPP adds: the four dependent ds_bpermute round trips of a __shfl_xor butterfly sat in the tail of every RESID launch -
             //  two per layer - between the last store of x and the store of its sums of squares)
-            sq = group_sum_f32<16>(sq);
-            if ((e_l & 15) == 0 && e_row < M) g.rowsq_out[(int64_t)(row_off + e_row) * g.rowsq_out_n + (g.rowsq_perm ? rowsq_slot((int)blockIdx.x, g.rowsq_out_n) : (int)blockIdx.x)] = sq;
+            if constexpr (HP) {                   // whole-tile workgroup, split-2 layout: columns 0..7 -> partial 2 nt, 8..15 -> 2 nt + 1
+                sq = group_sum_f32<8>(sq);
+                const int j = 2 * nt + ((e_l >> 3) & 1);
+                if ((e_l & 7) == 0 && e_row < M) g.rowsq_out[(int64_t)(row_off + e_row) * g.rowsq_out_n + (g.rowsq_perm ? rowsq_slot(j, g.rowsq_out_n) : j)] = sq;
+            } else {
+                sq = group_sum_f32<16>(sq);
+                if ((e_l & 15) == 0 && e_row < M) g.rowsq_out[(int64_t)(row_off + e_row) * g.rowsq_out_n + (g.rowsq_perm ? rowsq_slot((int)blockIdx.x, g.rowsq_out_n) : (int)blockIdx.x)] = sq;
+            }
         } else {                                  // COL_SILU: gate = tile nt, up = tile nt + offset
             if (ok) {
                 const float u = val[1][ps] * inv;
@@ -328,22 +344,22 @@ __global__ __launch_bounds__(512, (((EPI == COL_SILU && MT == 2) || (MT == 1 && 
     if (g.stamps && blockIdx.x == 0 && (!RB || blockIdx.y == 0) && tid == 0) g.stamps[5] = wall_clock64();
 }
 
-template <int EPI, int MT, int NPRE, bool X, bool NORM, int WQ, int CF, bool RB>
+template <int EPI, int MT, int NPRE, bool X, bool NORM, int WQ, int CF, bool RB, bool HP>
 void launch_one(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
-    if (!e0 && !e1) hipLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF, RB>), grid, dim3(512), 0, ctx->stream, g);   // plain launches are what a stream capture records
-    else hipExtLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF, RB>), grid, dim3(512), 0, ctx->stream, e0, e1, 0, g);   // device-side begin/end stamps
+    if (!e0 && !e1) hipLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF, RB, HP>), grid, dim3(512), 0, ctx->stream, g);   // plain launches are what a stream capture records
+    else hipExtLaunchKernelGGL((k_gemm_col<EPI, MT, NPRE, X, NORM, WQ, CF, RB, HP>), grid, dim3(512), 0, ctx->stream, e0, e1, 0, g);   // device-side begin/end stamps
 }
 
-template <int EPI, int MT, bool X, bool NORM, int WQ, int CF, bool RB>
+template <int EPI, int MT, bool X, bool NORM, int WQ, int CF, bool RB, bool HP>
 void launch_npre2(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     // every wave needs at least one k-tile for the clamped (branch-free) requests to be valid addresses
     constexpr int C = CF ? CF : col_chunk(EPI, (RB && MT == 1) ? 2 : MT, X);      // (as the kernel has it)
     const int kchunk = (g.KT + WAVES - 1) / WAVES;
     const bool all_waves_busy = g.KT >= WAVES && (WAVES - 1) * kchunk < g.KT;
     const int n_sc = (kchunk + C - 1) / C;
-    if (!all_waves_busy) launch_one<EPI, MT, 0, X, NORM, WQ, CF, RB>(ctx, g, grid, e0, e1);
-    else if (n_sc >= 2) launch_one<EPI, MT, 2, X, NORM, WQ, CF, RB>(ctx, g, grid, e0, e1);
-    else launch_one<EPI, MT, 1, X, NORM, WQ, CF, RB>(ctx, g, grid, e0, e1);
+    if (!all_waves_busy) launch_one<EPI, MT, 0, X, NORM, WQ, CF, RB, HP>(ctx, g, grid, e0, e1);
+    else if (n_sc >= 2) launch_one<EPI, MT, 2, X, NORM, WQ, CF, RB, HP>(ctx, g, grid, e0, e1);
+    else launch_one<EPI, MT, 1, X, NORM, WQ, CF, RB, HP>(ctx, g, grid, e0, e1);
 }
 
 // The chunk length follows the wave's run of k-tiles where it is known to be short (STORE / RESID launches of up to 32 rows, whose
@@ -351,27 +367,27 @@ void launch_npre2(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEv
 // requested up front without a branch.  With chunks of 8 the clamped requests of the tail re-load the run's last tile - as many
 // requests as the real ones at K = 1024, half of the second chunk at K = 3072.  Same k order inside a wave: the same bits.
 // A 16-row block of a row-blocked launch (RB, MT = 1) takes the same lengths: it has a CU, and so 256 VGPRs, to itself.
-template <int EPI, int MT, bool X, bool NORM, int WQ, bool RB>
+template <int EPI, int MT, bool X, bool NORM, int WQ, bool RB, bool HP>
 void launch_chunk(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     if constexpr (EPI != COL_SILU && (MT == 2 || (MT == 1 && RB))) {
         const int kchunk = (g.KT + WAVES - 1) / WAVES;
-        if (g_col_chunk_fit && kchunk <= 4) return launch_npre2<EPI, MT, X, NORM, WQ, 4, RB>(ctx, g, grid, e0, e1);
-        if (g_col_chunk_fit && kchunk > 8 && kchunk <= 12) return launch_npre2<EPI, MT, X, NORM, WQ, 6, RB>(ctx, g, grid, e0, e1);
+        if (g_col_chunk_fit && kchunk <= 4) return launch_npre2<EPI, MT, X, NORM, WQ, 4, RB, HP>(ctx, g, grid, e0, e1);
+        if (g_col_chunk_fit && kchunk > 8 && kchunk <= 12) return launch_npre2<EPI, MT, X, NORM, WQ, 6, RB, HP>(ctx, g, grid, e0, e1);
     }
-    launch_npre2<EPI, MT, X, NORM, WQ, 0, RB>(ctx, g, grid, e0, e1);
+    launch_npre2<EPI, MT, X, NORM, WQ, 0, RB, HP>(ctx, g, grid, e0, e1);
 }
 
 // (the residual epilogue never follows an RMSNorm in this model: one instantiation less per shape)
-template <int EPI, int MT, bool X = false, bool RB = false>
+template <int EPI, int MT, bool X = false, bool RB = false, bool HP = false>
 void launch_npre(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEvent_t e1) {
     if (g.post_scale) {
         if constexpr (EPI != COL_RESID) {
-            if (g.rowsq_wide == 2) launch_chunk<EPI, MT, X, true, 2, RB>(ctx, g, grid, e0, e1);
-            else if (g.rowsq_wide == 4) launch_chunk<EPI, MT, X, true, 4, RB>(ctx, g, grid, e0, e1);
-            else launch_chunk<EPI, MT, X, true, 0, RB>(ctx, g, grid, e0, e1);
+            if (g.rowsq_wide == 2) launch_chunk<EPI, MT, X, true, 2, RB, HP>(ctx, g, grid, e0, e1);
+            else if (g.rowsq_wide == 4) launch_chunk<EPI, MT, X, true, 4, RB, HP>(ctx, g, grid, e0, e1);
+            else launch_chunk<EPI, MT, X, true, 0, RB, HP>(ctx, g, grid, e0, e1);
         }
     } else {
-        launch_chunk<EPI, MT, X, false, 0, RB>(ctx, g, grid, e0, e1);
+        launch_chunk<EPI, MT, X, false, 0, RB, HP>(ctx, g, grid, e0, e1);
     }
 }
 
@@ -380,7 +396,10 @@ int dispatch_epi(rt_ctx* ctx, const ColArgs& g, dim3 grid, hipEvent_t e0, hipEve
         const bool b32 = g.row_block == 32;
         switch (g.epi) {
             case COL_STORE: b32 ? launch_npre<COL_STORE, 2, false, true>(ctx, g, grid, e0, e1) : launch_npre<COL_STORE, 1, false, true>(ctx, g, grid, e0, e1); break;
-            case COL_RESID: b32 ? launch_npre<COL_RESID, 2, false, true>(ctx, g, grid, e0, e1) : launch_npre<COL_RESID, 1, false, true>(ctx, g, grid, e0, e1); break;
+            case COL_RESID:
+                if (g.lay_split != g.split) b32 ? launch_npre<COL_RESID, 2, false, true, true>(ctx, g, grid, e0, e1) : launch_npre<COL_RESID, 1, false, true, true>(ctx, g, grid, e0, e1);   // tile blocks: both half-tile partials
+                else b32 ? launch_npre<COL_RESID, 2, false, true>(ctx, g, grid, e0, e1) : launch_npre<COL_RESID, 1, false, true>(ctx, g, grid, e0, e1);
+                break;
             case COL_SILU: b32 ? launch_npre<COL_SILU, 2, false, true>(ctx, g, grid, e0, e1) : launch_npre<COL_SILU, 1, false, true>(ctx, g, grid, e0, e1); break;
             default: return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: bad epilogue %d", g.epi);
         }
@@ -465,6 +484,18 @@ int col_row_blocks(int n_cu, int M, int wg, bool x_form) {
     return 0;
 }
 
+// Tile blocks (g_col_tile_blocks): a STORE / RESID launch at split 2 whose half tiles fit the CUs (tiles * 2 <= n_cu) but fill more
+// than half of them (so that the rule above does not hold) runs whole tiles instead and deals its rows over the freed half of the
+// workgroups - 33..64 rows as two 32-row blocks (value >= 1), 17..32 rows as two 16-row blocks (value 2).  The workgroup count stays;
+// every workgroup pulls (rows + 16) x K x 2 bytes through its CU's L1 instead of (2 rows + 8) x K x 2.  On 256 CUs: N in 1040..2048.
+int col_tile_blocks(int n_cu, int M, int tiles, int epi, int split) {
+    const int v = g_col_tile_blocks;
+    if (v < 1 || (epi != COL_STORE && epi != COL_RESID) || split != 2 || tiles < 1 || tiles * 2 > n_cu || 2 * tiles * 2 <= n_cu) return 0;
+    if (M >= 33 && M <= 64) return 32;
+    if (v >= 2 && M >= 17 && M <= 32) return 16;
+    return 0;
+}
+
 bool rowsq_permuted(int n) { return g_rowsq_wide && n % 64 == 0 && n >= 64 && n <= 256; }
 
 int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t ev_start, hipEvent_t ev_stop) {
@@ -504,6 +535,15 @@ int launch_gemm_col(rt_ctx* ctx, const ColArgs& a, const PackedW& w, hipEvent_t 
         return rt_fail(ctx, RT_ERR_INVALID, "gemm_col: rowsq rows read in 16-byte pieces must be 16-byte aligned");
     // rows dealt over the CUs a narrow launch leaves idle: grid.y row blocks, each workgroup reads its block of A alone
     g.row_block = col_row_blocks(ctx->n_cu, g.M, wg, x_form);
+    g.lay_split = g.split;
+    int wg_x = wg;
+    if (!g.row_block && !x_form) {      // ... or over the half of the workgroups that whole tiles free; `lay_split` stays the rowsq_out layout
+        g.row_block = col_tile_blocks(ctx->n_cu, g.M, tiles, g.epi, g.split);
+        if (g.row_block) {
+            g.split = 1;
+            wg_x = tiles;
+        }
+    }
     const int n_blocks = g.row_block ? (g.M + g.row_block - 1) / g.row_block : 1;
-    return dispatch_epi(ctx, g, dim3(wg, n_blocks), ev_start, ev_stop);
+    return dispatch_epi(ctx, g, dim3(wg_x, n_blocks), ev_start, ev_stop);
 }

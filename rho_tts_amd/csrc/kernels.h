@@ -118,12 +118,19 @@ struct ColArgs {
     int rowsq_wide = 0;             // NORM: 0 = plain rows, one dword request per partial; 2 / 4 = permuted rows, that many
                                     //       16-byte requests per lane and 32 rows (rowsq_permuted(rowsq_n))
     int row_block = 0;              // rows per row block (16 or 32: grid.y blocks of that many rows, the last one ragged); 0: no blocks,
-                                    //       one workgroup per column tile has all M rows (col_row_blocks)
+                                    //       one workgroup per column tile has all M rows (col_row_blocks, col_tile_blocks)
+    int lay_split = 0;              // the callers' `split`, kept as the LAYOUT of the rowsq_out row (NT * lay_split partials).  In the launcher's
+                                    //       copy `split` is the workgroups per tile AS LAUNCHED: a tile-blocked launch (col_tile_blocks) runs whole-tile
+                                    //       workgroups (split 1) under lay_split 2, each storing both half-tile partials of its tile
 };
 // The launcher's row-block rule as host arithmetic (g_col_row_blocks): rows per block for a launch of M rows whose column tiles make
 // `wg` workgroups (tiles x split, after the gate/up X decision), or 0.  A narrow launch that leaves at least half of the CUs
 // without a workgroup deals its rows over them: every workgroup then reads half of the A operand.
 int col_row_blocks(int n_cu, int M, int wg, bool x_form);
+// Tile blocks (g_col_tile_blocks): rows per block (16 / 32) when a STORE / RESID launch of `tiles` column tiles at sub-tile split
+// `split` (resolved: 1, 2 or 4) runs as whole-tile workgroups with its rows dealt over two blocks, or 0.  Round 24's rule above
+// comes first; the two never hold together.
+int col_tile_blocks(int n_cu, int M, int tiles, int epi, int split);
 // `wg` and the X decision of a launch (what launch_gemm_col computes): N is the weight's width (gate + up for COL_SILU), split <= 0
 // takes the automatic sub-tile split.
 int col_workgroups(int n_cu, int M, int N, int epi, int split, bool* x_form);

@@ -59,7 +59,11 @@
         "two of 6 for K = 3072: no clamped re-loads of the run's last tile), 0 chunks of 8 (same bits either way; profiles/r21_gemm_col_prologue.txt)") \
     X(3600, g_col_row_blocks, 2, 0, 2, "decode GEMM launches whose workgroups fill at most half of the CUs (the predictor's o / down / mtp: 128 on 256) deal their rows over " \
         "gridDim.y: 0 never, 1 launches of 33..64 rows as two 32-row blocks, 2 also launches of 17..32 rows as two 16-row blocks (same bits either way; " \
-        "profiles/r24_row_blocks.txt)")
+        "profiles/r24_row_blocks.txt)") \
+    X(3700, g_col_tile_blocks, 2, 0, 2, "STORE / RESID decode GEMM launches at split 2 whose half-tile workgroups fill more than half of the CUs (the 1.7B talker's o / down, the " \
+        "predictor's head: N = 2048, 256 workgroups of 32 rows x 8 columns) run whole-tile workgroups with their rows dealt over gridDim.y - as many workgroups, fewer bytes into " \
+        "each CU's L1: 0 never, 1 launches of 33..64 rows as 32-row blocks, 2 also launches of 17..32 rows as 16-row blocks (same bits either way, the rowsq row keeps its " \
+        "split-2 layout; profiles/r25_tile_blocks.txt)")
 
 // The one switch set by rt_debug_tune's SECOND argument: applied when the code is 0..2 and the argument lies in lo..hi.
 #define RT_KNOB_ARG(X) \

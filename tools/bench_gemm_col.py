@@ -84,6 +84,29 @@ if len(sys.argv) > 1 and sys.argv[1] == "rows":
                 cols.append(f"{'' if code is None else str(code) + ': '}{statistics.median(t):6.2f} us (min {min(t):.2f} max {max(t):.2f})")
             print(f"{name:22s} M={M:2d}  " + " | ".join(cols), flush=True)
     sys.exit(0)
+if len(sys.argv) > 1 and sys.argv[1] == "tiles":
+    # the N = 2048 launches whose 256 half-tile workgroups (32 rows x 8 columns) become 256 whole-tile workgroups of half the rows
+    # (16 x 16; 64 rows: 64 x 8 -> 32 x 16), HBM-cold with non-temporal and with cacheable weight loads; median of three runs of 300.
+    # `tiles`: one column per value of 3700 / 3701 / 3702; `tiles plain`: no switch is touched (a build without 3700)
+    import statistics
+    codes = (None,) if len(sys.argv) > 2 and sys.argv[2] == "plain" else (3700, 3701, 3702)
+    for N, K, norm, epi, name in ((2048, 2048, 0, 1, "talker o    RESID"), (2048, 6144, 0, 1, "talker down RESID"), (2048, 1024, 1, 0, "pred head   NORM STORE")):
+        mb = N * K * 2 / 1e6
+        n_mats = max(2, int(600 / mb) + 1)
+        for M in (16, 32, 64):
+            for cache, label in ((0, "non-temporal"), (2, "cacheable   ")):
+                cols = []
+                for code in codes:
+                    if code is not None:
+                        assert lib.rt_debug_tune(code, 0) == 0
+                    t = []
+                    for _ in range(3):
+                        us = C.c_double()
+                        assert lib.rt_bench_gemm_col(ctx.handle, M, N, K, norm | cache, epi, n_mats, 300, C.byref(us), None) == 0
+                        t.append(us.value)
+                    cols.append(f"{'' if code is None else str(code) + ': '}{statistics.median(t):6.2f} us (min {min(t):.2f} max {max(t):.2f})")
+                print(f"{name:24s} M={M:2d} {label}  " + " | ".join(cols), flush=True)
+    sys.exit(0)
 for M, N, K, norm, epi, name in shapes:
     mb = N * K * 2 / 1e6
     n_mats = max(2, int(600 / mb) + 1)
