@@ -709,6 +709,40 @@ RT_API int rt_forest_set_model(rt_forest* f, int32_t n_features, int32_t n_fores
                                const double* h_iso_y);
 RT_API int rt_forest_predict(rt_forest* f, const double* h_x, int32_t n_rows, double* h_prob);
 
+/* ------------------------------------------------------------------ drift classifier: fitting the forests
+ * Stands behind the RandomForestClassifier fits of validation/classifier/trainer.py:217-230: every tree of every forest of a
+ * cross-validated fit in ONE call, written in the table layout above (pre-order nodes, left child = k + 1, no calibrators - those
+ * are host arithmetic on held-out predictions, rho_tts_amd/forest_train.py).  forest_train.py states the rules - counter-hash random
+ * numbers, bootstrap multiplicities, the leaf conditions on distinct rows, the partial Fisher-Yates feature draw, the split score and
+ * its tie rule, the midpoint threshold - and DEFINES the result (fit_host): the tables returned here equal it bit for bit, and a tree
+ * does not depend on the other trees of the call.
+ *   h_x [n][n_features] float64 (rounded to float32, compared as doubles), h_y [n] 0 / 1, h_member [n_forests][n]: row i takes part
+ *   in forest c when h_member[c][i] != 0.  p->n_trees trees PER FOREST; max_features 0 = floor(sqrt(n_features)), at least 1.
+ *   h_tree_first [n_forests * n_trees + 1], h_node_feature / h_node_right / h_node_value [node_cap]: caller-owned; *h_n_nodes
+ *   receives the node count.  CAPACITY: a tree over m member rows has at most 2 * floor(m / min_samples_leaf) - 1 nodes (at least 1)
+ *   and never more than 2^(max_depth + 1) - 1 - rt_forest_fit_capacity(p, m) is that bound - and node_cap must be at least the sum of
+ *   the bounds of all trees of the call (RT_ERR_LENGTH otherwise, before any launch).
+ * Refused with no launch - RT_ERR_INVALID: a null pointer, a feature that is NaN, infinite or beyond float32's range, a y outside
+ * {0, 1}, a forest without members, n_trees < 1, min_samples_leaf < 1, min_samples_split < 2, max_features outside 0 .. n_features,
+ * a class weight that is not positive and finite, more than 64 forests; RT_ERR_LENGTH: n > 16384, n_features > 1024, max_depth > 64,
+ * node_cap below the bound.  One host-to-device copy, two launches (the per-feature rank table; one workgroup per tree), one
+ * device-to-host copy and one stream synchronisation on the context's stream, whatever the sizes; the workspaces are the context's
+ * and only grow.  No floating-point atomics, no grid-wide barrier; every device loop is bounded by the capacity or the depth bound. */
+typedef struct rt_forest_fit_params {
+    int32_t n_trees;               /* per forest */
+    int32_t max_depth;
+    int32_t min_samples_leaf;      /* distinct rows */
+    int32_t min_samples_split;     /* distinct rows */
+    int32_t max_features;          /* 0: floor(sqrt(n_features)), at least 1 */
+    int32_t bootstrap;             /* 0: every member row once */
+    double w0, w1;                 /* class weights */
+    uint64_t seed;
+} rt_forest_fit_params;
+RT_API int64_t rt_forest_fit_capacity(const rt_forest_fit_params* p, int32_t n_members);
+RT_API int rt_forest_fit(rt_ctx* ctx, const double* h_x, int32_t n, int32_t n_features, const uint8_t* h_y, const uint8_t* h_member,
+                         int32_t n_forests, const rt_forest_fit_params* p, int32_t node_cap, int32_t* h_tree_first, int32_t* h_node_feature,
+                         int32_t* h_node_right, double* h_node_value, int32_t* h_n_nodes);
+
 /* ------------------------------------------------------------------ speaker embedding: the GE2E encoder
  * Stands behind resemblyzer's VoiceEncoder.embed_utterance(preprocess_wav(...)) as the reference calls it for the first 256 of the
  * drift classifier's 286 dimensions (validation/classifier/trainer.py:23-68) and for _compute_speaker_similarity

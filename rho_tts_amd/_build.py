@@ -24,7 +24,7 @@ CXXFLAGS = ["-std=c++17", "-O3", "-fPIC", "-fvisibility=hidden", f"--offload-arc
 # must not have mul+add fused behind their back.
 PER_FILE = {"postprocess.hip": ["-ffp-contract=off"], "encoder.hip": ["-ffp-contract=off"], "features.hip": ["-ffp-contract=off"],
             "speedpitch.hip": ["-ffp-contract=off"], "forest.hip": ["-ffp-contract=off"],
-            "speaker.hip": ["-ffp-contract=off"]}
+            "speaker.hip": ["-ffp-contract=off"], "forest_fit.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -356,6 +356,24 @@ def make_drift_scorer(extractor: HandcraftedFeatures, classifier: Callable[[np.n
     return score
 
 
+def forest_rows(extractor, embed, audios: Sequence, sample_rate: int, width: Optional[int] = None) -> np.ndarray:
+    """The classifier's rows of a chunk of clips, float64 [n][k + 30]: ONE ``extractor.batch`` call for the 30 hand-crafted features
+    and, with ``embed`` (a batch callable ``(audios, sample_rate) -> [n][k]``), one call for the speaker-embedding dimensions that come
+    first in the reference's layout (trainer.py:61-65).  The one assembly behind inference (``make_forest_scorer``) and training
+    (``forest_train.train``): a classifier is fitted on exactly the rows it will score.  ``width``: the row width a model expects,
+    checked against what ``embed`` returned."""
+    audios = list(audios)
+    f = np.asarray(extractor.batch(audios, sample_rate), dtype=np.float64).reshape(len(audios), -1)
+    if embed is not None:
+        e = np.asarray(embed(audios, sample_rate), dtype=np.float64)
+        if e.ndim != 2 or e.shape[0] != len(audios) or (width is not None and e.shape[1] + f.shape[1] != width):
+            need = "" if width is None else (f": the classifier takes {width} features, {f.shape[1]} of them hand-crafted, so it needs "
+                                             f"[{len(audios)}][{width - f.shape[1]}]")
+            raise ValueError(f"embed returned an array of shape {e.shape} for {len(audios)} clips{need}")
+        f = np.concatenate([e, f], axis=1)
+    return f
+
+
 def make_forest_scorer(extractor: HandcraftedFeatures, forest, embed: Optional[Callable[[Sequence[torch.Tensor], int], np.ndarray]] = None
                        ) -> Callable[[torch.Tensor, int], float]:
     """A ``drift_scorer`` hook whose classifier runs on the GPU too (forest.DriftForest): ``score.batch(audios, sample_rate)`` makes ONE
@@ -376,14 +394,7 @@ def make_forest_scorer(extractor: HandcraftedFeatures, forest, embed: Optional[C
         audios = list(audios)
         if not audios:
             return []
-        f = np.asarray(extractor.batch(audios, sample_rate), dtype=np.float64).reshape(len(audios), -1)
-        if embed is not None:
-            e = np.asarray(embed(audios, sample_rate), dtype=np.float64)
-            if e.ndim != 2 or e.shape[0] != len(audios) or e.shape[1] + f.shape[1] != width:
-                raise ValueError(f"embed returned an array of shape {e.shape} for {len(audios)} clips: the classifier takes {width} features, "
-                                 f"{f.shape[1]} of them hand-crafted, so it needs [{len(audios)}][{width - f.shape[1]}]")
-            f = np.concatenate([e, f], axis=1)
-        return [float(p) for p in forest.predict(f)]
+        return [float(p) for p in forest.predict(forest_rows(extractor, embed, audios, sample_rate, width))]
 
     def score(audio: torch.Tensor, sample_rate: int) -> float:
         return batch([audio], sample_rate)[0]

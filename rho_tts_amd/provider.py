@@ -1010,6 +1010,29 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             self.drift_optimal_threshold = float(tables["optimal_threshold"])
             return scorer
 
+    def train_drift_classifier(self, dataset_dir: str, voice_id: Optional[str] = None, output_path: Optional[str] = None,
+                               progress_callback=None) -> str:
+        """The reference's ``train_drift_classifier`` (__init__.py:69) on this provider's context: ``forest_train.train`` over
+        ``dataset_dir/good`` and ``dataset_dir/bad`` - the folders ``_auto_sort_audio`` fills - with the rows the validation will see:
+        [256 GE2E | 30 hand-crafted] when ``speaker_encoder_path`` (or ``drift_embed``) is configured, the 30 alone otherwise.  Then
+        ``drift_model_path`` points at the written ``.npz`` and the cached native scorer is dropped, so the next validation scores with
+        the new model.  Returns the path.  Nothing changes unless this is called."""
+        from . import forest_train
+        with self._lock:
+            embed = self.drift_embed
+            if embed is None and self.speaker_encoder_path:
+                embed = self._speaker_embed()
+            path = forest_train.train(dataset_dir, voice_id=voice_id, output_path=output_path, progress_callback=progress_callback,
+                                      ctx=self._native_ctx(), embed=embed)
+            if self._drift_native is not None:                 # (the speaker embedder stays: the next scorer uses it again)
+                ex, forest, _ = self._drift_native
+                self._drift_native = None
+                forest.close()
+                ex.close()
+            self.drift_model_path = path
+            self.drift_optimal_threshold = None
+            return path
+
     def _close_drift(self) -> None:
         if self._drift_native is not None:
             ex, forest, _ = self._drift_native
