@@ -202,7 +202,7 @@ typedef struct rt_model_config {
     int32_t max_batch;            /* sequences decoded together, 1..128  */
     int32_t max_positions;        /* KV rows per sequence (prompt + frames) */
     int32_t max_codec_frames;     /* frames per sequence one rt_code2wav call may decode */
-    int32_t reserved[4];
+    int32_t reserved[4];          /* [0]: max_voices, the entries of the voice bank (0 = 1, at most 8: rt_voice_select); [1..3]: 0 */
     rt_encoder_config enc;
 } rt_model_config;
 
@@ -258,6 +258,29 @@ RT_API int32_t rt_voice_prefix_len(rt_model* m);
 RT_API int64_t rt_voice_blob_bytes(rt_model* m);
 RT_API int rt_voice_export(rt_model* m, void* d_blob, int64_t bytes);
 RT_API int rt_voice_import(rt_model* m, int32_t prefix_len, const void* d_blob, int64_t bytes);
+/* The voice bank: a model holds rt_model_config.reserved[0] voices at once (max_voices; 0 means 1, at most 8 - a larger value fails
+ * rt_model_create with RT_ERR_INVALID), voice v in talker cache slot max_batch + v with prefix tiles of its own.  Each extra voice
+ * costs one cache slot plus two tile copies: 2 * layers * kv_heads * head_dim * 2 bytes * (max_positions + 32 * ceil(max_positions
+ * / 32) [the tiles, head_dim 128 only]) - INTEGRATION.md works the figure out.  With max_voices 1 nothing is allocated that was
+ * not before.
+ *   rt_voice_capacity  max_voices.
+ *   rt_voice_select    the entry that rt_model_set_voice, rt_model_set_voice_pcm, rt_voice_prefix_len, rt_voice_blob_bytes,
+ *                      rt_voice_export and rt_voice_import act on, and the voice of every item of an rt_generate without item
+ *                      voices.  Entry 0 until a caller selects another; host bookkeeping only, nothing is copied.
+ *   rt_voice_clear     forgets an entry (its prefix length becomes 0: not set).
+ *   rt_generate_item_voices  a voice per item for the NEXT rt_generate / rt_generate_begin, which consumes the array (the call after
+ *                      it is a plain one again).  An item's codes are bit for bit the codes it gets alone with that voice selected.
+ *                      Rows are dealt in 4-row blocks of one voice (rt_debug_voice_row_plan), so a run may decode on fewer busy rows
+ *                      than a single-voice one.  Teacher forcing and the logit traces are refused with RT_ERR_UNSUPPORTED when the
+ *                      items name more than one voice.
+ * RT_ERR_INVALID: a voice outside 0 .. max_voices - 1, an item voice that is not set, n_items different from the generate call's.
+ * RT_ERR_STATE: any of them while a generation is in flight. */
+RT_API int32_t rt_voice_capacity(rt_model* m);
+RT_API int rt_voice_select(rt_model* m, int32_t voice);
+RT_API int rt_voice_clear(rt_model* m, int32_t voice);
+RT_API int rt_generate_item_voices(rt_model* m, const int32_t* h_voice, int32_t n_items);
+/* Of the last rt_generate: how many times a 4-row block whose rows had all come free was handed to another voice. */
+RT_API int64_t rt_generate_revoiced_blocks(rt_model* m);
 
 /* n_items may exceed the model's max_batch: the first max_batch items start on the decode rows, the others wait in a queue
  * (in array order - put the longest first) and take over a row as soon as the host has seen its item finish: the new item's

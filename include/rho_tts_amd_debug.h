@@ -75,6 +75,28 @@ RT_API int rt_debug_attention_fused(rt_ctx* ctx, const float* d_qkv, int32_t M, 
                                     const float* d_q_norm_w, const float* d_k_norm_w, float eps, const float* d_cos, const float* d_sin,
                                     const int32_t* d_row_slot, const int32_t* d_row_pos, int32_t pos_add, void* d_k, void* d_v,
                                     int32_t slots, int32_t max_pos, int32_t prefix_slot, int32_t prefix_len, void* d_out_bf16);
+/* The same launch as a decode step of a multi-voice generation takes it (rt_generate_item_voices): the M rows are cut into 4-row
+ * blocks, block b reads the prefix of voice h_block_voice[b] (host array, ceil(M / 4) entries), whose h_prefix_len[v] rows sit in
+ * cache slot slots - n_voices + v.  Every block takes the form its voice takes alone: the matrix-core one (head_dim 128, 2 query
+ * heads per kv head, >= 64 prefix rows; the call builds the tiles per voice) in one launch over those blocks, the vector one in a
+ * second launch over the rows of the others.  d_row_slot / d_row_pos are required.  RT_ERR_INVALID before any launch: M outside
+ * 1..128, n_voices outside 1..8, a block voice outside the voices, a prefix longer than max_pos. */
+RT_API int rt_debug_attention_fused_voices(rt_ctx* ctx, const float* d_qkv, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                                           const float* d_q_norm_w, const float* d_k_norm_w, float eps, const float* d_cos, const float* d_sin,
+                                           const int32_t* d_row_slot, const int32_t* d_row_pos, int32_t pos_add, void* d_k, void* d_v,
+                                           int32_t slots, int32_t max_pos, int32_t n_voices, const int32_t* h_prefix_len,
+                                           const int32_t* h_block_voice, void* d_out_bf16);
+/* The row plan of a multi-voice generation as host arithmetic (no GPU is touched).  Rows are cut into 4-row blocks and a block holds
+ * rows of one voice: an item takes the lowest free row of a block of its voice, else the first row of the lowest block whose rows are
+ * all free (the block is re-voiced), else it waits - and with it every later item of its voice; array order is kept within a voice.
+ *   first != 0: the first wave of n_items items (h_voice[i] in 0..7) on at most max_rows (1..128) rows.  Outputs h_row_item [max_rows]
+ *               (item on the row, -1 free), h_block_voice [ceil(max_rows / 4)] (-1: none), h_placed [n_items]; returns the run's rows:
+ *               max_rows while items wait, else the last occupied row + 1.  One distinct voice gives item b on row b.
+ *   first == 0: a hand-over on a run of max_rows rows: the three arrays hold the state (freed rows set to -1 by the caller) and are
+ *               updated; returns the number of items placed.  h_revoiced (optional): blocks that changed from one voice to another.
+ * A bad argument returns -1. */
+RT_API int rt_debug_voice_row_plan(const int32_t* h_voice, int32_t n_items, int32_t max_rows, int32_t first, int32_t* h_row_item,
+                                   int32_t* h_block_voice, int32_t* h_placed, int32_t* h_revoiced);
 /* Prompt-prefill attention behind a shared prefix: q [M][heads][d] f32 (normed, roped), row r = sequence slot row_slot[r] at position
  * row_pos[r], whose K / V rows up to that position are already in the caches; positions < prefix_len are read from prefix_slot.
  * mode 0: the vector-unit kernel, 1: the matrix-core form the model uses for prompt rows (head_dim 128, 2 query heads per kv head,
@@ -398,6 +420,12 @@ RT_API int rt_bench_sample(rt_ctx* ctx, const float* d_logits, int32_t M, int32_
  * prefix_len positions read from a shared prefix slot (shared = 1) or from each row's own slot (0), cycling through `layers`
  * cache regions; zeros as operands.  M <= 128; above 64 rows the launch is frame-indexed as a decode step's is, and shared | 2
  * runs the same rows as blocks of 64. */
+/* The same launch single-voice against multi-voice (tools/bench_voices.py): M rows behind n_voices (1..8) prefixes of prefix_len rows
+ * each; *us_single = every row behind voice 0 by the single-voice kernel, *us_multi = block b behind voice b % n_voices by the
+ * multi-voice kernel reading the block table; the form (vector unit / matrix cores) is the one rt_debug_tune 1500 / 1501 selects for
+ * both.  Two alternating passes of `iters` back-to-back launches each after a warm-up; microseconds per launch. */
+RT_API int rt_bench_attention_fused_voices(rt_ctx* ctx, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t prefix_len,
+                                           int32_t own_len, int32_t n_voices, int32_t layers, int32_t iters, double* us_single, double* us_multi);
 RT_API int rt_bench_attention_fused(rt_ctx* ctx, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t prefix_len, int32_t own_len,
                                     int32_t shared, int32_t layers, int32_t iters, double* avg_us);
 RT_API int rt_bench_gemm_skinny(rt_ctx* ctx, int32_t M, int32_t N, int32_t K, int32_t split_k, int32_t n_mats, int32_t iters,

@@ -74,6 +74,14 @@ def declare(lib: C.CDLL) -> None:
     lib.rt_voice_blob_bytes.argtypes = [vp]
     lib.rt_voice_export.argtypes = [vp, vp, i64]
     lib.rt_voice_import.argtypes = [vp, i32, vp, i64]
+    # the voice bank
+    lib.rt_voice_capacity.argtypes = [vp]
+    lib.rt_voice_select.argtypes = [vp, i32]
+    lib.rt_voice_clear.argtypes = [vp, i32]
+    lib.rt_generate_item_voices.argtypes = [vp, C.POINTER(i32), i32]
+    lib.rt_generate_revoiced_blocks.restype = i64
+    lib.rt_generate_revoiced_blocks.argtypes = [vp]
+    lib.rt_debug_voice_row_plan.argtypes = [C.POINTER(i32), i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.rt_generate.argtypes = [vp, C.POINTER(RtGenerateArgs)]
     lib.rt_generate_stats.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4
     lib.rt_generate_begin.argtypes = [vp, C.POINTER(RtGenerateArgs)]
@@ -92,6 +100,8 @@ def declare(lib: C.CDLL) -> None:
     f32 = C.c_float
     lib.rt_debug_gemm_col.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp]
     lib.rt_debug_attention_fused.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp]
+    lib.rt_debug_attention_fused_voices.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, vp, vp, vp, vp, i32, vp, vp, i32, i32, i32,
+                                                    C.POINTER(i32), C.POINTER(i32), vp]
     lib.rt_debug_attention_prefill.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.rt_debug_sample.argtypes = [vp, vp, i32, i32, C.POINTER(RtSampling), C.c_uint64, i32, i32, i32, i32, vp, vp]
     # the row kernels and the tiled GEMM's epilogue on their own (tests/test_rowops_gpu.py, tests/test_gemm_epilogue_gpu.py)
@@ -122,8 +132,9 @@ def _stack(d: TransformerDims) -> StackDims:
     return StackDims(d.hidden, d.layers, d.heads, d.kv_heads, d.head_dim, d.inter, d.rope_theta, d.rms_eps)
 
 
-def rt_config(cfg: ModelConfig, max_batch: int, max_positions: int, max_codec_frames: int) -> RtModelConfig:
+def rt_config(cfg: ModelConfig, max_batch: int, max_positions: int, max_codec_frames: int, max_voices: int = 1) -> RtModelConfig:
     c = RtModelConfig()
+    c.reserved[0] = 0 if max_voices == 1 else int(max_voices)      # (0 means 1: what every caller from before the bank passes)
     c.talker, c.predictor, c.codec_tf = _stack(cfg.talker), _stack(cfg.predictor), _stack(codec_transformer_dims(cfg))
     c.codec_vocab, c.predictor_vocab, c.text_vocab = cfg.codec_vocab, cfg.predictor_vocab, cfg.text_vocab
     c.text_hidden, c.n_groups = cfg.text_hidden, cfg.n_groups
@@ -278,15 +289,16 @@ class NativeModel:
     """One ``rt_model``: weights, KV caches and workspaces of a Qwen3-TTS-shaped model in HBM."""
 
     def __init__(self, ctx, cfg: ModelConfig, max_batch: int = 32, max_positions: Optional[int] = None,
-                 max_codec_frames: Optional[int] = None):
+                 max_codec_frames: Optional[int] = None, max_voices: int = 1):
         self.ctx, self.cfg, self.lib = ctx, cfg, ctx.lib
         self.max_batch = max_batch
         self.max_positions = max_positions or cfg.max_positions
         self.max_codec_frames = max_codec_frames or (cfg.codec.chunk_frames + cfg.codec.left_context_frames)
-        self.rt_cfg = rt_config(cfg, max_batch, self.max_positions, self.max_codec_frames)
+        self.rt_cfg = rt_config(cfg, max_batch, self.max_positions, self.max_codec_frames, max_voices)
         h = C.c_void_p()
         ctx.check(self.lib.rt_model_create(ctx.handle, C.byref(self.rt_cfg), C.byref(h)), "rt_model_create")
         self.handle = h
+        self.selected_voice = 0                                # the bank entry select_voice chose last
         self._keep = []
 
     def close(self):
@@ -441,6 +453,33 @@ class NativeModel:
         torch.cuda.current_stream(blob.device).synchronize()
         self.ctx.check(self.lib.rt_voice_import(self.handle, prefix_len, C.c_void_p(blob.data_ptr()), blob.numel() * 2), "rt_voice_import")
 
+    # ------------------------------------------------------------------ the voice bank
+    def voice_capacity(self) -> int:
+        """Entries of the model's voice bank (``max_voices``)."""
+        return int(self.lib.rt_voice_capacity(self.handle))
+
+    def select_voice(self, voice: int) -> None:
+        """The bank entry that ``set_voice`` / ``set_voice_pcm`` / ``prefix_len`` / ``export_voice`` / ``import_voice`` act on and that a
+        ``generate`` without ``voices`` speaks with.  Entry 0 until another is selected; nothing is copied."""
+        self.ctx.check(self.lib.rt_voice_select(self.handle, int(voice)), "rt_voice_select")
+        self.selected_voice = int(voice)
+
+    def clear_voice(self, voice: int) -> None:
+        self.ctx.check(self.lib.rt_voice_clear(self.handle, int(voice)), "rt_voice_clear")
+
+    def _item_voices(self, voices, n_items: int) -> None:
+        """Hand the next rt_generate / rt_generate_begin a bank entry per item (``None``: every item speaks with the selected one)."""
+        if voices is None:
+            return
+        v = [int(x) for x in voices]
+        if len(v) != n_items:
+            raise ValueError(f"{len(v)} voices for {n_items} items")
+        self.ctx.check(self.lib.rt_generate_item_voices(self.handle, (C.c_int32 * max(1, len(v)))(*v), len(v)), "rt_generate_item_voices")
+
+    def revoiced_blocks(self) -> int:
+        """Of the last ``generate``: how often a 4-row block whose rows had all come free was handed to another voice."""
+        return int(self.lib.rt_generate_revoiced_blocks(self.handle))
+
     # ------------------------------------------------------------------ decode
     def _generate_args(self, texts, max_frames, talker, predictor, seed, item_ids, ignore_eos, min_frames, forced_codes, cancel_flag, max_rows):
         """rt_generate_args for a list of token-id lists; returns (args, objects that must stay alive while the call runs)."""
@@ -482,7 +521,10 @@ class NativeModel:
 
     def generate(self, texts: Sequence[Sequence[int]], max_frames: Sequence[int], talker=None, predictor=None, seed: int = 789,
                  item_ids: Optional[Sequence[int]] = None, ignore_eos: bool = True, min_frames: int = 2,
-                 forced_codes: Optional[Sequence[torch.Tensor]] = None, trace: bool = False, cancel_flag=None, max_rows: int = 0):
+                 forced_codes: Optional[Sequence[torch.Tensor]] = None, trace: bool = False, cancel_flag=None, max_rows: int = 0,
+                 voices: Optional[Sequence[int]] = None):
+        """``voices``: a bank entry per item (``select_voice`` numbering).  An item's codes are bit for bit the codes it gets alone with
+        that voice selected."""
         c = self.cfg
         B, G = len(texts), c.n_groups
         a, keep = self._generate_args(texts, max_frames, talker, predictor, seed, item_ids, ignore_eos, min_frames, forced_codes, cancel_flag, max_rows)
@@ -499,6 +541,7 @@ class NativeModel:
             torch.cuda.synchronize()
             a.d_trace_talker = tr["talker"].data_ptr()
             a.d_trace_predictor = tr["predictor"].data_ptr()
+        self._item_voices(voices, B)
         self.ctx.check(self.lib.rt_generate(self.handle, C.byref(a)), "rt_generate")
         out, off = [], 0
         import numpy as np
@@ -511,9 +554,10 @@ class NativeModel:
 
     # ---- the same generation in pieces (rt_generate_begin / _step / _peek / _end): sub-segment streaming
     def generate_begin(self, texts, max_frames, talker=None, predictor=None, seed: int = 789, item_ids=None, ignore_eos: bool = True,
-                       min_frames: int = 2, cancel_flag=None, max_rows: int = 0) -> None:
+                       min_frames: int = 2, cancel_flag=None, max_rows: int = 0, voices: Optional[Sequence[int]] = None) -> None:
         a, keep = self._generate_args(texts, max_frames, talker, predictor, seed, item_ids, ignore_eos, min_frames, None, cancel_flag, max_rows)
         self._run_keep = (keep, [int(v) for v in max_frames])
+        self._item_voices(voices, len(texts))
         self.ctx.check(self.lib.rt_generate_begin(self.handle, C.byref(a)), "rt_generate_begin")
 
     def generate_step(self, n_frames: int):

@@ -15,15 +15,18 @@ typedef __attribute__((ext_vector_type(4))) unsigned u4_t;
 // the cache row (slot, pos) - then attends over the cache including the row it has just written.
 // LO (codec pre-transformer, which has to stay float32-faithful for the waveform RMSE bar): the cache holds K/V as hi + lo
 // bf16 planes (value = hi + lo, ~16 mantissa bits) and the output is written in float32.
-template <int D, int REP, bool FUSED, int NW, bool LO = false>
+// MV (FUSED decode rows of a multi-voice run): workgroup y takes row vrows[y] (-1: none - the launch covers the rows whose voice takes
+// this form) and reads the prefix slot and length of the row's 4-row block from vtable instead of the launch's one pair.
+template <int D, int REP, bool FUSED, int NW, bool LO = false, bool MV = false>
 __global__ __launch_bounds__(NW * 64) void k_attention(const float* __restrict__ q, int heads, int kv_heads,
                                                    const int32_t* __restrict__ row_slot, const int32_t* __restrict__ row_pos,
                                                    int pos_add, int window, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
                                                    int max_pos, bf16_t* __restrict__ out, const float* __restrict__ qw,
                                                    const float* __restrict__ kw, float eps, const float* __restrict__ cosT,
-                                                   const float* __restrict__ sinT, const int32_t* __restrict__ frame_ptr, int out_tiled, int prefix_slot,
-                                                   int prefix_len, const bf16_t* __restrict__ kc_lo, const bf16_t* __restrict__ vc_lo,
-                                                   float* __restrict__ out_f32, int slot_base, int pair_n) {
+                                                   const float* __restrict__ sinT, const int32_t* __restrict__ frame_ptr, int out_tiled, int prefix_slot_1,
+                                                   int prefix_len_1, const bf16_t* __restrict__ kc_lo, const bf16_t* __restrict__ vc_lo,
+                                                   float* __restrict__ out_f32, int slot_base, int pair_n,
+                                                   const VoiceBlock* __restrict__ vtable, const int32_t* __restrict__ vrows) {
     constexpr int LPP = D / 8;        // lanes per cached position
     constexpr int PPW = 64 / LPP;     // positions per wave step
     // positions in flight per lane.  (8 - a talker row's whole ~500-position context in ONE batch requested before the prologue,
@@ -41,7 +44,16 @@ __global__ __launch_bounds__(NW * 64) void k_attention(const float* __restrict__
 
     // x = kv head (fastest): workgroups are dealt round-robin over the 8 XCDs, so with 8 kv heads every XCD's L2 holds
     // ONE head's shared-prefix K/V and serves it to all the rows of that head
-    const int kh = blockIdx.x, row = blockIdx.y;
+    const int kh = blockIdx.x;
+    int row = blockIdx.y, prefix_slot = prefix_slot_1, prefix_len = prefix_len_1;
+    if constexpr (MV) {
+        // two dependent scalar loads in front of everything the row decides; the table entry is requested as soon as the row is
+        // known and is first needed by the K / V addresses, behind the prologue's own requests
+        row = vrows[blockIdx.y];
+        if (row < 0) return;
+        prefix_slot = vtable[row >> 2].prefix_slot;
+        prefix_len = vtable[row >> 2].prefix_len;
+    }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int sub = lane % LPP, pg = lane / LPP;
     // FUSED: the wave's first head vector (q / k / v of the new position) and its norm weights depend on the row only - they are
@@ -264,28 +276,30 @@ __global__ __launch_bounds__(NW * 64) void k_attention(const float* __restrict__
 }
 
 struct FusedArgs { const float *qw, *kw, *cosT, *sinT; float eps; const int32_t* frame_ptr; int out_tiled; int prefix_slot, prefix_len;
-                   const bf16_t *kc_lo = nullptr, *vc_lo = nullptr; float* out_f32 = nullptr; int slot_base = 0; int pair_n = 0; };
+                   const bf16_t *kc_lo = nullptr, *vc_lo = nullptr; float* out_f32 = nullptr; int slot_base = 0; int pair_n = 0;
+                   const VoiceBlock* vtable = nullptr; const int32_t* vrows = nullptr; };
 
-template <int D, bool FUSED, int NW, bool LO = false>
+template <int D, bool FUSED, int NW, bool LO = false, bool MV = false>
 int dispatch_rep(rt_ctx* ctx, int rep, dim3 grid, const float* q, int heads, int kv_heads, const int32_t* rs, const int32_t* rp,
                  int pos_add, int window, bf16_t* kc, bf16_t* vc, int max_pos, bf16_t* out, const FusedArgs& f) {
     switch (rep) {
-        case 1: hipLaunchKernelGGL((k_attention<D, 1, FUSED, NW, LO>), grid, dim3(NW * 64), 0, ctx->stream, q, heads, kv_heads, rs, rp, pos_add, window, kc, vc, max_pos, out, f.qw, f.kw, f.eps, f.cosT, f.sinT, f.frame_ptr, f.out_tiled, f.prefix_slot, f.prefix_len, f.kc_lo, f.vc_lo, f.out_f32, f.slot_base, f.pair_n); break;
-        case 2: hipLaunchKernelGGL((k_attention<D, 2, FUSED, NW, LO>), grid, dim3(NW * 64), 0, ctx->stream, q, heads, kv_heads, rs, rp, pos_add, window, kc, vc, max_pos, out, f.qw, f.kw, f.eps, f.cosT, f.sinT, f.frame_ptr, f.out_tiled, f.prefix_slot, f.prefix_len, f.kc_lo, f.vc_lo, f.out_f32, f.slot_base, f.pair_n); break;
-        case 4: hipLaunchKernelGGL((k_attention<D, 4, FUSED, NW, LO>), grid, dim3(NW * 64), 0, ctx->stream, q, heads, kv_heads, rs, rp, pos_add, window, kc, vc, max_pos, out, f.qw, f.kw, f.eps, f.cosT, f.sinT, f.frame_ptr, f.out_tiled, f.prefix_slot, f.prefix_len, f.kc_lo, f.vc_lo, f.out_f32, f.slot_base, f.pair_n); break;
+        case 1: hipLaunchKernelGGL((k_attention<D, 1, FUSED, NW, LO, MV>), grid, dim3(NW * 64), 0, ctx->stream, q, heads, kv_heads, rs, rp, pos_add, window, kc, vc, max_pos, out, f.qw, f.kw, f.eps, f.cosT, f.sinT, f.frame_ptr, f.out_tiled, f.prefix_slot, f.prefix_len, f.kc_lo, f.vc_lo, f.out_f32, f.slot_base, f.pair_n, f.vtable, f.vrows); break;
+        case 2: hipLaunchKernelGGL((k_attention<D, 2, FUSED, NW, LO, MV>), grid, dim3(NW * 64), 0, ctx->stream, q, heads, kv_heads, rs, rp, pos_add, window, kc, vc, max_pos, out, f.qw, f.kw, f.eps, f.cosT, f.sinT, f.frame_ptr, f.out_tiled, f.prefix_slot, f.prefix_len, f.kc_lo, f.vc_lo, f.out_f32, f.slot_base, f.pair_n, f.vtable, f.vrows); break;
+        case 4: hipLaunchKernelGGL((k_attention<D, 4, FUSED, NW, LO, MV>), grid, dim3(NW * 64), 0, ctx->stream, q, heads, kv_heads, rs, rp, pos_add, window, kc, vc, max_pos, out, f.qw, f.kw, f.eps, f.cosT, f.sinT, f.frame_ptr, f.out_tiled, f.prefix_slot, f.prefix_len, f.kc_lo, f.vc_lo, f.out_f32, f.slot_base, f.pair_n, f.vtable, f.vrows); break;
         default: return rt_fail(ctx, RT_ERR_UNSUPPORTED, "attention: heads/kv_heads = %d unsupported (1, 2, 4)", rep);
     }
     RT_HIP(ctx, hipGetLastError());
     return RT_OK;
 }
 
-template <bool FUSED>
+template <bool FUSED, bool MV = false>
 int attention_any(rt_ctx* ctx, const float* q, int M, int heads, int kv_heads, int head_dim, const int32_t* row_slot, const int32_t* row_pos,
                   int pos_add, int window, const KvCache& kv, int layer, bf16_t* out, const FusedArgs& f0) {
     if (M <= 0) return RT_OK;
     FusedArgs f = f0;
     f.prefix_slot = kv.prefix_slot;
     f.prefix_len = kv.prefix_slot >= 0 ? kv.prefix_len : 0;
+    if (MV) { f.vtable = kv.voices->blocks; f.vrows = kv.voices->vec_rows; }      // (the launch's own pair is not read)
     if (heads % kv_heads) return rt_fail(ctx, RT_ERR_INVALID, "attention: heads %d not a multiple of kv_heads %d", heads, kv_heads);
     const int rep = heads / kv_heads;
     bf16_t* kc = kv.k + layer * kv.layer_stride();
@@ -312,8 +326,8 @@ int attention_any(rt_ctx* ctx, const float* q, int M, int heads, int kv_heads, i
     const bool rows_ok = M * kv_heads <= 512 || (f0.frame_ptr && M > 64 && kv_heads <= 512);
     const bool wide = (FUSED || f0.frame_ptr) && rows_ok && kv.max_pos > 64 && (window <= 0 || window > 256);
 #define RT_ATT(DD)                                                                                                                   \
-    return wide ? dispatch_rep<DD, FUSED, 16>(ctx, rep, grid, q, heads, kv_heads, row_slot, row_pos, pos_add, window, kc, vc, kv.max_pos, out, f) \
-                : dispatch_rep<DD, FUSED, 4>(ctx, rep, grid, q, heads, kv_heads, row_slot, row_pos, pos_add, window, kc, vc, kv.max_pos, out, f)
+    return wide ? dispatch_rep<DD, FUSED, 16, false, MV>(ctx, rep, grid, q, heads, kv_heads, row_slot, row_pos, pos_add, window, kc, vc, kv.max_pos, out, f) \
+                : dispatch_rep<DD, FUSED, 4, false, MV>(ctx, rep, grid, q, heads, kv_heads, row_slot, row_pos, pos_add, window, kc, vc, kv.max_pos, out, f)
     switch (head_dim) {
         case 32: RT_ATT(32);
         case 64: RT_ATT(64);
@@ -348,6 +362,21 @@ int launch_attention_fused(rt_ctx* ctx, const float* qkv, int M, int heads, int 
     // pair_n: rows [pair_n, 2 pair_n) of the launch sit one position behind rows [0, pair_n) of the same slots (see the kernel)
     if (pair_n && (pair_n < 0 || M != 2 * pair_n || !row_slot || !row_pos || heads % kv_heads || heads / kv_heads > 2))
         return rt_fail(ctx, RT_ERR_INVALID, "attention: paired rows need M = 2 x %d rows with slot and position arrays and <= 2 query heads per kv head", pair_n);
+    // a multi-voice decode step (KvCache::voices): every 4-row block reads the prefix of its own voice and takes the form its voice takes
+    // alone - up to two launches, the matrix-core one over the blocks of voices with >= 64 prefix rows and the vector one over the
+    // rows of the others.  Both grids cover all the rows (a graph captured once serves every re-voicing); a workgroup whose list
+    // entry is -1 returns at once.  The wave split of the vector form is chosen from M as a single-voice step of these rows does.
+    if (kv.voices) {
+        const VoiceTable& vt = *kv.voices;
+        if (pair_n || !row_slot || !row_pos || window > 0 || M != vt.rows || (M + 3) / 4 != vt.n_blocks)
+            return rt_fail(ctx, RT_ERR_INVALID, "attention: a multi-voice step needs slot and position arrays for the %d rows of its table", vt.rows);
+        if (vt.any_mfma)
+            RT_TRY(launch_attention_prefix_mfma(ctx, qkv, M, heads, kv_heads, q_norm_w, k_norm_w, eps, rope_cos, rope_sin, row_slot, row_pos, pos_add, kv, layer,
+                                                out, frame_ptr, out_tiled));
+        if (!vt.any_vec) return RT_OK;
+        FusedArgs f{q_norm_w, k_norm_w, rope_cos, rope_sin, eps, frame_ptr, out_tiled, -1, 0, nullptr, nullptr, nullptr, 0, 0};
+        return attention_any<true, true>(ctx, qkv, M, heads, kv_heads, head_dim, row_slot, row_pos, pos_add, window, kv, layer, out, f);
+    }
     if (!pair_n && row_slot && row_pos && attention_mfma_ok(M, heads, kv_heads, head_dim, window, kv))
         return launch_attention_prefix_mfma(ctx, qkv, M, heads, kv_heads, q_norm_w, k_norm_w, eps, rope_cos, rope_sin, row_slot, row_pos, pos_add, kv, layer,
                                             out, frame_ptr, out_tiled);

@@ -52,10 +52,16 @@ struct MfmaAttnArgs {
     const int32_t* frame_ptr; int out_tiled; int prefix_slot, prefix_len;
     int block_prefix = 0;             // prefill of the prefix slot ITSELF (consecutive rows of one slot, causal): the keys in front of a
                                       // workgroup's first row play the part of the shared prefix, read from the tiles of the same slot
+    // MV only (a multi-voice decode step): workgroup y takes the 4-row block vblocks[y] (-1: none) and reads the prefix length and the
+    // tiles of the block's voice from vtable; kt / vt / prefix_len above are not read
+    const VoiceBlock* vtable = nullptr;
+    const int32_t* vblocks = nullptr;
+    int64_t vlayer_off = 0;           // elements from a voice's layer-0 tiles to this layer's
 };
 
-template <int ROWS, int NW, bool PREFILL>
+template <int ROWS, int NW, bool PREFILL, bool MV = false>
 __global__ __launch_bounds__(NW * 64) void k_attn_prefix_mfma(MfmaAttnArgs g) {
+    static_assert(!MV || (ROWS == 4 && !PREFILL), "the multi-voice form is the four-row decode step");
     constexpr int QR = ROWS * REP;                                         // live query vectors of the 16 MFMA columns
     constexpr int WPR = NW / ROWS;                                         // waves per row for the rows' own positions
     static_assert(QR <= 16 && NW % ROWS == 0 && (PREFILL || NW >= 4 * ROWS), "wave layout");
@@ -69,7 +75,22 @@ __global__ __launch_bounds__(NW * 64) void k_attn_prefix_mfma(MfmaAttnArgs g) {
     __shared__ float s_part[NW][REP][LPP][10];                             // suffix partials per wave
     __shared__ int s_hi[ROWS];
 
-    const int kh = blockIdx.x, r0 = blockIdx.y * ROWS;
+    const int kh = blockIdx.x;
+    int r0 = blockIdx.y * ROWS;
+    const bf16_t* kt_base = g.kt;
+    const bf16_t* vt_base = g.vt;
+    int Lp = g.prefix_len;
+    if constexpr (MV) {
+        // workgroup-uniform scalar loads: the block, then its voice's entry.  The entry is requested here, in front of the prologue's
+        // vector loads (which need the block alone), and first read by the tile addresses behind them
+        const int ub = g.vblocks[blockIdx.y];
+        if (ub < 0) return;
+        r0 = ub * ROWS;
+        const VoiceBlock vb = g.vtable[ub];
+        Lp = vb.prefix_len;
+        kt_base = vb.kt + g.vlayer_off;
+        vt_base = vb.vt + g.vlayer_off;
+    }
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int heads = g.heads, kv_heads = g.kv_heads;
     const float scale = rsqrtf((float)D);
@@ -99,14 +120,13 @@ __global__ __launch_bounds__(NW * 64) void k_attn_prefix_mfma(MfmaAttnArgs g) {
     }
     // the wave's first prefix block is requested BEFORE the prologue: it depends on nothing the prologue produces, so its L2
     // round trip runs under the prologue's own loads and reductions
-    int Lp = g.prefix_len;
-    if (PREFILL && g.block_prefix) {                         // (uniform per workgroup; rows r0 .. r0 + ROWS - 1 sit at consecutive positions)
+    if (PREFILL && g.block_prefix) {                        // (uniform per workgroup; rows r0 .. r0 + ROWS - 1 sit at consecutive positions)
         Lp = g.row_pos[r0 < g.M ? r0 : g.M - 1] + g.pos_add + frame;
         if (Lp < 0) Lp = 0;
     }
     const int gq = lane >> 4, n16 = lane & 15;               // MFMA lane split: k-octet / row-or-column
-    const s8_t* ktp = reinterpret_cast<const s8_t*>(g.kt + (int64_t)kh * g.vt_stride) + lane;      // [block][tile 0..7][64 lanes] x 16 B
-    const s8_t* vtp = reinterpret_cast<const s8_t*>(g.vt + (int64_t)kh * g.vt_stride) + lane;
+    const s8_t* ktp = reinterpret_cast<const s8_t*>(kt_base + (int64_t)kh * g.vt_stride) + lane;      // [block][tile 0..7][64 lanes] x 16 B
+    const s8_t* vtp = reinterpret_cast<const s8_t*>(vt_base + (int64_t)kh * g.vt_stride) + lane;
     const int n_blk = (Lp + 31) >> 5;
     s8_t kf[2][4], vf[8];
     {
@@ -423,6 +443,14 @@ bool attention_mfma_ok(int M, int heads, int kv_heads, int head_dim, int window,
            kv.kt_prefix && (kv.prefix_len + 31) / 32 * 4096 <= kv.vt_stride && M >= 1;
 }
 
+// ... the same question for one voice of a bank (a prefix of prefix_len rows whose tiles exist): the form its rows take alone under
+// g_attn_mfma 0 and 1.  Under 2 (one row per workgroup, which has no multi-voice instantiation) a multi-voice step falls back to the
+// DEFAULT form, the vector unit, for every voice: its items then equal themselves alone under the shipped switches, not under 2.
+bool attention_mfma_voice_ok(int heads, int kv_heads, int head_dim, const KvCache& kv, int prefix_len) {
+    return g_attn_mfma == 1 && head_dim == D && kv.head_dim == D && heads == REP * kv_heads && kv.vt_prefix && kv.kt_prefix && prefix_len >= 64 &&
+           (prefix_len + 31) / 32 * 4096 <= kv.vt_stride;
+}
+
 int launch_attention_prefix_mfma(rt_ctx* ctx, const float* qkv, int M, int heads, int kv_heads, const float* q_norm_w, const float* k_norm_w, float eps,
                                  const float* rope_cos, const float* rope_sin, const int32_t* row_slot, const int32_t* row_pos, int pos_add,
                                  const KvCache& kv, int layer, bf16_t* out, const int32_t* frame_ptr, int out_tiled) {
@@ -438,6 +466,12 @@ int launch_attention_prefix_mfma(rt_ctx* ctx, const float* qkv, int M, int heads
     // re-read per row from L2 like the cache rows of the vector kernel, which the counters show is not what bounds it
     // (profiles/r04_pmc_attention.csv: 33 MB of L2 -> L1 reads in a 12.9-us launch); what the matrix cores remove is the vector unit's
     // 2.8 us of dot products and rescales over the 460 prefix keys.
+    // a multi-voice step: the four-row form over the blocks of the table's list, each on the tiles of its own voice
+    if (kv.voices) {
+        g.vtable = kv.voices->blocks; g.vblocks = kv.voices->mfma_blocks; g.vlayer_off = (int64_t)layer * kv_heads * kv.vt_stride;
+        g.kt = nullptr; g.vt = nullptr; g.prefix_slot = -1; g.prefix_len = 0;
+        hipLaunchKernelGGL((k_attn_prefix_mfma<4, 16, false, true>), dim3(kv_heads, kv.voices->n_blocks), dim3(16 * 64), 0, ctx->stream, g);
+    } else
     if (g_attn_mfma == 2) hipLaunchKernelGGL((k_attn_prefix_mfma<1, 16, false>), dim3(kv_heads, M), dim3(16 * 64), 0, ctx->stream, g);
     else hipLaunchKernelGGL((k_attn_prefix_mfma<4, 16, false>), dim3(kv_heads, (M + 3) / 4), dim3(16 * 64), 0, ctx->stream, g);
     RT_HIP(ctx, hipGetLastError());

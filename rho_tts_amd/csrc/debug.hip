@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "voice_plan.h"
 
 namespace {
 __global__ void k_touch(float* p, int n) {
@@ -282,6 +283,102 @@ int rt_debug_attention_fused(rt_ctx* ctx, const float* d_qkv, int32_t M, int32_t
     if (vt) (void)hipFree(vt);
     RT_HIP(ctx, se);
     return rc;
+}
+
+// The same launch as a multi-voice decode step takes it: the rows are cut into 4-row blocks, block b reads the prefix of voice
+// h_block_voice[b], whose rows [0, h_prefix_len[v]) sit in slot slots - n_voices + v.  The tiles of every voice that takes the matrix-core
+// form are built here, as the entry above builds them for its one prefix.
+int rt_debug_attention_fused_voices(rt_ctx* ctx, const float* d_qkv, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim, const float* d_q_norm_w,
+                                    const float* d_k_norm_w, float eps, const float* d_cos, const float* d_sin, const int32_t* d_row_slot,
+                                    const int32_t* d_row_pos, int32_t pos_add, void* d_k, void* d_v, int32_t slots, int32_t max_pos, int32_t n_voices,
+                                    const int32_t* h_prefix_len, const int32_t* h_block_voice, void* d_out_bf16) {
+    if (!ctx || !d_qkv || !d_cos || !d_sin || !d_k || !d_v || !d_out_bf16 || !d_row_slot || !d_row_pos || !h_prefix_len || !h_block_voice)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_attention_fused_voices: null argument");
+    if (M < 1 || M > 128 || n_voices < 1 || n_voices > 8 || slots < n_voices || heads < 1 || kv_heads < 1 || heads % kv_heads || max_pos < 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_attention_fused_voices: bad shape");
+    const int n_blocks = (M + 3) / 4;
+    for (int v = 0; v < n_voices; ++v)
+        if (h_prefix_len[v] < 0 || h_prefix_len[v] > max_pos) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_attention_fused_voices: bad prefix length");
+    for (int b = 0; b < n_blocks; ++b)
+        if (h_block_voice[b] < 0 || h_block_voice[b] >= n_voices) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_attention_fused_voices: block %d names voice %d of %d", b, h_block_voice[b], n_voices);
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    KvCache kv;
+    kv.k = (bf16_t*)d_k; kv.v = (bf16_t*)d_v; kv.layers = 1; kv.slots = slots; kv.kv_heads = kv_heads; kv.max_pos = max_pos; kv.head_dim = head_dim;
+    bf16_t* tiles = nullptr;
+    void* d_tab = nullptr;
+    auto cleanup = [&]() { if (tiles) (void)hipFree(tiles); if (d_tab) (void)hipFree(d_tab); };
+    int longest = 0;
+    for (int v = 0; v < n_voices; ++v) longest = std::max(longest, h_prefix_len[v]);
+    const int64_t per_voice = (int64_t)kv_heads * ((longest + 31) / 32 * 4096);
+    if (head_dim == 128 && longest > 0) {
+        kv.vt_stride = (longest + 31) / 32 * 4096;
+        RT_HIP(ctx, hipMalloc((void**)&tiles, (size_t)2 * n_voices * per_voice * 2));
+        for (int v = 0; v < n_voices; ++v) {
+            if (h_prefix_len[v] < 1) continue;
+            kv.kt_prefix = tiles + (int64_t)2 * v * per_voice; kv.vt_prefix = kv.kt_prefix + per_voice; kv.prefix_slot_alloc = slots - n_voices + v;
+            const int rt = launch_transpose_prefix_v(ctx, kv, h_prefix_len[v]);
+            if (rt) { cleanup(); return rt; }
+        }
+    }
+    std::vector<VoiceBlock> blocks(n_blocks);
+    std::vector<int32_t> lists(n_blocks + M, -1);              // [the matrix-core launch's blocks][the vector launch's rows]
+    VoiceTable vt;
+    vt.rows = M; vt.n_blocks = n_blocks;
+    int n_mf = 0, n_vr = 0;
+    kv.kt_prefix = tiles; kv.vt_prefix = tiles;                // (what says that tiles exist; the launches read the table's pointers)
+    for (int b = 0; b < n_blocks; ++b) {
+        const int v = h_block_voice[b];
+        const bool mf = attention_mfma_voice_ok(heads, kv_heads, head_dim, kv, h_prefix_len[v]);
+        blocks[b].prefix_slot = slots - n_voices + v; blocks[b].prefix_len = h_prefix_len[v];
+        blocks[b].kt = mf ? tiles + (int64_t)2 * v * per_voice : nullptr; blocks[b].vt = mf ? blocks[b].kt + per_voice : nullptr;
+        if (mf) { lists[n_mf++] = b; vt.any_mfma = true; }
+        else { for (int r = 4 * b; r < std::min(M, 4 * b + 4); ++r) lists[n_blocks + n_vr++] = r; vt.any_vec = true; }
+    }
+    const size_t tab_bytes = blocks.size() * sizeof(VoiceBlock), list_bytes = lists.size() * 4;
+    hipError_t e = hipMalloc(&d_tab, tab_bytes + list_bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_tab, blocks.data(), tab_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy((char*)d_tab + tab_bytes, lists.data(), list_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { cleanup(); RT_HIP(ctx, e); }
+    vt.blocks = (const VoiceBlock*)d_tab;
+    vt.mfma_blocks = (const int32_t*)((char*)d_tab + tab_bytes);
+    vt.vec_rows = vt.mfma_blocks + n_blocks;
+    kv.voices = &vt;
+    const int rc = launch_attention_fused(ctx, d_qkv, M, heads, kv_heads, head_dim, d_q_norm_w, d_k_norm_w, eps, d_cos, d_sin, d_row_slot, d_row_pos,
+                                          pos_add, 0, kv, 0, (bf16_t*)d_out_bf16, nullptr, 0, 0);
+    const hipError_t se = hipStreamSynchronize(ctx->stream);
+    cleanup();
+    RT_HIP(ctx, se);
+    return rc;
+}
+
+// The row plan of a multi-voice generation (voice_plan.h) as host arithmetic; no GPU is touched.  first != 0: the first wave of
+// n_items items on at most max_rows rows - the three state arrays are outputs, the result is the run's row count.  first == 0: a
+// hand-over - max_rows is the run's row count, the arrays hold its state with the freed rows set to -1 in h_row_item; the waiting
+// items that find a row are placed and the result is their number.  h_revoiced (optional) receives the blocks that changed voice.
+int rt_debug_voice_row_plan(const int32_t* h_voice, int32_t n_items, int32_t max_rows, int32_t first, int32_t* h_row_item, int32_t* h_block_voice,
+                            int32_t* h_placed, int32_t* h_revoiced) {
+    if (!h_voice || !h_row_item || !h_block_voice || !h_placed || n_items < 1 || max_rows < 1 || max_rows > 128) return -1;
+    for (int i = 0; i < n_items; ++i) if (h_voice[i] < 0 || h_voice[i] >= 8) return -1;
+    voice_plan::State s;
+    int result = 0, revoiced = 0;
+    if (first) {
+        voice_plan::start(h_voice, n_items, max_rows, s, nullptr, nullptr);
+        result = s.rows;
+    } else {
+        s.rows = max_rows;
+        s.row_item.assign(h_row_item, h_row_item + max_rows);
+        s.block_voice.assign(h_block_voice, h_block_voice + s.n_blocks());
+        s.placed.resize(n_items);
+        for (int i = 0; i < n_items; ++i) s.placed[i] = h_placed[i] != 0;
+        for (int r = 0; r < max_rows; ++r) if (s.row_item[r] >= n_items) return -1;
+        result = voice_plan::place(h_voice, n_items, s, nullptr, nullptr, &revoiced);
+    }
+    for (int r = 0; r < max_rows; ++r) h_row_item[r] = r < s.rows ? s.row_item[r] : -1;
+    for (int b = 0; b < (max_rows + 3) / 4; ++b) h_block_voice[b] = b < s.n_blocks() ? s.block_voice[b] : -1;
+    for (int i = 0; i < n_items; ++i) h_placed[i] = s.placed[i];
+    if (h_revoiced) *h_revoiced = revoiced;
+    return result;
 }
 
 // Prompt-prefill attention behind a shared prefix slot (q prepared, K / V rows already in the caches): mode 0 = the vector-unit
@@ -990,6 +1087,108 @@ int rt_bench_attention_fused(rt_ctx* ctx, int32_t M, int32_t heads, int32_t kv_h
     *avg_us = (double)ms * 1e3 / iters;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     for (void* p : {(void*)kv.k, (void*)kv.v, (void*)qkv, (void*)cs, (void*)nw, (void*)pos, (void*)slot, (void*)out, (void*)tiles, (void*)frame}) if (p) (void)hipFree(p);
+    return rc;
+}
+
+// The decode step's attention launch back to back, single-voice kernel against multi-voice kernel (tools/bench_voices.py): M rows at
+// position prefix_len + own_len - 1 behind n_voices prefixes of prefix_len rows each (slots M ..), zeros as operands, cycling through
+// `layers` cache regions.  Single: every row behind voice 0 (launch_attention_fused as a single-voice run takes it).  Multi: block b
+// behind voice b % n_voices, read from the block table.  Two alternating passes of `iters` launches each; the mean per launch.
+int rt_bench_attention_fused_voices(rt_ctx* ctx, int32_t M, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t prefix_len, int32_t own_len,
+                                    int32_t n_voices, int32_t layers, int32_t iters, double* us_single, double* us_multi) {
+    if (!ctx || !us_single || !us_multi || M < 1 || M > 128 || heads < 1 || kv_heads < 1 || heads % kv_heads || prefix_len < 1 || own_len < 1 || layers < 1 ||
+        iters < 1 || n_voices < 1 || n_voices > 8 || (head_dim != 32 && head_dim != 64 && head_dim != 128))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_bench_attention_fused_voices: bad argument");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const int max_pos = std::max((prefix_len + own_len + 8 + 63) / 64 * 64, 128), slots = M + n_voices, width = (heads + 2 * kv_heads) * head_dim;
+    const int n_blocks = (M + 3) / 4;
+    KvCache kv;
+    kv.layers = layers; kv.slots = slots; kv.kv_heads = kv_heads; kv.max_pos = max_pos; kv.head_dim = head_dim;
+    const size_t cache_bytes = (size_t)layers * kv.layer_stride() * sizeof(bf16_t);
+    std::vector<void*> owned;
+    auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
+    auto alloc = [&](size_t bytes, bool zero) -> void* {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+        owned.push_back(p);
+        if (zero) (void)hipMemsetAsync(p, 0, bytes, ctx->stream);
+        return p;
+    };
+    kv.k = (bf16_t*)alloc(cache_bytes, true); kv.v = (bf16_t*)alloc(cache_bytes, true);
+    float* qkv = (float*)alloc((size_t)M * width * 4, true);
+    float* cs = (float*)alloc((size_t)max_pos * head_dim * 4, true);
+    float* nw = (float*)alloc((size_t)head_dim * 4, true);
+    int32_t* pos = (int32_t*)alloc((size_t)M * 4, false);
+    int32_t* slot = (int32_t*)alloc((size_t)M * 4, false);
+    int32_t* frame = (int32_t*)alloc(4, true);
+    bf16_t* out = (bf16_t*)alloc(((size_t)M + 31) / 32 * 32 * heads * head_dim * 2, false);
+    VoiceBlock* d_blocks = (VoiceBlock*)alloc((size_t)n_blocks * sizeof(VoiceBlock), false);
+    int32_t* d_lists = (int32_t*)alloc((size_t)(n_blocks + M) * 4, false);
+    if (!kv.k || !kv.v || !qkv || !cs || !nw || !pos || !slot || !frame || !out || !d_blocks || !d_lists) {
+        cleanup();
+        return rt_fail(ctx, RT_ERR_OOM, "rt_bench_attention_fused_voices: out of memory");
+    }
+    std::vector<int32_t> hp(M, prefix_len + own_len - 1), hs(M);
+    for (int i = 0; i < M; ++i) hs[i] = i;
+    hipError_t e = hipMemcpyAsync(pos, hp.data(), (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(slot, hs.data(), (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream);
+    // tiles per voice, where the matrix-core form takes them: [voice][K | V][layers][kv_heads][vt_stride]
+    bf16_t* tiles = nullptr;
+    int64_t per_plane = 0;
+    int rc = RT_OK;
+    if (e == hipSuccess && prefix_len >= 64 && head_dim == 128) {
+        kv.vt_stride = (prefix_len + 31) / 32 * 4096;
+        per_plane = (int64_t)layers * kv_heads * kv.vt_stride;
+        tiles = (bf16_t*)alloc((size_t)2 * n_voices * per_plane * 2, false);
+        if (!tiles) { cleanup(); return rt_fail(ctx, RT_ERR_OOM, "rt_bench_attention_fused_voices: out of memory"); }
+        for (int v = 0; v < n_voices && rc == RT_OK; ++v) {
+            kv.kt_prefix = tiles + 2 * v * per_plane; kv.vt_prefix = kv.kt_prefix + per_plane; kv.prefix_slot_alloc = M + v;
+            rc = launch_transpose_prefix_v(ctx, kv, prefix_len);
+        }
+    }
+    VoiceTable vt;
+    std::vector<VoiceBlock> blocks(n_blocks);
+    std::vector<int32_t> lists(n_blocks + M, -1);
+    vt.rows = M; vt.n_blocks = n_blocks; vt.blocks = d_blocks; vt.mfma_blocks = d_lists; vt.vec_rows = d_lists + n_blocks;
+    kv.kt_prefix = tiles; kv.vt_prefix = tiles ? tiles + per_plane : nullptr;        // voice 0: the single-voice launch's
+    const bool mf = attention_mfma_voice_ok(heads, kv_heads, head_dim, kv, prefix_len);
+    for (int b = 0, n_vr = 0; b < n_blocks; ++b) {
+        const int v = b % n_voices;
+        blocks[b].prefix_slot = M + v; blocks[b].prefix_len = prefix_len;
+        blocks[b].kt = mf ? tiles + 2 * v * per_plane : nullptr; blocks[b].vt = mf ? blocks[b].kt + per_plane : nullptr;
+        if (mf) lists[b] = b;
+        else for (int r = 4 * b; r < std::min(M, 4 * b + 4); ++r) lists[n_blocks + n_vr++] = r;
+    }
+    vt.any_mfma = mf; vt.any_vec = !mf;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blocks, blocks.data(), blocks.size() * sizeof(VoiceBlock), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    const float* cosT = cs;
+    const float* sinT = cs + (size_t)max_pos * head_dim / 2;
+    double total[2] = {0.0, 0.0};
+    for (int pass = 0; pass < 3 && rc == RT_OK && e == hipSuccess; ++pass)          // pass 0 warms both forms up and is not counted
+        for (int which = 0; which < 2 && rc == RT_OK && e == hipSuccess; ++which) {
+            kv.voices = which ? &vt : nullptr;
+            kv.prefix_slot = which ? -1 : M; kv.prefix_len = which ? 0 : prefix_len;
+            const int n = pass ? iters : layers;
+            e = hipEventRecord(ev[0], ctx->stream);
+            for (int i = 0; i < n && rc == RT_OK; ++i)
+                rc = launch_attention_fused(ctx, qkv, M, heads, kv_heads, head_dim, nw, nw, 1e-6f, cosT, sinT, slot, pos, 0, 0, kv, i % layers, out, frame, 1, -1);
+            if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            float ms = 0;
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+            if (pass) total[which] += ms;
+        }
+    *us_single = total[0] * 1e3 / (2.0 * iters);
+    *us_multi = total[1] * 1e3 / (2.0 * iters);
+    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    cleanup();
+    RT_HIP(ctx, e);
     return rc;
 }
 

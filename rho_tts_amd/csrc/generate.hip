@@ -2,6 +2,7 @@
 // Stands behind the third-party model call the reference makes at providers/qwen.py:247-258 (generate_custom_voice /
 // generate_voice_clone): text ids in, codec frames out.  Host-side orchestration only.
 #include "model_internal.h"
+#include "voice_plan.h"
 
 using namespace rtm;
 
@@ -62,9 +63,33 @@ struct rt_gen_run {
     int eos_every = 0;
     std::vector<int32_t> h_pos_b, h_off;
     std::vector<int64_t> h_items;
+    // voices (rt_generate_item_voices).  One distinct voice: the run is the run it always was, on that voice's prefix.  `multi`: the
+    // rows are planned in 4-row blocks of one voice (voice_plan.h), the prompts are prefilled one pass per voice, and the decode
+    // step's attention reads the prefix per block from a device table that a hand-over rewrites when a block changes voice.
+    std::vector<int32_t> voice;                            // [N] bank entry of each item
+    int sel_back = 0, run_voice = 0;                       // the selected entry to give back; the voice of a single-voice run
+    bool multi = false;
+    voice_plan::State plan;
+    int n_placed = 0;
+    int64_t n_revoiced = 0;
+    VoiceTable vtab;
+    std::vector<VoiceBlock> h_vblocks;
+    std::vector<int32_t> h_vlists;                         // [n_blocks] matrix-core blocks, then [B] vector rows (-1 padded)
+    VoiceBlock* d_vblocks = nullptr;
+    int32_t* d_vlists = nullptr;
 
+    bool none_waiting() const { return multi ? n_placed >= N : next_item >= N; }
+    void point_at(int v) {                                 // the talker cache's shared prefix <- bank entry v
+        m->voice_view(v);
+        m->talker.kv.prefix_slot = m->prefix_slot();
+        m->talker.kv.prefix_len = Lp = m->prefix_len;
+    }
+    int voice_tiles(int v);
+    void fill_voice_table();
+    int prefill_by_voice(const std::vector<int>& items, const std::vector<int>& rows, bool first, std::vector<int32_t>* last_of = nullptr);
+    int swap_in_voices(int t1);
     int init(const rt_generate_args* a);
-    int prefill(const std::vector<int>& items, const std::vector<int>& rows, bool first);
+    int prefill(const std::vector<int>& items, const std::vector<int>& rows, bool first, int r_off = 0, int i_off = 0);
     int enqueue_a(Lane& ln);
     int enqueue_b(Lane& ln);
     bool apply_frames(int upto);
@@ -80,6 +105,8 @@ void gen_release(rt_model* m) {
     if (!m->run) return;
     (void)hipStreamSynchronize(m->ctx->stream);
     for (auto& ln : m->run->lanes) if (ln.stream && ln.stream != m->ctx->stream) (void)hipStreamSynchronize(ln.stream);
+    m->voice_view(m->run->sel_back);
+    m->talker.kv.voices = nullptr;
     delete m->run;
     m->run = nullptr;
     m->rows128 = false;
@@ -104,6 +131,23 @@ int rt_gen_run::init(const rt_generate_args* a) {
     B = std::min(N, A.max_rows > 0 ? std::min(A.max_rows, c.max_batch) : c.max_batch);
     queued = N > B;
     if (!A.h_text_ids || !A.h_text_offsets || !A.h_max_frames || !A.h_item_ids) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: null array");
+    // ---- voices: the array of rt_generate_item_voices, else the selected entry for every item
+    if (voice.empty()) voice.assign(N, m->voice_sel);
+    if ((int)voice.size() != N) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: %d item voices for %d items", (int)voice.size(), N);
+    for (int b = 0; b < N; ++b) {
+        if (voice[b] < 0 || voice[b] >= m->max_voices || m->voice_len(voice[b]) < 1)
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: item %d asks for voice %d, which is not set (rt_model_set_voice)", b, voice[b]);
+        multi = multi || voice[b] != voice[0];
+    }
+    run_voice = voice[0];
+    if (multi) {
+        if (A.h_forced_codes || A.d_trace_talker || A.d_trace_predictor)
+            return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_generate: teacher forcing / logit traces with more than one voice among the items");
+        std::vector<int> it0, rw0;
+        n_placed = voice_plan::start(voice.data(), N, A.max_rows > 0 ? std::min(A.max_rows, c.max_batch) : c.max_batch, plan, &it0, &rw0);
+        B = plan.rows;
+        queued = n_placed < N;
+    }
     if (queued && (A.h_forced_codes || A.d_trace_talker || A.d_trace_predictor))
         return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: teacher forcing / logit traces need n_items <= max_batch (%d)", c.max_batch);
     // the caller's arrays need not outlive rt_generate_begin: keep copies
@@ -125,13 +169,18 @@ int rt_gen_run::init(const rt_generate_args* a) {
     }
     for (int i = 0; i < A.h_text_offsets[N]; ++i)
         if (A.h_text_ids[i] < 0 || A.h_text_ids[i] >= c.text_vocab) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: text id out of range");
-    Lp = m->prefix_len;
+    point_at(run_voice);                                   // (rt_generate_begin / _step give the selected entry back when they return)
     F_max = T_max;                                         // the longest single item
     // (a finished row keeps stepping until the host has seen its flag: up to `every` - 1 positions past its last frame)
-    if (Lp + max_suffix + F_max + (queued ? every : 0) + 1 > c.max_positions)
-        return rt_fail(ctx, RT_ERR_LENGTH, "rt_generate: prompt length %d + %d frames exceeds max_positions %d", Lp + max_suffix, F_max, c.max_positions);
+    // each item behind the prefix of its own voice (one voice: prefix + the longest suffix, as ever)
+    for (int b = 0; b < N; ++b) {
+        const int lp = m->voice_len(voice[b]), suffix = A.h_text_offsets[b + 1] - A.h_text_offsets[b] + 2;
+        if (lp + suffix + F_max + (queued ? every : 0) + 1 > c.max_positions)
+            return rt_fail(ctx, RT_ERR_LENGTH, "rt_generate: prompt length %d + %d frames exceeds max_positions %d", lp + suffix, F_max, c.max_positions);
+    }
     // frame-counter budget: list scheduling finishes within sum / rows + longest (each item charged its wait for the next check)
-    if (queued) T_max = (int)std::min<int64_t>(budget_sum / B + F_max + every + 1, (int64_t)1 << 24);
+    // (several voices: while an item waits every 4-row block has a busy row, else the item would take the free block)
+    if (queued) T_max = (int)std::min<int64_t>(budget_sum / (multi ? plan.n_blocks() : B) + F_max + every + 1, (int64_t)1 << 24);
     if (A.talker.do_sample && (A.talker.top_k < 1 || A.talker.top_k > 64 || !(A.talker.temperature > 0)))
         return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: sampling needs 1 <= top_k <= 64 and temperature > 0");
     if (A.predictor.do_sample && (A.predictor.top_k < 1 || A.predictor.top_k > 64 || !(A.predictor.temperature > 0)))
@@ -144,12 +193,10 @@ int rt_gen_run::init(const rt_generate_args* a) {
     }
 
     // ---- the voice prefix KV stays in its own slot: every sequence reads cache rows [0, Lp) from there (KvCache::prefix_slot)
-    m->talker.kv.prefix_slot = m->prefix_slot();
-    m->talker.kv.prefix_len = Lp;
-    if (g_attn_mfma && c.talker.head_dim == 128 && !m->prefix_tiles_valid) {
-        RT_TRY(launch_transpose_prefix_v(ctx, m->talker.kv, Lp));
-        m->prefix_tiles_valid = true;
-    }
+    // (point_at above; a multi-voice run re-points it per prefill pass and reads the prefix per block in the decode step)
+    for (int v = 0; v < m->max_voices; ++v)
+        if (std::find(voice.begin(), voice.end(), v) != voice.end()) RT_TRY(voice_tiles(v));
+    point_at(run_voice);
     // ---- suffix rows: [text tokens + tts_eos] x codec_pad, then (tts_pad, codec_bos).  Row 0 of the id / embedding buffers
     // is the projected tts_pad that every decode step adds to its input; the suffix rows of the items being prefilled follow.
     S_cap = queued ? B * max_suffix : n_suffix;
@@ -166,7 +213,19 @@ int rt_gen_run::init(const rt_generate_args* a) {
     pad_t = temb;
     RT_TRY(alloc_stack_ws(m, c.talker, S_cap, &w_prefill));
     RT_TRY(alloc_text_ws(m, S_cap + 1, &w_text));
-    {
+    if (multi) {
+        std::vector<int> items, rows;
+        for (int r = 0; r < B; ++r) if (plan.row_item[r] >= 0) { items.push_back(plan.row_item[r]); rows.push_back(r); }
+        std::vector<int32_t> last;                          // [i]: the row of x that holds the last prompt position of items[i]
+        RT_TRY(prefill_by_voice(items, rows, true, &last));
+        // the decode state is gathered per ROW: d_last <- the last prompt row of the row's item (a row without an item starts from
+        // the first item's state: it is parked, its frames are never read)
+        staging.emplace_back(new Staging());
+        std::vector<int32_t>& by_row = staging.back()->last;
+        by_row.assign(B, last[0]);
+        for (size_t i = 0; i < rows.size(); ++i) by_row[rows[i]] = last[i];
+        RT_HIP(ctx, hipMemcpyAsync(d_last, by_row.data(), B * 4, hipMemcpyHostToDevice, ctx->stream));
+    } else {
         std::vector<int> items(B), rows(B);
         for (int b = 0; b < B; ++b) { items[b] = b; rows[b] = b; }
         RT_TRY(prefill(items, rows, true));
@@ -211,7 +270,17 @@ int rt_gen_run::init(const rt_generate_args* a) {
     float* x_all = x;
 
     n_lanes = std::max(1, std::min(g_decode_lanes.load(), 8));
-    if (!col || m->prof || queued) n_lanes = 1;            // (per-launch profiling wants undisturbed launches)
+    if (!col || m->prof || queued || multi) n_lanes = 1;   // (per-launch profiling wants undisturbed launches; one block table per run)
+    if (multi && !col) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_generate: items with different voices need the column decode path");
+    // per ROW: position base and RNG stream (one voice: row b is item b; several: the plan's rows, free ones parked behind their block's prefix)
+    // (a multi-voice plan may have more rows than items: everything per row is sized by B and read through the row's item)
+    std::vector<int32_t> pos_row(B, 0);
+    std::vector<int64_t> ids_row(B, 0);
+    for (int r = 0; r < B; ++r) {
+        const int it = multi ? plan.row_item[r] : r;
+        pos_row[r] = it >= 0 ? P[it] : m->voice_len(plan.block_voice[r / voice_plan::BLOCK]);
+        ids_row[r] = it >= 0 ? A.h_item_ids[it] : 0;
+    }
     if (queued && !col) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_generate: queued items (n_items %d > %d rows) need the column decode path", N, B);
     while (n_lanes > 1 && B / n_lanes < 8) --n_lanes;      // a lane narrower than 8 rows only multiplies the weight traffic
     lanes.assign(n_lanes, Lane());
@@ -255,8 +324,8 @@ int rt_gen_run::init(const rt_generate_args* a) {
         for (int b = 0; b < n; ++b) { sl[b] = ln.b0 + b; sl[n + b] = ln.b0 + b; p2[b] = 0; p2[n + b] = 1; }
         RT_HIP(ctx, hipMemcpyAsync(ln.d_slot_b, sl.data(), n2 * 4, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(ctx, hipMemcpyAsync(ln.d_pos_p2, p2.data(), n2 * 4, hipMemcpyHostToDevice, ctx->stream));
-        RT_HIP(ctx, hipMemcpyAsync(ln.d_pos_b, P.data() + ln.b0, n * 4, hipMemcpyHostToDevice, ctx->stream));
-        RT_HIP(ctx, hipMemcpyAsync(ln.d_items, A.h_item_ids + ln.b0, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(ln.d_pos_b, pos_row.data() + ln.b0, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(ln.d_items, ids_row.data() + ln.b0, n * 8, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (sl / p2 are stack-local staging)
         if (col) {
             RT_TRY(pool_arr(m, (size_t)n * NTt, &ln.rowsq_t));
@@ -273,6 +342,26 @@ int rt_gen_run::init(const rt_generate_args* a) {
             RT_TRY(alloc_stack_ws(m, c.talker, n, &ln.wt));
             RT_TRY(alloc_stack_ws(m, c.predictor, n2, &ln.wp));
         }
+    }
+
+    // ---- several voices: the block table of the decode step's attention.  Which of its two launches a step takes (matrix cores for the
+    // blocks of voices with >= 64 prefix rows, vector unit for the rows of the others) is fixed here by the voices the items name;
+    // WHICH blocks each covers is device data, rewritten at a hand-over.  Under g_attn_mfma == 0 every voice takes the vector form, as
+    // it does alone; under g_attn_mfma == 2 (one row per workgroup, no multi-voice instantiation) too: the run falls back to the default form.
+    if (multi) {
+        const int nb = plan.n_blocks();
+        RT_TRY(pool_arr(m, nb, &d_vblocks));
+        RT_TRY(pool_arr(m, nb + B, &d_vlists));
+        vtab.blocks = d_vblocks; vtab.mfma_blocks = d_vlists; vtab.vec_rows = d_vlists + nb; vtab.rows = B; vtab.n_blocks = nb;
+        for (int32_t v : voice) {
+            const bool mf = attention_mfma_voice_ok(c.talker.heads, c.talker.kv_heads, c.talker.head_dim, m->talker.kv, m->voice_len(v));
+            vtab.any_mfma = vtab.any_mfma || mf;
+            vtab.any_vec = vtab.any_vec || !mf;
+        }
+        fill_voice_table();
+        RT_HIP(ctx, hipMemcpyAsync(d_vblocks, h_vblocks.data(), nb * sizeof(VoiceBlock), hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(d_vlists, h_vlists.data(), (nb + B) * 4, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
 
     // ---- graphs: capture A and B once per lane and launch signature, replay per frame
@@ -296,7 +385,10 @@ int rt_gen_run::init(const rt_generate_args* a) {
         mix(B); mix(col); mix(n_lanes); mix(A.ignore_eos); mix(A.min_frames); mix(g_tune_epoch);      // (any accepted rt_debug_tune call: the switches shape the launches inside the graphs)
         // the attention nodes carry the voice prefix (slot, length) by value: a voice of another length must not replay the
         // old graphs.  The prefix KV *content* is read through pointers, so re-setting a voice of the same length keeps them.
-        mix((uint64_t)Lp); mix((uint64_t)(int64_t)m->talker.kv.prefix_slot);
+        // A multi-voice run's nodes carry the block table's address and which launches it takes instead: the prefixes are device
+        // data, so the graphs survive every re-voicing.
+        if (multi) { mix((uint64_t)(uintptr_t)d_vblocks); mix((uint64_t)(uintptr_t)d_vlists); mix(2 + vtab.any_mfma); mix(4 + vtab.any_vec); }
+        else { mix((uint64_t)Lp); mix((uint64_t)(int64_t)m->talker.kv.prefix_slot); }
         for (const rt_sampling* sp : {&A.talker, &A.predictor}) {
             mix(sp->do_sample); mix(sp->top_k);
             uint32_t f;
@@ -341,7 +433,11 @@ int rt_gen_run::init(const rt_generate_args* a) {
     produced.assign(N, 0); start.assign(N, 0); item_row.assign(N, -1);   // per item: frames kept, first frame-counter value, row
     finished.assign(N, 0);
     row_item.assign(B, -1);                                // item on each row, -1 = idle
-    for (int b = 0; b < B; ++b) { row_item[b] = b; item_row[b] = b; }
+    for (int b = 0; b < B; ++b) {
+        const int it = multi ? plan.row_item[b] : b;
+        row_item[b] = it;
+        if (it >= 0) item_row[it] = b;
+    }
     next_item = B;
     // End-of-sequence is decided on the device (the sampler writes one flag per row and frame); the host only needs the
     // flags to know when to STOP launching (or to hand a row to the next queued item), so it fetches them every
@@ -350,23 +446,26 @@ int rt_gen_run::init(const rt_generate_args* a) {
     eos_every = A.ignore_eos ? 0 : every;
     lane_frames.assign(n_lanes, 0);                        // frame budget of a lane = its longest item (static batches)
     for (int l = 0; l < n_lanes; ++l) {
-        for (int bb = lanes[l].b0; bb < lanes[l].b0 + lanes[l].n; ++bb) lane_frames[l] = std::max(lane_frames[l], A.h_max_frames[bb]);
-        if (queued) lane_frames[l] = T_max;
+        for (int bb = lanes[l].b0; bb < lanes[l].b0 + lanes[l].n; ++bb)
+            if (row_item[bb] >= 0) lane_frames[l] = std::max(lane_frames[l], A.h_max_frames[row_item[bb]]);
+        if (queued || multi) lane_frames[l] = T_max;
     }
-    h_pos_b.assign(P.begin(), P.begin() + B);
+    h_pos_b = pos_row;
     h_off.assign(B, 0);
-    h_items.assign(A.h_item_ids, A.h_item_ids + B);
+    h_items = ids_row;
     parked.assign(B, 0);
+    for (int b = 0; b < B; ++b) parked[b] = row_item[b] < 0;      // (several voices: rows the first wave left free, already behind their block's prefix)
     return RT_OK;
 }
 
 // prefill the suffixes of `items` into the KV slots of `rows`; on return x holds the residual stream, d_last / d_dst
 // the (last suffix row, decode row) of each item
-int rt_gen_run::prefill(const std::vector<int>& items, const std::vector<int>& rows, bool first) {
+// (r_off / i_off: a pass of prefill_by_voice - its suffix rows follow the r_off rows, its items the i_off items, of the passes before it)
+int rt_gen_run::prefill(const std::vector<int>& items, const std::vector<int>& rows, bool first, int r_off, int i_off) {
     const int k = (int)items.size();
     int n = 0;
     for (int it : items) n += A.h_text_offsets[it + 1] - A.h_text_offsets[it] + 2;
-    if (n > S_cap) return rt_fail(ctx, RT_ERR_STATE, "rt_generate: prefill of %d rows exceeds its workspace (%d)", n, S_cap);
+    if (r_off + n > S_cap || i_off + k > B) return rt_fail(ctx, RT_ERR_STATE, "rt_generate: prefill of %d rows exceeds its workspace (%d)", r_off + n, S_cap);
     staging.emplace_back(new Staging());
     Staging& st = *staging.back();
     std::vector<int32_t>&s_tid = st.tid, &s_cid = st.cid, &s_slot = st.slot, &s_pos = st.pos, &last_row = st.last, &dst_row = st.dst;
@@ -381,20 +480,133 @@ int rt_gen_run::prefill(const std::vector<int>& items, const std::vector<int>& r
             s_slot[r] = rows[i];
             s_pos[r] = Lp + j;
         }
-        last_row[i] = r - 1;
+        last_row[i] = r_off + r - 1;
         dst_row[i] = rows[i];
         P[it] = Lp + nt + 2;
     }
-    RT_HIP(ctx, hipMemcpyAsync(d_tid, s_tid.data(), (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(d_cid, s_cid.data(), (size_t)n * G * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(d_slot, s_slot.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(d_pos, s_pos.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(d_last, last_row.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(ctx, hipMemcpyAsync(d_dst, dst_row.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (first) RT_HIP(ctx, hipMemcpyAsync(d_tid, s_tid.data(), (n + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    else RT_HIP(ctx, hipMemcpyAsync(d_tid + 1 + r_off, s_tid.data() + 1, n * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_cid + (size_t)r_off * G, s_cid.data(), (size_t)n * G * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_slot + r_off, s_slot.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_pos + r_off, s_pos.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_last + i_off, last_row.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(ctx, hipMemcpyAsync(d_dst + i_off, dst_row.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
+    float* temb_r = temb + (size_t)(1 + r_off) * H;
     if (first) RT_TRY(text_project(m, d_tid, n + 1, temb, &w_text));  // (the tts_pad row is projected once)
-    else RT_TRY(text_project(m, d_tid + 1, n, temb + H, &w_text));
-    RT_TRY(launch_gather_sum(ctx, m->d_frame_srcs, G, d_cid, n, H, nullptr, temb + H, nullptr, x, nullptr));
-    RT_TRY(stack_forward(m, m->talker, w_prefill, x, n, d_slot, d_pos, 0, nullptr, hn_all_f32));
+    else RT_TRY(text_project(m, d_tid + 1 + r_off, n, temb_r, &w_text));
+    RT_TRY(launch_gather_sum(ctx, m->d_frame_srcs, G, d_cid + (size_t)r_off * G, n, H, nullptr, temb_r, nullptr, x + (size_t)r_off * H, nullptr));
+    RT_TRY(stack_forward(m, m->talker, w_prefill, x + (size_t)r_off * H, n, d_slot + r_off, d_pos + r_off, 0, nullptr, hn_all_f32 + (size_t)r_off * H));
+    return RT_OK;
+}
+
+// fragment-tiled prefix copies of bank entry v, where the matrix-core forms need them and they are stale
+int rt_gen_run::voice_tiles(int v) {
+    point_at(v);
+    if (g_attn_mfma && m->cfg.talker.head_dim == 128 && !m->prefix_tiles_valid) {
+        RT_TRY(launch_transpose_prefix_v(ctx, m->talker.kv, Lp));
+        m->prefix_tiles_valid = true;
+    }
+    return RT_OK;
+}
+
+// one prefill pass per distinct voice among `items` (in the order the voices first appear): the prompt rows of a pass read the
+// prefix slot, length and tiles of its voice; the prefill kernels are the single-voice ones, and a prompt row gets the same bits
+// whatever it is batched with.  d_last / d_dst hold the items in pass order; last_of (optional) the same rows of x in `items` order.
+int rt_gen_run::prefill_by_voice(const std::vector<int>& items, const std::vector<int>& rows, bool first, std::vector<int32_t>* last_of) {
+    std::vector<char> done(items.size(), 0);
+    if (last_of) last_of->assign(items.size(), 0);
+    int r_off = 0, i_off = 0;
+    for (size_t i0 = 0; i0 < items.size(); ++i0) {
+        if (done[i0]) continue;
+        const int v = voice[items[i0]];
+        std::vector<int> its, rws;
+        std::vector<size_t> at;
+        for (size_t i = i0; i < items.size(); ++i)
+            if (!done[i] && voice[items[i]] == v) { its.push_back(items[i]); rws.push_back(rows[i]); at.push_back(i); done[i] = 1; }
+        point_at(v);
+        RT_TRY(prefill(its, rws, first && r_off == 0, r_off, i_off));
+        const std::vector<int32_t>& last = staging.back()->last;
+        for (size_t j = 0; j < at.size(); ++j) if (last_of) (*last_of)[at[j]] = last[j];
+        for (int it : its) r_off += A.h_text_offsets[it + 1] - A.h_text_offsets[it] + 2;
+        i_off += (int)its.size();
+    }
+    return RT_OK;
+}
+
+// the block table and the two launch lists from the plan's block voices (host copies; the caller uploads them)
+void rt_gen_run::fill_voice_table() {
+    const rt_stack_dims& d = m->cfg.talker;
+    const KvCache& kv = m->talker.kv;
+    const int nb = plan.n_blocks();
+    const int64_t per_voice = (int64_t)kv.layers * kv.kv_heads * kv.vt_stride;
+    h_vblocks.assign(nb, VoiceBlock{});
+    h_vlists.assign(nb + B, -1);
+    int n_mf = 0, n_vr = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int v = plan.block_voice[b], lp = m->voice_len(v);
+        const bool mf = attention_mfma_voice_ok(d.heads, d.kv_heads, d.head_dim, kv, lp);
+        h_vblocks[b].prefix_slot = m->voice_slot(v); h_vblocks[b].prefix_len = lp;
+        h_vblocks[b].kt = mf ? m->kt_bank + v * per_voice : nullptr;
+        h_vblocks[b].vt = mf ? m->vt_bank + v * per_voice : nullptr;
+        if (mf) h_vlists[n_mf++] = b;
+        else for (int r = b * voice_plan::BLOCK; r < std::min(B, (b + 1) * voice_plan::BLOCK); ++r) h_vlists[nb + n_vr++] = r;
+    }
+}
+
+// a hand-over of a multi-voice run: the plan places waiting items (a block whose rows are all free may change voice), one prefill
+// pass per voice, and the rows, the block table and the launch lists are re-pointed between two frames
+int rt_gen_run::swap_in_voices(int t1) {
+    Lane& ln = lanes[0];
+    for (int r = 0; r < B; ++r) if (row_item[r] < 0) plan.row_item[r] = -1;
+    const std::vector<int> voice_before = plan.block_voice;
+    std::vector<int> items, rows;
+    int revoiced = 0;
+    const bool waiting_before = n_placed < N;
+    n_placed += voice_plan::place(voice.data(), N, plan, &items, &rows, &revoiced);
+    n_revoiced += revoiced;
+    bool dirty = false;
+    if (plan.block_voice != voice_before) {
+        for (int b = 0; b < plan.n_blocks(); ++b)
+            if (plan.block_voice[b] != voice_before[b])       // its free rows restart behind the new voice's prefix
+                for (int r = b * voice_plan::BLOCK; r < std::min(B, (b + 1) * voice_plan::BLOCK); ++r) parked[r] = 0;
+        fill_voice_table();
+        RT_HIP(ctx, hipMemcpyAsync(d_vblocks, h_vblocks.data(), h_vblocks.size() * sizeof(VoiceBlock), hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(d_vlists, h_vlists.data(), h_vlists.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        dirty = true;
+    }
+    for (size_t i = 0; i < items.size(); ++i) {
+        const int r = rows[i], it = items[i];
+        row_item[r] = it; item_row[it] = r; start[it] = t1; parked[r] = 0;
+    }
+    // Free rows restart behind their block's prefix at EVERY hand-over while items wait (and at the one that places the last of them):
+    // unlike a single-voice run, where a row is parked only once nothing waits, a row here can be free from the first frame in a
+    // block that stays busy while another voice queues, and would otherwise step on for the whole run - past max_positions.  A free
+    // row thus never sits more than F_max + every positions behind its prefix, which rt_gen_run::init bounds for every voice.
+    for (int r = 0; r < B; ++r)
+        if (row_item[r] < 0 && (!parked[r] || waiting_before)) {
+            const int lp = m->voice_len(plan.block_voice[r / voice_plan::BLOCK]);
+            if (lp + F_max + every + 1 > m->cfg.max_positions)
+                return rt_fail(ctx, RT_ERR_STATE, "rt_generate: a free row behind a prefix of %d rows would pass max_positions %d", lp, m->cfg.max_positions);
+            parked[r] = 1; h_pos_b[r] = lp - t1; dirty = true;
+        }
+    if (!items.empty()) {
+        RT_TRY(prefill_by_voice(items, rows, false));
+        const int k = (int)items.size();
+        RT_TRY(launch_rowsq(ctx, x, k, H, ln.rowsq_t, NTt, ln.dwt.xT, ln.dwt.xa, m->talker.norm, d_last, d_dst));
+        for (int i = 0; i < k; ++i) {
+            const int r = rows[i], it = items[i];
+            h_pos_b[r] = P[it] - t1; h_off[r] = t1; h_items[r] = A.h_item_ids[it];
+            RT_HIP(ctx, hipMemsetAsync(ln.d_seen + (size_t)r * Vc, 0, Vc, ctx->stream));
+        }
+        dirty = true;
+        ++n_swaps;
+    }
+    if (dirty) {
+        RT_HIP(ctx, hipMemcpyAsync(ln.d_pos_b, h_pos_b.data(), B * 4, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(ln.d_frame_off, h_off.data(), B * 4, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipMemcpyAsync(ln.d_items, h_items.data(), B * 8, hipMemcpyHostToDevice, ctx->stream));
+        RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the host arrays are rewritten by the next hand-over)
+    }
     return RT_OK;
 }
 
@@ -513,7 +725,10 @@ int rt_gen_run::enqueue_b(Lane& ln) {
         if (col) RT_TRY(launch_rowsq(ctx, ln.xt, n, H, ln.rowsq_t, NTt, ln.dwt.xT, ln.dwt.xa, m->talker.L[0].ln1));
     }
     if (col) {
-        RT_TRY(stack_decode(m, m->talker, ln.dwt, ln.dwt.xT, ln.rowsq_t, n, ln.d_slot_b, ln.d_pos_b, inc_early ? -1 : 0, true, ln.d_frame));
+        m->talker.kv.voices = multi ? &vtab : nullptr;     // (several voices: the attention reads the prefix per 4-row block)
+        const int rc = stack_decode(m, m->talker, ln.dwt, ln.dwt.xT, ln.rowsq_t, n, ln.d_slot_b, ln.d_pos_b, inc_early ? -1 : 0, true, ln.d_frame);
+        m->talker.kv.voices = nullptr;
+        RT_TRY(rc);
     } else {
         RT_TRY(stack_forward(m, m->talker, ln.wt, ln.xt, n, ln.d_slot_b, ln.d_pos_b, 0, ln.hn, ln.hn_f32, ln.d_frame));
     }
@@ -539,13 +754,14 @@ bool rt_gen_run::apply_frames(int upto) {                  // bookkeeping of fra
     for (Lane& ln : lanes) {
         bool lane_done = true;
         for (int r = ln.b0; r < ln.b0 + ln.n; ++r) lane_done = lane_done && row_item[r] < 0;
-        ln.done = lane_done && next_item >= N;
+        ln.done = lane_done && none_waiting();
     }
     return n_finished == N;
 }
 
 // idle rows take the next queued items; the caller has launched part B of frame t1 - 1, so the new items' first frame is t1
 int rt_gen_run::swap_in(int t1) {
+    if (multi) return swap_in_voices(t1);
     Lane& ln = lanes[0];
     std::vector<int> items, rows;
     bool dirty = false;
@@ -610,6 +826,9 @@ int rt_gen_run::fetch(int upto, bool with_codes) {
 // (the last frame of a step is a check point), and part B of the last frame - the next talker step - is already in flight.
 int rt_gen_run::advance(int n_frames) {
     struct StreamGuard { rt_ctx* c; hipStream_t s; ~StreamGuard() { c->stream = s; } } stream_guard{ctx, main_stream};
+    // the talker cache's prefix stands for the run's voice while frames are launched, and for the selected entry again afterwards
+    struct VoiceGuard { rt_model* m; int back; ~VoiceGuard() { m->voice_view(back); } } voice_guard{m, sel_back};
+    point_at(run_voice);
     int done_here = 0;
     while (!all_done && !cancelled && t < T_max && done_here < n_frames) {
         if (A.h_cancel_flag && *A.h_cancel_flag) { cancelled = true; break; }
@@ -685,6 +904,7 @@ int rt_gen_run::finish(int32_t* h_codes, int32_t* h_n_frames) {
         off += A.h_max_frames[it];
     }
     m->last_frames_run = frames_run; m->last_rows = B; m->last_kept = kept; m->last_swaps = n_swaps; m->last_launch_host_us = launch_host_us;
+    m->last_revoiced = n_revoiced;
     if (getenv("RHO_TTS_AMD_TRACE_HOST")) fprintf(stderr, "rt_generate: %d frames, host time inside frame launches %.1f us (%.1f us per frame)\n", frames_run, launch_host_us, launch_host_us / std::max(1, frames_run));
     return RT_OK;
 }
@@ -694,15 +914,20 @@ extern "C" {
 static int gen_begin_locked(rt_model* m, const rt_generate_args* A) {
     rt_ctx* ctx = m->ctx;
     if (!m->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_generate: model not finalized");
-    if (m->prefix_len < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: no voice set (rt_model_set_voice)");
+    std::vector<int32_t> item_voices;
+    item_voices.swap(m->item_voices);                      // (rt_generate_item_voices: this call consumes the array, whatever becomes of it)
+    if (item_voices.empty() && m->prefix_len < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate: no voice set (rt_model_set_voice)");
     gen_release(m);                                        // (a run that was never ended: dropped)
     pool_release_all(m);
     m->run = new rt_gen_run();
     g_runs_in_flight.fetch_add(1);
     m->run->m = m; m->run->ctx = ctx;
+    m->run->sel_back = m->voice_sel;
+    m->run->voice.swap(item_voices);
     m->pool_tag = 1;
     const int rc = m->run->init(A);
     m->pool_tag = 0;
+    m->voice_view(m->run->sel_back);                       // (the run's voices are pointed at again by every rt_generate_step)
     if (rc) { ctx->stream = m->run->main_stream ? m->run->main_stream : ctx->stream; const std::string keep = ctx->last_error; gen_release(m); ctx->last_error = keep; }
     return rc;
 }
@@ -790,5 +1015,7 @@ int rt_generate_stats(rt_model* m, int64_t* frames_run, int64_t* rows, int64_t* 
     if (hand_overs) *hand_overs = m->last_swaps;
     return RT_OK;
 }
+
+int64_t rt_generate_revoiced_blocks(rt_model* m) { return m ? m->last_revoiced : -1; }
 
 }  // extern "C"

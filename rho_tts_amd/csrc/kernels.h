@@ -180,6 +180,21 @@ int launch_silu_mul(rt_ctx* ctx, const float* slabs, int n_slabs, int M, int I, 
 int launch_reduce_slabs(rt_ctx* ctx, const float* slabs, int n_slabs, int64_t M, int N, const float* bias, int act,
                         float* out_f32, bf16_t* out_bf16);
 
+// A multi-voice decode step (rt_generate_item_voices): the rows are cut into 4-row blocks and every block reads the prefix of its own
+// voice.  One entry per block in device memory, rewritten between two frames when a block changes voice (generate.hip).
+struct VoiceBlock {
+    int32_t prefix_slot, prefix_len;      // the voice's cache slot and its rows
+    const bf16_t* kt;                     // the voice's fragment-tiled prefix K / V, layer 0 (null: the voice takes the vector form)
+    const bf16_t* vt;
+};
+struct VoiceTable {
+    const VoiceBlock* blocks = nullptr;   // device [n_blocks]
+    const int32_t* mfma_blocks = nullptr; // device [n_blocks]: the blocks of the matrix-core launch, then -1
+    const int32_t* vec_rows = nullptr;    // device [rows]: the rows of the vector-unit launch, then -1
+    int rows = 0, n_blocks = 0;
+    bool any_mfma = false, any_vec = false;   // the launches a step takes: fixed for a run by the voices its items name
+};
+
 struct KvCache {
     bf16_t* k = nullptr;   // [layers][slots][kv_heads][max_pos][head_dim]
     bf16_t* v = nullptr;
@@ -198,6 +213,7 @@ struct KvCache {
     int vt_stride = 0;              // elements per (layer, kv head) = ceil(max_pos / 32) * 4096
     int prefix_slot_alloc = -1;     // the slot that holds the prefix (fixed per model; prefix_slot above is switched on / off around its prefill)
     int tiles_len = -1;             // prefix length kt_prefix / vt_prefix were built for (-1: stale)
+    const VoiceTable* voices = nullptr;   // set around the decode steps of a multi-voice run: launch_attention_fused reads the prefix per block
     size_t layer_stride() const { return (size_t)slots * kv_heads * max_pos * head_dim; }
 };
 // qkv slabs [S][M][(heads+2*kv_heads)*d] -> q (f32 [M][heads][d], normed + roped), k/v appended to the cache
@@ -222,6 +238,7 @@ int launch_attention_fused(rt_ctx* ctx, const float* qkv, int M, int heads, int 
 // decode attention with the shared prefix on the matrix cores (attention_mfma.hip): same contract as launch_attention_fused for
 // head_dim 128, 2 query heads per kv head, no window, a shared prefix of >= 64 rows with its transposed V copy in place
 bool attention_mfma_ok(int M, int heads, int kv_heads, int head_dim, int window, const KvCache& kv);
+bool attention_mfma_voice_ok(int heads, int kv_heads, int head_dim, const KvCache& kv, int prefix_len);   // one voice of a bank (no window)
 int launch_attention_prefix_mfma(rt_ctx* ctx, const float* qkv, int M, int heads, int kv_heads, const float* q_norm_w, const float* k_norm_w, float eps,
                                  const float* rope_cos, const float* rope_sin, const int32_t* row_slot, const int32_t* row_pos, int pos_add,
                                  const KvCache& kv, int layer, bf16_t* out, const int32_t* frame_ptr, int out_tiled);

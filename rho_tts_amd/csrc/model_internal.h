@@ -51,6 +51,7 @@ struct rt_model {
     int pool_tag = 0;                  // tag of the pool blocks handed out right now (1 while the generation in flight allocates)
     bool prefix_tiles_valid = false;   // kt_prefix / vt_prefix hold the current voice prefix (attention_mfma.hip)
     int64_t last_frames_run = 0, last_rows = 0, last_kept = 0, last_swaps = 0;   // rt_generate_stats
+    int64_t last_revoiced = 0;         // rt_generate_revoiced_blocks
     double last_launch_host_us = 0.0;  // host time spent inside the frame-part launches of the last rt_generate
     rt_ctx* ctx = nullptr;
     rt_model_config cfg{};
@@ -72,8 +73,14 @@ struct rt_model {
     GatherSrc* d_frame_srcs = nullptr;     // n_groups sources for frame embedding
     std::vector<float*> exp_vecs;          // expanded per-column vectors (owned)
     std::map<std::string, float*> xvec;    // name -> expanded vector (SnakeBeta parameters tiled over a transposed conv's r phases)
-    // voice
+    // voice: prefix_len / prefix_tiles_valid / talker.kv.{prefix_slot_alloc, kt_prefix, vt_prefix, tiles_len} describe the SELECTED
+    // entry of the voice bank (rt_voice_select; entry 0 unless a caller selects another); the other entries rest in `voices`
     int prefix_len = 0;
+    struct VoiceEntry { int prefix_len = 0; bool tiles_valid = false; int tiles_len = -1; };
+    int max_voices = 1, voice_sel = 0;
+    std::vector<VoiceEntry> voices;                  // [max_voices]; the selected one is stale while it is selected (see voice_view)
+    bf16_t *kt_bank = nullptr, *vt_bank = nullptr;   // the tile allocations: entry v at v * layers * kv_heads * vt_stride
+    std::vector<int32_t> item_voices;                // rt_generate_item_voices: consumed by the next rt_generate / rt_generate_begin
     // pool
     std::vector<PoolBlock> pool;
     // profiling
@@ -96,7 +103,22 @@ struct rt_model {
     int64_t weight_bytes = 0;
 
     bool has_mtp() const { return cfg.talker.hidden != cfg.predictor.hidden; }
-    int prefix_slot() const { return cfg.max_batch; }
+    int voice_slot(int v) const { return cfg.max_batch + v; }
+    int prefix_slot() const { return voice_slot(voice_sel); }
+    int voice_len(int v) const { return v == voice_sel ? prefix_len : voices[v].prefix_len; }
+    // the model's voice state and the talker cache's prefix tiles now stand for bank entry v (the state of the entry that was
+    // selected goes back to the bank).  Host bookkeeping only: no byte of the cache or of the tiles moves.
+    void voice_view(int v) {
+        KvCache& kv = talker.kv;
+        voices[voice_sel] = VoiceEntry{prefix_len, prefix_tiles_valid, kv.tiles_len};
+        voice_sel = v;
+        prefix_len = voices[v].prefix_len; prefix_tiles_valid = voices[v].tiles_valid; kv.tiles_len = voices[v].tiles_len;
+        kv.prefix_slot_alloc = voice_slot(v);
+        if (kt_bank) {
+            const int64_t per_voice = (int64_t)kv.layers * kv.kv_heads * kv.vt_stride;
+            kv.kt_prefix = kt_bank + v * per_voice; kv.vt_prefix = vt_bank + v * per_voice;
+        }
+    }
 };
 
 

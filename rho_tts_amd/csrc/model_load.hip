@@ -287,6 +287,8 @@ int rt_model_create(rt_ctx* ctx, const rt_model_config* cfg, rt_model** out_mode
         c.n_upsampling < 0 || c.n_upsampling > 4 || c.n_upsample_rates < 1 || c.n_upsample_rates > 8 || c.text_hidden % 16 ||
         c.max_positions < 8 || c.max_codec_frames < 1 || (c.decoder_dim >> c.n_upsample_rates) < 8 || (c.decoder_dim >> c.n_upsample_rates) % 8)
         return rt_fail(ctx, RT_ERR_INVALID, "rt_model_create: unsupported configuration (n_groups 2..32, max_batch 1..128, channels %% 8)");
+    // reserved[0] = max_voices, the entries of the voice bank: 0 (every caller from before the bank) means 1
+    if (c.reserved[0] < 0 || c.reserved[0] > 8) return rt_fail(ctx, RT_ERR_INVALID, "rt_model_create: max_voices %d out of range (1..8)", c.reserved[0]);
     if (c.enc.filters > 0) {
         const rt_encoder_config& e = c.enc;
         bool bad = e.n_ratios < 1 || e.n_ratios > 8 || e.filters % 16 || 256 % e.filters || e.kernel < 1 || e.kernel > 15 || e.res_kernel < 1 ||
@@ -300,6 +302,8 @@ int rt_model_create(rt_ctx* ctx, const rt_model_config* cfg, rt_model** out_mode
     rt_model* m = new rt_model();
     m->ctx = ctx;
     m->cfg = c;
+    m->max_voices = std::max(1, c.reserved[0]);
+    m->voices.assign(m->max_voices, rt_model::VoiceEntry());
     declare_slots(m);
     *out_model = m;
     return RT_OK;
@@ -314,6 +318,7 @@ int rt_model_destroy(rt_model* m) {
     rt_gen_drop(m);
     for (auto& s : m->slots) { if (s.raw) (void)hipFree(s.raw); if (s.raw16) (void)hipFree(s.raw16); }
     if (m->d_cbT) (void)hipFree((void*)m->d_cbT);
+    m->talker.kv.kt_prefix = m->kt_bank; m->talker.kv.vt_prefix = m->vt_bank;     // (the cache's pointers may stand inside the bank)
     for (StackW* S : {&m->talker, &m->pred, &m->ctf, &m->etf}) {
         if (S->kv.k) (void)hipFree(S->kv.k);
         if (S->kv.v) (void)hipFree(S->kv.v);
@@ -413,13 +418,15 @@ int rt_model_finalize(rt_model* m, const float* h_rope_cos[3], const float* h_ro
     for (auto& s : m->slots)
         if (!s.set) return rt_fail(ctx, RT_ERR_INVALID, "rt_model_finalize: tensor '%s' was never set", s.name.c_str());
     const rt_model_config& c = m->cfg;
-    RT_TRY(bind_stack(m, m->talker, "talker", c.talker, c.max_batch + 1, c.max_positions, 0));
+    // one cache slot per decode row, then one per voice of the bank (voice v in slot max_batch + v)
+    RT_TRY(bind_stack(m, m->talker, "talker", c.talker, c.max_batch + m->max_voices, c.max_positions, 0));
     if (c.talker.head_dim == 128) {   // transposed copy of the voice prefix's V for the matrix-core decode attention (attention_mfma.hip)
         KvCache& kv = m->talker.kv;
         kv.vt_stride = (c.max_positions + 31) / 32 * 4096;
         kv.prefix_slot_alloc = m->prefix_slot();
-        RT_HIP(ctx, hipMalloc((void**)&kv.kt_prefix, (size_t)kv.layers * kv.kv_heads * kv.vt_stride * sizeof(bf16_t)));
-        RT_HIP(ctx, hipMalloc((void**)&kv.vt_prefix, (size_t)kv.layers * kv.kv_heads * kv.vt_stride * sizeof(bf16_t)));
+        RT_HIP(ctx, hipMalloc((void**)&m->kt_bank, (size_t)m->max_voices * kv.layers * kv.kv_heads * kv.vt_stride * sizeof(bf16_t)));
+        RT_HIP(ctx, hipMalloc((void**)&m->vt_bank, (size_t)m->max_voices * kv.layers * kv.kv_heads * kv.vt_stride * sizeof(bf16_t)));
+        kv.kt_prefix = m->kt_bank; kv.vt_prefix = m->vt_bank;          // entry 0 is selected
     }
     RT_TRY(bind_stack(m, m->pred, "pred", c.predictor, c.max_batch, c.n_groups + 1, 0));
     RT_TRY(bind_stack(m, m->ctf, "ctf", c.codec_tf, c.max_batch, c.max_codec_frames, c.codec_sliding_window, true));

@@ -296,6 +296,49 @@ int rt_model_set_voice_pcm(rt_model* m, const float* h_pcm, int64_t n_samples, i
     return set_voice_impl(m, n_rows, tid.data(), cid.data(), h_speaker_row, h_speaker_row >= 0 ? spk.data() : nullptr);
 }
 
+// ------------------------------------------------------------------------------------------ the voice bank
+// max_voices entries (rt_model_config.reserved[0]), entry v in cache slot max_batch + v with tile copies of its own.  The calls above
+// and below act on the SELECTED entry; selecting is host bookkeeping (rt_model::voice_view), so a caller with several voices
+// switches between two rt_generate calls for nothing, and hands rt_generate a voice per item (rt_generate_item_voices).
+int32_t rt_voice_capacity(rt_model* m) { return m ? m->max_voices : -1; }
+
+int rt_voice_select(rt_model* m, int32_t voice) {
+    if (!m) return RT_ERR_INVALID;
+    rt_ctx* ctx = m->ctx;
+    CtxLock g(ctx);
+    if (voice < 0 || voice >= m->max_voices) return rt_fail(ctx, RT_ERR_INVALID, "rt_voice_select: voice %d outside the bank of %d", voice, m->max_voices);
+    if (m->run) return rt_fail(ctx, RT_ERR_STATE, "rt_voice_select: a generation is in flight (rt_generate_end first)");
+    m->voice_view(voice);
+    return RT_OK;
+}
+
+int rt_voice_clear(rt_model* m, int32_t voice) {
+    if (!m) return RT_ERR_INVALID;
+    rt_ctx* ctx = m->ctx;
+    CtxLock g(ctx);
+    if (voice < 0 || voice >= m->max_voices) return rt_fail(ctx, RT_ERR_INVALID, "rt_voice_clear: voice %d outside the bank of %d", voice, m->max_voices);
+    if (m->run) return rt_fail(ctx, RT_ERR_STATE, "rt_voice_clear: a generation is in flight (rt_generate_end first)");
+    m->voices[voice] = rt_model::VoiceEntry();
+    if (voice == m->voice_sel) { m->prefix_len = 0; m->prefix_tiles_valid = false; m->talker.kv.tiles_len = -1; }
+    return RT_OK;
+}
+
+int rt_generate_item_voices(rt_model* m, const int32_t* h_voice, int32_t n_items) {
+    if (!m) return RT_ERR_INVALID;
+    rt_ctx* ctx = m->ctx;
+    CtxLock g(ctx);
+    m->item_voices.clear();
+    if (!h_voice || n_items < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_item_voices: null argument");
+    if (m->run) return rt_fail(ctx, RT_ERR_STATE, "rt_generate_item_voices: a generation is in flight (rt_generate_end first)");
+    for (int i = 0; i < n_items; ++i) {
+        if (h_voice[i] < 0 || h_voice[i] >= m->max_voices)
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_item_voices: item %d asks for voice %d outside the bank of %d", i, h_voice[i], m->max_voices);
+        if (m->voice_len(h_voice[i]) < 1) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_item_voices: item %d asks for voice %d, which is not set", i, h_voice[i]);
+    }
+    m->item_voices.assign(h_voice, h_voice + n_items);
+    return RT_OK;
+}
+
 int32_t rt_voice_prefix_len(rt_model* m) { return m ? m->prefix_len : -1; }
 
 int64_t rt_voice_blob_bytes(rt_model* m) {

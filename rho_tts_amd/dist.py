@@ -57,23 +57,36 @@ def plan_corpus(costs: Sequence[float], world: int, batch: int) -> Tuple[List[Li
     return shards, plans
 
 
-def broadcast_voice(engine, dist, src: int = 0, comm_device=None) -> None:
+def broadcast_voice(engine, dist, src: int = 0, comm_device=None, voice_index: int = 0, name=None) -> None:
     """Rank ``src`` has computed the voice prefix (Engine.set_voice); every other rank imports its KV blob.
-    ``comm_device``: where the collective runs (the GPU for RCCL; "cpu" to rehearse on gloo)."""
+    ``comm_device``: where the collective runs (the GPU for RCCL; "cpu" to rehearse on gloo).
+    ``voice_index``: the entry of the engine's voice bank that travels (0: the engine's own voice); an entry above 0 is
+    registered on the receiving ranks under ``name`` (Engine.voices)."""
     rank = dist.get_rank()
     dev = comm_device or engine.device
     meta = torch.zeros(2, dtype=torch.int64, device=dev)
-    if rank == src:
-        blob = engine.model.export_voice().to(dev)
-        meta[0], meta[1] = engine.model.prefix_len(), blob.numel()
-    dist.broadcast(meta, src=src)
+    selected = int(getattr(engine.model, "selected_voice", 0))
+    if voice_index != selected:
+        engine.model.select_voice(voice_index)
+    try:
+        if rank == src:
+            blob = engine.model.export_voice().to(dev)
+            meta[0], meta[1] = engine.model.prefix_len(), blob.numel()
+        dist.broadcast(meta, src=src)
+        if rank != src:
+            blob = torch.empty(int(meta[1]), dtype=torch.bfloat16, device=dev)
+        dist.broadcast(blob, src=src)
+        if rank != src:
+            engine.model.import_voice(int(meta[0]), blob.to(engine.device))
+    finally:
+        if voice_index != selected:
+            engine.model.select_voice(selected)          # (the entry that was selected before the call)
     if rank != src:
-        blob = torch.empty(int(meta[1]), dtype=torch.bfloat16, device=dev)
-    dist.broadcast(blob, src=src)
-    if rank != src:
-        engine.model.import_voice(int(meta[0]), blob.to(engine.device))
-        if getattr(engine, "voice", None) is None:          # the conditioning now lives in the imported prefix KV
-            from .voice import VoiceConditioning
+        from .voice import VoiceConditioning
+        if voice_index:
+            engine.voices[name] = (voice_index, VoiceConditioning("(imported)", None, None, [], None))
+            engine._prefix_len[voice_index] = int(meta[0])
+        elif getattr(engine, "voice", None) is None:        # the conditioning now lives in the imported prefix KV
             engine.voice = VoiceConditioning("(imported)", None, None, [], None)
 
 

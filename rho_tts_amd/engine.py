@@ -11,7 +11,7 @@ import ctypes as C
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -102,7 +102,7 @@ class Engine:
 
     def __init__(self, model_path: str = "Qwen/Qwen3-TTS-12Hz-1.7B-Base", device_ordinal: int = 0, max_batch: int = 32,
                  weight_seed: int = 789, cfg: Optional[ModelConfig] = None, max_positions: Optional[int] = None,
-                 synthetic: Optional[bool] = None):
+                 synthetic: Optional[bool] = None, max_voices: int = 1):
         has_ckpt = find_checkpoint(model_path)
         if synthetic is None:
             synthetic = (not has_ckpt) and os.environ.get(SYNTHETIC_ENV, "") not in ("", "0")
@@ -126,12 +126,16 @@ class Engine:
             else:
                 state = synthetic_state(self.cfg, weight_seed, device=self.device)
             # (created after the load: a checkpoint without audio-encoder tensors has cleared cfg.codec.enc_filters by now)
-            self.model = NativeModel(self.ctx, self.cfg, max_batch=max_batch, max_positions=max_positions)
+            self.model = NativeModel(self.ctx, self.cfg, max_batch=max_batch, max_positions=max_positions, max_voices=max_voices)
             self.model.load_state(state)
             del state
             torch.cuda.empty_cache()
         self.tokenizer = load_tokenizer(model_path, self.cfg.text_vocab)
         self.voice: Optional[VoiceConditioning] = None
+        # the voice bank: entry 0 of the model's bank is `self.voice` (set_voice*), entries 1 .. max_voices - 1 hold named voices
+        self.max_voices = max_voices
+        self.voices: Dict[str, Tuple[int, VoiceConditioning]] = {}
+        self._prefix_len: Dict[int, int] = {}
         self.params = GenerationParams()
         # Synthetic weights never emit end-of-sequence, so every length is imposed (frames_for).  A real checkpoint ends where
         # its end-of-sequence falls, somewhere around the planner's estimate: length_jitter = e emulates that - every text ends
@@ -150,7 +154,50 @@ class Engine:
     # ------------------------------------------------------------------ voice
     def set_voice(self, v: VoiceConditioning) -> int:
         self.voice = v
-        return self.model.set_voice(v.language, v.speaker, v.speaker_embed, v.ref_text_ids, v.ref_codes)
+        self._prefix_len[0] = self.model.set_voice(v.language, v.speaker, v.speaker_embed, v.ref_text_ids, v.ref_codes)
+        return self._prefix_len[0]
+
+    def add_voice(self, name: str, v: VoiceConditioning) -> int:
+        """Make ``v`` resident under ``name`` beside the engine's own voice (a name already in the bank is replaced in its entry).
+        Returns the bank entry.  ValueError when every entry is taken."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("a bank voice needs a name")
+        index = self.voices[name][0] if name in self.voices else self.free_voice_entry()
+        self.model.select_voice(index)
+        try:
+            self._prefix_len[index] = self.model.set_voice(v.language, v.speaker, v.speaker_embed, v.ref_text_ids, v.ref_codes)
+        finally:
+            self.model.select_voice(0)
+        self.voices[name] = (index, v)
+        return index
+
+    def free_voice_entry(self) -> int:
+        taken = {i for i, _ in self.voices.values()}
+        for index in range(1, self.max_voices):
+            if index not in taken:
+                return index
+        raise ValueError(f"the voice bank is full: {len(taken)} named voices beside the engine's own (max_voices={self.max_voices})")
+
+    def remove_voice(self, name: str) -> None:
+        if name not in self.voices:
+            raise ValueError(f"unknown voice {name!r}")
+        index, _ = self.voices.pop(name)
+        self._prefix_len.pop(index, None)
+        self.model.clear_voice(index)
+
+    def voice_entries(self, voices, n: int) -> Optional[List[int]]:
+        """``voices`` of a call (None, one name for every text, or a list with None for the engine's own voice) -> bank entries, or
+        None when every text speaks with the engine's own voice.  ValueError: an unknown name, a list of the wrong length."""
+        if voices is None:
+            return None
+        names = [voices] * n if isinstance(voices, str) else list(voices)
+        if len(names) != n:
+            raise ValueError(f"{len(names)} voices for {n} texts")
+        unknown = sorted({v for v in names if v is not None and v not in self.voices})
+        if unknown:
+            raise ValueError(f"unknown voice {unknown[0]!r} (add_voice first; resident: {sorted(self.voices)})")
+        entries = [0 if v is None else self.voices[v][0] for v in names]
+        return entries if any(entries) else None
 
     def conditioning_from_audio(self, audio_or_path, ref_text: str, language: str = "english") -> VoiceConditioning:
         """The conditioning front-end (the reference re-runs it on every call via ref_audio=path, qwen.py:253-258): the clip is
@@ -188,18 +235,23 @@ class Engine:
 
     # ------------------------------------------------------------------ generate
     def generate_codes(self, texts: Sequence[str], seed: int, item_ids: Optional[Sequence[int]] = None, cancel_flag=None,
-                       max_frames: Optional[Sequence[int]] = None, max_rows: int = 0) -> List[torch.Tensor]:
-        if self.voice is None:
+                       max_frames: Optional[Sequence[int]] = None, max_rows: int = 0, voices=None) -> List[torch.Tensor]:
+        """``voices``: None, a bank name for every text, or one entry per text (None: the engine's own voice).  A text's codes are
+        those it gets alone with that voice."""
+        entries = self.voice_entries(voices, len(texts))
+        if self.voice is None and (entries is None or 0 in entries):
             raise ValueError("no voice set: reference audio (Base models) or a built-in speaker (CustomVoice) is required")
         ids = [self.tokenizer.encode(t) for t in texts]
         frames = list(max_frames) if max_frames is not None else [self.frames_actual(t, len(i)) for t, i in zip(texts, ids)]
-        limit = self.model.max_positions - self.model.prefix_len() - 12     # (queued items step a few positions past their last frame)
+        longest = max(self._prefix_len.get(e, 0) for e in set(entries)) if entries else self.model.prefix_len()
+        limit = self.model.max_positions - longest - 12     # (queued items step a few positions past their last frame)
+        f_max = max(frames) if entries else 0               # (several voices: a free row steps on until the longest item ends)
         for i, f in zip(ids, frames):
-            if len(i) + 2 + f > limit:
-                raise RuntimeError(f"length: text of {len(i)} tokens + {f} frames exceeds the {limit} free KV rows")
+            if len(i) + 2 + max(f, f_max) > limit:
+                raise RuntimeError(f"length: text of {len(i)} tokens + {max(f, f_max)} frames exceeds the {limit} free KV rows")
         ignore_eos = self.synthetic if self.ignore_eos is None else bool(self.ignore_eos)
         return self.model.generate(ids, frames, self.params.talker(), self.params.predictor(), seed=seed, item_ids=item_ids,
-                                   ignore_eos=ignore_eos, cancel_flag=cancel_flag, max_rows=max_rows)
+                                   ignore_eos=ignore_eos, cancel_flag=cancel_flag, max_rows=max_rows, voices=entries)
 
     def vocode(self, codes: Sequence[torch.Tensor]) -> List[torch.Tensor]:
         """Codec decoder with the reference architecture's chunking (chunk_frames + left_context_frames)."""
@@ -226,20 +278,21 @@ class Engine:
 
     # ------------------------------------------------------------------ sub-segment streaming
     def stream_codes(self, text: str, seed: int = 789, item_id: int = 0, first_chunk: int = 12, chunk: int = 36, cancel_flag=None,
-                     max_frames: Optional[int] = None):
+                     max_frames: Optional[int] = None, voice: Optional[str] = None):
         """One text decoded in pieces (rt_generate_begin / _step / _peek / _end): yields ``(codes [n, n_groups] int64, last)`` as
         the frames come off the GPU - ``first_chunk`` frames first (time to first audio), then ``chunk`` at a time.  The codes
         are those of the one-call ``generate_codes`` for the same (text, seed, item_id), however they are cut."""
-        if self.voice is None:
+        entries = self.voice_entries([voice], 1)
+        if self.voice is None and entries is None:
             raise ValueError("no voice set: reference audio (Base models) or a built-in speaker (CustomVoice) is required")
         ids = self.tokenizer.encode(text)
         frames = int(max_frames) if max_frames is not None else self.frames_actual(text, len(ids))
-        limit = self.model.max_positions - self.model.prefix_len() - 12
+        limit = self.model.max_positions - (self._prefix_len.get(entries[0], 0) if entries else self.model.prefix_len()) - 12
         if len(ids) + 2 + frames > limit:
             raise RuntimeError(f"length: text of {len(ids)} tokens + {frames} frames exceeds the {limit} free KV rows")
         ignore_eos = self.synthetic if self.ignore_eos is None else bool(self.ignore_eos)
         self.model.generate_begin([ids], [frames], self.params.talker(), self.params.predictor(), seed=seed, item_ids=[item_id],
-                                  ignore_eos=ignore_eos, cancel_flag=cancel_flag)
+                                  ignore_eos=ignore_eos, cancel_flag=cancel_flag, voices=entries)
         try:
             sent, step = 0, max(1, int(first_chunk))
             while True:
@@ -255,7 +308,7 @@ class Engine:
             self.model.generate_end()
 
     def stream_wav(self, text: str, seed: int = 789, item_id: int = 0, first_chunk: int = 12, chunk: int = 36, cancel_flag=None,
-                   max_frames: Optional[int] = None):
+                   max_frames: Optional[int] = None, voice: Optional[str] = None):
         """Raw waveform chunks (GPU float32) of one text while it is still being decoded: every batch of new codec frames is
         vocoded with ``left_context_frames`` of the frames before it - the codec decoder's own chunked decode, with the chunk
         boundaries where the frames arrive.  The pieces are cut by ABSOLUTE sample position: n frames decode to
@@ -267,7 +320,7 @@ class Engine:
         up = c.total_upsample
         have: Optional[torch.Tensor] = None
         emitted = 0                                            # samples handed out so far = absolute position of the next one
-        for codes, last in self.stream_codes(text, seed, item_id, first_chunk, chunk, cancel_flag, max_frames):
+        for codes, last in self.stream_codes(text, seed, item_id, first_chunk, chunk, cancel_flag, max_frames, voice):
             if codes.shape[0] == 0:
                 if last:
                     yield torch.zeros(0, device=self.device), True
@@ -292,7 +345,7 @@ class Engine:
 
     def synthesize(self, texts: Sequence[str], seed: int = 789, item_ids: Optional[Sequence[int]] = None, cancel_flag=None,
                    max_frames: Optional[Sequence[int]] = None, stats: Optional[dict] = None,
-                   continuous: Optional[bool] = None, plan_frames: Optional[Sequence[int]] = None) -> List[torch.Tensor]:
+                   continuous: Optional[bool] = None, plan_frames: Optional[Sequence[int]] = None, voices=None) -> List[torch.Tensor]:
         """Raw waveforms (GPU float32, 1-D) for any number of texts, in the order of ``texts``.
         The RNG stream of a text is its ``item_ids`` entry (default: its index), so the result does not depend on how the
         texts are scheduled.  More texts than ``max_batch`` are decoded with continuous batching (``continuous``, default on
@@ -303,6 +356,13 @@ class Engine:
         somewhere below its budget).  ``stats`` (optional dict) receives kept / launched row-frames of the schedule."""
         n = len(texts)
         ids = list(item_ids) if item_ids is not None else list(range(n))
+        # ``voices``: None, a bank name for every text, or a list (None entries: the engine's own voice) - they travel with the texts
+        # through every reordering below
+        names = None if voices is None else ([voices] * n if isinstance(voices, str) else list(voices))
+        self.voice_entries(names, n)                                       # (ValueError before anything is launched)
+
+        def pick(idx):
+            return None if names is None else [names[i] for i in idx]
         if max_frames is not None:
             frames = [int(f) for f in max_frames]
         else:
@@ -322,7 +382,7 @@ class Engine:
         if continuous and (n > self.max_batch or rows < n):
             order = sorted(range(n), key=lambda i: (-plan[i], i))          # longest first: short items fill the tail of the schedule
             codes = self.generate_codes([texts[i] for i in order], seed, [ids[i] for i in order], cancel_flag, [frames[i] for i in order],
-                                        max_rows=rows if rows < min(n, self.max_batch) else 0)
+                                        max_rows=rows if rows < min(n, self.max_batch) else 0, voices=pick(order))
             st = self.model.generate_stats()
             by_len = sorted(range(n), key=lambda j: (-int(codes[j].shape[0]), j))
             for j, w in zip(by_len, self.vocode([codes[j] for j in by_len])):
@@ -335,7 +395,7 @@ class Engine:
             return wavs  # type: ignore[return-value]
         batches = self.plan_batches(plan)
         for idx in batches:
-            codes = self.generate_codes([texts[i] for i in idx], seed, [ids[i] for i in idx], cancel_flag, [frames[i] for i in idx])
+            codes = self.generate_codes([texts[i] for i in idx], seed, [ids[i] for i in idx], cancel_flag, [frames[i] for i in idx], voices=pick(idx))
             for i, w in zip(idx, self.vocode(codes)):
                 wavs[i] = w
         if stats is not None:

@@ -108,6 +108,11 @@ class BatchedPipeline:
         decay: List[Tuple[float, bool]] = [(0.0, True)] * n
         scores: List[Tuple[List[float], List[float]]] = [([], []) for _ in range(n)]
         pending = list(owned)
+        cv = self._call_voices                               # (once per call, not per retry)
+        if cv is not None and self.max_iterations > 1 and any(cv[i] is not None for i in owned) and \
+                (getattr(self, "drift_scorer", None) is not None or hasattr(self, "_validate_accent_drift")):
+            logger.info(f"  {sum(cv[i] is not None for i in owned)} text(s) speak with a bank voice: accent drift is scored for the "
+                        "provider's own voice only")
         for attempt in range(self.max_decay_retries):
             if not pending:
                 break
@@ -148,10 +153,22 @@ class BatchedPipeline:
             out.append((final[i], len(seg_audio[i]), meta))
         return out
 
+    # Voices of the call in flight, one entry per TEXT (None: the provider's own voice), or None when the call names none
+    # (MI355XQwenTTS.generate(voices=...)).  Every segment of a text inherits its text's voice.
+    _call_voices: Optional[List[Optional[str]]] = None
+
+    def _work_voices(self, work) -> Optional[List[Optional[str]]]:
+        cv = self._call_voices
+        return None if cv is None else [cv[i] for i, _, _ in work]
+
     # one entry of `work` per (item, segment index, text); returns the accepted audio (or None) per entry
     def _generate_work(self, work, plans, token, progress_callback, scores, stream_ids=None, attempt: int = 0):
         if stream_ids is None:
             stream_ids = list(range(len(work)))
+        # the drift classifier is trained for the provider's own voice: segments of another voice are not scored (no drift_prob),
+        # their text match and the decay check run as ever
+        voices = self._work_voices(work)
+        foreign = None if voices is None else [v is not None for v in voices]
         accepted: List[Optional[torch.Tensor]] = [None] * len(work)
         # per-segment validation state, exactly the reference's locals (base_tts.py:765-768): best audio by drift, the
         # MINIMUM drift seen, the LAST text similarity computed (whenever the voice check passed), the last audio
@@ -174,9 +191,14 @@ class BatchedPipeline:
                 self._set_seeds()
                 # RNG stream of a segment = its index in the work list of the whole call: independent of how the list is cut into
                 # batches and of how many ranks share it
-                audios = self._generate_chunk([work[w][2] for w in chunk], [stream_ids[w] for w in chunk], token)
-                drifts = self._chunk_drifts(audios) if self.max_iterations > 1 else None
-                texts = self._chunk_texts(audios, drifts) if self.max_iterations > 1 else None
+                skip = None if foreign is None else [foreign[w] for w in chunk]
+                if voices is None:
+                    audios = self._generate_chunk([work[w][2] for w in chunk], [stream_ids[w] for w in chunk], token)
+                else:
+                    audios = self._generate_chunk([work[w][2] for w in chunk], [stream_ids[w] for w in chunk], token, [voices[w] for w in chunk])
+                scored = audios if skip is None else [None if f else a for a, f in zip(audios, skip)]
+                drifts = self._chunk_drifts(scored) if self.max_iterations > 1 else None
+                texts = self._chunk_texts(audios, drifts, skip) if self.max_iterations > 1 else None
                 for k, (w, a) in enumerate(zip(chunk, audios)):
                     if a is None:
                         retry.append(w)
@@ -189,7 +211,8 @@ class BatchedPipeline:
                             self._auto_sort_only(a)          # drift detection for auto-sort even without validation retries (:801-818)
                         continue
                     if self._validate_segment(a, work[w][2], state[w], None if drifts is None else drifts[k],
-                                              transcript=_NO_TRANSCRIPT if texts is None else texts[k]):
+                                              transcript=_NO_TRANSCRIPT if texts is None else texts[k],
+                                              score_drift=not (skip is not None and skip[k])):
                         accepted[w] = a                      # valid: this attempt's audio is kept (:859)
                     else:
                         retry.append(w)
@@ -224,11 +247,14 @@ class BatchedPipeline:
                 return [sorted(order[b0:b0 + bs]) for b0 in range(0, len(order), bs)]
         return [todo[b0:b0 + bs] for b0 in range(0, len(todo), bs)]
 
-    def _generate_chunk(self, segs: List[str], item_idx: List[int], token) -> List[Optional[torch.Tensor]]:
+    def _generate_chunk(self, segs: List[str], item_idx: List[int], token, voices=None) -> List[Optional[torch.Tensor]]:
         """One batched ``_generate_audio`` call; on failure fall back to one call per segment so that the
-        reference's per-segment error policy decides who fails."""
+        reference's per-segment error policy decides who fails.  ``voices``: a bank name (or None) per segment, handed on only when
+        the call names voices at all."""
+        def kw(k=None):
+            return {} if voices is None else {"voices": list(voices) if k is None else [voices[k]]}
         try:
-            out = self._generate_audio(list(segs), item_ids=item_idx, cancellation_token=token)
+            out = self._generate_audio(list(segs), item_ids=item_idx, cancellation_token=token, **kw())
             return list(out)
         except (ValueError, CancelledException):
             raise
@@ -236,9 +262,9 @@ class BatchedPipeline:
             if len(segs) == 1:
                 return [self._classify(first)]
         res: List[Optional[torch.Tensor]] = []
-        for seg, it in zip(segs, item_idx):
+        for k, (seg, it) in enumerate(zip(segs, item_idx)):
             try:
-                res.append(self._generate_audio(seg, item_ids=[it], cancellation_token=token))
+                res.append(self._generate_audio(seg, item_ids=[it], cancellation_token=token, **kw(k)))
             except (ValueError, CancelledException):
                 raise
             except Exception as e:  # noqa: BLE001
@@ -282,7 +308,7 @@ class BatchedPipeline:
         it = iter(vals)
         return [None if a is None else next(it) for a in audios]
 
-    def _chunk_texts(self, audios, drifts) -> Optional[list]:
+    def _chunk_texts(self, audios, drifts, skip=None) -> Optional[list]:
         """The transcript of every segment of a chunk that the per-segment order would transcribe, from ONE call of
         ``transcriber.batch`` (stt.WhisperTranscriber.batch: one native call for the chunk), aligned with ``audios``
         (``_NO_TRANSCRIPT`` where the segment is not in the call).  A segment is in the call when it has audio and its voice check
@@ -292,10 +318,12 @@ class BatchedPipeline:
         batch = getattr(getattr(self, "transcriber", None), "batch", None)
         if not callable(batch):
             return None
+        skip = list(skip) if skip is not None else [False] * len(audios)      # segments whose voice check is not run: they pass it
         if getattr(self, "drift_scorer", None) is not None:
-            if drifts is None:
+            if drifts is None and not all(f or a is None for a, f in zip(audios, skip)):
                 return None
-            take = [a is not None and d is not None and float(d) < self.accent_drift_threshold for a, d in zip(audios, drifts)]
+            drifts = drifts if drifts is not None else [None] * len(audios)
+            take = [a is not None and (f or (d is not None and float(d) < self.accent_drift_threshold)) for a, d, f in zip(audios, drifts, skip)]
         elif hasattr(self, "_validate_accent_drift"):
             return None
         else:
@@ -313,14 +341,37 @@ class BatchedPipeline:
         it = iter(vals)
         return [next(it) if t else _NO_TRANSCRIPT for t in take]
 
-    def _validate_segment(self, audio: torch.Tensor, text: str, st: dict, drift: Optional[float] = None, transcript=_NO_TRANSCRIPT) -> bool:
+    def _validate_segment(self, audio: torch.Tensor, text: str, st: dict, drift: Optional[float] = None, transcript=_NO_TRANSCRIPT,
+                          score_drift: bool = True) -> bool:
         """One validation attempt (base_tts.py:821-886), updating the segment's state in the reference's order: drift ->
         auto-sort -> best-by-drift -> text match only if the voice passed.  A validator that raises counts as a failed
         attempt but keeps what it had already recorded.  Returns True when the attempt is accepted.  ``drift``: the scorer's value
         for this audio when the chunk was scored in one call (``_chunk_drifts``); the scorer is then not called again.  ``transcript``:
-        likewise the transcriber's text from ``_chunk_texts`` (None is a transcript: "transcription failed")."""
+        likewise the transcriber's text from ``_chunk_texts`` (None is a transcript: "transcription failed").  ``score_drift=False``
+        (a segment of a bank voice, for which the classifier was not trained): the voice check is not run and passes, no drift is
+        recorded; the text check is the same."""
         scorer, transcriber = getattr(self, "drift_scorer", None), getattr(self, "transcriber", None)
         file_based = hasattr(self, "_validate_accent_drift")          # the reference's file-based validators (absent in the host mirror)
+        if not score_drift:
+            try:
+                if st["best"] is None:
+                    st["best"] = audio
+                text_ok = True
+                if transcriber is not None:
+                    from .validation import validate_text_match
+                    heard = transcriber(audio, self.sample_rate) if transcript is _NO_TRANSCRIPT else transcript
+                    text_ok, sim, _ = validate_text_match(heard, text, self.text_similarity_threshold)
+                    st["text_sim"] = sim
+                elif file_based:
+                    with self._validation_input(audio) as path:
+                        text_ok, sim, _ = self._validate_text_match(path, text)
+                    st["text_sim"] = sim
+                if text_ok:
+                    st["best"] = audio
+                return bool(text_ok)
+            except Exception as e:  # noqa: BLE001
+                logger.warning(f"    validation error ({e})")
+                return False
         if scorer is None and transcriber is None and not file_based:
             st["best"] = audio
             return True
@@ -616,7 +667,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
                  accent_drift_threshold: float = 0.17, text_similarity_threshold: float = 0.85,
                  sound_decay_threshold: float = 0.3, drift_model_path: Optional[str] = None,
                  phonetic_mapping: Optional[Dict[str, str]] = None, speaker_encoder_path: Optional[str] = None,
-                 speaker_similarity: str = "model"):
+                 speaker_similarity: str = "model", max_voices: int = 1):
         # Defaults are QwenTTS.__init__'s (providers/qwen.py:48-66) with ONE deviation: batch_size 32 instead of 5.  The reference
         # stores batch_size and never reads it (qwen.py:59,83), so no behaviour of its can depend on the value; here it is the
         # number of decode rows (BASELINE.json's headline batch).  max_iterations keeps the reference's 10: a caller who swaps
@@ -661,6 +712,14 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         self.drift_optimal_threshold: Optional[float] = None   # the exported file's metadata, known once the file is loaded
         self._lock = threading.RLock()
         self._voice_key = None
+        # The voice bank (an extension: the reference holds one voice per instance).  max_voices entries in the engine: the
+        # constructor's voice and up to max_voices - 1 named ones (add_voice), which generate(voices=...) / stream(voice=...) name per text.
+        if not 1 <= int(max_voices) <= 8:
+            raise ValueError(f"max_voices = {max_voices!r}: 1 .. 8")
+        self.max_voices = int(max_voices)
+        self._bank: Dict[str, tuple] = {}                      # name -> (reference_audio, reference_text, speaker, language)
+        self._bank_loaded: Dict[str, tuple] = {}               # name -> the configuration the engine's entry was built from
+        self._ge2e_bank: Dict[str, object] = {}                # name -> unit GE2E embedding of the voice's reference clip
         # decode-schedule figures of this instance's engine calls, accumulated until cleared: kept / launched row-frames
         # ("frames" / "padded_frames": their quotient is the row occupancy), rt_generate calls, row hand-overs
         self.last_schedule: Dict[str, int] = {}
@@ -687,7 +746,10 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
                     self._close_drift()
                     self._ctx.close()
                     self._ctx = None
-                self._engine = Engine(self.model_path, self._device_ordinal(), max_batch=max(1, min(128, int(self.batch_size))))
+                self._engine = Engine(self.model_path, self._device_ordinal(), max_batch=max(1, min(128, int(self.batch_size))),
+                                      max_voices=self.max_voices)
+                self._bank_loaded = {}
+                self._dp_bank_sent = {}                        # (a new engine holds no bank voice: data-parallel runs broadcast them again)
                 # the reference refines the limit from the checkpoint's max_position_embeddings (qwen.py:131-139); a checkpoint
                 # without one keeps MAX_MODEL_CHARS.  (The KV allocation - cfg.max_positions - is a separate number.)
                 hf_pos = int(getattr(self._engine.cfg, "hf_max_position_embeddings", 0) or 0)
@@ -705,8 +767,97 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
                              "Use a CustomVoice model with a named speaker, or provide reference audio.")
         return (self.speaker, self.language) if is_custom else (self.reference_audio_path, self.reference_text, self.language)
 
+    # ---------------------------------------------------------------- the voice bank
+    @property
+    def voices(self) -> List[str]:
+        """Names of the bank voices (the constructor's voice has none: it is what a text without a voice speaks with)."""
+        return sorted(self._bank)
+
+    def add_voice(self, name: str, reference_audio: Optional[str] = None, reference_text: Optional[str] = None,
+                  speaker: Optional[str] = None, language: Optional[str] = None) -> None:
+        """Register a voice beside the constructor's, by the constructor's mode rules (``_voice_config_key``): a named speaker with a
+        CustomVoice model, reference audio and its transcript with a Base model.  It is made resident on the GPU by the first call
+        that names it.  ValueError: no name, a mode the model does not have, a full bank."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("add_voice: a voice needs a name")
+        is_custom = "CustomVoice" in self.model_path
+        if is_custom and not speaker:
+            raise ValueError("CustomVoice model requires a named speaker. Select a built-in voice (e.g. Vivian, Ryan) "
+                             "or provide reference audio with a Base model for voice cloning.")
+        if not is_custom and reference_audio is None:
+            raise ValueError("Qwen Base model requires reference audio for voice cloning. "
+                             "Use a CustomVoice model with a named speaker, or provide reference audio.")
+        if reference_audio is not None and reference_text is None:
+            raise ValueError("reference_text (transcript of reference audio) is required when reference_audio is set")
+        if name not in self._bank and len(self._bank) >= self.max_voices - 1:
+            raise ValueError(f"the voice bank is full: {len(self._bank)} named voice(s) beside the constructor's (max_voices={self.max_voices})")
+        with self._lock:
+            self._bank[name] = (reference_audio, reference_text, speaker, language or self.language)
+            self._ge2e_bank.pop(name, None)
+
+    def remove_voice(self, name: str) -> None:
+        with self._lock:
+            if name not in self._bank:
+                raise ValueError(f"unknown voice {name!r}")
+            del self._bank[name]
+            self._ge2e_bank.pop(name, None)
+            if name in getattr(self, "_dp_bank_sent", {}):     # (a data-parallel run broadcasts it again if the name comes back)
+                self._dp_bank_sent = {k: v for k, v in self._dp_bank_sent.items() if k != name}
+            if self._bank_loaded.pop(name, None) is not None and self._engine is not None and name in self._engine.voices:
+                self._engine.remove_voice(name)
+
+    def _resolve_voices(self, voices, n: int) -> Optional[List[Optional[str]]]:
+        """``voices`` of a call -> one bank name (or None: the constructor's voice) per text, or None when the call names none.
+        ValueError before anything is launched: an unknown name, a list of the wrong length."""
+        if voices is None:
+            return None
+        names = [voices] * n if isinstance(voices, str) else list(voices)
+        if len(names) != n:
+            raise ValueError(f"voices: {len(names)} entries for {n} text(s)")
+        for v in names:
+            if v is not None and v not in self._bank:
+                raise ValueError(f"unknown voice {v!r} (add_voice first; bank: {self.voices})")
+        return names if any(v is not None for v in names) else None
+
+    def _ensure_bank(self, eng, names) -> None:
+        """The bank voices a call names, resident in the engine (built once per configuration)."""
+        for name in sorted({v for v in names if v is not None}):
+            cfg = self._bank[name]
+            if self._bank_loaded.get(name) == cfg and name in eng.voices:
+                continue
+            audio, text, speaker, language = cfg
+            from .voice import VoiceConditioning
+            cond = VoiceConditioning(language, speaker, None, [], None) if "CustomVoice" in self.model_path else \
+                eng.conditioning_from_audio(audio, text, language)
+            eng.add_voice(name, cond)
+            self._bank_loaded[name] = cfg
+
+    def _dp_share_bank(self, td, rank: int, dev, names) -> None:
+        """Data-parallel: rank 0 builds each bank voice the call names that the ranks do not hold yet; the others import its prefix
+        into the same entry.  The ranks agree by name and configuration, as they do for the constructor's voice by ``_voice_key``."""
+        from . import dist as D
+        eng = self._load_engine()
+        for name in sorted({v for v in names if v is not None}):
+            cfg = self._bank[name]
+            if getattr(self, "_dp_bank_sent", {}).get(name) == cfg:
+                continue
+            err = None
+            try:
+                if rank == 0:
+                    with self._lock:
+                        self._ensure_bank(eng, [name])
+            except BaseException as e:  # noqa: BLE001  (re-raised below, on every rank)
+                err = e
+            self._dp_agree(td, dev, err, f"voice conditioning of {name!r}")
+            index = eng.voices[name][0] if rank == 0 else (eng.voices[name][0] if name in eng.voices else eng.free_voice_entry())
+            D.broadcast_voice(eng, td, src=0, comm_device=dev, voice_index=index, name=name)
+            self._bank_loaded[name] = cfg
+            self._dp_bank_sent = dict(getattr(self, "_dp_bank_sent", {}), **{name: cfg})
+
     def _dp_share_voice(self, td, rank: int, dev) -> None:
         from . import dist as D
+        if self._call_voices is not None:
+            self._dp_share_bank(td, rank, dev, self._call_voices)
         eng, err, key = None, None, None
         try:
             eng = self._load_engine()
@@ -741,20 +892,27 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             return float(eng.frames_for(segment, len(eng.tokenizer.encode(segment))))
         return float(max(1, len(segment.split())))
 
-    def _compute_speaker_similarity(self, wav_tensor: torch.Tensor) -> float:
+    def _compute_speaker_similarity(self, wav_tensor: torch.Tensor, voice: Optional[str] = None) -> float:
         """Cosine similarity between generated audio and the reference voice (base_tts.py:325-346, which embeds both with
         resemblyzer on the CPU and is never called by the reference's own pipeline).  Here both embeddings come from the model's
         OWN speaker encoder on the GPU - the statistics-pooling head of the audio encoder that also conditions the talker
         (rt_voice_encode) - so the score says how close the output is in the space the model itself clones from.  Not comparable
         in value with resemblyzer's; same range and direction (1 = same voice).
         With ``speaker_similarity="ge2e"`` it is the reference's arithmetic instead: the dot product of the unit GE2E embeddings
-        (speaker.SpeakerEmbedder) of the reference clip and of the output; the reference clip's embedding is cached per voice."""
+        (speaker.SpeakerEmbedder) of the reference clip and of the output; the reference clip's embedding is cached per voice.
+        ``voice``: the bank voice the audio was generated with (None: the constructor's) - the comparison is against that voice's
+        own reference."""
+        self._resolve_voices(voice, 1)
         if self.speaker_similarity == "ge2e":
-            return self._ge2e_similarity(wav_tensor)
+            return self._ge2e_similarity(wav_tensor, voice)
         eng = self._load_engine()
         with self._lock:
-            self._ensure_voice(eng)
-            ref = None if eng.voice is None else eng.voice.speaker_embed
+            if voice is None:
+                self._ensure_voice(eng)
+                ref = None if eng.voice is None else eng.voice.speaker_embed
+            else:
+                self._ensure_bank(eng, [voice])
+                ref = eng.voices[voice][1].speaker_embed
             if ref is None:
                 raise ValueError("speaker similarity needs a cloned voice (reference audio with a Base model)")
             pcm = wav_tensor.detach().to(torch.float32).reshape(-1).cpu().numpy()
@@ -763,28 +921,36 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         ref = ref.detach().to(torch.float32).cpu().reshape(-1)
         return float(torch.dot(ref, emb) / (ref.norm() * emb.norm()).clamp_min(1e-12))
 
-    def _ge2e_reference_audio(self):
+    def _ge2e_reference_audio(self, voice: Optional[str] = None):
         """(samples, sample rate) of the configured reference clip, as the voice cloning reads it."""
-        if not self.reference_audio_path:
+        clip = self.reference_audio_path if voice is None else self._bank[voice][0]
+        if not clip:
             raise ValueError("speaker similarity needs a cloned voice (reference audio with a Base model)")
         import wave
         from .voice import load_audio
-        path = str(self.reference_audio_path)
+        path = str(clip)
         sr = self.sample_rate                                  # (a .npy clip is at the model's rate, as the cloning path takes it)
         if not path.endswith(".npy"):
             with wave.open(path, "rb") as wf:
                 sr = int(wf.getframerate())                    # the file's own rate: the encoder's resampler brings it to 16 kHz
         return torch.from_numpy(load_audio(path, sr)), sr
 
-    def _ge2e_similarity(self, wav_tensor: torch.Tensor) -> float:
+    def _ge2e_similarity(self, wav_tensor: torch.Tensor, voice: Optional[str] = None) -> float:
         with self._lock:
             emb = self._speaker_embed()
-            key = (self.reference_audio_path,)
-            if self._ge2e_ref is None or self._ge2e_ref[0] != key:
-                ref_pcm, ref_sr = self._ge2e_reference_audio()
-                self._ge2e_ref = (key, emb(ref_pcm, ref_sr).astype("float64"))
+            if voice is not None:                              # a bank voice: its reference embedding is cached under its name
+                if voice not in self._ge2e_bank:
+                    ref_pcm, ref_sr = self._ge2e_reference_audio(voice)
+                    self._ge2e_bank[voice] = emb(ref_pcm, ref_sr).astype("float64")
+                ref = self._ge2e_bank[voice]
+            else:
+                key = (self.reference_audio_path,)
+                if self._ge2e_ref is None or self._ge2e_ref[0] != key:
+                    ref_pcm, ref_sr = self._ge2e_reference_audio()
+                    self._ge2e_ref = (key, emb(ref_pcm, ref_sr).astype("float64"))
+                ref = self._ge2e_ref[1]
             out = emb(wav_tensor.detach().reshape(-1), self.sample_rate).astype("float64")
-            return float(self._ge2e_ref[1] @ out)
+            return float(ref @ out)
 
     def _cut_batches(self, todo: List[int], work, bs: int) -> List[List[int]]:
         """The engine decodes any number of segments on its ``batch_size`` rows with continuous batching (finished rows are handed
@@ -812,8 +978,13 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             watcher.start()
         try:
             with self._lock:
-                self._ensure_voice(eng)
-                wavs = eng.synthesize(texts, seed=int(self.seed), item_ids=kwargs.get("item_ids"), cancel_flag=flag, stats=self.last_schedule)
+                names = self._resolve_voices(kwargs.get("voices"), len(texts))
+                if names is None or any(v is None for v in names):
+                    self._ensure_voice(eng)
+                if names is not None:
+                    self._ensure_bank(eng, names)
+                wavs = eng.synthesize(texts, seed=int(self.seed), item_ids=kwargs.get("item_ids"), cancel_flag=flag, stats=self.last_schedule,
+                                      voices=names)
         except _native.CancelledError as e:
             raise CancelledException(str(e))
         finally:
@@ -823,10 +994,26 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         return wavs[0] if single else wavs
 
     def generate(self, texts, output_path: Optional[str] = None, cancellation_token: Optional[CancellationToken] = None,
-                 format: str = "wav", speed: float = 1.0, pitch_semitones: float = 0.0, progress_callback: Optional[Callable[[str], None]] = None):
+                 format: str = "wav", speed: float = 1.0, pitch_semitones: float = 0.0, progress_callback: Optional[Callable[[str], None]] = None,
+                 voices=None):
         """``BaseTTS.generate`` (base_tts.py:960-1101), inherited unchanged - except on the WORKER ranks of a data-parallel run
         (DataParallelPipeline): those do their share of the texts, deliver it to rank 0 and return nothing (``None`` for one
-        text, a list of ``None`` for a list) without writing any file; rank 0 returns and saves everything."""
+        text, a list of ``None`` for a list) without writing any file; rank 0 returns and saves everything.
+        ``voices`` (an extension): a bank name for every text, or a list as long as ``texts`` whose ``None`` entries mean the
+        constructor's voice; the segments of a text speak with its voice.  ValueError before anything runs: an unknown name, a list
+        of the wrong length."""
+        n_texts = 1 if isinstance(texts, str) else len(texts)
+        names = self._resolve_voices(voices, n_texts)
+        if names is None:
+            return self._generate_call(texts, output_path, cancellation_token, format, speed, pitch_semitones, progress_callback)
+        with self._lock:                                        # (the call's voices are instance state while the inherited body runs)
+            self._call_voices = names
+            try:
+                return self._generate_call(texts, output_path, cancellation_token, format, speed, pitch_semitones, progress_callback)
+            finally:
+                self._call_voices = None
+
+    def _generate_call(self, texts, output_path, cancellation_token, format, speed, pitch_semitones, progress_callback):
         dp = self._dp()
         if dp is None or dp[1] == 0:
             return super().generate(texts, output_path, cancellation_token, format, speed, pitch_semitones, progress_callback)
@@ -845,7 +1032,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         return None if single else [None] * len(texts)
 
     def stream(self, text: str, cancellation_token: Optional[CancellationToken] = None, speed: float = 1.0,
-               pitch_semitones: float = 0.0):
+               pitch_semitones: float = 0.0, voice: Optional[str] = None):
         """``BaseTTS.stream`` (base_tts.py:1132-1190): one result per segment, no crossfade, failed segments skipped - with the
         same audio per segment, produced in two calls instead of one per segment: the FIRST segment alone (time to first
         audio = one short decode), then ALL the others in one batched call while the caller is busy with the first.
@@ -853,8 +1040,12 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         sequential loop's."""
         from .api import GenerationResult
         token = cancellation_token or CancellationToken()
+        self._resolve_voices(voice, 1)                          # (``voice``: a bank name; ValueError for an unknown one before anything runs)
+        vkw = {} if voice is None else {"voices": voice}
         segments = self._split_text_into_segments(self._apply_phonetic_mapping(text), self._compute_max_chars())
         if int(getattr(self, "stream_chunk_frames", 0) or 0) > 0:
+            if voice is not None:
+                raise ValueError("sub-segment streaming (stream_chunk_frames) speaks with the constructor's voice only")
             yield from self._stream_chunks(segments, token, speed, pitch_semitones)
             return
 
@@ -872,14 +1063,14 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
                 continue
             self._set_seeds()
             try:
-                raws: List[Optional[torch.Tensor]] = list(self._generate_audio(list(group), item_ids=[0] * len(group), cancellation_token=token))
+                raws: List[Optional[torch.Tensor]] = list(self._generate_audio(list(group), item_ids=[0] * len(group), cancellation_token=token, **vkw))
             except CancelledException:
                 return
             except Exception as first_error:  # noqa: BLE001  (the batch failed: let every segment fail or pass on its own)
                 raws = []
                 for seg in group:
                     try:
-                        raws.append(self._generate_audio(seg, cancellation_token=token))
+                        raws.append(self._generate_audio(seg, cancellation_token=token, **vkw))
                     except CancelledException:
                         return
                     except Exception as e:  # noqa: BLE001
