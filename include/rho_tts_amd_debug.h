@@ -324,6 +324,50 @@ RT_API int rt_debug_gemm_epi(rt_ctx* ctx, const void* d_a, int32_t a_form, int64
                              int32_t rows_out, int32_t rows_in, const void* d_w_bf16, int32_t N, const rt_debug_epi* e, const void* d_w2_bf16,
                              const rt_debug_epi* e2, int32_t pair_mode);
 
+/* The sampler launch in the form the decode loop gives it (generate.hip, rt_gen_run::enqueue_a; tests/test_sampler_frame_gpu.py):
+ * every caller-visible field of SampleArgs (kernels.h).  The hook calls launch_sample - its dispatch and refusals are under test -
+ * synchronises once and returns the status.
+ *   logits [n_slabs][M][V] f32, summed in slab order; item_ids [M] (the low half keys the random stream); *seed and *frame are read
+ *   on the device; row r draws at its own frame *frame - frame_off[r] (frame_off NULL: 0) in code group `group`; the end of sequence
+ *   (eos_token, -1: none) is admitted for a row when eos_live != 0 and its own frame >= min_frames, tokens >= suppress_from are
+ *   forbidden otherwise; seen [M][V] (optional) is the penalty history, read and updated; forced (optional) [frames][forced_fs]:
+ *   row r takes forced[*frame * forced_fs + r] when that is >= 0.
+ *   Outputs of frame f = *frame: out[f * out_fs + r * out_stride] = the token (0 for an end of sequence),
+ *   eos_flag[f * eos_fs + r] (optional), logits_copy[f * copy_fs + r * V + i] = the summed logits (optional).
+ *   emb_table [V][emb_H] f32 (optional; V <= 4096, emb_H % 32 == 0): the drawn token's row becomes emb_x [M][emb_H] f32, emb_a [M][emb_H]
+ *   = bf16(emb_norm_w .* x) and emb_rowsq [M][emb_rowsq_n] = (sum of squares, 0, ...); with emb_qkv_table [V][emb_qkv_n] f32 its row of the
+ *   token is copied to emb_qkv_out [M][emb_qkv_n] and only emb_x is written.  emb_x / emb_a are row-major here: the kernel runs on
+ *   tiled copies made from them and copied back (see the row-kernel hooks above).
+ * Refused before any launch: a NULL ctx / args / logits / item_ids / seed / frame / out, M < 1, V < 1, n_slabs < 1, out_stride < 1,
+ * *frame < 0, a frame_off entry above *frame, and - with an embedding - a forced token >= V. */
+typedef struct rt_debug_sample_frame_args {
+    const float* d_logits;
+    const int64_t* d_item_ids;
+    const uint64_t* d_seed;
+    const int32_t* d_frame;
+    const int32_t* d_frame_off;
+    uint8_t* d_seen;
+    const int32_t* d_forced;
+    int32_t* d_out;
+    int32_t* d_eos_flag;
+    float* d_logits_copy;
+    const float* d_emb_table;
+    const float* d_emb_norm_w;
+    float* d_emb_rowsq;
+    float* d_emb_x;
+    void* d_emb_a_bf16;
+    const float* d_emb_qkv_table;
+    float* d_emb_qkv_out;
+    int64_t out_fs, eos_fs, forced_fs, copy_fs;
+    rt_sampling sp;
+    int32_t n_slabs, M, V;
+    int32_t suppress_from, group;
+    int32_t eos_token, eos_live, min_frames;
+    int32_t out_stride;
+    int32_t emb_H, emb_rowsq_n, emb_qkv_n;
+} rt_debug_sample_frame_args;
+RT_API int rt_debug_sample_frame(rt_ctx* ctx, const rt_debug_sample_frame_args* args);
+
 /* ------------------------------------------------------------------ the conditioning front-end's own kernels (encoder.hip;
  * tests/test_encoder_kernels_gpu.py).  Each hook checks its pointers, calls the production launch_* function (whose dispatch and
  * refusals are under test too), synchronises the stream once and returns the status.  All pointers are HBM unless named h_*.

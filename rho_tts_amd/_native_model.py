@@ -56,6 +56,16 @@ class RtDebugEpi(C.Structure):
                [("ldc", C.c_int64), ("act", C.c_int32), ("act2", C.c_int32)]
 
 
+class RtDebugSampleFrame(C.Structure):
+    """rt_debug_sample_frame_args (include/rho_tts_amd_debug.h): the sampler launch as the decode loop gives it."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_logits", "d_item_ids", "d_seed", "d_frame", "d_frame_off", "d_seen", "d_forced", "d_out",
+                                          "d_eos_flag", "d_logits_copy", "d_emb_table", "d_emb_norm_w", "d_emb_rowsq", "d_emb_x",
+                                          "d_emb_a_bf16", "d_emb_qkv_table", "d_emb_qkv_out")] + \
+               [(n, C.c_int64) for n in ("out_fs", "eos_fs", "forced_fs", "copy_fs")] + [("sp", RtSampling)] + \
+               [(n, C.c_int32) for n in ("n_slabs", "M", "V", "suppress_from", "group", "eos_token", "eos_live", "min_frames", "out_stride",
+                                         "emb_H", "emb_rowsq_n", "emb_qkv_n")]
+
+
 def declare(lib: C.CDLL) -> None:
     vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     lib.rt_model_create.argtypes = [vp, C.POINTER(RtModelConfig), C.POINTER(vp)]
@@ -104,6 +114,7 @@ def declare(lib: C.CDLL) -> None:
                                                     C.POINTER(i32), C.POINTER(i32), vp]
     lib.rt_debug_attention_prefill.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     lib.rt_debug_sample.argtypes = [vp, vp, i32, i32, C.POINTER(RtSampling), C.c_uint64, i32, i32, i32, i32, vp, vp]
+    lib.rt_debug_sample_frame.argtypes = [vp, C.POINTER(RtDebugSampleFrame)]
     # the row kernels and the tiled GEMM's epilogue on their own (tests/test_rowops_gpu.py, tests/test_gemm_epilogue_gpu.py)
     pvp, pi64 = C.POINTER(vp), C.POINTER(i64)
     lib.rt_debug_add_rmsnorm.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp, f32, vp, vp]

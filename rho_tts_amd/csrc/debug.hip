@@ -602,6 +602,53 @@ int rt_debug_embed_rowsq(rt_ctx* ctx, const void* const* h_tables, const int64_t
     return dbg_finish(ctx, rc);
 }
 
+int rt_debug_sample_frame(rt_ctx* ctx, const rt_debug_sample_frame_args* p) {
+    if (!ctx || !p || !p->d_logits || !p->d_item_ids || !p->d_seed || !p->d_frame || !p->d_out || p->M < 1 || p->V < 1 || p->n_slabs < 1 ||
+        p->out_stride < 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_sample_frame: bad argument (logits, item ids, seed, frame and out are needed; M, V, n_slabs, out_stride >= 1)");
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    const int M = p->M, H = p->emb_H;
+    // what moves an address is read back first: the frame (every frame-strided buffer), the rows' starts, forced tokens that index a table
+    std::vector<int32_t> hf, h;
+    RT_TRY(dbg_read_i32(ctx, p->d_frame, 1, hf));
+    if (hf[0] < 0) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_sample_frame: frame %d", hf[0]);
+    if (p->d_frame_off) {
+        RT_TRY(dbg_read_i32(ctx, p->d_frame_off, M, h));
+        for (int32_t v : h) if (v > hf[0]) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_sample_frame: a row starts at frame %d, after frame %d", v, hf[0]);
+    }
+    if (p->d_forced && p->d_emb_table) {
+        RT_TRY(dbg_read_i32(ctx, p->d_forced + (int64_t)hf[0] * p->forced_fs, M, h));
+        for (int32_t v : h) if (v >= p->V) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_sample_frame: forced token %d outside the embedding table", v);
+    }
+    DbgBufs bufs(ctx);
+    float* x_t = p->d_emb_x;
+    bf16_t* a_t = (bf16_t*)p->d_emb_a_bf16;
+    // (a width the tiled layout cannot hold goes to the launcher as it is: the refusal is launch_sample's, and nothing is launched)
+    const bool tiled = p->d_emb_table && H >= 32 && H % 32 == 0;
+    if (tiled && x_t) RT_TRY(dbg_tile_in(ctx, bufs, (const float*)p->d_emb_x, M, H, &x_t));
+    if (tiled && a_t) RT_TRY(dbg_tile_in(ctx, bufs, (const bf16_t*)p->d_emb_a_bf16, M, H, &a_t));
+    SampleArgs a{};
+    a.logits = p->d_logits; a.n_slabs = p->n_slabs; a.M = M; a.V = p->V;
+    a.do_sample = p->sp.do_sample; a.temperature = p->sp.temperature; a.top_k = p->sp.top_k; a.top_p = p->sp.top_p; a.rep_penalty = p->sp.repetition_penalty;
+    a.seen = p->d_seen; a.suppress_from = p->suppress_from; a.allow_token = -1;
+    a.seed_ptr = p->d_seed; a.item_ids = p->d_item_ids; a.frame = 0; a.group = p->group;
+    a.forced = p->d_forced; a.forced_fs = p->forced_fs;
+    a.out = p->d_out; a.out_stride = p->out_stride; a.out_fs = p->out_fs;
+    a.eos_token = p->eos_token; a.eos_flag = p->d_eos_flag; a.eos_fs = p->eos_fs;
+    a.logits_copy = p->d_logits_copy; a.copy_fs = p->copy_fs;
+    a.frame_ptr = p->d_frame; a.frame_off = p->d_frame_off; a.eos_live = p->eos_live; a.min_frames = p->min_frames;
+    a.emb_table = p->d_emb_table; a.emb_H = H; a.emb_norm_w = p->d_emb_norm_w; a.emb_rowsq = p->d_emb_rowsq; a.emb_rowsq_n = p->emb_rowsq_n;
+    a.emb_x_tiled = x_t; a.emb_a_tiled = a_t;
+    a.emb_qkv_table = p->d_emb_qkv_table; a.emb_qkv_out = p->d_emb_qkv_out; a.emb_qkv_n = p->emb_qkv_n;
+    int rc = launch_sample(ctx, a);
+    if (!rc && tiled) {
+        rc = dbg_tile_out(ctx, (const float*)x_t, M, H, p->d_emb_x);
+        if (!rc) rc = dbg_tile_out(ctx, (const bf16_t*)a_t, M, H, (bf16_t*)p->d_emb_a_bf16);
+    }
+    return dbg_finish(ctx, rc);
+}
+
 int rt_debug_silu_mul(rt_ctx* ctx, const float* d_slabs, int32_t n_slabs, int32_t M, int32_t I, void* d_out_bf16, float* d_out_f32) {
     if (!ctx || !d_slabs || n_slabs < 1 || M < 1 || I < 1 || (!d_out_bf16 && !d_out_f32)) return rt_fail(ctx, RT_ERR_INVALID, "rt_debug_silu_mul: bad argument");
     CtxLock g(ctx);

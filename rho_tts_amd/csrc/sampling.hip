@@ -626,8 +626,10 @@ int launch_sample(rt_ctx* ctx, const SampleArgs& a) {
     if (a.do_sample && (a.top_k < 1 || a.top_k > 64)) return rt_fail(ctx, RT_ERR_INVALID, "sampling needs 1 <= top_k <= 64 (got %d)", a.top_k);
     if (a.do_sample && !(a.temperature > 0.f)) return rt_fail(ctx, RT_ERR_INVALID, "sampling needs temperature > 0");
     if (a.V > 16384) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "vocabulary %d too large for the sampler", a.V);
-    if (a.emb_table && (a.V > 4096 || a.emb_H % 8 || !a.emb_norm_w || !a.emb_rowsq || a.emb_rowsq_n < 1 || !a.emb_x_tiled || !a.emb_a_tiled))
-        return rt_fail(ctx, RT_ERR_INVALID, "sample: fused embedding needs V <= 4096, H %% 8 == 0 and all its buffers");
+    // (H % 32: the tiled layout's k-tiles are whole - common.h tile_off folds a row block's last partial tile onto the next block's
+    //  first one, and behind the buffer's end in the last block)
+    if (a.emb_table && (a.V > 4096 || a.emb_H < 32 || a.emb_H % 32 || !a.emb_norm_w || !a.emb_rowsq || a.emb_rowsq_n < 1 || !a.emb_x_tiled || !a.emb_a_tiled))
+        return rt_fail(ctx, RT_ERR_INVALID, "sample: fused embedding needs V <= 4096, H %% 32 == 0 and all its buffers");
     if (a.emb_qkv_table && (!a.emb_table || !a.emb_qkv_out || a.emb_qkv_n < 4 || a.emb_qkv_n % 4))
         return rt_fail(ctx, RT_ERR_INVALID, "sample: the q/k/v table needs the fused embedding, an output and a row width that is a multiple of 4");
     if (a.V <= 1024) hipLaunchKernelGGL((k_sample_w<4, 4>), dim3(a.M), dim3(256), 0, ctx->stream, a);
