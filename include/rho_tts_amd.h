@@ -167,6 +167,12 @@ RT_API int rt_pcm16(rt_ctx* ctx, const float* d_in, int64_t n, int16_t* d_out);
 #define RT_STREAM_FADE_OUT   0x10u
 RT_API int rt_stream_chunk(rt_ctx* ctx, const rt_post_params* p, const float* d_in, int64_t n, uint32_t flags, double* h_dc_gain,
                            float* d_out, int64_t* h_out_len);
+/* rt_stream_chunk for the chunks of several listeners at once: one upload, one launch (a workgroup per item), one download.
+ *   h_in_ptr / h_out_ptr [n_items] device pointers, h_n / h_flags [n_items], h_dc_gain [n_items][2] in/out, h_out_len [n_items] out.
+ * Every item gets exactly the samples, length, dc and gain that rt_stream_chunk gives it alone (the two kernels share one body).  An
+ * item with n == 0 writes nothing and keeps its state (h_out_len 0). */
+RT_API int rt_stream_chunks(rt_ctx* ctx, const rt_post_params* p, int32_t n_items, const float* const* h_in_ptr, const int64_t* h_n,
+                            const uint32_t* h_flags, double* h_dc_gain, float* const* h_out_ptr, int64_t* h_out_len);
 
 /* ------------------------------------------------------------------ model
  * Stands behind the third-party model object the reference drives
@@ -334,6 +340,57 @@ RT_API int rt_generate_end(rt_model* m, int32_t* h_codes, int32_t* h_n_frames);
 /* Figures of the last rt_generate: decode frames launched, rows, frames kept over all items (row occupancy =
  * frames_kept / (frames_run * rows)) and the number of row hand-overs to queued items.  Any pointer may be NULL. */
 RT_API int rt_generate_stats(rt_model* m, int64_t* frames_run, int64_t* rows, int64_t* frames_kept, int64_t* hand_overs);
+
+/* An OPEN run: a generation whose item list grows while it decodes (a serving session: requests join a running batch).  Everything
+ * that sizes a buffer is declared when the run is opened; the items come later, one rt_generate_submit each.  An item's codes are bit
+ * for bit the codes it gets alone with its voice (rt_generate with one item), whatever else is on the rows and whenever it arrived.
+ *   rows              decode rows of the run, 1 .. max_batch (they are all stepped every frame, busy or not)
+ *   max_text_tokens   longest text of a later submit          max_frames   largest max_frames of a later submit
+ *   horizon           frame-counter values the run may use (it sizes the code and end-of-sequence buffers: horizon * rows *
+ *                     (n_groups + 1) * 4 bytes in HBM and as much on the host).  Frames are only counted while items decode.
+ *   h_voices          [n_voices] the bank entries items may name (each set).  The run always takes the block-table form of a
+ *                     multi-voice run (rt_generate_item_voices), and which attention launches a step takes is fixed by THIS list.
+ *   seed, talker, predictor, ignore_eos, min_frames, the special ids, h_cancel_flag: of the run, as in rt_generate_args.
+ *   n_items, h_text_ids, h_text_offsets, h_max_frames, h_item_ids, h_item_voices: an optional first list (n_items may be 0), each item
+ *                     submitted in order as rt_generate_submit would.
+ *   h_forced_codes, d_trace_talker, d_trace_predictor: must be NULL (RT_ERR_UNSUPPORTED).
+ * rt_generate_submit appends one item and returns its index in *h_item (what rt_generate_peek takes).  The item gets a row at the
+ * next hand-over look by the voice plan's rule (4-row blocks of one voice, submission order within a voice); until then it waits.
+ * Refused, the run undisturbed: RT_ERR_INVALID - text longer or more frames than declared, a voice outside the declared list or not
+ * set, a text id out of range; RT_ERR_LENGTH - prefix + text + frames exceed max_positions, or the remaining horizon cannot hold the
+ * item ("horizon spent": let the run drain, end it and open another); RT_ERR_STATE - no run in flight, or a closed-list run.
+ * rt_generate_cancel_item ends one item: its row is free at the next look, its frames so far stay readable, rt_generate_peek reports
+ * it finished; nobody else's codes change.
+ * rt_generate_step on an open run with nothing decoding and nothing waiting launches no frame and returns *h_all_done = 1; the run
+ * stays open (RT_ERR_STATE, and the run is dropped, should it ever reach its horizon with items unfinished), and after a later submit the next step places the new items on the empty rows as a first wave is placed.
+ * rt_generate_end closes the run (h_codes / h_n_frames as for rt_generate_begin: every submitted item must have ended);
+ * rt_generate_stats then reports the whole run.  Only the host waits, and only for launched work: nothing spins on the device. */
+typedef struct rt_generate_open_args {
+    int32_t rows, max_text_tokens, max_frames, horizon;
+    int32_t n_voices;
+    const int32_t* h_voices;
+    uint64_t seed;
+    rt_sampling talker, predictor;
+    int32_t ignore_eos, min_frames;
+    int32_t tts_eos_id, tts_pad_id, codec_pad_id, codec_bos_id;
+    const volatile int32_t* h_cancel_flag;
+    int32_t n_items;
+    const int32_t* h_text_ids;
+    const int32_t* h_text_offsets;
+    const int32_t* h_max_frames;
+    const int64_t* h_item_ids;
+    const int32_t* h_item_voices;
+    const int32_t* h_forced_codes;
+    float* d_trace_talker;
+    float* d_trace_predictor;
+} rt_generate_open_args;
+RT_API int rt_generate_open(rt_model* m, const rt_generate_open_args* args);
+RT_API int rt_generate_submit(rt_model* m, const int32_t* h_text_ids, int32_t n_text, int32_t max_frames, int64_t item_id, int32_t voice,
+                              int32_t* h_item);
+RT_API int rt_generate_cancel_item(rt_model* m, int32_t item);
+/* Frames between two looks at the rows (hand-over cadence): of the run in flight, else what the next open run will take.  The bounds
+ * of rt_generate_open / rt_generate_submit count 2 x this value of slack, and a caller that steps an open run steps by it. */
+RT_API int32_t rt_generate_cadence(rt_model* m);
 
 /* Codec decoder: h_codes [n_items][t_max][num_quantizers] (right-padded), h_n_frames [n_items];
  * d_wav [n_items][wav_stride] float32 in HBM, h_wav_len out.  rt_wav_length(frames) = samples produced. */

@@ -95,8 +95,15 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_post_process_host.argtypes = post_args
     lib.rt_pcm16.argtypes = [vp, vp, i64, vp]
     lib.rt_stream_chunk.argtypes = [vp, C.POINTER(PostParams), vp, i64, C.c_uint32, C.POINTER(C.c_double), vp, C.POINTER(i64)]
+    lib.rt_stream_chunks.argtypes = [vp, C.POINTER(PostParams), i32, C.POINTER(vp), C.POINTER(i64), C.POINTER(C.c_uint32), C.POINTER(C.c_double),
+                                     C.POINTER(vp), C.POINTER(i64)]
     from . import _native_model
     _native_model.declare(lib)
+
+
+class LengthError(RuntimeError):
+    """RT_ERR_LENGTH.  A RuntimeError whose text says "length", as every caller before it saw; a class of its own so that a caller can
+    tell the status without reading the text."""
 
 
 def raise_for_status(lib, ctx, rc: int, what: str) -> None:
@@ -110,8 +117,8 @@ def raise_for_status(lib, ctx, rc: int, what: str) -> None:
         raise CancelledError(text)
     if rc == RT_ERR_OOM and "out of memory" not in text.lower():
         text = "out of memory: " + text
-    if rc == RT_ERR_LENGTH and "length" not in text.lower():
-        text = "length: " + text
+    if rc == RT_ERR_LENGTH:
+        raise LengthError(text if "length" in text.lower() else "length: " + text)
     raise RuntimeError(text)
 
 
@@ -230,6 +237,34 @@ class Context:
                                             C.c_void_p(out.data_ptr()), C.byref(n_out)), "rt_stream_chunk")
         state[0], state[1] = float(st[0]), float(st[1])
         return out[: n_out.value]
+
+    @staticmethod
+    def stream_flags(first: bool, last: bool) -> int:
+        return (STREAM_MEASURE | STREAM_TRIM_START | STREAM_FADE_IN if first else 0) | (STREAM_TRIM_END | STREAM_FADE_OUT if last else 0)
+
+    def stream_chunks(self, params: PostParams, xs, states, flags):
+        """rt_stream_chunks: ``stream_chunk`` for the chunks of several listeners in ONE launch.  ``xs``: 1-D float32 GPU tensors (an
+        empty one is left alone), ``states``: one ``[dc, gain]`` list per item (updated in place), ``flags``: the RT_STREAM_* bits per
+        item (``stream_flags``).  Returns the processed chunks; each equals what ``stream_chunk`` returns for that item alone."""
+        import torch
+        n = len(xs)
+        if n == 0:
+            return []
+        xs = [x.detach().reshape(-1).to(torch.float32).contiguous() for x in xs]
+        if not all(x.is_cuda for x in xs):
+            raise ValueError("stream_chunks expects GPU tensors")
+        outs = [torch.empty(max(1, x.numel()), dtype=torch.float32, device=x.device) for x in xs]
+        ins = (C.c_void_p * n)(*[C.c_void_p(x.data_ptr() if x.numel() else 0) for x in xs])
+        ops = (C.c_void_p * n)(*[C.c_void_p(o.data_ptr()) for o in outs])
+        lens = (C.c_int64 * n)(*[int(x.numel()) for x in xs])
+        fl = (C.c_uint32 * n)(*[int(f) for f in flags])
+        st = (C.c_double * (2 * n))(*[float(v) for s in states for v in (s[0], s[1])])
+        n_out = (C.c_int64 * n)()
+        torch.cuda.current_stream(xs[0].device).synchronize()
+        self.check(self.lib.rt_stream_chunks(self.handle, C.byref(params), n, ins, lens, fl, st, ops, n_out), "rt_stream_chunks")
+        for i, s in enumerate(states):
+            s[0], s[1] = float(st[2 * i]), float(st[2 * i + 1])
+        return [o[: n_out[i]] for i, o in enumerate(outs)]
 
     def pcm16(self, x):
         import torch

@@ -49,6 +49,18 @@ class RtGenerateArgs(C.Structure):
                 ("d_trace_talker", C.c_void_p), ("d_trace_predictor", C.c_void_p), ("max_rows", C.c_int32)]
 
 
+class RtGenerateOpenArgs(C.Structure):
+    """rt_generate_open_args: the capacities, voices and sampling of an open run (items come by rt_generate_submit)."""
+    _fields_ = [("rows", C.c_int32), ("max_text_tokens", C.c_int32), ("max_frames", C.c_int32), ("horizon", C.c_int32),
+                ("n_voices", C.c_int32), ("h_voices", C.POINTER(C.c_int32)), ("seed", C.c_uint64),
+                ("talker", RtSampling), ("predictor", RtSampling), ("ignore_eos", C.c_int32), ("min_frames", C.c_int32),
+                ("tts_eos_id", C.c_int32), ("tts_pad_id", C.c_int32), ("codec_pad_id", C.c_int32), ("codec_bos_id", C.c_int32),
+                ("h_cancel_flag", C.POINTER(C.c_int32)), ("n_items", C.c_int32), ("h_text_ids", C.POINTER(C.c_int32)),
+                ("h_text_offsets", C.POINTER(C.c_int32)), ("h_max_frames", C.POINTER(C.c_int32)), ("h_item_ids", C.POINTER(C.c_int64)),
+                ("h_item_voices", C.POINTER(C.c_int32)), ("h_forced_codes", C.POINTER(C.c_int32)),
+                ("d_trace_talker", C.c_void_p), ("d_trace_predictor", C.c_void_p)]
+
+
 class RtDebugEpi(C.Structure):
     """rt_debug_epi (include/rho_tts_amd_debug.h): the tiled GEMM's epilogue as rt_debug_gemm_epi takes it."""
     _fields_ = [(n, C.c_void_p) for n in ("bias", "scale", "residual", "out_f32", "out_bf16", "out_hi", "out_lo", "snake_a", "snake_ib",
@@ -98,6 +110,11 @@ def declare(lib: C.CDLL) -> None:
     lib.rt_generate_step.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.rt_generate_peek.argtypes = [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.rt_generate_end.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    lib.rt_generate_open.argtypes = [vp, C.POINTER(RtGenerateOpenArgs)]
+    lib.rt_generate_submit.argtypes = [vp, C.POINTER(i32), i32, i32, i64, i32, C.POINTER(i32)]
+    lib.rt_generate_cancel_item.argtypes = [vp, i32]
+    lib.rt_generate_cadence.restype = i32
+    lib.rt_generate_cadence.argtypes = [vp]
     lib.rt_wav_length.restype = i64
     lib.rt_wav_length.argtypes = [vp, i32]
     lib.rt_code2wav.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), vp, i64, C.POINTER(i64)]
@@ -605,6 +622,65 @@ class NativeModel:
             out.append(flat[off: off + nfr[b]].clone())
             off += max_frames[b]
         return out
+
+    # ---- an open run (rt_generate_open / _submit / _cancel_item): the item list grows while the run decodes
+    def generate_open(self, rows: int, max_text_tokens: int, max_frames: int, horizon: int, voices: Sequence[int], talker=None,
+                      predictor=None, seed: int = 789, ignore_eos: bool = True, min_frames: int = 2, cancel_flag=None,
+                      first: Optional[Sequence[Tuple[Sequence[int], int, int, int]]] = None, _forced=None, _trace=None) -> None:
+        """Open a run on ``rows`` decode rows for texts of up to ``max_text_tokens`` tokens and ``max_frames`` frames, ``horizon`` frame
+        counter values, and items that speak with the bank entries ``voices``.  ``first``: optional (text ids, max_frames, item id, voice)
+        tuples submitted with the call.  Step it with ``generate_step``, read it with ``generate_peek``, close it with ``generate_end``."""
+        c = self.cfg
+        a = RtGenerateOpenArgs()
+        a.rows, a.max_text_tokens, a.max_frames, a.horizon = int(rows), int(max_text_tokens), int(max_frames), int(horizon)
+        vs = [int(v) for v in voices]
+        varr = (C.c_int32 * max(1, len(vs)))(*vs)
+        a.n_voices, a.h_voices = len(vs), varr
+        a.seed = seed
+        a.talker = talker or RtSampling(0, 0.9, 50, 1.0, 1.0)
+        a.predictor = predictor or a.talker
+        a.ignore_eos, a.min_frames = int(ignore_eos), min_frames
+        a.tts_eos_id, a.tts_pad_id, a.codec_pad_id, a.codec_bos_id = c.tts_eos_id, c.tts_pad_id, c.codec_pad_id, c.codec_bos_id
+        keep = [varr]
+        if cancel_flag is not None:
+            a.h_cancel_flag = C.pointer(cancel_flag)
+            keep.append(cancel_flag)
+        if first:
+            flat = [int(t) for f in first for t in f[0]]
+            offs = [0]
+            for f in first:
+                offs.append(offs[-1] + len(f[0]))
+            n = len(first)
+            a.n_items = n
+            a.h_text_ids = (C.c_int32 * max(1, len(flat)))(*flat)
+            a.h_text_offsets = (C.c_int32 * (n + 1))(*offs)
+            a.h_max_frames = (C.c_int32 * n)(*[int(f[1]) for f in first])
+            a.h_item_ids = (C.c_int64 * n)(*[int(f[2]) for f in first])
+            a.h_item_voices = (C.c_int32 * n)(*[int(f[3]) for f in first])
+        if _forced is not None:                                # (refused by the library: tests/test_open_run_gpu.py)
+            a.h_forced_codes = _forced
+        if _trace is not None:
+            a.d_trace_talker = _trace
+        self._run_keep = (keep, [int(f[1]) for f in (first or [])])
+        self.ctx.check(self.lib.rt_generate_open(self.handle, C.byref(a)), "rt_generate_open")
+
+    def generate_submit(self, text: Sequence[int], max_frames: int, item_id: int, voice: int) -> int:
+        """Append one item to the open run; returns its index (what ``generate_peek`` and ``generate_cancel_item`` take)."""
+        ids = (C.c_int32 * max(1, len(text)))(*[int(t) for t in text])
+        item = C.c_int32(-1)
+        self.ctx.check(self.lib.rt_generate_submit(self.handle, ids, len(text), int(max_frames), int(item_id), int(voice), C.byref(item)),
+                       "rt_generate_submit")
+        keep = getattr(self, "_run_keep", None)
+        if keep:
+            keep[1].append(int(max_frames))
+        return int(item.value)
+
+    def cadence(self) -> int:
+        """Frames between two looks at the rows: of the run in flight, else what the next open run will take."""
+        return int(self.lib.rt_generate_cadence(self.handle))
+
+    def generate_cancel_item(self, item: int) -> None:
+        self.ctx.check(self.lib.rt_generate_cancel_item(self.handle, int(item)), "rt_generate_cancel_item")
 
     def generate_stats(self) -> dict:
         """Figures of the last ``generate``: decode frames launched, rows, frames kept, row hand-overs to queued items."""

@@ -78,6 +78,27 @@ struct rt_gen_run {
     VoiceBlock* d_vblocks = nullptr;
     int32_t* d_vlists = nullptr;
 
+    // an OPEN run (rt_generate_open): the item list grows by rt_generate_submit while the run decodes.  Always the multi-voice form on
+    // a fixed number of rows; the capacities and the voices items may name are declared when it is opened.  Every item - the first
+    // ones too - gets its row at a hand-over look; a look with no part B in flight (the run's start, or after it went idle with every
+    // item ended) places onto empty rows exactly as a look between two frames does, the prefill simply has nothing behind it to follow.
+    bool open = false;
+    std::vector<int32_t> declared;                         // bank entries items may name
+    int cap_text = 0;                                      // longest text of a submit
+    bool b_in_flight = false;                              // part B of frame t - 1 is enqueued: the rows hold the state part A of frame t reads
+    bool pad_done = false;                                 // the projected tts_pad row exists (the first placement's prefill makes it)
+    int dev_frame = 0;                                     // the device's frame counter, mirrored (it lags t by one after the run went idle)
+    std::vector<int> park_t;                               // [B] frame at which a parked row was put behind its prefix
+    int block_v(int b) const { const int v = plan.block_voice[b]; return v >= 0 ? v : declared[0]; }   // (a block no item has had yet: its rows are parked behind the first declared voice)
+    int open_init(const rt_generate_open_args* a);
+    int submit(const int32_t* ids, int n, int mf, int64_t item_id, int v, int32_t* h_item);
+    int cancel_item(int it);
+    void repoint() {                                       // A's input arrays point into vectors that an append may have moved
+        A.n_items = N;
+        A.h_text_ids = text_ids.data(); A.h_text_offsets = text_offsets.data(); A.h_max_frames = max_frames.data(); A.h_item_ids = item_ids.data();
+    }
+    void stats_out();
+
     bool none_waiting() const { return multi ? n_placed >= N : next_item >= N; }
     void point_at(int v) {                                 // the talker cache's shared prefix <- bank entry v
         m->voice_view(v);
@@ -89,6 +110,7 @@ struct rt_gen_run {
     int prefill_by_voice(const std::vector<int>& items, const std::vector<int>& rows, bool first, std::vector<int32_t>* last_of = nullptr);
     int swap_in_voices(int t1);
     int init(const rt_generate_args* a);
+    int init_state();
     int prefill(const std::vector<int>& items, const std::vector<int>& rows, bool first, int r_off = 0, int i_off = 0);
     int enqueue_a(Lane& ln);
     int enqueue_b(Lane& ln);
@@ -230,6 +252,12 @@ int rt_gen_run::init(const rt_generate_args* a) {
         for (int b = 0; b < B; ++b) { items[b] = b; rows[b] = b; }
         RT_TRY(prefill(items, rows, true));
     }
+    return init_state();
+}
+
+// the decode state of a run whose rows, capacities and first wave (none, for an open run) are settled
+int rt_gen_run::init_state() {
+    const rt_model_config& c = m->cfg;
     // ---- decode state.  The batch is cut into `lanes` groups of consecutive items, each decoding on its own stream with
     // its own workspaces: a decode step is a chain of ~600 short dependent kernels whose cost is latency, not bytes, so two
     // chains in flight overlap each other's launch/drain gaps (items are independent: same results for any lane count).
@@ -278,7 +306,7 @@ int rt_gen_run::init(const rt_generate_args* a) {
     std::vector<int64_t> ids_row(B, 0);
     for (int r = 0; r < B; ++r) {
         const int it = multi ? plan.row_item[r] : r;
-        pos_row[r] = it >= 0 ? P[it] : m->voice_len(plan.block_voice[r / voice_plan::BLOCK]);
+        pos_row[r] = it >= 0 ? P[it] : m->voice_len(block_v(r / voice_plan::BLOCK));
         ids_row[r] = it >= 0 ? A.h_item_ids[it] : 0;
     }
     if (queued && !col) return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_generate: queued items (n_items %d > %d rows) need the column decode path", N, B);
@@ -353,7 +381,7 @@ int rt_gen_run::init(const rt_generate_args* a) {
         RT_TRY(pool_arr(m, nb, &d_vblocks));
         RT_TRY(pool_arr(m, nb + B, &d_vlists));
         vtab.blocks = d_vblocks; vtab.mfma_blocks = d_vlists; vtab.vec_rows = d_vlists + nb; vtab.rows = B; vtab.n_blocks = nb;
-        for (int32_t v : voice) {
+        for (int32_t v : open ? declared : voice) {          // (an open run: the DECLARED voices, not the items present)
             const bool mf = attention_mfma_voice_ok(c.talker.heads, c.talker.kv_heads, c.talker.head_dim, m->talker.kv, m->voice_len(v));
             vtab.any_mfma = vtab.any_mfma || mf;
             vtab.any_vec = vtab.any_vec || !mf;
@@ -455,7 +483,122 @@ int rt_gen_run::init(const rt_generate_args* a) {
     h_items = ids_row;
     parked.assign(B, 0);
     for (int b = 0; b < B; ++b) parked[b] = row_item[b] < 0;      // (several voices: rows the first wave left free, already behind their block's prefix)
+    park_t.assign(B, 0);
     return RT_OK;
+}
+
+// ---- an open run: no items yet, every capacity declared
+int rt_gen_run::open_init(const rt_generate_open_args* a) {
+    const rt_model_config& c = m->cfg;
+    if (a->h_forced_codes || a->d_trace_talker || a->d_trace_predictor)
+        return rt_fail(ctx, RT_ERR_UNSUPPORTED, "rt_generate_open: teacher forcing / logit traces on an open run");
+    if (a->rows < 1 || a->rows > c.max_batch) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_open: rows %d outside 1 .. max_batch %d", a->rows, c.max_batch);
+    if (a->max_text_tokens < 0 || a->max_frames < 1 || a->horizon < 1 || a->horizon > (1 << 24))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_open: bad capacities (text %d, frames %d, horizon %d)", a->max_text_tokens, a->max_frames, a->horizon);
+    if (a->n_voices < 1 || !a->h_voices) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_open: no voices declared");
+    if (a->n_items < 0 || (a->n_items > 0 && (!a->h_text_ids || !a->h_text_offsets || !a->h_max_frames || !a->h_item_ids)))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_open: bad first list");
+    open = true; multi = true; queued = true;
+    A = rt_generate_args{};
+    A.seed = a->seed; A.talker = a->talker; A.predictor = a->predictor; A.ignore_eos = a->ignore_eos; A.min_frames = a->min_frames;
+    A.tts_eos_id = a->tts_eos_id; A.tts_pad_id = a->tts_pad_id; A.codec_pad_id = a->codec_pad_id; A.codec_bos_id = a->codec_bos_id;
+    A.h_cancel_flag = a->h_cancel_flag; A.max_rows = a->rows;
+    N = 0; G = c.n_groups; H = c.talker.hidden; Hp = c.predictor.hidden; Vc = c.codec_vocab; Vp = c.predictor_vocab;
+    B = a->rows;
+    every = std::max(1, g_handover_every.load());
+    T_max = a->horizon; F_max = a->max_frames; cap_text = a->max_text_tokens; max_suffix = cap_text + 2;
+    for (int i = 0; i < a->n_voices; ++i) {
+        const int v = a->h_voices[i];
+        if (v < 0 || v >= m->max_voices || m->voice_len(v) < 1)
+            return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_open: declared voice %d is not set (rt_model_set_voice)", v);
+        if (std::find(declared.begin(), declared.end(), v) == declared.end()) declared.push_back(v);
+        // (a parked row steps up to F_max + every positions past the prefix between two looks that put it back)
+        if (m->voice_len(v) + F_max + 2 * every + 1 > c.max_positions)
+            return rt_fail(ctx, RT_ERR_LENGTH, "rt_generate_open: prefix length %d + %d frames exceeds max_positions %d", m->voice_len(v), F_max, c.max_positions);
+    }
+    run_voice = declared[0];
+    if (A.talker.do_sample && (A.talker.top_k < 1 || A.talker.top_k > 64 || !(A.talker.temperature > 0)))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_open: sampling needs 1 <= top_k <= 64 and temperature > 0");
+    if (A.predictor.do_sample && (A.predictor.top_k < 1 || A.predictor.top_k > 64 || !(A.predictor.temperature > 0)))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_open: predictor sampling needs 1 <= top_k <= 64 and temperature > 0");
+    plan.rows = B;
+    plan.row_item.assign(B, -1);
+    plan.block_voice.assign(plan.n_blocks(), -1);
+    plan.placed.clear();
+    text_offsets.assign(1, 0);
+    repoint();
+    for (int v : declared) RT_TRY(voice_tiles(v));
+    point_at(run_voice);
+    S_cap = B * max_suffix;
+    RT_TRY(pool_arr(m, S_cap + 1, &d_tid));
+    RT_TRY(pool_arr(m, (size_t)S_cap * G, &d_cid));
+    RT_TRY(pool_arr(m, S_cap, &d_slot));
+    RT_TRY(pool_arr(m, S_cap, &d_pos));
+    RT_TRY(pool_arr(m, B, &d_last));
+    RT_TRY(pool_arr(m, B, &d_dst));
+    RT_TRY(pool_arr(m, (size_t)(S_cap + 1) * H, &temb));
+    RT_TRY(pool_arr(m, (size_t)S_cap * H, &x));
+    RT_TRY(pool_arr(m, (size_t)S_cap * H, &hn_all_f32));
+    pad_t = temb;
+    RT_TRY(alloc_stack_ws(m, c.talker, S_cap, &w_prefill));
+    RT_TRY(alloc_text_ws(m, S_cap + 1, &w_text));
+    // no first wave: every row starts parked, from a residual stream of zeros (the state is gathered from row 0 of x; nobody reads a
+    // parked row's frames, it only has to stay finite)
+    RT_HIP(ctx, hipMemsetAsync(d_last, 0, B * 4, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(x, 0, (size_t)H * 4, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(hn_all_f32, 0, (size_t)H * 4, ctx->stream));
+    RT_HIP(ctx, hipMemsetAsync(temb, 0, (size_t)H * 4, ctx->stream));
+    RT_TRY(init_state());
+    for (int i = 0; i < a->n_items; ++i) {
+        const int o = a->h_text_offsets[i];
+        RT_TRY(submit(a->h_text_ids + o, a->h_text_offsets[i + 1] - o, a->h_max_frames[i], a->h_item_ids[i],
+                      a->h_item_voices ? a->h_item_voices[i] : declared[0], nullptr));
+    }
+    return RT_OK;
+}
+
+int rt_gen_run::submit(const int32_t* ids, int n, int mf, int64_t item_id, int v, int32_t* h_item) {
+    const rt_model_config& c = m->cfg;
+    if (n < 0 || (n > 0 && !ids)) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_submit: bad text");
+    if (n > cap_text) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_submit: %d text tokens, the run was opened for %d", n, cap_text);
+    if (mf < 1 || mf > F_max) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_submit: max_frames %d, the run was opened for 1 .. %d", mf, F_max);
+    if (std::find(declared.begin(), declared.end(), v) == declared.end() || m->voice_len(v) < 1)
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_submit: voice %d is not among the run's declared voices, or not set", v);
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= c.text_vocab) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_submit: text id out of range");
+    if (m->voice_len(v) + n + 2 + mf + every + 1 > c.max_positions)
+        return rt_fail(ctx, RT_ERR_LENGTH, "rt_generate_submit: prompt length %d + %d frames exceeds max_positions %d", m->voice_len(v) + n + 2, mf, c.max_positions);
+    // the frame counter the item can reach: list scheduling ends every unfinished item within (their budgets, each charged its wait for
+    // the next look) / blocks + the item's own budget from now (rt_gen_run::init's bound, from frame t on)
+    int64_t owed = mf + every;
+    for (int it = 0; it < N; ++it) if (!finished[it]) owed += max_frames[it] + every;
+    if ((int64_t)t + owed / plan.n_blocks() + mf + 2 * every + 2 > T_max)
+        return rt_fail(ctx, RT_ERR_LENGTH, "rt_generate_submit: the horizon is spent (frame %d of %d): let the run drain, end it and open another", t, T_max);
+    text_ids.insert(text_ids.end(), ids, ids + n);
+    text_offsets.push_back((int32_t)text_ids.size());
+    max_frames.push_back(mf); item_ids.push_back(item_id); voice.push_back(v);
+    P.push_back(0); produced.push_back(0); start.push_back(0); item_row.push_back(-1); finished.push_back(0);
+    plan.placed.push_back(0);
+    ++N;
+    repoint();
+    if (h_item) *h_item = N - 1;
+    return RT_OK;
+}
+
+int rt_gen_run::cancel_item(int it) {
+    if (it < 0 || it >= N) return rt_fail(ctx, RT_ERR_INVALID, "rt_generate_cancel_item: item %d out of range", it);
+    if (finished[it]) return RT_OK;
+    finished[it] = 1; ++n_finished;
+    if (!plan.placed[it]) { plan.placed[it] = 1; ++n_placed; }       // it never gets a row
+    else if (item_row[it] >= 0 && row_item[item_row[it]] == it) row_item[item_row[it]] = -1;   // the next look hands the row on
+    return RT_OK;
+}
+
+void rt_gen_run::stats_out() {
+    int64_t kept = 0;
+    for (int it = 0; it < N; ++it) kept += frames_of(it);
+    m->last_frames_run = frames_run; m->last_rows = B; m->last_kept = kept; m->last_swaps = n_swaps; m->last_launch_host_us = launch_host_us;
+    m->last_revoiced = n_revoiced;
 }
 
 // prefill the suffixes of `items` into the KV slots of `rows`; on return x holds the residual stream, d_last / d_dst
@@ -543,7 +686,7 @@ void rt_gen_run::fill_voice_table() {
     h_vlists.assign(nb + B, -1);
     int n_mf = 0, n_vr = 0;
     for (int b = 0; b < nb; ++b) {
-        const int v = plan.block_voice[b], lp = m->voice_len(v);
+        const int v = block_v(b), lp = m->voice_len(v);
         const bool mf = attention_mfma_voice_ok(d.heads, d.kv_heads, d.head_dim, kv, lp);
         h_vblocks[b].prefix_slot = m->voice_slot(v); h_vblocks[b].prefix_len = lp;
         h_vblocks[b].kt = mf ? m->kt_bank + v * per_voice : nullptr;
@@ -582,15 +725,21 @@ int rt_gen_run::swap_in_voices(int t1) {
     // unlike a single-voice run, where a row is parked only once nothing waits, a row here can be free from the first frame in a
     // block that stays busy while another voice queues, and would otherwise step on for the whole run - past max_positions.  A free
     // row thus never sits more than F_max + every positions behind its prefix, which rt_gen_run::init bounds for every voice.
-    for (int r = 0; r < B; ++r)
-        if (row_item[r] < 0 && (!parked[r] || waiting_before)) {
-            const int lp = m->voice_len(plan.block_voice[r / voice_plan::BLOCK]);
+    // An open run has no last item: a row can stay parked while others serve one item after another with nobody waiting at a look.  It
+    // is put back behind its prefix before its position gets within 2 x `every` of max_positions (the next look is `every` frames away).
+    for (int r = 0; r < B; ++r) {
+        if (row_item[r] >= 0) continue;
+        const int lp = m->voice_len(block_v(r / voice_plan::BLOCK));
+        const bool far = open && parked[r] && lp + (t1 - park_t[r]) + 2 * every + 1 > m->cfg.max_positions;
+        if (!parked[r] || waiting_before || far) {
             if (lp + F_max + every + 1 > m->cfg.max_positions)
                 return rt_fail(ctx, RT_ERR_STATE, "rt_generate: a free row behind a prefix of %d rows would pass max_positions %d", lp, m->cfg.max_positions);
-            parked[r] = 1; h_pos_b[r] = lp - t1; dirty = true;
+            parked[r] = 1; h_pos_b[r] = lp - t1; park_t[r] = t1; dirty = true;
         }
+    }
     if (!items.empty()) {
-        RT_TRY(prefill_by_voice(items, rows, false));
+        RT_TRY(prefill_by_voice(items, rows, open && !pad_done));      // (an open run's first placement also projects the tts_pad row, as a first wave does)
+        pad_done = true;
         const int k = (int)items.size();
         RT_TRY(launch_rowsq(ctx, x, k, H, ln.rowsq_t, NTt, ln.dwt.xT, ln.dwt.xa, m->talker.norm, d_last, d_dst));
         for (int i = 0; i < k; ++i) {
@@ -606,6 +755,7 @@ int rt_gen_run::swap_in_voices(int t1) {
         RT_HIP(ctx, hipMemcpyAsync(ln.d_frame_off, h_off.data(), B * 4, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(ctx, hipMemcpyAsync(ln.d_items, h_items.data(), B * 8, hipMemcpyHostToDevice, ctx->stream));
         RT_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (the host arrays are rewritten by the next hand-over)
+        if (open) staging.clear();                         // (every upload has landed: an open run does not keep its staging for ever)
     }
     return RT_OK;
 }
@@ -830,6 +980,27 @@ int rt_gen_run::advance(int n_frames) {
     struct VoiceGuard { rt_model* m; int back; ~VoiceGuard() { m->voice_view(back); } } voice_guard{m, sel_back};
     point_at(run_voice);
     int done_here = 0;
+    if (open) {
+        // nothing decoding and nothing waiting: no frame is launched, the run stays open.  (A part B still in flight - the last live
+        // item was cancelled - has advanced the device's counter already; its rows are parked by the next placement.)
+        if (n_finished == N) { b_in_flight = false; all_done = true; return RT_OK; }
+        all_done = false;
+        if (!b_in_flight && t < T_max) {
+            // items came while the run was idle: they take empty rows the way a first wave does - prefill, then part A.  The run went
+            // idle behind part A of its last frame, so the device's counter is brought up to t first.
+            for (Lane& ln : lanes) ln.done = false;
+            for (; dev_frame < t; ++dev_frame) hipLaunchKernelGGL(k_frame_inc, dim3(1), dim3(64), 0, ctx->stream, lanes[0].d_frame);
+            RT_HIP(ctx, hipGetLastError());
+            RT_TRY(swap_in(t));
+            for (Lane& ln : lanes) {
+                bool any = false;
+                for (int r = ln.b0; r < ln.b0 + ln.n; ++r) any = any || row_item[r] >= 0;
+                if (!any) return rt_fail(ctx, RT_ERR_STATE, "rt_generate_step: no waiting item found a row on an idle run");
+            }
+        } else if (b_in_flight && n_placed < N && t < T_max) {
+            RT_TRY(swap_in(t));                            // items submitted since the last step: a look now, part B of frame t - 1 being in flight
+        }
+    }
     while (!all_done && !cancelled && t < T_max && done_here < n_frames) {
         if (A.h_cancel_flag && *A.h_cancel_flag) { cancelled = true; break; }
         for (int l = 0; l < n_lanes; ++l) {
@@ -853,7 +1024,7 @@ int rt_gen_run::advance(int n_frames) {
             all_done = apply_frames(t + 1);
         }
         ++done_here;
-        if (all_done || t + 1 == T_max) { ++t; break; }
+        if (all_done || t + 1 == T_max) { ++t; b_in_flight = false; break; }
         for (int l = 0; l < n_lanes; ++l) {
             Lane& ln = lanes[l];
             if (ln.done || t + 1 >= lane_frames[l]) continue;
@@ -865,6 +1036,7 @@ int rt_gen_run::advance(int n_frames) {
             if (g_sync_parts) RT_HIP(ctx, hipStreamSynchronize(ln.stream));
         }
         ctx->stream = main_stream;
+        b_in_flight = true; ++dev_frame;
         if (queued && check) RT_TRY(swap_in(t + 1));
         ++t;
     }
@@ -876,6 +1048,9 @@ int rt_gen_run::advance(int n_frames) {
         all_done = apply_frames(frames_run) || all_done;
     }
     if (t >= T_max) all_done = true;                       // the frame budget is spent: nothing more can run
+    // (an open run admits an item only if the horizon can hold it: reaching it with items unfinished means that bound was wrong)
+    if (open && t >= T_max && n_finished < N)
+        return rt_fail(ctx, RT_ERR_STATE, "rt_generate_step: the open run reached its horizon (%d frames) with %d of %d items unfinished", T_max, N - n_finished, N);
     return RT_OK;
 }
 
@@ -957,6 +1132,53 @@ int rt_generate_begin(rt_model* m, const rt_generate_args* A) {
     return gen_begin_locked(m, A);
 }
 
+int rt_generate_open(rt_model* m, const rt_generate_open_args* a) {
+    if (!m || !a) return rt_fail(m ? m->ctx : nullptr, RT_ERR_INVALID, "rt_generate_open: null argument");
+    rt_ctx* ctx = m->ctx;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    if (!m->finalized) return rt_fail(ctx, RT_ERR_STATE, "rt_generate_open: model not finalized");
+    m->item_voices.clear();                                // (an open run names its voices itself)
+    gen_release(m);
+    pool_release_all(m);
+    m->run = new rt_gen_run();
+    g_runs_in_flight.fetch_add(1);
+    m->run->m = m; m->run->ctx = ctx;
+    m->run->sel_back = m->voice_sel;
+    m->pool_tag = 1;
+    const int rc = m->run->open_init(a);
+    m->pool_tag = 0;
+    m->voice_view(m->run->sel_back);
+    if (rc) { ctx->stream = m->run->main_stream ? m->run->main_stream : ctx->stream; const std::string keep = ctx->last_error; gen_release(m); ctx->last_error = keep; }
+    return rc;
+}
+
+int rt_generate_submit(rt_model* m, const int32_t* h_text_ids, int32_t n_text, int32_t max_frames, int64_t item_id, int32_t voice, int32_t* h_item) {
+    if (!m) return RT_ERR_INVALID;
+    rt_ctx* ctx = m->ctx;
+    CtxLock g(ctx);
+    if (!m->run) return rt_fail(ctx, RT_ERR_STATE, "rt_generate_submit: no run in flight (rt_generate_open)");
+    if (!m->run->open) return rt_fail(ctx, RT_ERR_STATE, "rt_generate_submit: the run in flight has a closed item list (rt_generate_begin)");
+    return m->run->submit(h_text_ids, n_text, max_frames, item_id, voice, h_item);
+}
+
+int32_t rt_generate_cadence(rt_model* m) {
+    if (m) {
+        CtxLock g(m->ctx);                                 // (the run may be replaced by another thread's rt_generate_open / _end)
+        if (m->run) return m->run->every;
+    }
+    return std::max(1, g_handover_every.load());
+}
+
+int rt_generate_cancel_item(rt_model* m, int32_t item) {
+    if (!m) return RT_ERR_INVALID;
+    rt_ctx* ctx = m->ctx;
+    CtxLock g(ctx);
+    if (!m->run) return rt_fail(ctx, RT_ERR_STATE, "rt_generate_cancel_item: no run in flight");
+    if (!m->run->open) return rt_fail(ctx, RT_ERR_STATE, "rt_generate_cancel_item: the run in flight has a closed item list");
+    return m->run->cancel_item(item);
+}
+
 int rt_generate_step(rt_model* m, int32_t n_frames, int32_t* h_frames_run, int32_t* h_all_done) {
     if (!m || n_frames < 1) return rt_fail(m ? m->ctx : nullptr, RT_ERR_INVALID, "rt_generate_step: bad argument");
     rt_ctx* ctx = m->ctx;
@@ -999,7 +1221,9 @@ int rt_generate_end(rt_model* m, int32_t* h_codes, int32_t* h_n_frames) {
     RT_HIP(ctx, hipSetDevice(ctx->device));
     if (!m->run) return RT_OK;                              // nothing in flight
     int rc = RT_OK;
-    if (m->run->all_done && !m->run->cancelled) rc = m->run->finish(h_codes, h_n_frames);      // (an abandoned run reports nothing)
+    if (m->run->open && !h_codes && !h_n_frames) m->run->stats_out();        // (an open run is closed whenever its owner says so: its figures stand)
+    else if (m->run->open && m->run->n_finished == m->run->N && !m->run->cancelled) rc = m->run->finish(h_codes, h_n_frames);
+    else if (m->run->all_done && !m->run->cancelled) rc = m->run->finish(h_codes, h_n_frames);      // (an abandoned run reports nothing)
     else if (h_codes || h_n_frames) rc = rt_fail(ctx, RT_ERR_STATE, "rt_generate_end: the generation was ended before every item finished");
     const std::string keep = ctx->last_error;
     gen_release(m);

@@ -414,10 +414,9 @@ __global__ void k_pcm16(const float* __restrict__ in, int64_t n, int16_t* __rest
 // avg_pool1d: base_tts.py:366-377) in float64.
 struct StreamState { double dc, gain; int64_t out_len, start; };
 __device__ __forceinline__ float stream_y(const float* x, int64_t i, float gain, float amp) { return amp * tanhf(__fdiv_rn(__fmul_rn(x[i], gain), amp)); }
-__global__ __launch_bounds__(kThreads) void k_stream_chunk(rt_post_params P, const float* __restrict__ x, int64_t n, uint32_t flags, StreamState* st,
-                                                           float* __restrict__ out) {
-    __shared__ double sh_red[kWaves];
-    __shared__ long long sh_first, sh_last;
+// (the body of both kernels below: one workgroup, one chunk.  sh_red [kWaves], sh_first / sh_last: the workgroup's LDS)
+__device__ __forceinline__ void stream_chunk_body(const rt_post_params& P, const float* __restrict__ x, int64_t n, uint32_t flags, StreamState* st,
+                                                  float* __restrict__ out, double* sh_red, long long& sh_first, long long& sh_last) {
     double gain_d = st->gain, dc_d = st->dc;
     const float amp = (float)P.max_amplitude;
     bool measured = true;
@@ -506,6 +505,22 @@ __global__ __launch_bounds__(kThreads) void k_stream_chunk(rt_post_params P, con
         out[i] = v;
     }
     if (threadIdx.x == 0) { st->dc = measured ? dc_d : 0.0; st->gain = measured ? gain_d : 0.0; st->out_len = m; st->start = lo; }
+}
+__global__ __launch_bounds__(kThreads) void k_stream_chunk(rt_post_params P, const float* __restrict__ x, int64_t n, uint32_t flags, StreamState* st,
+                                                           float* __restrict__ out) {
+    __shared__ double sh_red[kWaves];
+    __shared__ long long sh_first, sh_last;
+    stream_chunk_body(P, x, n, flags, st, out, sh_red, sh_first, sh_last);
+}
+// the chunks of several listeners in one launch (rt_stream_chunks): workgroup i runs the body above on item i's descriptor, so an
+// item gets the bits rt_stream_chunk gives it alone.  An item of no samples is left as it is: nothing written, its state kept.
+struct StreamItem { const float* x; float* out; int64_t n; uint32_t flags, pad; StreamState st; };
+__global__ __launch_bounds__(kThreads) void k_stream_chunks(rt_post_params P, StreamItem* items) {
+    __shared__ double sh_red[kWaves];
+    __shared__ long long sh_first, sh_last;
+    StreamItem* it = items + blockIdx.x;
+    if (it->n <= 0) return;                                          // (uniform over the workgroup)
+    stream_chunk_body(P, it->x, it->n, it->flags, &it->st, it->out, sh_red, sh_first, sh_last);
 }
 
 int post_impl(rt_ctx* ctx, const rt_post_params* p, int32_t n_items, const int32_t* first, const float* const* seg_ptr,
@@ -656,6 +671,42 @@ int rt_stream_chunk(rt_ctx* ctx, const rt_post_params* p, const float* d_in, int
     RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     h_dc_gain[0] = hs->dc; h_dc_gain[1] = hs->gain;
     *h_out_len = hs->out_len;
+    return RT_OK;
+}
+
+int rt_stream_chunks(rt_ctx* ctx, const rt_post_params* p, int32_t n_items, const float* const* h_in_ptr, const int64_t* h_n, const uint32_t* h_flags,
+                     double* h_dc_gain, float* const* h_out_ptr, int64_t* h_out_len) {
+    if (!ctx || !p || n_items < 0 || (n_items > 0 && (!h_in_ptr || !h_n || !h_flags || !h_dc_gain || !h_out_ptr || !h_out_len)))
+        return rt_fail(ctx, RT_ERR_INVALID, "rt_stream_chunks: null argument");
+    if (p->window < 2 || p->fade < 0) return rt_fail(ctx, RT_ERR_INVALID, "rt_stream_chunks: bad geometry (window=%d fade=%d)", p->window, p->fade);
+    bool any = false;
+    for (int i = 0; i < n_items; ++i) {
+        if (h_n[i] < 0 || (h_n[i] > 0 && (!h_in_ptr[i] || !h_out_ptr[i]))) return rt_fail(ctx, RT_ERR_INVALID, "rt_stream_chunks: item %d: bad length or null buffer", i);
+        h_out_len[i] = 0;
+        any = any || h_n[i] > 0;
+    }
+    if (!any) return RT_OK;
+    CtxLock g(ctx);
+    RT_HIP(ctx, hipSetDevice(ctx->device));
+    void *dv = nullptr, *hv = nullptr;
+    const size_t bytes = sizeof(StreamItem) * (size_t)n_items;
+    RT_TRY_POST(rt_ctx_scratch(ctx, bytes, &dv));
+    RT_TRY_POST(rt_ctx_pinned(ctx, bytes, &hv));
+    StreamItem* hs = (StreamItem*)hv;
+    for (int i = 0; i < n_items; ++i) {
+        hs[i].x = h_in_ptr[i]; hs[i].out = h_out_ptr[i]; hs[i].n = h_n[i]; hs[i].flags = h_flags[i]; hs[i].pad = 0;
+        hs[i].st.dc = h_dc_gain[2 * i]; hs[i].st.gain = h_dc_gain[2 * i + 1]; hs[i].st.out_len = 0; hs[i].st.start = 0;
+    }
+    RT_HIP(ctx, hipMemcpyAsync(dv, hs, bytes, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_stream_chunks, dim3((unsigned)n_items), dim3(kThreads), 0, ctx->stream, *p, (StreamItem*)dv);
+    RT_HIP(ctx, hipGetLastError());
+    RT_HIP(ctx, hipMemcpyAsync(hs, dv, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < n_items; ++i) {
+        if (h_n[i] <= 0) continue;
+        h_dc_gain[2 * i] = hs[i].st.dc; h_dc_gain[2 * i + 1] = hs[i].st.gain;
+        h_out_len[i] = hs[i].st.out_len;
+    }
     return RT_OK;
 }
 

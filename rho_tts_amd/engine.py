@@ -334,6 +334,43 @@ class Engine:
             emitted += int(piece.numel())
             yield piece, last
 
+    # ------------------------------------------------------------------ an open run (rt_generate_open / _submit / _cancel_item)
+    def open_run(self, rows: Optional[int] = None, voices: Sequence[Optional[str]] = (None,), max_text_tokens: int = 256,
+                 max_frames: Optional[int] = None, horizon: int = 4096, seed: int = 789, cancel_flag=None) -> dict:
+        """Open a run whose items come later (``submit``): ``rows`` decode rows (default: all), items that speak with ``voices`` (bank
+        names; None: the engine's own voice).  ``max_frames`` defaults to the longest budget ``frames_actual`` gives, cut to what fits
+        behind the longest declared prefix.  Returns the capacities it was opened with.  HBM beyond the model: ``horizon * rows *
+        (n_groups + 1) * 4`` bytes of codes and flags (and as much host memory) plus the prefill workspace of ``rows * (max_text_tokens
+        + 2)`` prompt rows."""
+        entries = sorted({0 if v is None else self.voice_entries([v], 1)[0] for v in voices})
+        if 0 in entries and self.voice is None:
+            raise ValueError("no voice set: reference audio (Base models) or a built-in speaker (CustomVoice) is required")
+        longest = max(self._prefix_len.get(e, 0) if e else self.model.prefix_len() for e in entries)
+        fit = self.model.max_positions - longest - 2 * self.model.cadence() - 1     # (rt_generate_open's own bound)
+        if max_frames is None:
+            max_frames = int(self.params.max_seconds * self.cfg.frame_rate * (1.0 + max(0.0, self.length_jitter))) + 1
+        caps = dict(rows=int(rows or self.max_batch), max_text_tokens=int(max_text_tokens), max_frames=max(1, min(int(max_frames), fit)),
+                    horizon=int(horizon), voices=entries)
+        ignore_eos = self.synthetic if self.ignore_eos is None else bool(self.ignore_eos)
+        self.model.generate_open(caps["rows"], caps["max_text_tokens"], caps["max_frames"], caps["horizon"], entries, self.params.talker(),
+                                 self.params.predictor(), seed=seed, ignore_eos=ignore_eos, cancel_flag=cancel_flag)
+        return caps
+
+    def submit(self, text: str, voice: Optional[str] = None, item_id: int = 0, max_frames: Optional[int] = None):
+        """One more text for the open run: (its item index, its frame budget).  Its codes are those ``generate_codes`` gives it alone."""
+        ids = self.tokenizer.encode(text)
+        frames = int(max_frames) if max_frames is not None else self.frames_actual(text, len(ids))
+        entry = 0 if voice is None else self.voice_entries([voice], 1)[0]
+        # the positions are checked here, as generate_codes / stream_codes check them: the one length refusal left to the library is
+        # then the spent horizon (_native.LengthError), which a session answers by draining and reopening
+        limit = self.model.max_positions - (self._prefix_len.get(entry, 0) if entry else self.model.prefix_len()) - self.model.cadence() - 1
+        if len(ids) + 2 + frames > limit:
+            raise ValueError(f"text of {len(ids)} tokens + {frames} frames exceeds the {limit} free KV rows")
+        return self.model.generate_submit(ids, frames, item_id, entry), frames
+
+    def cancel(self, item: int) -> None:
+        self.model.generate_cancel_item(item)
+
     def plan_batches(self, frames: Sequence[int]) -> List[List[int]]:
         """Batches of ``max_batch`` text indices.  One batch keeps arrival order; more are bucketed by frame budget, longest
         first: a batch decodes until its longest member is done, so similar lengths keep its rows busy (dist.bucket_batches)."""

@@ -778,6 +778,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         """Register a voice beside the constructor's, by the constructor's mode rules (``_voice_config_key``): a named speaker with a
         CustomVoice model, reference audio and its transcript with a Base model.  It is made resident on the GPU by the first call
         that names it.  ValueError: no name, a mode the model does not have, a full bank."""
+        self._no_session("add_voice")
         if not isinstance(name, str) or not name:
             raise ValueError("add_voice: a voice needs a name")
         is_custom = "CustomVoice" in self.model_path
@@ -796,6 +797,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
             self._ge2e_bank.pop(name, None)
 
     def remove_voice(self, name: str) -> None:
+        self._no_session("remove_voice")
         with self._lock:
             if name not in self._bank:
                 raise ValueError(f"unknown voice {name!r}")
@@ -961,6 +963,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
 
     # ---------------------------------------------------------------- provider contract
     def _generate_audio(self, text: Union[str, List[str]], **kwargs) -> Union[torch.Tensor, List[torch.Tensor]]:
+        self._no_session("_generate_audio")
         single = isinstance(text, str)
         texts = [text] if single else list(text)
         eng = self._load_engine()
@@ -1002,6 +1005,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         ``voices`` (an extension): a bank name for every text, or a list as long as ``texts`` whose ``None`` entries mean the
         constructor's voice; the segments of a text speak with its voice.  ValueError before anything runs: an unknown name, a list
         of the wrong length."""
+        self._no_session("generate")
         n_texts = 1 if isinstance(texts, str) else len(texts)
         names = self._resolve_voices(voices, n_texts)
         if names is None:
@@ -1039,6 +1043,7 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         Every segment keeps RNG stream 0, which is what a one-segment ``_generate_audio`` call uses, so the results equal the
         sequential loop's."""
         from .api import GenerationResult
+        self._no_session("stream")
         token = cancellation_token or CancellationToken()
         self._resolve_voices(voice, 1)                          # (``voice``: a bank name; ValueError for an unknown one before anything runs)
         vkw = {} if voice is None else {"voices": voice}
@@ -1130,6 +1135,54 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
                 return
             except Exception as e:  # noqa: BLE001  (as the reference: a failed segment is skipped, base_tts.py:1166-1168)
                 logger.warning(f"Segment {seg_idx + 1} failed: {e}")
+
+    # ---------------------------------------------------------------- serving sessions (an extension)
+    _session = None                                            # the serving session in flight (serve), which owns the engine's run
+
+    def _no_session(self, what: str) -> None:
+        s = self._session
+        if s is not None and not s.is_worker():
+            raise RuntimeError(f"{what}: a serving session is open on this instance and owns its decode rows - submit the text to the "
+                               "session, or close it first")
+
+    def serve(self, rows: Optional[int] = None, voices: Optional[Sequence[str]] = None, stream_chunk_frames: int = 12,
+              stream_next_chunk_frames: int = 36, max_text_tokens: int = 256, horizon: int = 4096, timeout: float = 120.0):
+        """A serving session: requests join ONE decode batch in flight instead of queueing behind each other's calls.
+
+            with tts.serve(voices=["b"]) as session:
+                h1 = session.submit("A text", stream=True)            # any thread
+                h2 = session.submit("Another one", voice="b")
+                for piece in h1: ...                                  # GenerationResults, as stream() yields them
+                result = h2.result(timeout=30)                        # the GenerationResult generate() returns
+
+        The constructor's voice and the bank voices ``voices`` are made resident and the run is opened on ``rows`` decode rows
+        (default: ``batch_size``); one worker thread drives it (serving.Session).  ``handle.result()`` is what ``generate(text,
+        voices=voice)`` returns for that text alone with ``max_iterations == 1`` (no validation loop and no decay retry in a session,
+        as in ``stream()``); iterating a ``stream=True`` handle yields the pieces of sub-segment streaming with the two chunk sizes -
+        with a bank voice too.  A request's audio is bit for bit what it gets alone, whoever else is connected.  A segment of more
+        than ``max_text_tokens`` tokens fails its request (``ValueError``).  ``horizon``: the frame-counter values of one run - when
+        they are spent the worker drains the run, opens another and goes on with the queue; callers see nothing of it.  While the
+        session is open ``generate`` / ``stream`` / ``add_voice`` on this instance raise; closing it (leaving the ``with`` block)
+        cancels pending requests - their handles raise - and restores them.  Every wait has a timeout (``timeout`` seconds unless
+        the call gives one) that raises ``TimeoutError``."""
+        from .serving import EngineRun, Session
+        self._no_session("serve")
+        names = [v for v in (voices or []) if v is not None]
+        eng = self._load_engine()
+        with self._lock:
+            if self._session is not None:
+                raise RuntimeError("serve: a serving session is already open on this instance")
+            self._resolve_voices(names or None, len(names))
+            self._ensure_voice(eng)
+            self._ensure_bank(eng, names)
+            self._set_seeds()
+            run = EngineRun(self, eng, rows, [None] + sorted(set(names)), int(max_text_tokens), None, int(horizon))
+
+            def release():
+                self._session = None
+            session = Session(run, int(stream_chunk_frames), int(stream_next_chunk_frames), float(timeout), on_close=release)
+            self._session = session
+        return session
 
     def _apply_speed_pitch(self, audio: torch.Tensor, speed: float, pitch_semitones: float) -> torch.Tensor:
         """``BaseTTS._apply_speed_pitch`` (base_tts.py:618-650) on the GPU, without torchaudio: the resampler and the phase-vocoder
@@ -1259,6 +1312,8 @@ class MI355XQwenTTS(DataParallelPipeline, HipAudioLeaves, BaseTTS):
         return align([audio], self.sample_rate, [text])[0]
 
     def close(self) -> None:
+        if self._session is not None:
+            self._session.close()
         with self._lock:
             self._close_speed_pitch()                          # (before the context they live on)
             self._close_drift()
